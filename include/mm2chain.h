@@ -334,6 +334,9 @@ int mm2c_seedplan_set_heap_sort(mm2c_seedplan_t *plan, int on);   /* mm2c_tune("
                                                                     * mm2c_seed_hits_batch_host / mm2c_seed_chain_batch_host / _pool included (a host that maps with MM_F_HEAP_SORT) */
 int mm2c_seedplan_check(mm2c_seedplan_t *plan, int64_t *n_reads_with_ties);   /* waits; MM2C_E_ARG if a read's counts disagreed */
 int mm2c_seedplan_last_ms(mm2c_seedplan_t *plan, float *ms);
+/* *n_reads = the reads the plan's last run expanded on the sixteen waves of a workgroup (reads of more than 16 384 anchors of capacity and at most 2^20 matches,
+ * with and without skip_seed; none when the environment switch MM2C_MW_SORT=0 was set as the plan was made); 0 before the first run */
+int mm2c_seedplan_last_expand_mw(mm2c_seedplan_t *plan, int64_t *n_reads);
 /* host buffers in, anchors out (computes the anchor offsets itself): anchor_off[n_reads+1], anchors with room for the sum of all n */
 int mm2c_seed_hits_batch_host(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits,
                               int64_t n_hits, const int32_t *h_qlen, int64_t *anchor_off, mm2c_anchor_t *anchors);
@@ -358,6 +361,33 @@ int mm2c_seed_chain_batch_host(const mm2c_params_t *par, int min_cnt, int min_sc
 int mm2c_seed_chain_batch_pool(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
                                const mm2c_match_t *h_matches, const mm2c_hitpool_t *pool, const int32_t *h_qlen,
                                int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b);
+
+/* ---- the host-buffer entries with skip_seed (map.c:122-147): -x ava-ont (NO_DIAG | NO_DUAL) and the strand-restricted modes (FOR_ONLY / REV_ONLY) ----
+ * The skip description of mm2c_seed_skip_t with host arrays.  Names travel as ranks, as there: ref_rank[rid] = rank of reference rid's name among the distinct
+ * reference names in strcmp order, ref_len[rid] = its length; per read q_lo = number of those names below the read's name, q_eq = 1 when the read's name is one of
+ * them.  ref_rank == NULL stands for qname == NULL (map.c:125): no name comparison.  Every hit's rid must be below n_ref when ref_rank is given (checked before any
+ * kernel runs; a resident pool records its largest rid when it is made).
+ * Capacity sizes the buffers: anchors, u and b need room for the sum of all hits (n over every match).  On return anchor_off[r+1] - anchor_off[r] is the number of
+ * anchors read r KEPT -- its anchors are anchors[anchor_off[r] ..) for the seed-hit entry --, and u / b hold what mm_chain_dp returns on the anchors collect_seed_hits
+ * leaves with these flags.  flag == 0 gives the results of the entries above.  Flag bits other than these four are refused, as are NO_DIAG / NO_DUAL with
+ * ref_rank but without ref_len, q_lo or q_eq.  mm2c_tune("heap_sort", 1) applies (collect_seed_hits_heap). */
+typedef struct {
+	int32_t flag;                              /* MM_F_NO_DIAG 0x001 | MM_F_NO_DUAL 0x002 | MM_F_FOR_ONLY 0x100000 | MM_F_REV_ONLY 0x200000 */
+	int32_t n_ref;                             /* entries of ref_rank / ref_len */
+	const int32_t *ref_rank, *ref_len;         /* host, per reference sequence; ref_rank == NULL: qname == NULL (map.c:125) */
+	const int32_t *q_lo, *q_eq;                /* host, per read (required when ref_rank != NULL and flag has 0x001 | 0x002) */
+} mm2c_seed_skip_host_t;
+int mm2c_seed_hits_batch_host_skip(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits,
+                                   int64_t n_hits, const int32_t *h_qlen, const mm2c_seed_skip_host_t *skip,
+                                   int64_t *anchor_off, mm2c_anchor_t *anchors);
+int mm2c_seed_chain_batch_host_skip(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
+                                    const mm2c_match_t *h_matches, const uint64_t *h_hits, int64_t n_hits, const int32_t *h_qlen,
+                                    const mm2c_seed_skip_host_t *skip,
+                                    int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b);
+int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
+                                    const mm2c_match_t *h_matches, const mm2c_hitpool_t *pool, const int32_t *h_qlen,
+                                    const mm2c_seed_skip_host_t *skip,
+                                    int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b);
 
 /* ---- anchor streams on disk (csrc/anchor_stream.c documents the layout) ------------------------ */
 typedef struct {

@@ -120,11 +120,12 @@ struct WholeSlot {
 struct SeedSlot {
 	hipStream_t st = nullptr;
 	hipEvent_t ev[6] = {};                    // begin, uploaded, anchors made, DP done, chains made, offsets downloaded
-	char *d_buf = nullptr, *h_meta = nullptr; // grow-only arena [matches | hits | qlen | anchors | f | p | u_off | b_off | u | b]; pinned [u_off | b_off]
+	char *d_buf = nullptr, *h_meta = nullptr; // grow-only arena [matches | hits | qlen | (q_lo | q_eq: skip_seed) | anchors | f | p | u_off | b_off | u | b | (packed anchor_off)];
+	                                          // pinned [u_off | b_off | (packed anchor_off)]
 	size_t cap_buf = 0, cap_hmeta = 0;
 	void *seedplan = nullptr, *plan = nullptr;   // the chunk's plans (their workspace comes from the device cache)
 	int64_t k0 = 0, k1 = 0;
-	size_t o_uo = 0, o_bo = 0, o_u = 0, o_b = 0;
+	size_t o_uo = 0, o_bo = 0, o_u = 0, o_b = 0, o_ao = 0;
 	bool busy = false, timed = false;
 	void release()
 	{

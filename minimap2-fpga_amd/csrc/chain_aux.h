@@ -73,6 +73,7 @@ struct SeedArgs {
 int seed_tie_lds_max();
 int seed_tie_mid_lower();
 int seed_sort_lds_cap();
+bool seed_expand_mw_takes_host(int64_t cap, int64_t n_matches);   // the reads seed_expand_mw takes (capacity, matches of the read), when mw_sort is on
 int seed_sort_lds_cap0();
 const int64_t *seed_tie_class_lower();          // six lower bounds (exclusive) of the size classes of seed_ties, shortest class first
 // aux: three helper streams (or nullptr: everything on st), ev: four events without timing

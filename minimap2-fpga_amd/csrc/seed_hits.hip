@@ -82,12 +82,16 @@ __device__ __forceinline__ bool hit_anchor(const SeedArgs &A, uint64_t r, uint32
 	return keep;
 }
 
-// Long reads (round 6): which reads the sixteen-wave expansion takes (seed_expand_mw below) -- more anchors than the LDS sorts hold, every hit kept (with skip_seed the
-// place of an anchor depends on what the hits before it decided: one wave), no more chunks of 64 matches than its table of chunk totals holds
+// Long reads (round 6): which reads the sixteen-wave expansion takes (seed_expand_mw below) -- more anchors (capacity, with skip_seed) than the LDS sorts hold, no more
+// chunks of 64 matches than its table of chunk totals holds.  The host counts the same reads (seed_expand_mw_takes_host, mm2c_seedplan_last_expand_mw).
 constexpr int EXPAND_MW_WAVES = 16, EXPAND_MW_CHUNKS = 16384, EXPAND_MW_ABOVE = 16384;   // (EXPAND_MW_ABOVE = SORT_LDS_CAP below: the reads the host counts in n_sort_huge)
+__host__ __device__ __forceinline__ bool expand_mw_fits(int64_t cap, int64_t n_matches)
+{
+	return cap > EXPAND_MW_ABOVE && (n_matches + 63) / 64 <= EXPAND_MW_CHUNKS;
+}
 __device__ __forceinline__ bool expand_mw_takes(const SeedArgs &A, int read)
 {
-	return A.mw_sort && !A.d_count && A.d_anchor_off[read + 1] - A.d_anchor_off[read] > EXPAND_MW_ABOVE && (A.d_match_off[read + 1] - A.d_match_off[read] + 63) / 64 <= EXPAND_MW_CHUNKS;
+	return A.mw_sort && expand_mw_fits(A.d_anchor_off[read + 1] - A.d_anchor_off[read], A.d_match_off[read + 1] - A.d_match_off[read]);
 }
 
 // ---- kernel 1: expansion (map.c:222-243) ----------------------------------------------------------------------------
@@ -152,8 +156,11 @@ __global__ __launch_bounds__(64) void seed_expand(SeedArgs A)
 // ---- kernel 1b (round 6): the expansion of a LONG read on sixteen waves.  seed_expand walks a read's matches 64 at a time on one wave -- 34 ms for a read of 10^6
 // anchors, one read per CU and the other waves of the CU idle.  Where an anchor lands is the prefix sum of the hit counts before its match, so: (1) every wave adds up the hit
 // counts of its chunks of 64 matches, (2) one block-wide exclusive scan over the chunk totals, (3) every wave expands its chunks at their places -- the same lanes, the same
-// owner search, the same encoding (hit_anchor) as seed_expand, chunk by chunk.  Every hit is kept here (no skip_seed), so the totals are the places.
-template <int NW>
+// owner search, the same encoding (hit_anchor) as seed_expand, chunk by chunk.  Without skip_seed every hit is kept, so the totals are the places.
+// SKIP (skip_seed, d_count != nullptr): a kept anchor's place depends on what every hit before it decided, so (1) enumerates the chunk's hits once already and counts the ones
+// hit_anchor keeps (the chunk table holds KEPT counts; the hit counts only go into the check against the capacity), (2) scans those, (3) enumerates again and writes the kept
+// hits compacted in hit order as seed_expand does (ballot over keep, rank within the 64 hits of a step, a running offset from the chunk's place).  The hits are read twice.
+template <int NW, bool SKIP>
 __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 {
 	constexpr int NT = 64 * NW;
@@ -162,35 +169,78 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 	__shared__ uint32_t s_qpos[NW][64], s_span[NW][64], s_segt[NW][64];
 	__shared__ int64_t s_cr[NW][64];
 	__shared__ int s_part[NT], s_bad;
-	__shared__ unsigned long long s_or, s_and;
+	__shared__ unsigned long long s_or, s_and, s_hits;                             // s_hits (SKIP): the read's hits, summed in (1)
 	const int read = A.d_order ? A.d_order[blockIdx.x] : (int)blockIdx.x;
 	if (!expand_mw_takes(A, read)) return;
 	const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int64_t m0 = A.d_match_off[read], a0 = A.d_anchor_off[read];
 	const int nm = (int)(A.d_match_off[read + 1] - m0), na = (int)(A.d_anchor_off[read + 1] - a0);
 	const int qlen = A.d_qlen[read];
+	const int q_lo = SKIP && A.d_q_lo ? A.d_q_lo[read] : 0, q_eq = SKIP && A.d_q_eq ? A.d_q_eq[read] : 0;
 	const Match *m = A.d_matches + m0;
 	ulonglong2 *out = A.unsorted + a0;
 	const int n_chunks = (nm + 63) / 64;
-	if (tid == 0) { s_bad = 0; s_or = 0; s_and = ~0ull; }
+	if (tid == 0) { s_bad = 0; s_or = 0; s_and = ~0ull; s_hits = 0; }
 	__syncthreads();
+	// the rows of one chunk of the wave's matches (owner search and encoding) and the chunk's hit total; a wave's own rows: no workgroup barrier
+	auto load_rows = [&](const Match &q) -> int {
+		const int incl = wave_incl_scan((int)q.n, lane);
+		const int total = __shfl(incl, 63);
+		s_start[wave][lane] = incl - (int)q.n; s_cr[wave][lane] = q.cr_off; s_qpos[wave][lane] = q.q_pos; s_span[wave][lane] = q.q_span; s_segt[wave][lane] = q.seg_tandem;
+		if (lane == 63) s_start[wave][64] = total;
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		return total;
+	};
+	// hit t of the wave's chunk as an anchor (false: skip_seed drops it)
+	auto hit_at = [&](int t, ulonglong2 &a) -> bool {
+		int lo = 0, hi = 63;                                                        // last match of the chunk with start <= t
+		while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[wave][mid] <= t) lo = mid; else hi = mid - 1; }
+		const uint64_t r = A.d_hits[s_cr[wave][lo] + (t - s_start[wave][lo])];
+		return hit_anchor(A, r, s_qpos[wave][lo], s_span[wave][lo], s_segt[wave][lo], qlen, q_lo, q_eq, a);   // (without SKIP skip_flag is 0: every hit is kept)
+	};
+	auto rows_done = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); };
 	// (1) totals of the chunks (and the check of seed_expand: no match may reach beyond the hit pool the caller declared)
+	unsigned long long hits = 0;                                                    // SKIP: the hits of the wave's chunks
 	for (int c = wave; c < n_chunks; c += NW) {
 		const int i = 64 * c + lane;
 		Match q = {};
 		if (i < nm) q = m[i];
-		if (A.n_hits > 0 && i < nm && (q.cr_off < 0 || q.cr_off + (int64_t)q.n > A.n_hits)) s_bad = 2;
+		const bool outside = A.n_hits > 0 && i < nm && (q.cr_off < 0 || q.cr_off + (int64_t)q.n > A.n_hits);
+		if (outside) s_bad = 2;
 		unsigned long long n64 = q.n;                                               // the chunk's hits in 64 bits: a chunk with more than the read's anchors is an error (and keeps the int sums exact)
 		for (int d = 1; d < 64; d <<= 1) n64 += (unsigned long long)__shfl_xor((long long)n64, d);
 		if (n64 > (unsigned long long)na) { if (!s_bad) s_bad = 1; n64 = 0; }
-		if (lane == 63) s_tot[c] = (int)n64;
+		if constexpr (SKIP) {
+			int kept = 0;
+			if (n64 > 0 && !__ballot(outside)) {                                     // (a chunk with a match outside the pool is not enumerated: its hits are not there)
+				const int total = load_rows(q);
+				for (int t0 = 0; t0 < total; t0 += 64) {
+					ulonglong2 a;
+					const bool keep = t0 + lane < total && hit_at(t0 + lane, a);
+					kept += (int)__builtin_popcountll(__ballot(keep));
+				}
+				rows_done();                                                            // the rows are rewritten for the wave's next chunk
+			}
+			hits += n64;
+			if (lane == 63) s_tot[c] = kept;
+		} else {
+			if (lane == 63) s_tot[c] = (int)n64;
+		}
 	}
+	if constexpr (SKIP) { if (lane == 0) atomicAdd(&s_hits, hits); }
 	__syncthreads();
-	if (s_bad) { if (tid == 0) A.status[read] = s_bad; return; }
+	if constexpr (SKIP) {
+		// the hits of the read's matches must add up to its capacity (checked before the scan: the kept counts then add up to at most na < 2^31)
+		const int bad = s_bad ? s_bad : s_hits != (unsigned long long)na ? 1 : 0;
+		if (bad) { if (tid == 0) { A.status[read] = bad; A.d_count[read] = 0; } return; }
+	} else {
+		if (s_bad) { if (tid == 0) A.status[read] = s_bad; return; }
+	}
 	// (2) exclusive scan over the chunk totals: every thread a run of consecutive chunks
 	const int per = (n_chunks + NT - 1) / NT, c_lo = min(tid * per, n_chunks), c_hi = min(c_lo + per, n_chunks);
 	long long mine = 0;
 	for (int c = c_lo; c < c_hi; ++c) mine += s_tot[c];
+	int grand = 0;
 	{
 		// (an int suffices for the places: the grand total must equal na < 2^31, checked below; a partial sum that overflowed shows up as a mismatch there)
 		int v = (int)min(mine, (long long)INT_MAX);
@@ -200,11 +250,14 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 		int before = 0;
 		for (int w = 0; w < wave; ++w) before += s_part[w];
 		int at = before + incl - v;
-		int grand = 0;
 		for (int w = 0; w < NW; ++w) grand += s_part[w];
 		__syncthreads();
 		for (int c = c_lo; c < c_hi; ++c) { const int t = s_tot[c]; s_tot[c] = at; at += t; }
-		if (grand != na || mine > INT_MAX) { if (tid == 0) A.status[read] = 1; return; }        // the caller's anchor offsets do not match the hit counts (uniform: every thread sees the same sums)
+		if constexpr (SKIP) {
+			if (tid == 0) A.d_count[read] = grand;                                  // the anchors the read keeps (seed_offsets packs the reads by them)
+		} else {
+			if (grand != na || mine > INT_MAX) { if (tid == 0) A.status[read] = 1; return; }   // the caller's anchor offsets do not match the hit counts (uniform: every thread sees the same sums)
+		}
 	}
 	__syncthreads();
 	// (3) expansion, chunk by chunk as seed_expand does it
@@ -213,30 +266,27 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 		const int i = 64 * c + lane;
 		Match q = {};
 		if (i < nm) q = m[i];
-		const int incl = wave_incl_scan((int)q.n, lane);
-		const int total = __shfl(incl, 63);
-		s_start[wave][lane] = incl - (int)q.n; s_cr[wave][lane] = q.cr_off; s_qpos[wave][lane] = q.q_pos; s_span[wave][lane] = q.q_span; s_segt[wave][lane] = q.seg_tandem;
-		if (lane == 63) s_start[wave][64] = total;
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // (a wave's own rows: no workgroup barrier)
-		const int run = s_tot[c];
+		const int total = load_rows(q);
+		int run = s_tot[c];
 		for (int t0 = 0; t0 < total; t0 += 64) {
 			const int t = t0 + lane;
-			if (t < total) {
-				int lo = 0, hi = 63;                                            // last match of the chunk with start <= t
-				while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_start[wave][mid] <= t) lo = mid; else hi = mid - 1; }
-				const uint64_t r = A.d_hits[s_cr[wave][lo] + (t - s_start[wave][lo])];
-				ulonglong2 a = {0, 0};
-				hit_anchor(A, r, s_qpos[wave][lo], s_span[wave][lo], s_segt[wave][lo], qlen, 0, 0, a);   // (skip_flag is 0 here: every hit is kept)
+			ulonglong2 a = {0, 0};
+			const bool keep = t < total && hit_at(t, a);
+			if constexpr (SKIP) {
+				const uint64_t km = __ballot(keep);                                   // kept hits stay in hit order (the order collect_seed_hits fills a[])
+				if (keep) { out[run + lanes_before(km)] = a; x_or |= a.x; x_and &= a.x; }
+				run += (int)__builtin_popcountll(km);
+			} else if (keep) {
 				out[run + t] = a;
 				x_or |= a.x; x_and &= a.x;
 			}
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // the rows are rewritten for the wave's next chunk
+		rows_done();                                                                // the rows are rewritten for the wave's next chunk
 	}
 	x_or = wave_or(x_or); x_and = ~wave_or(~x_and);
 	if (lane == 0) { atomicOr(&s_or, x_or); atomicAnd(&s_and, x_and); }
 	__syncthreads();
-	if (tid == 0) A.xdiff[read] = na > 0 ? s_or ^ s_and : 0;
+	if (tid == 0) A.xdiff[read] = (SKIP ? grand : na) > 0 ? s_or ^ s_and : 0;   // over the kept anchors only, as seed_expand
 }
 
 // ---- packed offsets of the result: exclusive prefix sums of the per-read counts (one block of 1024 threads) ----------------
@@ -866,6 +916,7 @@ int seed_tie_lds_max() { return TIE_CAP4; }
 int seed_tie_mid_lower() { return TIE_CAP2; }
 static int64_t lower_of_class(int c) { static const int64_t lower[6] = { 64, TIE_CAP0, TIE_CAP1, TIE_CAP2, TIE_CAP3, TIE_CAP4 }; return lower[c]; }
 int seed_sort_lds_cap() { return SORT_LDS_CAP; }
+bool seed_expand_mw_takes_host(int64_t cap, int64_t n_matches) { return expand_mw_fits(cap, n_matches); }
 int seed_sort_lds_cap0() { return SORT_LDS_CAP0; }
 const int64_t *seed_tie_class_lower()
 {
@@ -882,8 +933,9 @@ hipError_t launch_seed_hits(const SeedArgs &A, hipStream_t st, int *n_launches, 
 	hipError_t e;
 	hipLaunchKernelGGL(seed_expand, dim3(nr), dim3(64), 0, st, A);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
-	if (A.mw_sort && !A.d_count && (A.d_order ? A.n_sort_huge : (int64_t)nr) > 0) {   // long reads: sixteen waves each (the first workgroups of the launch order)
-		hipLaunchKernelGGL((seed_expand_mw<EXPAND_MW_WAVES>), dim3(A.d_order ? (unsigned)A.n_sort_huge : nr), dim3(64 * EXPAND_MW_WAVES), 0, st, A);
+	if (A.mw_sort && (A.d_order ? A.n_sort_huge : (int64_t)nr) > 0) {            // long reads: sixteen waves each (the first workgroups of the launch order); before seed_offsets
+		if (A.d_count) hipLaunchKernelGGL((seed_expand_mw<EXPAND_MW_WAVES, true>), dim3(A.d_order ? (unsigned)A.n_sort_huge : nr), dim3(64 * EXPAND_MW_WAVES), 0, st, A);
+		else hipLaunchKernelGGL((seed_expand_mw<EXPAND_MW_WAVES, false>), dim3(A.d_order ? (unsigned)A.n_sort_huge : nr), dim3(64 * EXPAND_MW_WAVES), 0, st, A);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 		if (n_launches) ++*n_launches;
 	}

@@ -99,11 +99,17 @@ C_SYMBOLS = {
     "mm2c_seedplan_set_heap_sort": (C.c_int, [C.c_void_p, C.c_int]),
     "mm2c_seedplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mm2c_seedplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_seedplan_last_expand_mw": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mm2c_seed_hits_batch_host": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_seed_chain_batch_host": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_seed_chain_batch_pool": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_seed_hits_batch_host_skip": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_seed_chain_batch_host_skip": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_seed_chain_batch_pool_skip": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_hitpool_create": (C.c_void_p, [C.c_void_p, C.c_int64]),
     "mm2c_hitpool_size": (C.c_int64, [C.c_void_p]),
     "mm2c_hitpool_destroy": (None, [C.c_void_p]),
@@ -147,6 +153,11 @@ def load():
 class SeedSkip(C.Structure):
     """mm2c_seed_skip_t"""
     _fields_ = [("flag", C.c_int32), ("d_ref_rank", C.c_void_p), ("d_ref_len", C.c_void_p), ("d_q_lo", C.c_void_p), ("d_q_eq", C.c_void_p)]
+
+
+class SeedSkipHost(C.Structure):
+    """mm2c_seed_skip_host_t"""
+    _fields_ = [("flag", C.c_int32), ("n_ref", C.c_int32), ("ref_rank", C.c_void_p), ("ref_len", C.c_void_p), ("q_lo", C.c_void_p), ("q_eq", C.c_void_p)]
 
 
 class Mm2cError(RuntimeError):

@@ -383,6 +383,12 @@ class SeedPlan:
         N.check(self.lib.mm2c_seedplan_last_ms(self.handle, C.byref(ms)), "mm2c_seedplan_last_ms")
         return ms.value
 
+    def last_expand_mw(self):
+        """the reads the last run expanded on sixteen waves (mm2c_seedplan_last_expand_mw)"""
+        n = C.c_int64(0)
+        N.check(self.lib.mm2c_seedplan_last_expand_mw(self.handle, C.byref(n)), "mm2c_seedplan_last_expand_mw")
+        return int(n.value)
+
     def close(self):
         if self.handle:
             self.lib.mm2c_seedplan_destroy(self.handle)
@@ -430,6 +436,70 @@ def seed_chain_batch(params: Params, min_cnt, min_sc, match_off, matches, hits, 
     return _split_chains(n_reads, u_off, u, b_off, b)
 
 
+class SeedSkip:
+    """skip_seed (map.c:122-147) for the host-buffer entries (mm2c_seed_skip_host_t).  flag: NO_DIAG | NO_DUAL (-x ava-ont), FOR_ONLY, REV_ONLY.  Names as ranks
+    (include/mm2chain.h): ref_rank / ref_len per reference sequence, q_lo / q_eq per read; ref_rank None: no name comparison (qname == NULL, map.c:125)."""
+    NO_DIAG, NO_DUAL, FOR_ONLY, REV_ONLY = 0x001, 0x002, 0x100000, 0x200000      # minimap.h:8-9,28-29
+
+    def __init__(self, flag, ref_rank=None, ref_len=None, q_lo=None, q_eq=None):
+        as_i32 = lambda x: None if x is None else np.ascontiguousarray(np.asarray(x, dtype=np.int32)).reshape(-1)
+        self.flag = int(flag)
+        self.ref_rank, self.ref_len, self.q_lo, self.q_eq = as_i32(ref_rank), as_i32(ref_len), as_i32(q_lo), as_i32(q_eq)
+        if self.flag & ~(self.NO_DIAG | self.NO_DUAL | self.FOR_ONLY | self.REV_ONLY):
+            raise ValueError(f"skip flag {self.flag:#x} has bits other than NO_DIAG, NO_DUAL, FOR_ONLY, REV_ONLY")
+        if self.ref_rank is None:
+            if self.ref_len is not None:
+                raise ValueError("ref_len without ref_rank")
+            return
+        if self.ref_len is not None and self.ref_len.size != self.ref_rank.size:
+            raise ValueError(f"ref_len has {self.ref_len.size} entries, ref_rank {self.ref_rank.size}")
+        if (self.q_lo is None) != (self.q_eq is None) or (self.q_lo is not None and self.q_lo.size != self.q_eq.size):
+            raise ValueError("q_lo and q_eq go together, one entry per read each")
+        if self.flag & (self.NO_DIAG | self.NO_DUAL) and (self.ref_len is None or self.q_lo is None):
+            raise ValueError("NO_DIAG / NO_DUAL with ref_rank need ref_len, q_lo and q_eq")
+
+    def _native(self, n_reads):
+        """the C struct for a batch of n_reads reads (checks the per-read lengths; the arrays must outlive the call)"""
+        if self.q_lo is not None and self.q_lo.size != n_reads:
+            raise ValueError(f"q_lo / q_eq have {self.q_lo.size} entries for {n_reads} reads")
+        p = lambda a: None if a is None else a.ctypes.data
+        return N.SeedSkipHost(self.flag, 0 if self.ref_rank is None else self.ref_rank.size, p(self.ref_rank), p(self.ref_len), p(self.q_lo), p(self.q_eq))
+
+
+def _seed_args(match_off, matches, qlen):
+    mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64))
+    m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+    q = np.ascontiguousarray(qlen, dtype=np.int32)
+    n_reads = mo.size - 1
+    if q.size != n_reads or mo[-1] > m.size or mo[0] < 0:
+        raise ValueError("offsets do not fit the arrays")
+    return mo, m, q, n_reads, max(int(m["n"][mo[0]:mo[-1]].sum()), 1)
+
+
+def seed_hits_batch_skip(match_off, matches, hits, qlen, skip: SeedSkip):
+    """mm2c_seed_hits_batch_host_skip: collect_seed_hits with skip_seed.  Returns (anchor_off int64 [n_reads+1] of the KEPT anchors, anchors uint64 [kept, 2])"""
+    mo, m, q, n_reads, cap = _seed_args(match_off, matches, qlen)
+    sk = skip._native(n_reads)
+    h = np.ascontiguousarray(hits, dtype=np.uint64)
+    ao = np.zeros(n_reads + 1, np.int64)
+    a = np.zeros((cap, 2), np.uint64)
+    N.check(N.load().mm2c_seed_hits_batch_host_skip(n_reads, _np_ptr(mo), _np_ptr(m), _np_ptr(h), h.size, _np_ptr(q), C.byref(sk), _np_ptr(ao), _np_ptr(a)),
+            "mm2c_seed_hits_batch_host_skip")
+    return ao, a[:ao[-1]]
+
+
+def seed_chain_batch_skip(params: Params, min_cnt, min_sc, match_off, matches, hits, qlen, skip: SeedSkip):
+    """mm2c_seed_chain_batch_host_skip: seed_chain_batch with skip_seed.  Returns (anchor_off of the kept anchors, [(u, b), ...])"""
+    mo, m, q, n_reads, cap = _seed_args(match_off, matches, qlen)
+    sk = skip._native(n_reads)
+    h = np.ascontiguousarray(hits, dtype=np.uint64)
+    ao = np.zeros(n_reads + 1, np.int64); u_off = np.zeros(n_reads + 1, np.int64); b_off = np.zeros(n_reads + 1, np.int64)
+    u = np.zeros(cap, np.uint64); b = np.zeros((cap, 2), np.uint64)
+    N.check(N.load().mm2c_seed_chain_batch_host_skip(C.byref(params), min_cnt, min_sc, n_reads, _np_ptr(mo), _np_ptr(m), _np_ptr(h), h.size, _np_ptr(q), C.byref(sk),
+                                                     _np_ptr(ao), _np_ptr(u_off), _np_ptr(u), _np_ptr(b_off), _np_ptr(b)), "mm2c_seed_chain_batch_host_skip")
+    return ao, _split_chains(n_reads, u_off, u, b_off, b)
+
+
 class HitPool:
     """mm2c_hitpool_t: the index's position arrays resident in HBM (uploaded once per index)"""
 
@@ -468,6 +538,17 @@ def seed_chain_batch_pool(params: Params, min_cnt, min_sc, match_off, matches, p
     N.check(lib.mm2c_seed_chain_batch_pool(C.byref(params), min_cnt, min_sc, n_reads, _np_ptr(mo), _np_ptr(m), pool.handle, _np_ptr(q),
                                            _np_ptr(ao), _np_ptr(u_off), _np_ptr(u), _np_ptr(b_off), _np_ptr(b)), "mm2c_seed_chain_batch_pool")
     return _split_chains(n_reads, u_off, u, b_off, b)
+
+
+def seed_chain_batch_pool_skip(params: Params, min_cnt, min_sc, match_off, matches, pool: HitPool, qlen, skip: SeedSkip):
+    """mm2c_seed_chain_batch_pool_skip: seed_chain_batch_skip with the hits taken from a resident pool"""
+    mo, m, q, n_reads, cap = _seed_args(match_off, matches, qlen)
+    sk = skip._native(n_reads)
+    ao = np.zeros(n_reads + 1, np.int64); u_off = np.zeros(n_reads + 1, np.int64); b_off = np.zeros(n_reads + 1, np.int64)
+    u = np.zeros(cap, np.uint64); b = np.zeros((cap, 2), np.uint64)
+    N.check(N.load().mm2c_seed_chain_batch_pool_skip(C.byref(params), min_cnt, min_sc, n_reads, _np_ptr(mo), _np_ptr(m), pool.handle, _np_ptr(q), C.byref(sk),
+                                                     _np_ptr(ao), _np_ptr(u_off), _np_ptr(u), _np_ptr(b_off), _np_ptr(b)), "mm2c_seed_chain_batch_pool_skip")
+    return ao, _split_chains(n_reads, u_off, u, b_off, b)
 
 
 def stage_stats(reset=False):

@@ -3,8 +3,10 @@
 seed-hit path on batches that have FEWER tasks than the GPU has wave slots, at the anchor density of the bench's ava-ont stream (20 000 anchors in a
 400 kb locus = 50 per kb: locus = 20 x anchors per read; -x ava-ont scalars, options.c:83-86).
 
-usage: python tools/long_reads.py [--sizes 2048x100000,1024x300000,256x1000000] [--routes auto,one-wave,coop16,coop8] [--no-seed] [--distinct N] [--profile mixed]
-Every route's f / p of the first distinct reads are compared with the CPU oracle; one line per (size, route).  bench.py imports measure() for its `long_reads` leg."""
+usage: python tools/long_reads.py [--sizes 2048x100000,1024x300000,256x1000000] [--routes auto,one-wave,coop16,coop8] [--no-seed] [--skip] [--distinct N] [--profile mixed]
+Every route's f / p of the first distinct reads are compared with the CPU oracle; one line per (size, route).  bench.py imports measure() for its `long_reads` leg.
+--skip adds the seed-hit path under skip_seed as -x ava-ont runs it (measure_skip): the hits spread over 64 references as long as the reads, read r named as reference
+r % 64, flag NO_DIAG | NO_DUAL -- once with the long reads expanded on sixteen waves (MM2C_MW_SORT=1) and once on one (=0), every distinct read against the oracle."""
 import argparse
 import os
 import sys
@@ -76,18 +78,9 @@ def measure(reads, per, routes=("auto",), dp=True, seed=True, reps=3, check=2, p
         set_route("auto")
         del d_f, d_p
     if seed:
-        # matches -> sorted anchors: matches derived from the same reads (one match per query position, hits = the anchors at that position)
-        ms_, hs_, mo_, ao_ = [], [], [0], [0]
-        for k in range(distinct):
-            m_k, h_k = synth.matches_from_anchors(a1_h[off1_h[k]:off1_h[k + 1]], QLEN)
-            m_k["cr_off"] += ao_[-1]
-            ms_.append(m_k); hs_.append(h_k); mo_.append(mo_[-1] + m_k.size); ao_.append(ao_[-1] + h_k.size)
-        m1_, h1_ = np.concatenate(ms_), np.concatenate(hs_)
-        mt_ = np.tile(m1_, times); mt_["cr_off"] += np.repeat(np.arange(times, dtype=np.int64) * h1_.size, m1_.size)
-        mo_t = np.concatenate([[0], np.tile(np.diff(mo_), times).cumsum()]).astype(np.int64)
-        ao_t = np.concatenate([[0], np.tile(np.diff(ao_), times).cumsum()]).astype(np.int64)
+        ms_, hs_, mo_, ao_, mt_, ht_, mo_t, ao_t = _seed_batch(a1_h, off1_h, distinct, times)
         sp = mm2chain.SeedPlan(mo_t, ao_t)
-        d_m = torch.from_numpy(mt_.view(np.uint8)).cuda(); d_h = torch.from_numpy(np.tile(h1_, times).view(np.int64)).cuda()
+        d_m = torch.from_numpy(mt_.view(np.uint8)).cuda(); d_h = torch.from_numpy(ht_.view(np.int64)).cuda()
         d_q = torch.full((n_tasks,), QLEN, dtype=torch.int32, device="cuda")
         d_as = sp.run(d_m, d_h, d_q)
         sms = []
@@ -111,6 +104,88 @@ def measure(reads, per, routes=("auto",), dp=True, seed=True, reps=3, check=2, p
     return out
 
 
+def _seed_batch(a1_h, off1_h, distinct, times, n_refs=0):
+    """matches -> sorted anchors: matches derived from the reads (one match per query position, hits = the anchors at that position), the distinct reads replicated
+    `times` times; n_refs > 0: the hits' reference ids spread over that many references.  Returns the per-read matches / hits of the distinct reads with their
+    offsets, and the replicated batch (matches, hits, match offsets, hit offsets)"""
+    rng = np.random.default_rng(64)
+    ms_, hs_, mo_, ao_ = [], [], [0], [0]
+    for k in range(distinct):
+        m_k, h_k = synth.matches_from_anchors(a1_h[off1_h[k]:off1_h[k + 1]], QLEN)
+        if n_refs:
+            h_k = (h_k & np.uint64(0xffffffff)) | (rng.integers(0, n_refs, h_k.size).astype(np.uint64) << np.uint64(32))
+        m_k["cr_off"] += ao_[-1]
+        ms_.append(m_k); hs_.append(h_k); mo_.append(mo_[-1] + m_k.size); ao_.append(ao_[-1] + h_k.size)
+    m1_, h1_ = np.concatenate(ms_), np.concatenate(hs_)
+    mt_ = np.tile(m1_, times); mt_["cr_off"] += np.repeat(np.arange(times, dtype=np.int64) * h1_.size, m1_.size)
+    mo_t = np.concatenate([[0], np.tile(np.diff(mo_), times).cumsum()]).astype(np.int64)
+    ao_t = np.concatenate([[0], np.tile(np.diff(ao_), times).cumsum()]).astype(np.int64)
+    return ms_, hs_, mo_, ao_, mt_, np.tile(h1_, times), mo_t, ao_t
+
+
+N_REFS = 64
+
+
+def measure_skip(reads, per, reps=3, profile="mixed", distinct=0, say=None):
+    """the seed-hit path of one size under skip_seed as -x ava-ont runs it (NO_DIAG | NO_DUAL): hits over N_REFS references of the reads' length, read r named as
+    reference r % N_REFS (so about half of every read's hits name a reference below it and are dropped, and the diagonal goes).  Long reads on sixteen waves
+    (MM2C_MW_SORT=1) and on one (=0): ms, hits/s, how many reads took the sixteen-wave expansion, the share of hits kept and whether every distinct read's anchors
+    equal the oracle's collect_seed_hits with the same flags."""
+    say = say or (lambda *a: None)
+    distinct = distinct or max(2, min(reads, 3_200_000 // per))
+    times = max(1, reads // distinct)
+    off1, a1 = synth.make_stream(profile, distinct, per, seed=11, device="cuda", locus=20 * per)   # the reads of measure()'s seed leg
+    a1_h = a1.cpu().numpy().view(np.uint64); off1_h = off1.numpy()
+    del a1
+    ms_, hs_, mo_, ao_, mt_, ht_, mo_t, ao_t = _seed_batch(a1_h, off1_h, distinct, times, n_refs=N_REFS)
+    n_reads = mo_t.size - 1
+    flag = ob.F_NO_DIAG | ob.F_NO_DUAL
+    ref_rank = np.arange(N_REFS, dtype=np.int32); ref_len = np.full(N_REFS, QLEN, np.int32)
+    q_lo = (np.arange(n_reads) % N_REFS).astype(np.int32); q_eq = np.ones(n_reads, np.int32)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    d_m = torch.from_numpy(mt_.view(np.uint8)).cuda(); d_h = torch.from_numpy(ht_.view(np.int64)).cuda()
+    d_q = torch.full((n_reads,), QLEN, dtype=torch.int32, device="cuda")
+    d_rr, d_rl, d_lo, d_eq = dev(ref_rank), dev(ref_len), dev(q_lo), dev(q_eq)
+    hits = int(ao_t[-1])
+    out = {"reads": n_reads, "hits_per_read": per, "hits": hits, "distinct_reads": distinct, "flag": flag, "refs": N_REFS}
+    say(f"== skip_seed (NO_DIAG | NO_DUAL): {n_reads} reads x {per} hits = {hits} hits ({distinct} distinct), {N_REFS} references")
+    old = os.environ.get("MM2C_MW_SORT")
+    try:
+        for mw in ("1", "0"):
+            os.environ["MM2C_MW_SORT"] = mw                                     # read when a seed plan is made
+            sp = mm2chain.SeedPlan(mo_t, ao_t)
+            d_as, d_off = sp.run_skip(d_m, d_h, d_q, flag, d_rr, d_rl, d_lo, d_eq)
+            sms = []
+            for _ in range(reps):
+                d_as, d_off = sp.run_skip(d_m, d_h, d_q, flag, d_rr, d_rl, d_lo, d_eq, anchors=d_as)
+                torch.cuda.synchronize()
+                sms.append(sp.last_ms())
+            sp.check()
+            n_mw = sp.last_expand_mw()
+            off_h = d_off.cpu().numpy()
+            got = d_as[: int(off_h[distinct])].cpu().numpy().view(np.uint64)
+            ok = True
+            for k in range(distinct):
+                mk = ms_[k].copy(); mk["cr_off"] -= ao_[k]
+                ref = ob.collect_seed_hits(mk, hs_[k], QLEN, flag, ref_rank, ref_len, int(q_lo[k]), int(q_eq[k]))
+                ok = ok and np.array_equal(got[off_h[k]:off_h[k + 1]], ref)
+            s_ms = min(sms)
+            kept = int(off_h[-1])
+            out[f"mw_sort={mw}"] = {"ms": round(s_ms, 3), "value": hits / (s_ms * 1e-3), "unit": "hits/s", "reads_expanded_on_16_waves": n_mw,
+                                    "kept_share": round(kept / hits, 4), "identical_to_oracle": bool(ok)}
+            say(f"seed hits with skip_seed, MM2C_MW_SORT={mw}: {s_ms:9.2f} ms = {hits / (s_ms * 1e-3) / 1e9:6.3f} G hits/s  (all runs {[round(m, 2) for m in sms]})  "
+                f"reads on 16 waves {n_mw}; kept {kept} of {hits} hits ({kept / hits:.3f}); identical to the oracle ({distinct} distinct reads): {bool(ok)}")
+            sp.close(); del d_as, d_off
+    finally:
+        if old is None:
+            os.environ.pop("MM2C_MW_SORT", None)
+        else:
+            os.environ["MM2C_MW_SORT"] = old
+    del d_m, d_h
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048x100000,1024x300000,256x1000000")
@@ -119,6 +194,7 @@ def main():
     ap.add_argument("--distinct", type=int, default=0, help="distinct reads generated per size (0: about 3.2e6 anchors' worth, at least 2)")
     ap.add_argument("--no-seed", action="store_true")
     ap.add_argument("--no-dp", action="store_true")
+    ap.add_argument("--skip", action="store_true", help="also the seed-hit path under skip_seed (NO_DIAG | NO_DUAL), long reads on sixteen waves and on one")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--check", type=int, default=2, help="reads per size compared with the oracle")
     args = ap.parse_args()
@@ -129,6 +205,8 @@ def main():
         reads, per = (int(v) for v in spec.split("x"))
         measure(reads, per, routes=args.routes.split(","), dp=not args.no_dp, seed=not args.no_seed, reps=args.reps, check=args.check, profile=args.profile,
                 distinct=args.distinct, say=lambda *a: print(*a, flush=True))
+        if args.skip:
+            measure_skip(reads, per, reps=args.reps, profile=args.profile, distinct=args.distinct, say=lambda *a: print(*a, flush=True))
     mm2chain.shutdown()
 
 
