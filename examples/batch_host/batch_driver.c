@@ -56,9 +56,11 @@ static void defaults(mm_idxopt_t *io, mm_mapopt_t *mo)               /* as drive
  * table type comes from the reference's khash.h through the macro index.c itself uses (index.c:20). */
 __KHASH_TYPE(idx, uint64_t, uint64_t)
 typedef struct { mm128_v a; int32_t n; uint64_t *p; void *h; } idx_bucket_t;
-typedef struct { int64_t *base_p, *base_v, n; mm2c_hitpool_t *dev; } pool_t;
+typedef struct { int64_t *base_p, *base_v, n; mm2c_hitpool_t *dev; mm2c_minidx_t *idx; } pool_t;
 
-static int pool_build(const mm_idx_t *mi, pool_t *pl)
+/* with_keys (MM2_BATCH_GPU_SKETCH=1): the same walk also rebuilds every minimizer of the index from its bucket and its table key -- (kh_key >> 1) << b | bucket,
+ * the rows index.c:89-97 looks up -- with (offset into the pool, n) beside it, and puts that key table on the GPU (mm2c_minidx_create) for the device lookups */
+static int pool_build(const mm_idx_t *mi, pool_t *pl, int with_keys)
 {
 	const idx_bucket_t *B = (const idx_bucket_t *)mi->B;
 	const int nb = 1 << mi->b;
@@ -78,6 +80,29 @@ static int pool_build(const mm_idx_t *mi, pool_t *pl)
 	}
 	pl->dev = mm2c_hitpool_create(host, pl->n);
 	free(host);
+	if (pl->dev && with_keys) {
+		int64_t n_keys = 0, k = 0;
+		uint64_t *keys;
+		int64_t *cr;
+		uint32_t *cnt;
+		for (i = 0; i < nb; ++i) if (B[i].h) n_keys += ((const kh_idx_t *)B[i].h)->size;
+		keys = (uint64_t *)malloc((size_t)(n_keys + 1) * 8); cr = (int64_t *)malloc((size_t)(n_keys + 1) * 8); cnt = (uint32_t *)malloc((size_t)(n_keys + 1) * 4);
+		for (i = 0; i < nb; ++i) {
+			const kh_idx_t *h = (const kh_idx_t *)B[i].h;
+			khint_t j;
+			if (!h) continue;
+			for (j = 0; j < h->n_buckets; ++j) {
+				if (!kh_exist(h, j)) continue;
+				keys[k] = (h->keys[j] >> 1) << mi->b | (uint64_t)i;
+				if (h->keys[j] & 1) { cnt[k] = 1; cr[k] = pl->base_v[i] + j; }                      /* one occurrence: the hit is the value itself */
+				else { cnt[k] = (uint32_t)h->vals[j]; cr[k] = pl->base_p[i] + (int64_t)(h->vals[j] >> 32); }
+				++k;
+			}
+		}
+		pl->idx = mm2c_minidx_create(pl->dev, mi->k, mi->w, mi->flag & MM_I_HPC, k, keys, cr, cnt);
+		free(keys); free(cr); free(cnt);
+		if (!pl->idx) return -1;
+	}
 	return pl->dev ? 0 : -1;
 }
 
@@ -89,7 +114,7 @@ static inline int64_t pool_offset(const mm_idx_t *mi, const pool_t *pl, uint64_t
 	return pl->base_v[i] + (cr - ((const kh_idx_t *)b->h)->vals);
 }
 
-static void pool_free(pool_t *pl) { mm2c_hitpool_destroy(pl->dev); free(pl->base_p); free(pl->base_v); memset(pl, 0, sizeof(*pl)); }
+static void pool_free(pool_t *pl) { mm2c_minidx_destroy(pl->idx); mm2c_hitpool_destroy(pl->dev); free(pl->base_p); free(pl->base_v); memset(pl, 0, sizeof(*pl)); }
 
 typedef struct {
 	uint32_t hash;
@@ -118,6 +143,7 @@ typedef struct {
 	/* batch arrays (in bf) */
 	int64_t *match_off, *hit_off, *anchor_off, *u_off, *b_off;
 	mm2c_match_t *matches; uint64_t *hits, *u; mm2c_anchor_t *b; int32_t *qlen;
+	int64_t *seq_off; uint8_t *bases;   /* MM2_BATCH_GPU_SKETCH=1: the mini-batch's sequences, what crosses PCIe instead of the matches */
 } batch_t;
 
 /* stage A, per read: map.c:281-295 up to the point where the anchors would be made */
@@ -166,6 +192,23 @@ static void seed_one(void *data, long i, int tid)
 	}
 	r->rep_len += rep_en - rep_st;
 	kfree(km, mv.a);
+}
+
+/* stage A with the sketch and the lookups on the GPU (MM2_BATCH_GPU_SKETCH=1): only the name hash stays on the host (map.c:285-287); the bases go
+ * into one array.  A read that the reference would skip (map.c:282-283) goes in with length 0: no minimizers, no chains. */
+static void hash_one(void *data, long i, int tid)
+{
+	batch_t *bt = (batch_t *)data;
+	const mm_mapopt_t *opt = bt->opt;
+	mm_bseq1_t *t = &bt->seq[i];
+	read_t *r = &bt->rd[i];
+	(void)tid;
+	memset(r, 0, sizeof(*r));
+	if (bt->seq_off[i + 1] > bt->seq_off[i]) memcpy(bt->bases + bt->seq_off[i], t->seq, (size_t)(bt->seq_off[i + 1] - bt->seq_off[i]));
+	if (t->l_seq == 0 || (opt->max_qlen > 0 && t->l_seq > opt->max_qlen)) return;
+	r->hash = t->name ? __ac_X31_hash_string(t->name) : 0;
+	r->hash ^= __ac_Wang_hash(t->l_seq) + __ac_Wang_hash(opt->seed);
+	r->hash = __ac_Wang_hash(r->hash);
 }
 
 /* stage A', per read: its matches and hits into the batch arrays (a host that kept the index's position arrays on the GPU would
@@ -223,7 +266,8 @@ static void post_one(void *data, long i, int tid)
  * the steps of consecutive mini-batches overlap, so the GPU call of one batch hides behind the seeding of the next */
 typedef struct {
 	const mm_idx_t *mi; const mm_mapopt_t *opt; mm_bseq_file_t *fp; mm2c_params_t par; int n_threads;
-	pool_t ipool; int use_pool, pageable_out;
+	pool_t ipool; int use_pool, pageable_out, gpu_sketch;
+	mm2c_read_result_t *res;      /* MM2_BATCH_GPU_SKETCH=1: the library's result object, reused by every mini-batch (step 3 runs one mini-batch at a time) */
 	kstring_t str;
 	void **km;
 	bufs_t pool[6];
@@ -248,12 +292,23 @@ static void *pipeline_step(void *shared, int step, void *in)
 		batch_t *bt = (batch_t *)in;
 		bt->rd = (read_t *)calloc((size_t)bt->n, sizeof(read_t));
 		bt->km = sh->km; bt->pool = sh->use_pool ? &sh->ipool : 0;
-		kt_for(sh->n_threads, seed_one, bt, bt->n);
+		if (sh->gpu_sketch) {
+			int i;
+			bt->seq_off = (int64_t *)malloc((size_t)(bt->n + 1) * 8);
+			bt->seq_off[0] = 0;
+			for (i = 0; i < bt->n; ++i) {
+				const int l = bt->seq[i].l_seq;
+				bt->seq_off[i + 1] = bt->seq_off[i] + (l == 0 || (mo->max_qlen > 0 && l > mo->max_qlen) ? 0 : l);
+			}
+			bt->bases = (uint8_t *)malloc((size_t)bt->seq_off[bt->n] + 1);
+			kt_for(sh->n_threads, hash_one, bt, bt->n);
+		} else kt_for(sh->n_threads, seed_one, bt, bt->n);
 		sh->t_seed += realtime() - tt;
 		return bt;
 	} else if (step == 2) {                                                                        /* pack: the matches of all reads into one page-locked array */
 		batch_t *bt = (batch_t *)in;
 		int i;
+		if (sh->gpu_sketch) return bt;                                                             /* nothing to pack: the bases are the batch */
 		int64_t n_m = 0, n_h = 0;
 		for (i = 0; i < bt->n; ++i) { n_m += bt->rd[i].n_m; n_h += bt->rd[i].n_a; }
 		{	/* a free set of page-locked buffers, grown if this mini-batch is bigger than the ones it served before */
@@ -296,6 +351,27 @@ static void *pipeline_step(void *shared, int step, void *in)
 		return bt;
 	} else if (step == 3) {                                                                        /* chain the batch, post all */
 		batch_t *bt = (batch_t *)in;
+		if (sh->gpu_sketch) {                                                                      /* reads in, chains out */
+			const mm2c_read_result_t *res = sh->res;
+			int i;
+			if (mm2c_read_chain_batch(&sh->par, mo->min_cnt, mo->min_chain_score, sh->ipool.idx, mo->mid_occ, bt->n, bt->seq_off, bt->bases, 0, sh->res) != 0) {
+				fprintf(stderr, "ERROR: %s\n", mm2c_last_error()); exit(1);
+			}
+			free(bt->seq_off); free(bt->bases); bt->seq_off = 0; bt->bases = 0;
+			bt->u_off = res->u_off; bt->u = res->u; bt->b_off = res->b_off; bt->b = res->b;
+			for (i = 0; i < bt->n; ++i) {                                                          /* what mm_est_err / mm_set_mapq read (map.c:360,364) */
+				read_t *r = &bt->rd[i];
+				r->rep_len = res->rep_len[i];
+				r->n_mini_pos = (int32_t)(res->mini_off[i + 1] - res->mini_off[i]);
+				r->mini_pos = (uint64_t *)malloc((size_t)(r->n_mini_pos + 1) * 8);
+				if (r->n_mini_pos) memcpy(r->mini_pos, res->mini_pos + res->mini_off[i], (size_t)r->n_mini_pos * 8);
+			}
+			sh->t_gpu += realtime() - tt; sh->tot_anchors += res->n_anchors; sh->tot_reads += bt->n;
+			tt = realtime();
+			kt_for(sh->n_threads, post_one, bt, bt->n);
+			sh->t_post += realtime() - tt;
+			return bt;
+		}
 		const int64_t n_h = bt->hit_off[bt->n];
 		if ((sh->use_pool ? mm2c_seed_chain_batch_pool(&sh->par, mo->min_cnt, mo->min_chain_score, bt->n, bt->match_off, bt->matches, sh->ipool.dev, bt->qlen,
 		                                               bt->anchor_off, bt->u_off, bt->u, bt->b_off, bt->b)
@@ -326,7 +402,7 @@ static void *pipeline_step(void *shared, int step, void *in)
 			if (bt->seq[i].comment) free(bt->seq[i].comment);
 		}
 		free(bt->seq); free(bt->rd);
-		bt->bf->busy = 0;
+		if (bt->bf) bt->bf->busy = 0;
 		free(bt);
 		sh->t_out += realtime() - tt;
 	}
@@ -367,9 +443,13 @@ int main(int argc, char *argv[])
 		sh.mi = mi; sh.opt = &mo; sh.n_threads = n_threads;
 		sh.use_pool = !(getenv("MM2_BATCH_HOSTPOOL") && atoi(getenv("MM2_BATCH_HOSTPOOL")));
 		sh.pageable_out = !(getenv("MM2_BATCH_PINNED_OUT") && atoi(getenv("MM2_BATCH_PINNED_OUT")));   /* default: plain memory for the chains */
+		/* MM2_BATCH_GPU_SKETCH=1: mm_sketch and the lookups of collect_matches on the GPU as well (reads in, chains out); needs the resident pool */
+		sh.gpu_sketch = getenv("MM2_BATCH_GPU_SKETCH") && atoi(getenv("MM2_BATCH_GPU_SKETCH"));
+		if (sh.gpu_sketch && !sh.use_pool) { fprintf(stderr, "ERROR: MM2_BATCH_GPU_SKETCH=1 needs the resident pool (not MM2_BATCH_HOSTPOOL=1)\n"); return 1; }
+		if (sh.gpu_sketch && !sh.res) sh.res = mm2c_read_result_create();
 		if (sh.use_pool) {
 			double tp = realtime();
-			if (pool_build(mi, &sh.ipool) != 0) { fprintf(stderr, "ERROR: %s\n", mm2c_last_error()); return 1; }
+			if (pool_build(mi, &sh.ipool, sh.gpu_sketch) != 0) { fprintf(stderr, "ERROR: %s\n", mm2c_last_error()); return 1; }
 			t_pool += realtime() - tp;
 			fprintf(stderr, "[mm2_batchhost] position arrays of the index resident on the GPU: %lld entries (%.1f MB), %.2f s\n", (long long)sh.ipool.n, sh.ipool.n * 8e-6, realtime() - tp);
 		}
@@ -383,6 +463,7 @@ int main(int argc, char *argv[])
 		tt = realtime();
 	}
 	free(sh.str.s);
+	mm2c_read_result_free(sh.res);
 	mm_idx_reader_close(rd);
 	fprintf(stderr, "[mm2_batchhost] stages (summed over mini-batches, they overlap): index %.2f s, read %.2f, seed all %.2f, pack %.2f, GPU call %.2f, post all %.2f, output %.2f\n",
 	        t_idx, sh.t_read, sh.t_seed, sh.t_pack, sh.t_gpu, sh.t_post, sh.t_out);
@@ -395,6 +476,13 @@ int main(int argc, char *argv[])
 		        "blocked %.3f; device (chunks overlap): upload %.3f, seed hits %.3f, DP %.3f, epilogue %.3f, offsets down %.3f; index pool upload %.2f s\n",
 		        (unsigned long long)st.calls, (unsigned long long)st.chunks, st.total_ns * 1e-9, st.setup_ns * 1e-9, st.alloc_ns * 1e-9, (unsigned long long)st.n_alloc,
 		        st.free_ns * 1e-9, (unsigned long long)st.n_free, st.wait_ns * 1e-9, st.h2d_ns * 1e-9, st.seed_ns * 1e-9, st.dp_ns * 1e-9, st.epi_ns * 1e-9, st.d2h_ns * 1e-9, t_pool);
+	}
+	if (sh.gpu_sketch) {
+		mm2c_sketch_stats_t ks;
+		mm2c_get_sketch_stats(&ks);
+		fprintf(stderr, "[mm2_batchhost] sketch and lookups on the device (mm2c_get_sketch_stats): %llu calls in %llu chunks, %llu bases, %llu minimizers, %llu matches; "
+		        "device: bases up %.3f s, sketch %.3f s, lookups %.3f s\n", (unsigned long long)ks.calls, (unsigned long long)ks.chunks, (unsigned long long)ks.bases,
+		        (unsigned long long)ks.minimizers, (unsigned long long)ks.matches, ks.h2d_ns * 1e-9, ks.sketch_ns * 1e-9, ks.lookup_ns * 1e-9);
 	}
 	tt = realtime();
 	mm2c_shutdown();

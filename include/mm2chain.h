@@ -389,6 +389,68 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
                                     const mm2c_seed_skip_host_t *skip,
                                     int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b);
 
+/* ---- reads in: mm_sketch (sketch.c:77-143) and collect_matches (map.c:90-123) on the device ------------------------------
+ * Reads are raw bytes, concatenated: read r is seq[seq_off[r] .. seq_off[r+1]) (seq_off: n_reads + 1 entries, seq_off[0] = 0, monotone).  Every byte value is
+ * legal; the nucleotide table of sketch.c:9-26 applies.  A read of length 0 has no minimizers.  Every read is ONE segment with rid 0, as collect_minimizers
+ * (map.c:64-77) with n_segs = 1.  Results are bit for bit those of the reference, in its order (minimizers, matches, mini_pos).
+ * Out of scope here -- a host that needs one of these keeps its own sketching for those reads:
+ *   - SDUST masking (sdust_thres > 0, map.c:73-74; no preset sets it, options.c:22);
+ *   - reads of several segments (n_segs > 1, --frag);
+ *   - building the index (the host builds it and hands its key table to mm2c_minidx_create);
+ *   - alignment;
+ *   - the max_occ re-chaining of map.c:318-340 (max_occ is never set by this reference's options). */
+
+/* A minimizer index resident on every configured device (as mm2c_hitpool_create keeps the pool): one row per indexed minimizer, keys[i] = the minimizer
+ * (mm128_t.x >> 8), its hits pool[cr_off[i] .. cr_off[i] + n[i]).  A lookup returns exactly what mm_idx_get (index.c:81-98) returns: (cr_off, n) for a key that
+ * is present, n = 0 for an absent one.  MM2C_E_ARG (NULL returned, mm2c_last_error says why): k outside 1..28, w outside 1..255, a duplicate key,
+ * a key >= 2^(2k), an offset + n outside the pool.  A minimap2 host rebuilds each key from its hash buckets: (kh_key >> 1) << b | bucket; a kh_key & 1 row
+ * has n = 1 and its one hit in the value (put it into the pool). */
+typedef struct mm2c_minidx mm2c_minidx_t;
+mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int is_hpc, int64_t n_keys, const uint64_t *keys,
+                                  const int64_t *cr_off, const uint32_t *n);
+void mm2c_minidx_destroy(mm2c_minidx_t *idx);                                    /* not while a call that uses it is running */
+/* the lookups on their own (tests): n_q keys in, (cr_off, n) out, on the primary device */
+int mm2c_minidx_lookup(const mm2c_minidx_t *idx, int64_t n_q, const uint64_t *keys, int64_t *cr_off, uint32_t *n);
+
+/* Results of the reads-in entries: LIBRARY-OWNED and reusable (the counts are only known once the device has run).  Create one, hand it to as many calls
+ * as you like (each overwrites it; the arrays stay valid until the next call on the same object or mm2c_read_result_free).  Fields an entry does not fill
+ * have count 0.  Offsets have n_reads + 1 entries. */
+typedef struct {
+	int64_t n_reads;
+	/* mm2c_sketch_batch: the mm128_t list mm_sketch appends per read, x = hash << 8 | span, y = pos << 1 | strand (rid 0) */
+	int64_t n_sketch; int64_t *sketch_off; mm2c_anchor_t *sketch;
+	/* mm2c_sketch_match_batch: collect_matches per read -- matches in minimizer order, their anchor counts' prefix sums */
+	int64_t n_matches; int64_t *match_off; mm2c_match_t *matches;
+	/* both reads-in entries: anchor_off (mm2c_sketch_match_batch: sum of n per read; mm2c_read_chain_batch: the anchors each read KEPT), rep_len per read
+	 * (map.c:104-110,120) and mini_pos per read (q_span << 32 | q_pos >> 1 of every kept match, what mm_est_err / mm_set_mapq read) */
+	int64_t n_anchors; int64_t *anchor_off;
+	int32_t *rep_len;
+	int64_t n_mini_pos; int64_t *mini_off; uint64_t *mini_pos;
+	/* mm2c_read_chain_batch: what mm_chain_dp returns per read, as mm2c_mm_chain_dp_batch_host lays it out */
+	int64_t n_u, n_b; int64_t *u_off; uint64_t *u; int64_t *b_off; mm2c_anchor_t *b;
+	void *priv;
+} mm2c_read_result_t;
+mm2c_read_result_t *mm2c_read_result_create(void);
+void mm2c_read_result_free(mm2c_read_result_t *res);
+
+/* mm_sketch for every read of a batch with w (1..255), k (1..28), is_hpc (MM_I_HPC) -> res->sketch_off / sketch.  This entry and mm2c_sketch_match_batch take the
+ * batch in one pass: about 20 bytes of device memory per base (a host with more bases than that calls them per mini-batch; mm2c_read_chain_batch chunks itself). */
+int mm2c_sketch_batch(int k, int w, int is_hpc, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res);
+/* reads in, matches out: mm_sketch with the index's k / w / is_hpc, then collect_matches with max_occ = mid_occ.  Every minimizer with t < mid_occ gives a
+ * match, t = 0 included; is_tandem compares with the neighbours in the unfiltered list; cr_off points into the index's pool.  Fills match_off / matches,
+ * anchor_off, rep_len, mini_off / mini_pos (the sketch fields stay empty). */
+int mm2c_sketch_match_batch(const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res);
+/* reads in, chains out: sketch -> matches -> seed hits -> DP -> epilogue on the device, in chunks of whole reads ("read_chunk_bases", mm2c_tune, default
+ * 2^27 bases); per chunk only the per-read counts come back before the chains.  par / min_cnt / min_sc as mm2c_seed_chain_batch_pool; skip as
+ * mm2c_seed_chain_batch_pool_skip (NULL: no skip_seed); mm2c_tune("heap_sort", 1) applies.  Fills anchor_off, u_off / u, b_off / b, rep_len,
+ * mini_off / mini_pos; the results equal mm2c_seed_chain_batch_pool(_skip) fed the matches of mm2c_sketch_match_batch. */
+int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads,
+                          const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip, mm2c_read_result_t *res);
+/* device time of the sketch and of the lookups (HIP events around them, summed since mm2c_init or the last reset), and what they processed */
+typedef struct { uint64_t calls, chunks, bases, minimizers, matches, h2d_ns, sketch_ns, lookup_ns; } mm2c_sketch_stats_t;
+void mm2c_get_sketch_stats(mm2c_sketch_stats_t *out);
+void mm2c_reset_sketch_stats(void);
+
 /* ---- anchor streams on disk (csrc/anchor_stream.c documents the layout) ------------------------ */
 typedef struct {
 	mm2c_params_t par;            /* scalars of the mm_chain_dp calls the tasks came from */

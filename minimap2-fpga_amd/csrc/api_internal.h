@@ -82,6 +82,7 @@ struct Global {
 	uint64_t epoch = 0;                     // bumped by shutdown so stale thread-local pointers are dropped
 };
 extern Global G;
+extern std::atomic<int64_t> read_chunk_bases;   // mm2c_read_chain_batch: bases per chunk of whole reads (mm2c_tune("read_chunk_bases"); mm2chain_sketch.cpp)
 // mm2c_init_async: the initialisation runs on a thread of its own while the host does something else (a minimap2 host loads its index, main.c:371-399, before the
 // first chaining call); every entry that needs the device joins that thread first.  async_init_join is a no-op when none is pending and on the thread itself.
 void async_init_join();

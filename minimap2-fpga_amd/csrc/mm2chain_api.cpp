@@ -800,6 +800,11 @@ int mm2c_tune(const char *key, int value)
 		G.noskip_loop = value;
 		return 0;
 	}
+	if (strcmp(key, "read_chunk_bases") == 0) {              // mm2c_read_chain_batch: bases per chunk of whole reads
+		if (value < 1) return fail(MM2C_E_ARG, "read_chunk_bases must be >= 1");
+		read_chunk_bases = value;
+		return 0;
+	}
 	if (strcmp(key, "heap_sort") == 0) {
 		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "heap_sort must be 0 or 1");
 		G.heap_sort = value;

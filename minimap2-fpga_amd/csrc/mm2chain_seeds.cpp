@@ -759,4 +759,8 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
 
 } // extern "C"
 
-namespace mm2c_api { void seedplan_destroy_synced(mm2c_seedplan_t *pl) { seedplan_destroy_impl(pl, false); } }
+namespace mm2c_api {
+void seedplan_destroy_synced(mm2c_seedplan_t *pl) { seedplan_destroy_impl(pl, false); }
+const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device) { return hp ? pool_on(hp, device) : nullptr; }   // the reads-in entries (mm2chain_sketch.cpp)
+int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool) { return check_skip(skip, n_reads, nullptr, nullptr, nullptr, pool->n, pool); }
+}

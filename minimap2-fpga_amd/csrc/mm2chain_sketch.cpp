@@ -1,0 +1,533 @@
+// Reads in: the minimizer index resident on the devices, the reads-in entries (mm2c_sketch_batch, mm2c_sketch_match_batch, mm2c_read_chain_batch) and their
+// library-owned result object.  The kernels are in sketch.hip; the seed hits, the DP and the epilogue are the seed / chain plans of the matches-in path.
+#include "api_internal.h"
+
+using namespace mm2c_api;
+
+namespace mm2c_api {
+int sketch_count(const uint8_t *seq, const int64_t *seq_off, const int64_t *chunk_off, const int64_t *sc_off, int64_t n_reads, int64_t n_chunks, int64_t n_sc,
+                 int k, int w, int hpc, void *push, void *lsum, uint64_t *sx, uint64_t *sy, uint16_t *sl, int64_t *n_slots, int64_t *cnt, int64_t *mini_off,
+                 void *scan_tmp, size_t scan_bytes, hipStream_t st);
+int sketch_write(const uint8_t *seq, const int64_t *seq_off, const int64_t *sc_off, int64_t n_reads, int64_t n_sc, int k, int w,
+                 const uint64_t *sx, const uint64_t *sy, const uint16_t *sl, const int64_t *n_slots, const int64_t *cnt, mm2c_anchor_t *out, hipStream_t st);
+int lookup_run(const mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_reads, int64_t n_mini, const uint64_t *keys, const int64_t *key_cr,
+               const uint32_t *key_n, int64_t n_keys, int mid_occ, int32_t *t, int64_t *cr, int64_t *keep, int64_t *acnt, mm2c_match_t *matches,
+               uint64_t *mini_pos, int64_t *match_off, int64_t *anchor_off, int32_t *rep_len, void *scan_tmp, size_t scan_bytes, hipStream_t st);
+size_t sketch_scan_bytes(int64_t n_chunks, int64_t n_sc);
+size_t lookup_scan_bytes(int64_t n_mini);
+size_t sketch_push_bytes();
+size_t sketch_lsum_bytes();
+const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device);          // mm2chain_seeds.cpp
+int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool);
+int minidx_image(const uint64_t *h_keys, const int64_t *h_cr, const uint32_t *h_n, int64_t n, int key_bits, char *d_img, int *h_dup, hipStream_t st);
+std::atomic<int64_t> read_chunk_bases{1 << 27};                             // mm2c_tune("read_chunk_bases")
+}
+
+namespace {
+
+struct SketchStats { std::atomic<uint64_t> calls{0}, chunks{0}, bases{0}, minimizers{0}, matches{0}, h2d_ns{0}, sketch_ns{0}, lookup_ns{0}; } SK;
+
+// grow-only host arrays: a result object that serves many calls keeps its pages (no zeroing, no page faults on the next call)
+template <class T> struct Buf {
+	T *p = nullptr; size_t n = 0, cap = 0;
+	~Buf() { free(p); }
+	void resize(size_t m)
+	{
+		if (m > cap) {
+			const size_t c = std::max(m, cap + cap / 2);
+			T *q = (T *)realloc(p, std::max<size_t>(c, 1) * sizeof(T));
+			if (!q) throw std::bad_alloc();
+			p = q; cap = c;
+		}
+		n = m;
+	}
+	void assign(size_t m, T v) { resize(m); std::fill(p, p + m, v); }
+	void clear() { n = 0; }
+	bool empty() const { return n == 0; }
+	T *data() { return p; }
+	T &back() { return p[n - 1]; }
+	T &operator[](size_t i) { return p[i]; }
+};
+
+struct ResPriv {
+	Buf<int64_t> sketch_off, match_off, anchor_off, mini_off, u_off, b_off;
+	Buf<mm2c_anchor_t> sketch, b;
+	Buf<mm2c_match_t> matches;
+	Buf<int32_t> rep_len;
+	Buf<uint64_t> mini_pos, u;
+};
+
+void publish(mm2c_read_result_t *res, int64_t n_reads)
+{
+	ResPriv &P = *(ResPriv *)res->priv;
+	auto off = [&](Buf<int64_t> &v) { return v.empty() ? nullptr : v.data(); };
+	res->n_reads = n_reads;
+	res->sketch_off = off(P.sketch_off); res->n_sketch = P.sketch_off.empty() ? 0 : P.sketch_off.back(); res->sketch = P.sketch.data();
+	res->match_off = off(P.match_off); res->n_matches = P.match_off.empty() ? 0 : P.match_off.back(); res->matches = P.matches.data();
+	res->anchor_off = off(P.anchor_off); res->n_anchors = P.anchor_off.empty() ? 0 : P.anchor_off.back();
+	res->rep_len = P.rep_len.data();
+	res->mini_off = off(P.mini_off); res->n_mini_pos = P.mini_off.empty() ? 0 : P.mini_off.back(); res->mini_pos = P.mini_pos.data();
+	res->u_off = off(P.u_off); res->n_u = P.u_off.empty() ? 0 : P.u_off.back(); res->u = P.u.data();
+	res->b_off = off(P.b_off); res->n_b = P.b_off.empty() ? 0 : P.b_off.back(); res->b = P.b.data();
+}
+
+void clear(mm2c_read_result_t *res)
+{
+	ResPriv &P = *(ResPriv *)res->priv;
+	for (auto *v : { &P.sketch_off, &P.match_off, &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->clear();
+	P.sketch.clear(); P.b.clear(); P.matches.clear(); P.rep_len.clear(); P.mini_pos.clear(); P.u.clear();
+}
+
+int check_reads(int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	if (!res || !res->priv) return fail(MM2C_E_ARG, "result object is NULL (mm2c_read_result_create)");
+	if (n_reads < 0 || (n_reads > 0 && !seq_off)) return fail(MM2C_E_ARG, "bad argument");
+	if (n_reads > 0 && seq_off[0] != 0) return fail(MM2C_E_ARG, "seq_off[0] must be 0");
+	for (int64_t r = 0; r < n_reads; ++r)
+		if (seq_off[r + 1] < seq_off[r]) return fail(MM2C_E_ARG, "sequence offsets not monotone at read %lld", (long long)r);
+		else if (seq_off[r + 1] - seq_off[r] > INT32_MAX) return fail(MM2C_E_TOOBIG, "read %lld is longer than 2^31 - 1 bases", (long long)r);
+	if (n_reads > 0 && seq_off[n_reads] > 0 && !seq) return fail(MM2C_E_ARG, "seq is NULL");
+	return 0;
+}
+
+int check_kw(int k, int w)
+{
+	if (k <= 0 || k > 28) return fail(MM2C_E_ARG, "k = %d: 0 < k <= 28 (sketch.c:91)", k);
+	if (w <= 0 || w >= 256) return fail(MM2C_E_ARG, "w = %d: 0 < w < 256 (sketch.c:91)", w);
+	return 0;
+}
+
+struct Evts {
+	hipEvent_t e[4] = {};
+	int make() { for (auto &x : e) HIP_TRY(hipEventCreate(&x)); return 0; }
+	~Evts() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+	float ms(int a, int b) { float v = 0; (void)hipEventElapsedTime(&v, e[a], e[b]); return v; }
+};
+
+// One run of the sketch (and the lookups) over reads [r0, r1) of the caller's batch, on `st`.  Device memory from the cache, freed by release().
+struct Run {
+	hipStream_t st = nullptr;
+	std::vector<void *> blocks;
+	int64_t nr = 0, n_mini = 0, n_matches = 0;
+	int64_t *d_seq_off = nullptr, *d_mini_off = nullptr;
+	mm2c_anchor_t *d_mini = nullptr;
+	mm2c_match_t *d_matches = nullptr;
+	uint64_t *d_mini_pos = nullptr;
+	int64_t *d_match_off = nullptr, *d_anchor_off = nullptr;
+	int32_t *d_rep_len = nullptr;
+	std::vector<int64_t> h_seq_off;
+	Evts ev;
+
+	hipError_t take(void **p, size_t bytes) { hipError_t e = dev_alloc(p, bytes); if (e == hipSuccess) blocks.push_back(*p); return e; }
+	void release() { for (void *p : blocks) dev_free(p); blocks.clear(); }
+	~Run() { release(); }
+
+	int sketch(int k, int w, int hpc, const int64_t *seq_off, const uint8_t *seq, int64_t r0, int64_t r1)
+	{
+		nr = r1 - r0;
+		const int64_t b0 = seq_off[r0], nb = seq_off[r1] - b0;
+		h_seq_off.resize((size_t)nr + 1);
+		std::vector<int64_t> chunk_off((size_t)nr + 1, 0), sc_off((size_t)nr + 1, 0);
+		for (int64_t r = 0; r <= nr; ++r) h_seq_off[(size_t)r] = seq_off[r0 + r] - b0;
+		for (int64_t r = 0; r < nr; ++r) {
+			const int64_t L = h_seq_off[(size_t)r + 1] - h_seq_off[(size_t)r];
+			chunk_off[(size_t)r + 1] = chunk_off[(size_t)r] + (L + 63) / 64;
+			sc_off[(size_t)r + 1] = sc_off[(size_t)r] + (L + 255) / 256;
+		}
+		const int64_t n_chunks = chunk_off[(size_t)nr], n_sc = sc_off[(size_t)nr];
+		const size_t scan_bytes = sketch_scan_bytes(n_chunks, n_sc);
+		size_t at = 0;
+		auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
+		const size_t o_seq = lay((size_t)nb), o_so = lay(((size_t)nr + 1) * 8), o_co = lay(((size_t)nr + 1) * 8), o_sco = lay(((size_t)nr + 1) * 8),
+		             o_push = lay(2 * (size_t)n_chunks * sketch_push_bytes()), o_lsum = lay(2 * (size_t)n_chunks * sketch_lsum_bytes()),
+		             o_sx = lay((size_t)nb * 8), o_sy = lay((size_t)nb * 8), o_sl = lay((size_t)nb * 2), o_ns = lay(((size_t)nr + 1) * 8),
+		             o_cnt = lay(2 * ((size_t)n_sc + 1) * 8), o_mo = lay(((size_t)nr + 1) * 8), o_tmp = lay(scan_bytes);
+		char *d = nullptr;
+		HIP_TRY(take((void **)&d, at));
+		if (int rc0 = ev.make()) return rc0;
+		HIP_TRY(hipEventRecord(ev.e[0], st));
+		if (nb > 0) HIP_TRY(hipMemcpyAsync(d + o_seq, seq + b0, (size_t)nb, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d + o_so, h_seq_off.data(), ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d + o_co, chunk_off.data(), ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d + o_sco, sc_off.data(), ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipEventRecord(ev.e[1], st));
+		const uint8_t *d_seq = (const uint8_t *)(d + o_seq);
+		d_seq_off = (int64_t *)(d + o_so); d_mini_off = (int64_t *)(d + o_mo);
+		const int64_t *d_sc_off = (const int64_t *)(d + o_sco);
+		int rc;
+		if ((rc = sketch_count(d_seq, d_seq_off, (const int64_t *)(d + o_co), d_sc_off, nr, n_chunks, n_sc, k, w, hpc, d + o_push, d + o_lsum, (uint64_t *)(d + o_sx),
+		                       (uint64_t *)(d + o_sy), (uint16_t *)(d + o_sl), (int64_t *)(d + o_ns), (int64_t *)(d + o_cnt), d_mini_off, d + o_tmp, scan_bytes, st))) return rc;
+		HIP_TRY(hipMemcpyAsync(&n_mini, d_mini_off + nr, 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		HIP_TRY(take((void **)&d_mini, (size_t)std::max<int64_t>(n_mini, 1) * 16));
+		if ((rc = sketch_write(d_seq, d_seq_off, d_sc_off, nr, n_sc, k, w, (const uint64_t *)(d + o_sx), (const uint64_t *)(d + o_sy), (const uint16_t *)(d + o_sl),
+		                       (const int64_t *)(d + o_ns), (const int64_t *)(d + o_cnt), d_mini, st))) return rc;
+		HIP_TRY(hipEventRecord(ev.e[2], st));
+		SK.bases += (uint64_t)nb; SK.minimizers += (uint64_t)n_mini;
+		return 0;
+	}
+
+	int lookup(const mm2c_minidx_t *idx, int device, int mid_occ);   // after sketch(); below
+	void time_it(bool looked_up)
+	{
+		(void)hipEventSynchronize(looked_up ? ev.e[3] : ev.e[2]);
+		SK.h2d_ns += (uint64_t)(ev.ms(0, 1) * 1e6f); SK.sketch_ns += (uint64_t)(ev.ms(1, 2) * 1e6f);
+		if (looked_up) SK.lookup_ns += (uint64_t)(ev.ms(2, 3) * 1e6f);
+	}
+};
+
+} // namespace
+
+struct mm2c_minidx {
+	int k = 0, w = 0, hpc = 0;
+	int64_t n = 0;
+	const mm2c_hitpool_t *pool = nullptr;
+	int n_dev = 0;
+	int dev[64] = {};
+	char *d[64] = {};                            // [keys sorted (8 B) | cr_off (8 B) | n (4 B)] per device
+};
+
+static const char *minidx_on(const mm2c_minidx_t *ix, int device)
+{
+	for (int j = 0; j < ix->n_dev; ++j) if (ix->dev[j] == device) return ix->d[j];
+	return nullptr;
+}
+
+int Run::lookup(const mm2c_minidx_t *idx, int device, int mid_occ)
+{
+	const char *dk = minidx_on(idx, device);
+	if (!dk) return fail(MM2C_E_ARG, "the minimizer index has no copy on device %d (created before mm2c_init_devices?)", device);
+	const size_t nk = (size_t)idx->n, scan_bytes = lookup_scan_bytes(n_mini), nm = (size_t)n_mini;
+	size_t at = 0;
+	auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
+	const size_t o_t = lay(nm * 4), o_cr = lay((nm + 1) * 8), o_keep = lay(2 * (nm + 1) * 8), o_acnt = lay(2 * (nm + 1) * 8), o_m = lay(nm * sizeof(mm2c_match_t)),
+	             o_mp = lay(nm * 8), o_mo = lay(((size_t)nr + 1) * 8), o_ao = lay(((size_t)nr + 1) * 8), o_rl = lay((size_t)nr * 4), o_tmp = lay(scan_bytes);
+	char *d = nullptr;
+	HIP_TRY(take((void **)&d, at));
+	d_matches = (mm2c_match_t *)(d + o_m); d_mini_pos = (uint64_t *)(d + o_mp);
+	d_match_off = (int64_t *)(d + o_mo); d_anchor_off = (int64_t *)(d + o_ao); d_rep_len = (int32_t *)(d + o_rl);
+	int rc;
+	if ((rc = lookup_run(d_mini, d_mini_off, nr, n_mini, (const uint64_t *)dk, (const int64_t *)(dk + nk * 8), (const uint32_t *)(dk + nk * 16), idx->n, mid_occ,
+	                     (int32_t *)(d + o_t), (int64_t *)(d + o_cr), (int64_t *)(d + o_keep), (int64_t *)(d + o_acnt), d_matches, d_mini_pos, d_match_off,
+	                     d_anchor_off, d_rep_len, d + o_tmp, scan_bytes, st))) return rc;
+	HIP_TRY(hipEventRecord(ev.e[3], st));
+	HIP_TRY(hipMemcpyAsync(&n_matches, d_match_off + nr, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	SK.matches += (uint64_t)n_matches;
+	return 0;
+}
+
+namespace {
+struct OwnStream {                               // a private stream of the calling thread's device for one call
+	hipStream_t st = nullptr;
+	int make() { HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); return 0; }
+	~OwnStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+};
+}
+
+extern "C" {
+
+mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int is_hpc, int64_t n_keys, const uint64_t *keys,
+                                  const int64_t *cr_off, const uint32_t *n)
+{
+	if (!lib_ready()) { fail_not_ready(); return nullptr; }
+	if (!pool) { fail(MM2C_E_ARG, "pool is NULL"); return nullptr; }
+	if (check_kw(k, w)) return nullptr;
+	if (n_keys < 0 || (n_keys > 0 && (!keys || !cr_off || !n))) { fail(MM2C_E_ARG, "bad argument"); return nullptr; }
+	const int64_t pool_n = mm2c_hitpool_size(pool);
+	const uint64_t lim = 1ULL << 2 * k;
+	for (int64_t i = 0; i < n_keys; ++i) {
+		if (keys[i] >= lim) { fail(MM2C_E_ARG, "key %lld is %llu, not below 2^(2k) = %llu", (long long)i, (unsigned long long)keys[i], (unsigned long long)lim); return nullptr; }
+		if (cr_off[i] < 0 || cr_off[i] + (int64_t)n[i] > pool_n) { fail(MM2C_E_ARG, "row %lld reaches beyond the pool of %lld hits", (long long)i, (long long)pool_n); return nullptr; }
+	}
+	if (n_keys > (int64_t)UINT32_MAX) { fail(MM2C_E_TOOBIG, "more than 2^32 - 1 keys"); return nullptr; }
+	const size_t nk = (size_t)n_keys, img_bytes = std::max<size_t>(nk * 20, 1);
+	std::vector<char> img;                                    // the sorted image, downloaded once when a second device needs a copy
+	mm2c_minidx *ix = new mm2c_minidx();
+	ix->k = k; ix->w = w; ix->hpc = is_hpc ? 1 : 0; ix->n = n_keys; ix->pool = pool;
+	for (size_t q = 0; q < G.devices.size() && ix->n_dev < 64; ++q) {
+		const int dv = G.devices[q];
+		bool seen = false;
+		for (int j = 0; j < ix->n_dev; ++j) seen = seen || ix->dev[j] == dv;
+		if (seen) continue;
+		DeviceScope on(dv);
+		void *p = nullptr;
+		hipError_t e = on.err;
+		{ ScopedNs timed(SS.alloc_ns); ++SS.n_alloc; if (e == hipSuccess) e = hipMalloc(&p, img_bytes); }
+		if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_minidx_create: %s", hipGetErrorString(e)); mm2c_minidx_destroy(ix); return nullptr; }
+		ix->dev[ix->n_dev] = dv; ix->d[ix->n_dev] = (char *)p; ++ix->n_dev;
+		if (ix->n_dev == 1) {                                  // sorted on the first device
+			OwnStream os;
+			int dup = 0, rc = os.make();
+			if (rc == 0) rc = minidx_image(keys, cr_off, n, n_keys, 2 * k, (char *)p, &dup, os.st);
+			if (rc == 0 && dup) rc = fail(MM2C_E_ARG, "duplicate key in the index");
+			if (rc) { mm2c_minidx_destroy(ix); return nullptr; }
+			continue;
+		}
+		if (img.empty()) {
+			img.resize(img_bytes);
+			DeviceScope first(ix->dev[0]);
+			e = first.err;
+			if (e == hipSuccess) e = hipMemcpy(img.data(), ix->d[0], img_bytes, hipMemcpyDeviceToHost);
+		}
+		if (e == hipSuccess) e = hipMemcpy(p, img.data(), img_bytes, hipMemcpyHostToDevice);
+		if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_minidx_create: %s", hipGetErrorString(e)); mm2c_minidx_destroy(ix); return nullptr; }
+	}
+	return ix;
+}
+
+void mm2c_minidx_destroy(mm2c_minidx_t *ix)
+{
+	if (!ix) return;
+	for (int j = 0; j < ix->n_dev; ++j) { DeviceScope on(ix->dev[j]); ScopedNs timed(SS.free_ns); ++SS.n_free; (void)hipDeviceSynchronize(); (void)hipFree(ix->d[j]); }
+	delete ix;
+}
+
+mm2c_read_result_t *mm2c_read_result_create(void)
+{
+	mm2c_read_result_t *res = new mm2c_read_result_t();
+	res->priv = new ResPriv();
+	return res;
+}
+
+void mm2c_read_result_free(mm2c_read_result_t *res)
+{
+	if (!res) return;
+	delete (ResPriv *)res->priv;
+	delete res;
+}
+
+int mm2c_sketch_batch(int k, int w, int is_hpc, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	int rc;
+	if (!lib_ready()) return fail_not_ready();
+	if ((rc = check_kw(k, w)) || (rc = check_reads(n_reads, seq_off, seq, res))) return rc;
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	P.sketch_off.assign((size_t)n_reads + 1, 0);
+	if (n_reads > 0) {
+		DeviceScope on(cur_device());
+		HIP_TRY(on.err);
+		OwnStream os;
+		if ((rc = os.make())) return rc;
+		Run R; R.st = os.st;
+		if ((rc = R.sketch(k, w, is_hpc ? 1 : 0, seq_off, seq, 0, n_reads))) return rc;
+		P.sketch.resize((size_t)R.n_mini);
+		HIP_TRY(hipMemcpyAsync(P.sketch_off.data(), R.d_mini_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		if (R.n_mini) HIP_TRY(hipMemcpyAsync(P.sketch.data(), R.d_mini, (size_t)R.n_mini * 16, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipStreamSynchronize(os.st));
+		R.time_it(false);
+		++SK.calls; ++SK.chunks;
+	}
+	publish(res, n_reads);
+	return 0;
+}
+
+int mm2c_sketch_match_batch(const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	int rc;
+	if (!lib_ready()) return fail_not_ready();
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	if ((rc = check_reads(n_reads, seq_off, seq, res))) return rc;
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	P.match_off.assign((size_t)n_reads + 1, 0); P.anchor_off.assign((size_t)n_reads + 1, 0); P.mini_off.assign((size_t)n_reads + 1, 0);
+	P.rep_len.assign((size_t)n_reads, 0);
+	if (n_reads > 0) {
+		const int device = cur_device();
+		DeviceScope on(device);
+		HIP_TRY(on.err);
+		OwnStream os;
+		if ((rc = os.make())) return rc;
+		Run R; R.st = os.st;
+		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, 0, n_reads)) || (rc = R.lookup(idx, device, mid_occ))) return rc;
+		P.matches.resize((size_t)R.n_matches); P.mini_pos.resize((size_t)R.n_matches);
+		HIP_TRY(hipMemcpyAsync(P.match_off.data(), R.d_match_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.anchor_off.data(), R.d_anchor_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.rep_len.data(), R.d_rep_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, os.st));
+		if (R.n_matches) {
+			HIP_TRY(hipMemcpyAsync(P.matches.data(), R.d_matches, (size_t)R.n_matches * sizeof(mm2c_match_t), hipMemcpyDeviceToHost, os.st));
+			HIP_TRY(hipMemcpyAsync(P.mini_pos.data(), R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, os.st));
+		}
+		HIP_TRY(hipStreamSynchronize(os.st));
+		P.mini_off.resize(P.match_off.n);           // one mini_pos per kept match
+		std::copy(P.match_off.p, P.match_off.p + P.match_off.n, P.mini_off.p);
+		R.time_it(true);
+		++SK.calls; ++SK.chunks;
+	}
+	publish(res, n_reads);
+	return 0;
+}
+
+int mm2c_minidx_lookup(const mm2c_minidx_t *idx, int64_t n_q, const uint64_t *keys, int64_t *cr_off, uint32_t *n)
+{
+	if (!lib_ready()) return fail_not_ready();
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	if (n_q < 0 || (n_q > 0 && (!keys || !cr_off || !n))) return fail(MM2C_E_ARG, "bad argument");
+	if (n_q == 0) return 0;
+	// the lookups of collect_matches on a made-up read whose minimizers are the keys (keys that no index of this k can hold are answered here)
+	std::vector<int64_t> pos;
+	std::vector<mm2c_anchor_t> mini;
+	for (int64_t i = 0; i < n_q; ++i) {
+		cr_off[i] = 0; n[i] = 0;
+		if (keys[i] < (1ULL << 2 * idx->k)) { pos.push_back(i); mini.push_back(mm2c_anchor_t{ keys[i] << 8, 0 }); }
+	}
+	if (mini.empty()) return 0;
+	const int device = cur_device();
+	DeviceScope on(device);
+	HIP_TRY(on.err);
+	OwnStream os;
+	int rc;
+	if ((rc = os.make())) return rc;
+	Run R; R.st = os.st; R.nr = 1; R.n_mini = (int64_t)mini.size();
+	const int64_t mo[2] = { 0, R.n_mini };
+	HIP_TRY(R.take((void **)&R.d_mini, mini.size() * 16));
+	HIP_TRY(R.take((void **)&R.d_mini_off, 16));
+	HIP_TRY(hipMemcpyAsync(R.d_mini, mini.data(), mini.size() * 16, hipMemcpyHostToDevice, os.st));
+	HIP_TRY(hipMemcpyAsync(R.d_mini_off, mo, 16, hipMemcpyHostToDevice, os.st));
+	if ((rc = R.ev.make())) return rc;
+	HIP_TRY(hipEventRecord(R.ev.e[2], os.st));
+	if ((rc = R.lookup(idx, device, INT32_MAX))) return rc;
+	std::vector<mm2c_match_t> m((size_t)R.n_matches);
+	HIP_TRY(hipMemcpy(m.data(), R.d_matches, m.size() * sizeof(mm2c_match_t), hipMemcpyDeviceToHost));
+	for (size_t j = 0; j < m.size() && j < pos.size(); ++j) { cr_off[pos[j]] = m[j].cr_off; n[pos[j]] = m[j].n; }
+	return 0;
+}
+
+int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads,
+                          const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip, mm2c_read_result_t *res)
+{
+	int rc;
+	if (!lib_ready()) return fail_not_ready();
+	if ((rc = check_params(par))) return rc;
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	if ((rc = check_reads(n_reads, seq_off, seq, res))) return rc;
+	if (skip && (rc = check_skip_pool(skip, n_reads, idx->pool))) return rc;
+	ScopedNs timed_total(SS.total_ns);
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	for (auto *v : { &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->assign((size_t)n_reads + 1, 0);
+	P.rep_len.assign((size_t)n_reads, 0);
+	if (n_reads == 0) { publish(res, 0); return 0; }
+	const int device = cur_device();
+	DeviceScope on(device);
+	HIP_TRY(on.err);
+	const uint64_t *d_pool = hitpool_on(idx->pool, device);
+	if (!d_pool) return fail(MM2C_E_ARG, "the hit pool has no copy on device %d", device);
+	const int64_t n_hits = mm2c_hitpool_size(idx->pool);
+	OwnStream os;
+	if ((rc = os.make())) return rc;
+	hipStream_t st = os.st;
+	++SS.calls;
+	const bool names = skip && skip->ref_rank, per_read = names && skip->q_lo && skip->q_eq;
+	const size_t n_ref = names ? (size_t)std::max<int32_t>(skip->n_ref, 1) : 0;
+	Run refs; refs.st = st;                                    // [ref_rank | ref_len] once per call
+	int32_t *d_ref = nullptr;
+	if (names) {
+		HIP_TRY(refs.take((void **)&d_ref, 2 * n_ref * 4));
+		if (skip->n_ref > 0) HIP_TRY(hipMemcpyAsync(d_ref, skip->ref_rank, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st));
+		if (skip->n_ref > 0 && skip->ref_len) HIP_TRY(hipMemcpyAsync(d_ref + n_ref, skip->ref_len, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st));
+	}
+	const int64_t chunk_bases = std::max<int64_t>(read_chunk_bases.load(), 1);
+	int64_t A = 0, U = 0, B = 0, M = 0;
+	for (int64_t r0 = 0; r0 < n_reads;) {
+		int64_t r1 = r0 + 1;
+		while (r1 < n_reads && seq_off[r1 + 1] - seq_off[r0] <= chunk_bases) ++r1;
+		const size_t nr = (size_t)(r1 - r0);
+		Run R; R.st = st;
+		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, r0, r1)) || (rc = R.lookup(idx, device, mid_occ))) return rc;
+		std::vector<int64_t> mo(nr + 1), cap(nr + 1);
+		std::vector<int32_t> qlen(nr);
+		for (size_t r = 0; r < nr; ++r) qlen[r] = (int32_t)(seq_off[r0 + (int64_t)r + 1] - seq_off[r0 + (int64_t)r]);
+		P.mini_pos.resize((size_t)(M + R.n_matches));
+		HIP_TRY(hipMemcpyAsync(mo.data(), R.d_match_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(cap.data(), R.d_anchor_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(P.rep_len.data() + r0, R.d_rep_len, nr * 4, hipMemcpyDeviceToHost, st));
+		if (R.n_matches) HIP_TRY(hipMemcpyAsync(P.mini_pos.data() + M, R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		R.time_it(true);
+		for (size_t r = 1; r <= nr; ++r) P.mini_off[(size_t)r0 + r] = M + mo[r];
+		M += R.n_matches;
+		const int64_t tot = cap[nr];
+		if (tot >= (int64_t)INT32_MAX) return fail(MM2C_E_TOOBIG, "a chunk of reads with 2^31 anchors or more (lower read_chunk_bases)");
+		if (tot > 0) {
+			mm2c_seedplan_t *sp = mm2c_seedplan_create((int64_t)nr, mo.data(), cap.data());
+			if (!sp) return MM2C_E_HIP;
+			mm2c_plan_t *pl = mm2c_plan_create(par, (int64_t)nr, cap.data());
+			if (!pl) { mm2c_seedplan_destroy(sp); return MM2C_E_HIP; }
+			auto body = [&]() -> int {
+				int r;
+				size_t at = 0;
+				auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
+				const size_t o_q = lay(nr * 4), o_lo = lay(per_read ? nr * 4 : 0), o_eq = lay(per_read ? nr * 4 : 0), o_a = lay((size_t)tot * 16), o_f = lay((size_t)tot * 4),
+				             o_p = lay((size_t)tot * 4), o_uo = lay((nr + 1) * 8), o_bo = lay((nr + 1) * 8), o_u = lay((size_t)tot * 8), o_b = lay((size_t)tot * 16),
+				             o_ao = lay((nr + 1) * 8);
+				char *d = nullptr;
+				HIP_TRY(R.take((void **)&d, at));
+				HIP_TRY(hipMemcpyAsync(d + o_q, qlen.data(), nr * 4, hipMemcpyHostToDevice, st));
+				if (per_read) {
+					HIP_TRY(hipMemcpyAsync(d + o_lo, skip->q_lo + r0, nr * 4, hipMemcpyHostToDevice, st));
+					HIP_TRY(hipMemcpyAsync(d + o_eq, skip->q_eq + r0, nr * 4, hipMemcpyHostToDevice, st));
+				}
+				hipEvent_t e0, e1;
+				HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+				struct EvDrop { hipEvent_t a, b; ~EvDrop() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } drop{ e0, e1 };
+				HIP_TRY(hipEventRecord(e0, st));
+				if (skip) {
+					mm2c_seed_skip_t sk = { skip->flag, names ? d_ref : nullptr, names && skip->ref_len ? d_ref + n_ref : nullptr,
+					                        per_read ? (const int32_t *)(d + o_lo) : nullptr, per_read ? (const int32_t *)(d + o_eq) : nullptr };
+					if ((r = mm2c_seedplan_run_device_skip(sp, R.d_matches, R.n_matches, d_pool, n_hits, (const int32_t *)(d + o_q), (int64_t)nr, &sk, d + o_a, tot,
+					                                       (int64_t *)(d + o_ao), st))) return r;
+					if ((r = mm2c_plan_set_device_offsets(pl, (const int64_t *)(d + o_ao)))) return r;
+				} else if ((r = mm2c_seedplan_run_device(sp, R.d_matches, d_pool, (const int32_t *)(d + o_q), d + o_a, st))) return r;
+				HIP_TRY(hipEventRecord(e1, st));
+				if ((r = mm2c_plan_run_device(pl, d + o_a, nullptr, (int32_t *)(d + o_f), (int32_t *)(d + o_p), st))) return r;
+				if ((r = mm2c_plan_chains_device(pl, d + o_a, (int32_t *)(d + o_f), (int32_t *)(d + o_p), min_cnt, min_sc, (int64_t *)(d + o_uo), (uint64_t *)(d + o_u),
+				                                 (int64_t *)(d + o_bo), d + o_b, st))) return r;
+				std::vector<int64_t> uo(nr + 1), bo(nr + 1), ao(nr + 1);
+				HIP_TRY(hipMemcpyAsync(uo.data(), d + o_uo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipMemcpyAsync(bo.data(), d + o_bo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+				if (skip) HIP_TRY(hipMemcpyAsync(ao.data(), d + o_ao, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipStreamSynchronize(st));
+				if ((r = mm2c_seedplan_check(sp, nullptr))) return r;
+				float ms = 0;
+				(void)hipEventElapsedTime(&ms, e0, e1);
+				SS.seed_ns += (uint64_t)(ms * 1e6f);
+				if (!skip) ao = cap;
+				P.u.resize((size_t)(U + uo[nr])); P.b.resize((size_t)(B + bo[nr]));
+				if (uo[nr]) HIP_TRY(hipMemcpyAsync(P.u.data() + U, d + o_u, (size_t)uo[nr] * 8, hipMemcpyDeviceToHost, st));
+				if (bo[nr]) HIP_TRY(hipMemcpyAsync(P.b.data() + B, d + o_b, (size_t)bo[nr] * 16, hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipStreamSynchronize(st));
+				for (size_t k = 1; k <= nr; ++k) {
+					P.u_off[(size_t)r0 + k] = U + uo[k]; P.b_off[(size_t)r0 + k] = B + bo[k]; P.anchor_off[(size_t)r0 + k] = A + ao[k];
+				}
+				U += uo[nr]; B += bo[nr]; A += ao[nr];
+				return 0;
+			};
+			rc = body();
+			mm2c_plan_destroy(pl);
+			mm2c_seedplan_destroy(sp);
+			if (rc) return rc;
+		} else
+			for (size_t k = 1; k <= nr; ++k) { P.u_off[(size_t)r0 + k] = U; P.b_off[(size_t)r0 + k] = B; P.anchor_off[(size_t)r0 + k] = A; }
+		++SK.chunks; ++SS.chunks;
+		r0 = r1;
+	}
+	++SK.calls;
+	G.tasks += (uint64_t)n_reads; G.anchors += (uint64_t)A;
+	publish(res, n_reads);
+	return 0;
+}
+
+void mm2c_get_sketch_stats(mm2c_sketch_stats_t *out)
+{
+	if (!out) return;
+	*out = mm2c_sketch_stats_t{ SK.calls, SK.chunks, SK.bases, SK.minimizers, SK.matches, SK.h2d_ns, SK.sketch_ns, SK.lookup_ns };
+}
+
+void mm2c_reset_sketch_stats(void)
+{
+	for (auto *a : { &SK.calls, &SK.chunks, &SK.bases, &SK.minimizers, &SK.matches, &SK.h2d_ns, &SK.sketch_ns, &SK.lookup_ns }) *a = 0;
+}
+
+} // extern "C"

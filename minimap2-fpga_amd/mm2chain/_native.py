@@ -39,6 +39,22 @@ class StageStats(C.Structure):
 
 
 # every symbol include/mm2chain.h declares with C linkage: name -> (restype, argtypes)
+class ReadResult(C.Structure):
+    """mm2c_read_result_t (library-owned arrays)"""
+    _fields_ = [("n_reads", C.c_int64),
+                ("n_sketch", C.c_int64), ("sketch_off", C.c_void_p), ("sketch", C.c_void_p),
+                ("n_matches", C.c_int64), ("match_off", C.c_void_p), ("matches", C.c_void_p),
+                ("n_anchors", C.c_int64), ("anchor_off", C.c_void_p), ("rep_len", C.c_void_p),
+                ("n_mini_pos", C.c_int64), ("mini_off", C.c_void_p), ("mini_pos", C.c_void_p),
+                ("n_u", C.c_int64), ("n_b", C.c_int64), ("u_off", C.c_void_p), ("u", C.c_void_p), ("b_off", C.c_void_p), ("b", C.c_void_p),
+                ("priv", C.c_void_p)]
+
+
+class SketchStats(C.Structure):
+    """mm2c_sketch_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "matches", "h2d_ns", "sketch_ns", "lookup_ns")]
+
+
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
     "mm2c_init_devices": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
@@ -113,6 +129,17 @@ C_SYMBOLS = {
     "mm2c_hitpool_create": (C.c_void_p, [C.c_void_p, C.c_int64]),
     "mm2c_hitpool_size": (C.c_int64, [C.c_void_p]),
     "mm2c_hitpool_destroy": (None, [C.c_void_p]),
+    "mm2c_minidx_create": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_minidx_destroy": (None, [C.c_void_p]),
+    "mm2c_minidx_lookup": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_read_result_create": (C.POINTER(ReadResult), []),
+    "mm2c_read_result_free": (None, [C.POINTER(ReadResult)]),
+    "mm2c_sketch_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_sketch_match_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_read_chain_batch": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(ReadResult)]),
+    "mm2c_get_sketch_stats": (None, [C.POINTER(SketchStats)]),
+    "mm2c_reset_sketch_stats": (None, []),
     "mm2c_get_stats": (None, [C.POINTER(Stats)]),
     "mm2c_get_stage_stats": (None, [C.POINTER(StageStats)]),
     "mm2c_reset_stage_stats": (None, []),

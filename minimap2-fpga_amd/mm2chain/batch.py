@@ -551,6 +551,131 @@ def seed_chain_batch_pool_skip(params: Params, min_cnt, min_sc, match_off, match
     return ao, _split_chains(n_reads, u_off, u, b_off, b)
 
 
+def _reads_args(seqs):
+    """reads as (seq_off int64 [n+1], seq uint8): a list of bytes / str / uint8 arrays, or such a pair already"""
+    if isinstance(seqs, tuple) and len(seqs) == 2:
+        off = np.ascontiguousarray(np.asarray(seqs[0], dtype=np.int64))
+        seq = np.ascontiguousarray(np.asarray(seqs[1], dtype=np.uint8)).reshape(-1)
+    else:
+        parts = [np.frombuffer(x.encode() if isinstance(x, str) else bytes(x), dtype=np.uint8) for x in seqs]
+        off = np.zeros(len(parts) + 1, np.int64)
+        off[1:] = np.cumsum([p.size for p in parts]) if parts else []
+        seq = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    if off.size < 1 or off[0] != 0 or off[-1] > seq.size:
+        raise ValueError("sequence offsets do not fit the bases")
+    return off, np.ascontiguousarray(seq) if seq.size else np.zeros(1, np.uint8)
+
+
+def _arr(ptr, n, dtype):
+    """copy n elements of a library-owned array"""
+    dt = np.dtype(dtype)
+    if n == 0 or not ptr:
+        return np.zeros(n, dt)
+    return np.frombuffer(C.string_at(ptr, n * dt.itemsize), dtype=dt).copy()
+
+
+class _Result:
+    """mm2c_read_result_t, kept for the reads-in calls of one object"""
+
+    def __init__(self):
+        self.lib = N.load()
+        self.p = self.lib.mm2c_read_result_create()
+
+    def __del__(self):
+        try:
+            self.lib.mm2c_read_result_free(self.p)
+        except Exception:
+            pass
+
+
+class MinimizerIndex:
+    """mm2c_minidx_t: a minimizer index resident on every configured device.  keys = minimizers (x >> 8), their hits pool[cr_off : cr_off + n] of a HitPool
+    (or of `hits`, uploaded as a pool owned by the index).  Lookups return what mm_idx_get returns (n = 0 for an absent key)."""
+
+    def __init__(self, k, w, is_hpc, keys, cr_off, n, pool: "HitPool" = None, hits=None):
+        self.lib = N.load()
+        if pool is None:
+            if hits is None:
+                raise ValueError("give a HitPool or the hits")
+            pool = HitPool(hits)
+        self.pool, self.k, self.w, self.is_hpc = pool, int(k), int(w), int(bool(is_hpc))
+        kk = np.ascontiguousarray(keys, dtype=np.uint64)
+        cr = np.ascontiguousarray(cr_off, dtype=np.int64)
+        nn = np.ascontiguousarray(n, dtype=np.uint32)
+        if not (kk.size == cr.size == nn.size):
+            raise ValueError("keys, cr_off and n differ in length")
+        self.handle = self.lib.mm2c_minidx_create(pool.handle, self.k, self.w, self.is_hpc, kk.size, _np_ptr(kk), _np_ptr(cr), _np_ptr(nn))
+        if not self.handle:
+            N.check(-2, "mm2c_minidx_create")
+        self.size = kk.size
+
+    def lookup(self, keys):
+        """(cr_off int64, n uint32) per key"""
+        q = np.ascontiguousarray(keys, dtype=np.uint64)
+        cr = np.zeros(q.size, np.int64); n = np.zeros(q.size, np.uint32)
+        N.check(self.lib.mm2c_minidx_lookup(self.handle, q.size, _np_ptr(q), _np_ptr(cr), _np_ptr(n)), "mm2c_minidx_lookup")
+        return cr, n
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_minidx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sketch_batch(seqs, k, w, is_hpc=False):
+    """mm2c_sketch_batch: mm_sketch per read.  seqs: list of reads (bytes / str) or (seq_off, seq).  Returns (off int64 [n+1], minimizers uint64 [m, 2] = x, y)"""
+    off, seq = _reads_args(seqs)
+    R = _Result()
+    N.check(R.lib.mm2c_sketch_batch(int(k), int(w), int(bool(is_hpc)), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p), "mm2c_sketch_batch")
+    r = R.p.contents
+    so = _arr(r.sketch_off, off.size, np.int64)
+    return so, _arr(r.sketch, 2 * r.n_sketch, np.uint64).reshape(-1, 2)
+
+
+def sketch_match_batch(seqs, idx: MinimizerIndex, mid_occ):
+    """mm2c_sketch_match_batch: reads in, matches out.  Returns a dict of numpy arrays: match_off, matches (MATCH_DTYPE), anchor_off, rep_len, mini_off, mini_pos"""
+    off, seq = _reads_args(seqs)
+    R = _Result()
+    N.check(R.lib.mm2c_sketch_match_batch(idx.handle, int(mid_occ), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p), "mm2c_sketch_match_batch")
+    r, nr = R.p.contents, off.size - 1
+    return {"match_off": _arr(r.match_off, nr + 1, np.int64), "matches": _arr(r.matches, r.n_matches, MATCH_DTYPE),
+            "anchor_off": _arr(r.anchor_off, nr + 1, np.int64), "rep_len": _arr(r.rep_len, nr, np.int32),
+            "mini_off": _arr(r.mini_off, nr + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+
+
+def read_chain_batch(params: Params, min_cnt, min_sc, seqs, idx: MinimizerIndex, mid_occ, skip: SeedSkip = None):
+    """mm2c_read_chain_batch: reads in, chains out (sketch, lookups, seed hits, DP and epilogue on the device).  Returns a dict: anchor_off, u_off, u, b_off,
+    b (uint64 [n_b, 2]), rep_len, mini_off, mini_pos, and chains = [(u, b), ...] per read"""
+    off, seq = _reads_args(seqs)
+    nr = off.size - 1
+    sk = skip._native(nr) if skip is not None else None
+    R = _Result()
+    N.check(R.lib.mm2c_read_chain_batch(C.byref(params), int(min_cnt), int(min_sc), idx.handle, int(mid_occ), nr, _np_ptr(off), _np_ptr(seq),
+                                        C.byref(sk) if sk is not None else None, R.p), "mm2c_read_chain_batch")
+    r = R.p.contents
+    out = {"anchor_off": _arr(r.anchor_off, nr + 1, np.int64), "u_off": _arr(r.u_off, nr + 1, np.int64), "u": _arr(r.u, r.n_u, np.uint64),
+           "b_off": _arr(r.b_off, nr + 1, np.int64), "b": _arr(r.b, 2 * r.n_b, np.uint64).reshape(-1, 2), "rep_len": _arr(r.rep_len, nr, np.int32),
+           "mini_off": _arr(r.mini_off, nr + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+    out["chains"] = _split_chains(nr, out["u_off"], out["u"], out["b_off"], out["b"])
+    return out
+
+
+def sketch_stats(reset=False):
+    """mm2c_get_sketch_stats as a dict (ns and counts); reset=True clears the counters afterwards"""
+    lib = N.load()
+    st = N.SketchStats()
+    lib.mm2c_get_sketch_stats(C.byref(st))
+    if reset:
+        lib.mm2c_reset_sketch_stats()
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
 def stage_stats(reset=False):
     """mm2c_get_stage_stats as a dict (ns and counts); reset=True clears the counters afterwards"""
     lib = N.load()
