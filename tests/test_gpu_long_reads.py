@@ -288,3 +288,24 @@ def test_exit_without_shutdown_after_a_split_batch_keeps_the_exit_code():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 7, (r.returncode, r.stdout[-300:], r.stderr[-600:])
     assert "ran 128000" in r.stdout
+
+
+def test_one_read_of_a_million_anchors_among_short_ones_on_both_routes():
+    """BASELINE config 5's largest task in the suite, not only in bench.py: 10^6 anchors at ava-ont density (mixed, locus = 20 x anchors) among short reads
+    through a ChainPlan, on the default route and on one wave per piece (coop_plans 0); f / p against the oracle on both"""
+    import mm2chain
+    from mm2chain import params
+    P = params.ava_ont()
+    o1, a1 = _stream("mixed", 1, 1_000_000, seed=43, locus=20_000_000)
+    o2, a2 = _stream("mixed", 300, (200, 3000), seed=44)
+    a = np.concatenate([a2[:o2[150]], a1, a2[o2[150]:]])
+    off = np.concatenate([o2[:151], o2[150] + o1[1:], o2[151:] + o1[-1]])
+    assert np.diff(off).max() == 1_000_000 and off[-1] == a.shape[0]
+    f_ref, p_ref = oracle_batch(P, off, a)
+    try:
+        for coop in (2, 0):
+            mm2chain.tune("coop_plans", coop)
+            f, p, route, variant = _plan_run(P, off, a)
+            assert_same(f, p, f_ref, p_ref, off, f"coop_plans {coop}: {variant}, route {route}")
+    finally:
+        mm2chain.tune("coop_plans", 2)

@@ -462,3 +462,42 @@ def test_heap_sort_through_the_host_batch_entry():
         assert np.array_equal(a[ao[k]:ao[k + 1]], hp[f"r{k}_anchors_heap"]), k
     ao, a = mm2chain.seed_hits_batch(mo, m, h, ql)
     assert all(np.array_equal(a[ao[k]:ao[k + 1]], d[f"r{k}_anchors"]) for k in range(len(reads)))
+
+
+def test_one_read_of_a_million_anchors_with_equal_x_through_a_seed_plan():
+    """a read of more than 10^6 hits whose repeated hit lists give anchors with equal x, among short reads: SeedPlan.run and run_skip (-x ava-ont's pair with names)
+    against the oracle's collect_seed_hits; the plan reports the tie read and expands the long read on sixteen waves"""
+    import mm2chain
+    rng = np.random.default_rng(1000000)
+    n_ref = 40
+    big = _random_read(rng, 170_000, 12, n_ref, 1 << 28, qlen=1_500_000, dup_frac=0.1)
+    reads = [_random_read(rng, 300, 5, n_ref, 1 << 20), big, _random_read(rng, 0, 0, 1, 10), _random_read(rng, 2500, 8, n_ref, 1 << 22, qlen=40000)]
+    sizes = [int(r[1]["n"].sum()) for r in reads]
+    assert sizes[1] >= 1_000_000 and max(sizes[0], sizes[3]) <= 16384, sizes
+    mo, m, h, ql = _batch(reads)
+    ao = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    d_m = torch.from_numpy(m.view(np.uint8).copy()).cuda(); d_h = torch.from_numpy(h.view(np.int64)).cuda(); d_q = torch.from_numpy(ql).cuda()
+    sp = mm2chain.SeedPlan(mo, ao)
+    a = sp.run(d_m, d_h, d_q).cpu().numpy().view(np.uint64)
+    n_ties = sp.check()
+    assert n_ties >= 1 and sp.last_expand_mw() >= 1, (n_ties, sp.last_expand_mw())
+    for r, (qlen, mr, hr) in enumerate(reads):
+        ref = ob.collect_seed_hits(mr, hr, qlen)
+        if r == 1:
+            assert (ref[1:, 0] == ref[:-1, 0]).any(), "the long read has anchors with equal x"
+        bad = np.nonzero((a[ao[r]:ao[r + 1]] != ref).any(axis=1))[0]
+        assert ref.shape[0] == sizes[r] and bad.size == 0, f"read {r}: {bad.size} of {ref.shape[0]} anchors differ"
+    rank = rng.permutation(n_ref).astype(np.int32)
+    ref_len = rng.integers(1000, 2_000_000, n_ref).astype(np.int32)
+    q_lo = np.full(len(reads), n_ref // 2, np.int32); q_eq = np.ones(len(reads), np.int32)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).cuda()
+    d_a, d_off = sp.run_skip(d_m, d_h, d_q, ob.F_NO_DIAG | ob.F_NO_DUAL, dev(rank), dev(ref_len), dev(q_lo), dev(q_eq))
+    sp.check()
+    assert sp.last_expand_mw() >= 1
+    off = d_off.cpu().numpy(); a = d_a.cpu().numpy().view(np.uint64)
+    for r, (qlen, mr, hr) in enumerate(reads):
+        ref = ob.collect_seed_hits(mr, hr, qlen, ob.F_NO_DIAG | ob.F_NO_DUAL, rank, ref_len, int(q_lo[r]), int(q_eq[r]))
+        if r == 1:
+            assert 0 < ref.shape[0] < sizes[1], "dual pairs were skipped"
+        assert off[r + 1] - off[r] == ref.shape[0] and np.array_equal(a[off[r]:off[r + 1]], ref), f"skip: read {r} differs"
+    sp.close()

@@ -174,3 +174,53 @@ def test_errors(fx):
     assert lib.mm2c_read_chain_batch(C.byref(P), 3, 40, None, 10, 1, off.ctypes.data, seq.ctypes.data, None, res) == -2
     lib.mm2c_read_result_free(res)
     pool.close()
+
+
+@pytest.mark.parametrize("k", [15, 28])
+def test_lookup_bounds_of_a_key_table_with_both_end_keys(k):
+    """keys 0 and 2^(2k) - 1 present: every key returns exactly its (cr_off, n); its neighbours, 0, 2^(2k) - 1 and 2^64 - 1, when absent, return (0, 0)"""
+    import mm2chain
+    rng = np.random.default_rng(k)
+    top = (1 << 2 * k) - 1
+    keys = np.unique(np.concatenate([np.array([0, 1, top - 1, top], np.uint64), rng.integers(2, top - 1, 3000, dtype=np.uint64) & ~np.uint64(1)]))
+    n = rng.integers(1, 9, keys.size).astype(np.uint32)
+    cr = np.concatenate([[0], np.cumsum(n.astype(np.int64))[:-1]])
+    pool = mm2chain.HitPool(np.arange(int(n.sum()), dtype=np.uint64))
+    perm = rng.permutation(keys.size)                               # the table is handed over unsorted
+    idx = mm2chain.MinimizerIndex(k, 10, 0, keys[perm], cr[perm], n[perm], pool=pool)
+    table = {int(a): (int(b), int(c)) for a, b, c in zip(keys, cr, n)}
+    q = np.unique(np.concatenate([keys, keys + np.uint64(1), keys[keys > 0] - np.uint64(1), np.array([0, top, top + 1, (1 << 64) - 1], np.uint64)]))
+    assert q.dtype == np.uint64 and q.max() == np.uint64((1 << 64) - 1) and top + 1 in q
+    got_cr, got_n = idx.lookup(q)
+    exp = np.array([table.get(int(x), (0, 0)) for x in q], np.int64).reshape(-1, 2)
+    assert (exp[:, 1] == 0).sum() > 1000 and 0 in table and top in table
+    assert np.array_equal(got_cr, exp[:, 0]) and np.array_equal(got_n.astype(np.int64), exp[:, 1])
+    idx.close()
+    for one in (0, top, 12345):                                     # a one-key index
+        idx = mm2chain.MinimizerIndex(k, 10, 0, [one], [3], [2], pool=pool)
+        q1 = np.array([0, 1, one - 1 if one else 2, one, one + 1, top, (1 << 64) - 1], np.uint64)
+        c1, n1 = idx.lookup(q1)
+        assert np.array_equal(n1, np.where(q1 == one, 2, 0)) and np.array_equal(c1, np.where(q1 == one, 3, 0)), one
+        idx.close()
+    pool.close()
+
+
+def test_a_zero_key_index_matches_nothing():
+    """mm2c_minidx_create with n_keys = 0: every lookup returns n = 0; reads in give their minimizers and no matches, no anchors, no chains, rep_len 0"""
+    import mm2chain
+    from mm2chain import params
+    pool = mm2chain.HitPool(np.zeros(1, np.uint64))
+    idx = mm2chain.MinimizerIndex(15, 10, 0, np.zeros(0, np.uint64), np.zeros(0, np.int64), np.zeros(0, np.uint32), pool=pool)
+    cr, n = idx.lookup(np.array([0, 1, 12345, (1 << 30) - 1, (1 << 64) - 1], np.uint64))
+    assert not n.any() and not cr.any()
+    reads = _rand_reads(np.random.default_rng(5), [0, 14, 15, 3000, 20000])
+    so, mini = mm2chain.sketch_batch(reads, 15, 10)
+    assert mini.shape[0] > 1000
+    s = mm2chain.sketch_match_batch(reads, idx, 300)
+    ref = [sm.collect_matches(mini[so[r]:so[r + 1]], lambda key: (0, 0), 300) for r in range(len(reads))]
+    assert np.array_equal(s["match_off"], so) and not s["matches"]["n"].any() and not s["rep_len"].any()
+    assert np.array_equal(s["matches"], sm.match_array([x for mt, _, _ in ref for x in mt]))
+    got = mm2chain.read_chain_batch(params.map_ont(), 3, 40, reads, idx, 300)
+    assert np.array_equal(got["mini_off"], so) and not got["anchor_off"].any() and got["u"].size == 0 and got["b"].size == 0 and not got["rep_len"].any()
+    assert np.array_equal(got["mini_pos"], np.array([p for _, _, mp in ref for p in mp], np.uint64))
+    idx.close(); pool.close()
