@@ -8,8 +8,13 @@ collective (weak scaling: the per-GPU batch is fixed); one all-reduce of counter
 `python bench.py --gpus N`, from this script itself (launch_ranks: N child processes started before any GPU call).
 
 Prints ONE JSON line on rank 0 (see the keys below).  `roofline` prices the dominant kernel against HBM with
-24 algorithmic bytes per anchor (16 B mm128_t read + 4 B f + 4 B p written); `cpu_baseline` times the
-CPU oracle (a port of chain.c's loop) on the host cores over a bounded sample of the same batch.
+24 algorithmic bytes per anchor (16 B mm128_t read + 4 B f + 4 B p written), from the HIP events of the timed steps.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.  Everything
+else is behind --full: the check of the timed step against the CPU oracle (`verified_vs_oracle`), the secondary legs (whole
+mm_chain_dp, seed hits, lone call, host-streamed, long reads), `cpu_baseline` (the CPU oracle, a port of chain.c's loop, on the
+host cores over a bounded sample of the same batch) and the end-to-end leg; --no-secondary, --no-long, --no-e2e and --cpu-seconds
+trim a --full run.
 """
 import argparse
 import json
@@ -258,7 +263,9 @@ def main():
     ap.add_argument("--anchors-per-read", type=int, default=5000)
     ap.add_argument("--ragged", action="store_true", help="anchors per read ~ U[0.2, 1.8] x --anchors-per-read (SURVEY 8d ragged variant)")
     ap.add_argument("--seed", type=int, default=20240)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: check the timed step against the CPU oracle, then the secondary legs, the CPU baseline and the end-to-end leg")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU baseline leg (0 = skip; --full only)")
     ap.add_argument("--preset", default="map-ont", choices=["map-ont", "asm20", "ava-ont"],
                     help="chaining scalars + stream shape: map-ont (BASELINE config 2, default), asm20 (config 4 stand-in: span 19, "
                          "7500 anchors/read), ava-ont (config 5 stand-in: bw 2000, max_gap 10000, 20000 anchors/read)")
@@ -269,9 +276,9 @@ def main():
                     help="strong scaling: ONE fixed batch of --reads reads (the same on every rank), its tasks dealt to the ranks by "
                          "sharding.shard_tasks (longest first, on anchors per task) and gathered into a rank-local CSR batch; "
                          "value = anchors of the whole batch / max-over-ranks time")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (extra launches); used when profiling")
-    ap.add_argument("--no-long", action="store_true", help="skip the long-read leg (BASELINE config 5's regime: 1e5 .. 1e6 anchors per read, about half a minute)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end map-ont leg (three host processes over a synthetic genome, about half a minute)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (extra launches; --full only)")
+    ap.add_argument("--no-long", action="store_true", help="skip the long-read leg (BASELINE config 5's regime: 1e5 .. 1e6 anchors per read, about half a minute; --full only)")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end map-ont leg (three host processes over a synthetic genome, about half a minute; --full only)")
     ap.add_argument("--e2e-reads", type=int, default=120000)
     ap.add_argument("--e2e-genome-mb", type=float, default=50.0)
     ap.add_argument("--e2e-mini-batch", type=int, default=100_000_000, help="-K of the three hosts (bases per mini-batch)")
@@ -437,26 +444,27 @@ def main():
     if args.dump_outputs and rank == 0:                         # outside the timed region: what the last timed step left in d_f / d_p
         dump_outputs(args.dump_outputs, d_f, d_p)
 
-    # ---- correctness of what was just timed (outside the timed region): f / p of EVERY distinct read of this rank's batch against the oracle -- the replicas behind
-    # them are copies of the same reads, compared with the first replica on the device.  The oracle pass doubles as the first pass of the cpu_baseline leg.
-    import oracle_binding as ob
-    n_check = distinct_chk
-    end = int(off1[n_check])
-    chk_threads = max(1, host_cores() // max(world, 1))
-    a1_np = a1[:end].cpu().numpy().view(np.uint64)
-    f_ref, p_ref, chk_s = ob.chain_batch(P, off1[: n_check + 1].numpy(), a1_np, chk_threads)
-    verified = bool(np.array_equal(d_f[:end].cpu().numpy(), f_ref) and np.array_equal(d_p[:end].cpu().numpy(), p_ref))
-    del f_ref, p_ref
-    if not args.strong:
-        last = total - int(off1[-1])                            # the last replica must equal the first one
-        verified = verified and bool(torch.equal(d_f[last:], d_f[: int(off1[-1])])) and bool(torch.equal(d_p[last:], d_p[: int(off1[-1])]))
-        if times > 2:                                            # ... and one in the middle
-            mid = (times // 2) * int(off1[-1])
-            verified = verified and bool(torch.equal(d_f[mid: mid + int(off1[-1])], d_f[: int(off1[-1])])) and bool(torch.equal(d_p[mid: mid + int(off1[-1])], d_p[: int(off1[-1])]))
-    if world > 1:                                               # every rank's check counts
-        vt = torch.tensor([1 if verified else 0], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(vt, op=dist.ReduceOp.MIN)
-        verified = bool(int(vt[0]))
+    # ---- correctness of what was just timed (--full, outside the timed region): f / p of EVERY distinct read of this rank's batch against the oracle -- the replicas
+    # behind them are copies of the same reads, compared with the first replica on the device.  The oracle pass doubles as the first pass of the cpu_baseline leg.
+    if args.full:
+        import oracle_binding as ob
+        n_check = distinct_chk
+        end = int(off1[n_check])
+        chk_threads = max(1, host_cores() // max(world, 1))
+        a1_np = a1[:end].cpu().numpy().view(np.uint64)
+        f_ref, p_ref, chk_s = ob.chain_batch(P, off1[: n_check + 1].numpy(), a1_np, chk_threads)
+        verified = bool(np.array_equal(d_f[:end].cpu().numpy(), f_ref) and np.array_equal(d_p[:end].cpu().numpy(), p_ref))
+        del f_ref, p_ref
+        if not args.strong:
+            last = total - int(off1[-1])                            # the last replica must equal the first one
+            verified = verified and bool(torch.equal(d_f[last:], d_f[: int(off1[-1])])) and bool(torch.equal(d_p[last:], d_p[: int(off1[-1])]))
+            if times > 2:                                            # ... and one in the middle
+                mid = (times // 2) * int(off1[-1])
+                verified = verified and bool(torch.equal(d_f[mid: mid + int(off1[-1])], d_f[: int(off1[-1])])) and bool(torch.equal(d_p[mid: mid + int(off1[-1])], d_p[: int(off1[-1])]))
+        if world > 1:                                               # every rank's check counts
+            vt = torch.tensor([1 if verified else 0], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(vt, op=dist.ReduceOp.MIN)
+            verified = bool(int(vt[0]))
 
     if rank != 0:
         if world > 1:
@@ -476,17 +484,18 @@ def main():
                    "reads_per_gpu_per_step": n_tasks, "reads_whole_batch": (global_total and (args.reads if args.strong else n_tasks * world)), "distinct_reads": distinct, "anchors_per_read": args.anchors_per_read,
                    "profile": args.profile, "preset": args.preset, "ragged": bool(args.ragged),
                    "parallelism": f"read-sharded x{world}" + (" (one batch, tasks dealt longest-first)" if args.strong else "")},
-        "verified_vs_oracle": verified, "verified_reads": n_check,
-        "verified_what": "f[] and p[] of the step just timed, every distinct read of the batch element-wise against the CPU oracle; the first, middle and last replica equal on the device",
+        **({"verified_vs_oracle": verified, "verified_reads": n_check,
+            "verified_what": "f[] and p[] of the step just timed, every distinct read of the batch element-wise against the CPU oracle; the first, middle and last replica equal on the device"}
+           if args.full else {}),
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": measured_traffic(args.profile, total, args.preset), "kernel": "chain_dp_tile", "kernel_ms_avg": k_avg_ms,
                      "prepass_kernel_ms_avg": float(np.mean(prepass_ms)),
                      "algorithmic_bytes_per_launch": total * ALGO_BYTES_PER_ANCHOR},
     }
 
-    # ---- secondary figures (outside the timed region, rank 0)
+    # ---- secondary figures (--full, outside the timed region, rank 0)
     try:
-        if args.no_secondary or world > 1 or args.strong:                                # N = 1 only: keep multi-GPU runs lean
+        if not args.full or args.no_secondary or world > 1 or args.strong:               # N = 1 only: keep multi-GPU runs lean
             raise StopIteration
         _, _, tt = plan_predict_totals(mm2chain, P, off1, a1)
         out["secondary"] = {"nominal_cells_per_s": float(tt) * times / (k_avg_ms * 1e-3),
@@ -610,8 +619,8 @@ def main():
     except Exception as e:                                                   # never let a secondary figure break the line
         out["secondary_error"] = repr(e)
 
-    # ---- CPU baseline: the oracle (port of chain.c:184-238) on the host cores, bounded sample of the same batch
-    if args.cpu_seconds > 0 and world == 1:                                  # rank 0 at N = 1 only
+    # ---- CPU baseline (--full): the oracle (port of chain.c:184-238) on the host cores, bounded sample of the same batch
+    if args.full and args.cpu_seconds > 0 and world == 1:                    # rank 0 at N = 1 only
         cores = host_cores()
         off_np = off1.numpy()
         a_np = a1.cpu().numpy().view(np.uint64)
@@ -639,12 +648,12 @@ def main():
                                "sample": f"first {n_s} reads of the same batch x {reps} passes ({reps * int(off_np[n_s])} anchors), "
                                          f"{cores} threads, tasks round-robin, {s_all:.1f} s wall",
                                "value_1thread": int(off_np[n1]) / s_one}
-    # ---- end to end (BASELINE.json's second metric): after everything else, the GPU memory of this process given back first
+    # ---- end to end (BASELINE.json's second metric; --full): after everything else, the GPU memory of this process given back first
     # N > 1: the other ranks have ended by now (they return right after the verification all-reduce) and this rank leaves the process group first; the two
     # GPU hosts then run as one process each over the ranks' devices (MM2C_DEVICES)
     if world > 1:
         dist.destroy_process_group()
-    if not args.strong and not args.no_e2e and (world > 1 or not args.no_secondary) and args.preset == "map-ont":
+    if args.full and not args.strong and not args.no_e2e and (world > 1 or not args.no_secondary) and args.preset == "map-ont":
         try:
             del d_f, d_p, anchors
             plan.close(); plan = None

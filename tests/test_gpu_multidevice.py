@@ -128,19 +128,23 @@ def test_devices_named_in_the_environment_for_hosts_whose_init_hook_carries_no_o
 
 def test_bench_gpus_2_starts_two_ranks_on_the_gpu():
     """`python bench.py --gpus 2` (no launcher): two rank processes, here sharing the box's one MI355X (MM2C_BENCH_ONE_DEVICE) and talking gloo
-    (RCCL needs one GPU per rank); each runs the real timed loop on its own batch, the line reports n_gpus 2 and both ranks' checks"""
+    (RCCL needs one GPU per rank); each runs the real timed loop on its own batch, the line reports n_gpus 2 and, with --full, both ranks' checks"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MM2C_BENCH_BACKEND="gloo", MM2C_BENCH_ONE_DEVICE="1")
-    for extra in ([], ["--strong", "--ragged"]):
+    for extra in (["--full"], ["--full", "--strong", "--ragged"], []):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "512", "--distinct", "256",
                             "--anchors-per-read", "2000", "--cpu-seconds", "0"] + extra, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert out["n_gpus"] == 2 and out["world_size_seen"] == 2 and len(out["per_rank_ms_per_step"]) == 2
-        assert out["verified_vs_oracle"] is True and out["value"] > 0
-        assert out["scaling"] == ("strong" if extra else "weak")
+        assert out["value"] > 0
+        if "--full" in extra:
+            assert out["verified_vs_oracle"] is True
+        else:                                   # a plain run: the headline only
+            assert "verified_vs_oracle" not in out
+        assert out["scaling"] == ("strong" if "--strong" in extra else "weak")
 
 
 @pytest.mark.parametrize("n_ctx", [2, 3])

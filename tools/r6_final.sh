@@ -15,5 +15,5 @@ LONG_PROFILE=1 LONG_PMC="--routes coop16 --sizes 256x1000000 --distinct 2" timeo
 fi
 if [ $step = all ] || [ $step = bench ]; then
 timeout -k 10 900 bash tools/results_table.sh > $O/results_table.log 2>&1; cp gpurun_out/results_table.md $O/ 2>/dev/null
-timeout -k 10 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
+timeout -k 10 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json
 fi

@@ -5,7 +5,7 @@ echo "| preset | stream profile | reads x anchors | G anchors/s | DP kernel ms /
 echo "|---|---|---|---|---|---|" >> $OUT
 row() {   # label-preset, label-profile, bench args...
   local lp="$1" lf="$2"; shift; shift
-  timeout -k 10 300 python bench.py --cpu-seconds 0 --steps 3 --warmup 1 --no-secondary "$@" 2>/dev/null | tail -1 | python3 -c "
+  timeout -k 10 300 python bench.py --full --cpu-seconds 0 --steps 3 --warmup 1 --no-secondary "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 c = d['config']
