@@ -1,5 +1,5 @@
 // api_internal.h -- shared between the translation units of the C-ABI shim (mm2chain_api.cpp: init, plans; mm2chain_host.cpp: host-buffer
-// paths; mm2chain_seeds.cpp: seed-hit entries).  Not installed; include/mm2chain.h is the public interface.
+// paths; mm2chain_seeds.cpp: seed-hit entries; mm2chain_sketch.cpp: reads-in entries).  Not installed; include/mm2chain.h is the public interface.
 #ifndef MM2C_API_INTERNAL_H
 #define MM2C_API_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -126,7 +126,7 @@ struct SeedSlot {
 	size_t cap_buf = 0, cap_hmeta = 0;
 	void *seedplan = nullptr, *plan = nullptr;   // the chunk's plans (their workspace comes from the device cache)
 	int64_t k0 = 0, k1 = 0;
-	size_t o_uo = 0, o_bo = 0, o_u = 0, o_b = 0, o_ao = 0;
+	size_t o_u = 0, o_b = 0;                  // where the chains of the chunk in flight lie in the arena
 	bool busy = false, timed = false;
 	void release()
 	{
@@ -196,6 +196,11 @@ hipError_t create_partner_stream(hipStream_t *st);
 int grow_device(char **p, size_t *cap, size_t need);
 int grow_pinned(char **p, size_t *cap, size_t need, bool gpu_addressed = false);
 inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// offsets of the pieces of one arena, each on a 256-byte boundary; `at` ends up as the arena's size
+struct Layout {
+	size_t at = 0;
+	size_t take(size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; }
+};
 int check_params(const mm2c_params_t *p);
 mm2c::KParams to_kparams(const mm2c_params_t *p);
 int check_offsets(int64_t n_tasks, const int64_t *off);
@@ -228,6 +233,35 @@ inline int resolve_stream(void *stream, int device, hipStream_t *out)
 	} else *out = (hipStream_t)stream;             // NULL = the HIP null stream (what a default-stream caller such as PyTorch works on)
 	return 0;
 }
+// the devices the library drives, each once, in configured order (G.devices may name a device twice)
+inline std::vector<int> distinct_devices(const std::vector<int> &devs)
+{
+	std::vector<int> out;
+	for (int dv : devs) if (std::find(out.begin(), out.end(), dv) == out.end()) out.push_back(dv);
+	return out;
+}
+// something resident with one copy per device the library drives (a split batch reads the copy of its own device)
+struct PerDevice {
+	std::vector<int> dev;
+	std::vector<void *> d;
+	hipError_t add(int device, size_t bytes)             // the copy of `device`, which the caller has made current; not filled yet
+	{
+		void *p = nullptr;
+		ScopedNs timed(SS.alloc_ns); ++SS.n_alloc;
+		const hipError_t e = hipMalloc(&p, bytes);
+		if (e == hipSuccess) { dev.push_back(device); d.push_back(p); }
+		return e;
+	}
+	void *on(int device) const
+	{
+		for (size_t j = 0; j < dev.size(); ++j) if (dev[j] == device) return d[j];
+		return nullptr;
+	}
+	void destroy()                                       // each copy after whatever its device still runs; the owner goes with them
+	{
+		for (size_t j = 0; j < dev.size(); ++j) { DeviceScope on(dev[j]); ScopedNs timed(SS.free_ns); ++SS.n_free; (void)hipDeviceSynchronize(); (void)hipFree(d[j]); }
+	}
+};
 void dev_cache_release();
 void release_combiner();                            // mm2chain_host.cpp
 int get_slot_stats(int slot, uint64_t *passes, uint64_t *calls, uint64_t *anchors);   // per-device combiner counters (mm2chain_host.cpp)
@@ -241,6 +275,26 @@ void aux_release(const AuxSet &a);
 // for callers that have already waited for the stream(s) the plan ran on: no device-wide wait (chunks of a pipelined batch overlap)
 void plan_destroy_synced(mm2c_plan_t *pl);          // mm2chain_api.cpp
 void seedplan_destroy_synced(mm2c_seedplan_t *pl);  // mm2chain_seeds.cpp
+
+// ---- shared by the matches-in entries (mm2chain_seeds.cpp, where all of this lives) and the reads-in entries (mm2chain_sketch.cpp)
+const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device);
+int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool);   // skip_seed against a resident pool, before any kernel runs
+// skip_seed from the host description to the device.  The rules, written once: without ref_rank no name is compared and nothing goes up; the two reference arrays
+// hold max(n_ref, 1) entries each; ref_len may be NULL (only NO_DIAG / NO_DUAL read it, and check_skip refuses them without); q_lo / q_eq go up when both are given.
+inline size_t skip_n_ref(const mm2c_seed_skip_host_t *skip) { return skip && skip->ref_rank ? (size_t)std::max<int32_t>(skip->n_ref, 1) : 0; }
+inline bool skip_per_read(const mm2c_seed_skip_host_t *skip) { return skip && skip->ref_rank && skip->q_lo && skip->q_eq; }
+hipError_t skip_upload_refs(const mm2c_seed_skip_host_t *skip, int32_t *d_rank, int32_t *d_len, hipStream_t st);   // enqueues ref_rank / ref_len (once per call)
+// enqueues q_lo / q_eq of reads [k0, k1) and fills the description the seed plan of those reads runs with
+hipError_t skip_upload_reads(const mm2c_seed_skip_host_t *skip, int64_t k0, int64_t k1, const int32_t *d_rank, const int32_t *d_len, int32_t *d_lo, int32_t *d_eq,
+                             hipStream_t st, mm2c_seed_skip_t *sk);
+// One chunk of whole reads on the device.  The part of its arena both paths lay out alike, behind whatever the caller has taken from `L` before ...
+struct ChunkLayout { size_t o_q, o_lo, o_eq, o_a, o_f, o_p, o_uo, o_bo, o_u, o_b, o_ao; };   // qlen | (q_lo | q_eq) | anchors | f | p | u_off | b_off | u | b | (packed anchor_off)
+ChunkLayout chunk_layout(Layout &L, size_t nr, size_t tot, bool per_read, bool packed_off);
+// ... and everything from the seed hits to the offsets' way down, enqueued on `st`: seed plan (sk != NULL: with skip_seed, and the chain plan then goes by the packed
+// offsets) -> DP -> epilogue -> h_off = [u_off | b_off | (packed anchor_off)] on the host.  qlen, q_lo, q_eq are in the arena `d` already, the matches wherever the
+// caller has them on the device.  ev_seed / ev_dp / ev_epi are recorded behind the stage they name; any of them may be NULL.
+int chunk_step(mm2c_seedplan_t *sp, mm2c_plan_t *pl, const mm2c_match_t *d_matches, const uint64_t *d_hits, int64_t n_hits, const mm2c_seed_skip_t *sk, char *d,
+               const ChunkLayout &o, int min_cnt, int min_sc, hipStream_t st, hipEvent_t ev_seed, hipEvent_t ev_dp, hipEvent_t ev_epi, int64_t *h_off);
 
 } // namespace mm2c_api
 #endif

@@ -659,11 +659,9 @@ int mm2c_warm_up(void)
 	int prev = -1;
 	(void)hipGetDevice(&prev);
 	hipError_t e = hipSuccess;
-	for (size_t k = 0; k < devs.size() && e == hipSuccess; ++k) {
-		bool seen = false;
-		for (size_t j = 0; j < k; ++j) seen = seen || devs[j] == devs[k];
-		if (seen) continue;
-		e = hipSetDevice(devs[k]);
+	for (int dv : distinct_devices(devs)) {
+		if (e != hipSuccess) break;
+		e = hipSetDevice(dv);
 		if (e == hipSuccess) e = mm2c::warm_chain_kernels();
 		if (e == hipSuccess) e = mm2c::warm_epilogue_kernels();
 		if (e == hipSuccess) e = mm2c::warm_seed_kernels();

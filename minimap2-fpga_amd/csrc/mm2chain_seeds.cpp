@@ -21,6 +21,13 @@ struct mm2c_seedplan {
 	bool ran = false;
 };
 
+// the index's position arrays resident on the device(s)
+struct mm2c_hitpool {
+	int64_t n = 0;
+	int64_t max_rid = -1;                      // the largest reference id among the hits (-1: none): the skip_seed entries check it against n_ref
+	PerDevice copies;
+};
+
 // helper streams and fork / join events of the seed plans, kept between plans: a pipelined batch makes a plan per chunk, and creating three
 // streams of distinct priority per plan cost milliseconds each
 namespace {
@@ -82,6 +89,115 @@ void release_seed_aux()                       // mm2c_shutdown
 	for (AuxSet &a : g_aux_free) aux_destroy(a);
 	g_aux_free.clear();
 }
+
+namespace {
+// One walk over the matches of reads [0, n_reads), the only one a host-buffer entry makes.  cap[0 .. n_reads]: the prefix sums of the reads' hit counts (their anchor
+// capacities).  cr_lo / cr_hi (unless NULL): per read the range of the hit pool its matches point into (INT64_MAX, 0: no hit); range: that of all reads.
+int scan_matches(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, int64_t n_hits, int64_t *cap, int64_t *cr_lo, int64_t *cr_hi, int64_t range[2])
+{
+	if (h_match_off[n_reads] > h_match_off[0] && !h_matches) return fail(MM2C_E_ARG, "matches is NULL");
+	range[0] = INT64_MAX; range[1] = cap[0] = 0;
+	for (int64_t r = 0; r < n_reads; ++r) {
+		int64_t sum = 0, lo = INT64_MAX, hi = 0;
+		if (h_match_off[r + 1] < h_match_off[r]) return fail(MM2C_E_ARG, "match offsets not monotone at read %lld", (long long)r);
+		for (int64_t i = h_match_off[r]; i < h_match_off[r + 1]; ++i) {
+			const int64_t c0 = h_matches[i].cr_off, c1 = c0 + (int64_t)h_matches[i].n;
+			if (c0 < 0 || c1 > n_hits) return fail(MM2C_E_ARG, "match %lld reaches beyond the hit pool", (long long)i);
+			sum += h_matches[i].n;
+			if (h_matches[i].n) { lo = std::min(lo, c0); hi = std::max(hi, c1); }
+		}
+		if (cr_lo) { cr_lo[r] = lo; cr_hi[r] = hi; }
+		range[0] = std::min(range[0], lo); range[1] = std::max(range[1], hi);
+		cap[r + 1] = cap[r] + sum;
+	}
+	return 0;
+}
+
+// skip_seed on the host-buffer entries, checked before any kernel runs: the flag bits and the arrays NO_DIAG / NO_DUAL read ...
+int check_skip(const mm2c_seed_skip_host_t *skip, int64_t n_reads)
+{
+	if (!skip) return fail(MM2C_E_ARG, "skip description is NULL");
+	if (skip->flag & ~(0x001 | 0x002 | 0x100000 | 0x200000)) return fail(MM2C_E_ARG, "skip flag 0x%x has bits other than NO_DIAG, NO_DUAL, FOR_ONLY, REV_ONLY", (unsigned)skip->flag);
+	if (!skip->ref_rank) return 0;                                   // qname == NULL: no name comparison, no rid looked up
+	if (skip->n_ref < 0) return fail(MM2C_E_ARG, "n_ref is negative");
+	if ((skip->flag & (0x001 | 0x002)) && (!skip->ref_len || (n_reads > 0 && (!skip->q_lo || !skip->q_eq))))
+		return fail(MM2C_E_ARG, "NO_DIAG / NO_DUAL with ref_rank need ref_len, q_lo and q_eq");
+	return 0;
+}
+
+// ... and every hit the device will look up in ref_rank (rid < n_ref): for a resident pool the largest rid recorded when it was made, for host hits
+// that of the range [lo, hi) of the pool the matches point into (scan_matches)
+int check_skip_rids(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool *pool, const uint64_t *h_hits, int64_t lo, int64_t hi)
+{
+	if (!skip->ref_rank || n_reads <= 0) return 0;
+	if (!pool && hi > lo && !h_hits) return fail(MM2C_E_ARG, "host pointer is NULL");
+	int64_t max_rid = pool ? pool->max_rid : -1;
+	for (int64_t i = lo; !pool && i < hi; ++i) max_rid = std::max(max_rid, (int64_t)(h_hits[i] >> 32));
+	if (max_rid >= skip->n_ref) return fail(MM2C_E_ARG, "a hit names reference %lld, beyond the %d of ref_rank", (long long)max_rid, (int)skip->n_ref);
+	return 0;
+}
+}
+
+const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device) { return hp ? (const uint64_t *)hp->copies.on(device) : nullptr; }
+
+int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool)
+{
+	const int rc = check_skip(skip, n_reads);
+	return rc ? rc : check_skip_rids(skip, n_reads, pool, nullptr, 0, 0);
+}
+
+hipError_t skip_upload_refs(const mm2c_seed_skip_host_t *skip, int32_t *d_rank, int32_t *d_len, hipStream_t st)
+{
+	if (!skip_n_ref(skip) || skip->n_ref <= 0) return hipSuccess;
+	hipError_t e = hipMemcpyAsync(d_rank, skip->ref_rank, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess && skip->ref_len) e = hipMemcpyAsync(d_len, skip->ref_len, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st);
+	return e;
+}
+
+hipError_t skip_upload_reads(const mm2c_seed_skip_host_t *skip, int64_t k0, int64_t k1, const int32_t *d_rank, const int32_t *d_len, int32_t *d_lo, int32_t *d_eq,
+                             hipStream_t st, mm2c_seed_skip_t *sk)
+{
+	const bool names = skip->ref_rank != nullptr;
+	*sk = mm2c_seed_skip_t{ skip->flag, names ? d_rank : nullptr, names && skip->ref_len ? d_len : nullptr, nullptr, nullptr };
+	if (!skip_per_read(skip)) return hipSuccess;
+	const size_t bytes = (size_t)(k1 - k0) * 4;
+	hipError_t e = hipMemcpyAsync(d_lo, skip->q_lo + k0, bytes, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_eq, skip->q_eq + k0, bytes, hipMemcpyHostToDevice, st);
+	sk->d_q_lo = d_lo; sk->d_q_eq = d_eq;
+	return e;
+}
+
+ChunkLayout chunk_layout(Layout &L, size_t nr, size_t tot, bool per_read, bool packed_off)
+{
+	ChunkLayout o;
+	o.o_q = L.take(nr * 4); o.o_lo = L.take(per_read ? nr * 4 : 0); o.o_eq = L.take(per_read ? nr * 4 : 0);
+	o.o_a = L.take(tot * 16); o.o_f = L.take(tot * 4); o.o_p = L.take(tot * 4);
+	o.o_uo = L.take((nr + 1) * 8); o.o_bo = L.take((nr + 1) * 8); o.o_u = L.take(tot * 8); o.o_b = L.take(tot * 16);
+	o.o_ao = L.take(packed_off ? (nr + 1) * 8 : 0);
+	return o;
+}
+
+int chunk_step(mm2c_seedplan_t *sp, mm2c_plan_t *pl, const mm2c_match_t *d_matches, const uint64_t *d_hits, int64_t n_hits, const mm2c_seed_skip_t *sk, char *d,
+               const ChunkLayout &o, int min_cnt, int min_sc, hipStream_t st, hipEvent_t ev_seed, hipEvent_t ev_dp, hipEvent_t ev_epi, int64_t *h_off)
+{
+	int r;
+	const int64_t nr = sp->n_reads;
+	const int32_t *d_qlen = (const int32_t *)(d + o.o_q);
+	int32_t *d_f = (int32_t *)(d + o.o_f), *d_p = (int32_t *)(d + o.o_p);
+	if (sk) {
+		if ((r = mm2c_seedplan_run_device_skip(sp, d_matches, sp->n_matches, d_hits, n_hits, d_qlen, nr, sk, d + o.o_a, sp->total, (int64_t *)(d + o.o_ao), st))) return r;
+		if ((r = mm2c_plan_set_device_offsets(pl, (const int64_t *)(d + o.o_ao)))) return r;   // the chains go by the packed offsets
+	} else if ((r = mm2c_seedplan_run_device(sp, d_matches, d_hits, d_qlen, d + o.o_a, st))) return r;
+	if (ev_seed) HIP_TRY(hipEventRecord(ev_seed, st));
+	if ((r = mm2c_plan_run_device(pl, d + o.o_a, nullptr, d_f, d_p, st))) return r;
+	if (ev_dp) HIP_TRY(hipEventRecord(ev_dp, st));
+	if ((r = mm2c_plan_chains_device(pl, d + o.o_a, d_f, d_p, min_cnt, min_sc, (int64_t *)(d + o.o_uo), (uint64_t *)(d + o.o_u), (int64_t *)(d + o.o_bo), d + o.o_b, st))) return r;
+	if (ev_epi) HIP_TRY(hipEventRecord(ev_epi, st));
+	HIP_TRY(hipMemcpyAsync(h_off, d + o.o_uo, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(h_off + nr + 1, d + o.o_bo, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (sk) HIP_TRY(hipMemcpyAsync(h_off + 2 * (nr + 1), d + o.o_ao, ((size_t)nr + 1) * 8, hipMemcpyDeviceToHost, st));
+	return 0;
+}
 }
 
 extern "C" {
@@ -111,15 +227,14 @@ mm2c_seedplan_t *mm2c_seedplan_create(int64_t n_reads, const int64_t *h_match_of
 	int64_t tie_global_above = mm2c::seed_tie_lds_max();
 	{ const char *tg = getenv("MM2C_TIE_GLOBAL_ABOVE"); if (tg) tie_global_above = std::max(64, atoi(tg)); else if (n_mid > 512) tie_global_above = mm2c::seed_tie_mid_lower(); }
 	const bool big = biggest > tie_global_above;
-	size_t at = 0;
-	auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-	const size_t o_moff = take((nr + 1) * 8), o_aoff = take((nr + 1) * 8), o_ord = take(nr * 4), o_stat = take(nr * 4), o_ties = take(nr * 4),
-	             o_stack = take(4 * (tot / 64 + 2 * nr + 2) * 4), o_un = take(tot * 16), o_scr = take(tot * 16), o_tc = take(tot * 4), o_xd = take(nr * 8),
-	             o_bid = take(tot * 4), o_bdg = take(big ? tot + nr + 64 : 1), o_cnt = take(nr * 4), o_oo = take((nr + 1) * 8);
+	Layout L;
+	const size_t o_moff = L.take((nr + 1) * 8), o_aoff = L.take((nr + 1) * 8), o_ord = L.take(nr * 4), o_stat = L.take(nr * 4), o_ties = L.take(nr * 4),
+	             o_stack = L.take(4 * (tot / 64 + 2 * nr + 2) * 4), o_un = L.take(tot * 16), o_scr = L.take(tot * 16), o_tc = L.take(tot * 4), o_xd = L.take(nr * 8),
+	             o_bid = L.take(tot * 4), o_bdg = L.take(big ? tot + nr + 64 : 1), o_cnt = L.take(nr * 4), o_oo = L.take((nr + 1) * 8);
 	pl->device = cur_device();
 	DeviceScope on(pl->device);
 	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, at);
+	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
 	if (e == hipSuccess && n_reads > 0) {
 		std::vector<int64_t> off((size_t)n_reads + 1);
 		for (int64_t k = 0; k <= n_reads; ++k) off[(size_t)k] = h_match_off[k] - h_match_off[0];
@@ -288,64 +403,7 @@ int mm2c_seedplan_last_ms(mm2c_seedplan_t *pl, float *ms)
 	return 0;
 }
 
-int mm2c_seed_hits_batch_host(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits,
-                              int64_t n_hits, const int32_t *h_qlen, int64_t *anchor_off, mm2c_anchor_t *anchors)
-{
-	if (n_reads < 0 || !anchor_off) return fail(MM2C_E_ARG, "bad argument");
-	anchor_off[0] = 0;
-	if (n_reads == 0) return 0;
-	if (!h_match_off || !h_qlen) return fail(MM2C_E_ARG, "host pointer is NULL");
-	const int64_t mb = h_match_off[0], n_m = h_match_off[n_reads] - mb;
-	if (n_m > 0 && !h_matches) return fail(MM2C_E_ARG, "matches is NULL");
-	for (int64_t r = 0; r < n_reads; ++r) {
-		int64_t sum = 0;
-		if (h_match_off[r + 1] < h_match_off[r]) return fail(MM2C_E_ARG, "match offsets not monotone at read %lld", (long long)r);
-		for (int64_t i = h_match_off[r]; i < h_match_off[r + 1]; ++i) {
-			if (h_matches[i].cr_off < 0 || h_matches[i].cr_off + (int64_t)h_matches[i].n > n_hits)
-				return fail(MM2C_E_ARG, "match %lld reaches beyond the hit pool", (long long)i);
-			sum += h_matches[i].n;
-		}
-		anchor_off[r + 1] = anchor_off[r] + sum;
-	}
-	const int64_t total = anchor_off[n_reads];
-	if (total == 0) return 0;
-	if (!h_hits || !anchors) return fail(MM2C_E_ARG, "host pointer is NULL");
-	mm2c_seedplan_t *pl = mm2c_seedplan_create(n_reads, h_match_off, anchor_off);
-	if (!pl) return MM2C_E_HIP;
-	char *d = nullptr;
-	size_t at = 0;
-	auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-	const size_t o_m = take((size_t)n_m * sizeof(mm2c_match_t)), o_h = take((size_t)n_hits * 8), o_q = take((size_t)n_reads * 4), o_a = take((size_t)total * 16);
-	auto body = [&]() -> int {
-		int r;
-		HIP_TRY(dev_alloc((void **)&d, at));
-		HIP_TRY(hipMemcpyAsync(d + o_m, h_matches + mb, (size_t)n_m * sizeof(mm2c_match_t), hipMemcpyHostToDevice, G.stream));
-		HIP_TRY(hipMemcpyAsync(d + o_h, h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice, G.stream));
-		HIP_TRY(hipMemcpyAsync(d + o_q, h_qlen, (size_t)n_reads * 4, hipMemcpyHostToDevice, G.stream));
-		if ((r = mm2c_seedplan_run_device(pl, (const mm2c_match_t *)(d + o_m), (const uint64_t *)(d + o_h), (const int32_t *)(d + o_q), d + o_a, G.stream))) return r;
-		HIP_TRY(hipMemcpyAsync(anchors, d + o_a, (size_t)total * 16, hipMemcpyDeviceToHost, G.stream));
-		HIP_TRY(hipStreamSynchronize(G.stream));
-		return mm2c_seedplan_check(pl, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
-	mm2c_seedplan_destroy(pl);
-	return rc;
-}
-
 // ---- the index's position arrays resident on the device(s)
-struct mm2c_hitpool;
-static int check_skip(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches,
-                      const uint64_t *h_hits, int64_t n_hits, const mm2c_hitpool *pool);
-
-struct mm2c_hitpool {
-	int64_t n = 0;
-	int64_t max_rid = -1;                      // the largest reference id among the hits (-1: none): the skip_seed entries check it against n_ref
-	int n_dev = 0;
-	int dev[64] = {};
-	uint64_t *d[64] = {};                       // one copy per device the library drives (a split batch reads the copy of its own device)
-};
-
 mm2c_hitpool_t *mm2c_hitpool_create(const uint64_t *h_hits, int64_t n_hits)
 {
 	if (!lib_ready()) { fail_not_ready(); return nullptr; }
@@ -353,18 +411,12 @@ mm2c_hitpool_t *mm2c_hitpool_create(const uint64_t *h_hits, int64_t n_hits)
 	mm2c_hitpool *hp = new mm2c_hitpool();
 	hp->n = n_hits;
 	for (int64_t i = 0; i < n_hits; ++i) hp->max_rid = std::max(hp->max_rid, (int64_t)(h_hits[i] >> 32));
-	for (size_t k = 0; k < G.devices.size() && hp->n_dev < 64; ++k) {
-		const int dv = G.devices[k];
-		bool seen = false;
-		for (int j = 0; j < hp->n_dev; ++j) seen = seen || hp->dev[j] == dv;
-		if (seen) continue;
+	for (int dv : distinct_devices(G.devices)) {
 		DeviceScope on(dv);
-		void *p = nullptr;
 		hipError_t e = on.err;
-		{ ScopedNs timed(SS.alloc_ns); ++SS.n_alloc; if (e == hipSuccess) e = hipMalloc(&p, (size_t)std::max<int64_t>(n_hits, 1) * 8); }
-		if (e == hipSuccess && n_hits > 0) e = hipMemcpy(p, h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice);
-		if (e != hipSuccess) { if (p) (void)hipFree(p); fail(MM2C_E_HIP, "mm2c_hitpool_create: %s", hipGetErrorString(e)); mm2c_hitpool_destroy(hp); return nullptr; }
-		hp->dev[hp->n_dev] = dv; hp->d[hp->n_dev] = (uint64_t *)p; ++hp->n_dev;
+		if (e == hipSuccess) e = hp->copies.add(dv, (size_t)std::max<int64_t>(n_hits, 1) * 8);
+		if (e == hipSuccess && n_hits > 0) e = hipMemcpy(hp->copies.d.back(), h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice);
+		if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_hitpool_create: %s", hipGetErrorString(e)); mm2c_hitpool_destroy(hp); return nullptr; }
 	}
 	return hp;
 }
@@ -374,108 +426,75 @@ int64_t mm2c_hitpool_size(const mm2c_hitpool_t *hp) { return hp ? hp->n : 0; }
 void mm2c_hitpool_destroy(mm2c_hitpool_t *hp)
 {
 	if (!hp) return;
-	for (int j = 0; j < hp->n_dev; ++j) { DeviceScope on(hp->dev[j]); ScopedNs timed(SS.free_ns); ++SS.n_free; (void)hipDeviceSynchronize(); (void)hipFree(hp->d[j]); }
+	hp->copies.destroy();
 	delete hp;
 }
 
-static const uint64_t *pool_on(const mm2c_hitpool_t *hp, int device)
+// matches in, sorted anchors out (collect_seed_hits for a batch of reads).  skipping: skip_seed -- the reads keep fewer anchors than they have hits; the plan is
+// then sized by the capacities (every hit, in `cap`), packs each read's kept anchors, and the caller's anchor_off receives the packed offsets.
+static int seed_hits_impl(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits, int64_t n_hits, const int32_t *h_qlen,
+                          const mm2c_seed_skip_host_t *skip, bool skipping, int64_t *anchor_off, mm2c_anchor_t *anchors)
 {
-	for (int j = 0; j < hp->n_dev; ++j) if (hp->dev[j] == device) return hp->d[j];
-	return nullptr;
+	if (n_reads < 0 || !anchor_off) return fail(MM2C_E_ARG, "bad argument");
+	anchor_off[0] = 0;
+	if (n_reads == 0) return skipping && !skip ? fail(MM2C_E_ARG, "skip description is NULL") : 0;
+	if (!h_match_off || !h_qlen) return fail(MM2C_E_ARG, "host pointer is NULL");
+	const int64_t mb = h_match_off[0], n_m = h_match_off[n_reads] - mb;
+	std::vector<int64_t> cap_off(skipping ? (size_t)n_reads + 1 : 0);   // (without skip_seed anchor_off holds the capacities, exact)
+	int64_t *cap = skipping ? cap_off.data() : anchor_off;
+	int64_t range[2];
+	int rc;
+	if ((rc = scan_matches(n_reads, h_match_off, h_matches, n_hits, cap, nullptr, nullptr, range))) return rc;
+	if (skipping && ((rc = check_skip(skip, n_reads)) || (rc = check_skip_rids(skip, n_reads, nullptr, h_hits, range[0], range[1])))) return rc;
+	const int64_t total = cap[n_reads];
+	if (total == 0) { for (int64_t r = 1; r <= n_reads; ++r) anchor_off[r] = 0; return 0; }
+	if (!h_hits || !anchors) return fail(MM2C_E_ARG, "host pointer is NULL");
+	mm2c_seedplan_t *pl = mm2c_seedplan_create(n_reads, h_match_off, cap);
+	if (!pl) return MM2C_E_HIP;
+	const size_t n_ref = skipping ? std::max<size_t>(skip_n_ref(skip), 1) : 0, nr = skipping ? (size_t)n_reads : 0;
+	char *d = nullptr;
+	Layout L;
+	const size_t o_m = L.take((size_t)n_m * sizeof(mm2c_match_t)), o_h = L.take((size_t)n_hits * 8), o_q = L.take((size_t)n_reads * 4), o_a = L.take((size_t)total * 16),
+	             o_rr = L.take(n_ref * 4), o_rl = L.take(n_ref * 4), o_lo = L.take(nr * 4), o_eq = L.take(nr * 4), o_ao = L.take(skipping ? (nr + 1) * 8 : 0);
+	auto body = [&]() -> int {
+		int r;
+		HIP_TRY(dev_alloc((void **)&d, L.at));
+		const mm2c_match_t *d_m = (const mm2c_match_t *)(d + o_m);
+		HIP_TRY(hipMemcpyAsync(d + o_m, h_matches + mb, (size_t)n_m * sizeof(mm2c_match_t), hipMemcpyHostToDevice, G.stream));
+		HIP_TRY(hipMemcpyAsync(d + o_h, h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice, G.stream));
+		HIP_TRY(hipMemcpyAsync(d + o_q, h_qlen, (size_t)n_reads * 4, hipMemcpyHostToDevice, G.stream));
+		if (skipping) {
+			mm2c_seed_skip_t sk;
+			HIP_TRY(skip_upload_refs(skip, (int32_t *)(d + o_rr), (int32_t *)(d + o_rl), G.stream));
+			HIP_TRY(skip_upload_reads(skip, 0, n_reads, (const int32_t *)(d + o_rr), (const int32_t *)(d + o_rl), (int32_t *)(d + o_lo), (int32_t *)(d + o_eq), G.stream, &sk));
+			if ((r = mm2c_seedplan_run_device_skip(pl, d_m, n_m, (const uint64_t *)(d + o_h), n_hits, (const int32_t *)(d + o_q), n_reads, &sk, d + o_a, total,
+			                                       (int64_t *)(d + o_ao), G.stream))) return r;
+			HIP_TRY(hipMemcpyAsync(anchor_off, d + o_ao, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, G.stream));
+		} else {
+			if ((r = mm2c_seedplan_run_device(pl, d_m, (const uint64_t *)(d + o_h), (const int32_t *)(d + o_q), d + o_a, G.stream))) return r;
+			HIP_TRY(hipMemcpyAsync(anchors, d + o_a, (size_t)total * 16, hipMemcpyDeviceToHost, G.stream));
+		}
+		HIP_TRY(hipStreamSynchronize(G.stream));
+		if ((r = mm2c_seedplan_check(pl, nullptr))) return r;
+		if (skipping && anchor_off[n_reads] > 0) HIP_TRY(hipMemcpy(anchors, d + o_a, (size_t)anchor_off[n_reads] * 16, hipMemcpyDeviceToHost));   // the kept ones
+		return 0;
+	};
+	rc = body();
+	dev_free(d);
+	mm2c_seedplan_destroy(pl);
+	return rc;
 }
 
-// skip_seed on the host-buffer entries, checked before any kernel runs: the flag bits, the arrays NO_DIAG / NO_DUAL read, and every hit the device will look up in
-// ref_rank (rid < n_ref) -- for host hits the range of the pool the matches point into, for a resident pool the largest rid recorded when it was made
-static int check_skip(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches,
-                      const uint64_t *h_hits, int64_t n_hits, const mm2c_hitpool *pool)
+int mm2c_seed_hits_batch_host(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits,
+                              int64_t n_hits, const int32_t *h_qlen, int64_t *anchor_off, mm2c_anchor_t *anchors)
 {
-	if (!skip) return fail(MM2C_E_ARG, "skip description is NULL");
-	if (skip->flag & ~(0x001 | 0x002 | 0x100000 | 0x200000)) return fail(MM2C_E_ARG, "skip flag 0x%x has bits other than NO_DIAG, NO_DUAL, FOR_ONLY, REV_ONLY", (unsigned)skip->flag);
-	if (!skip->ref_rank) return 0;                                   // qname == NULL: no name comparison, no rid looked up
-	if (skip->n_ref < 0) return fail(MM2C_E_ARG, "n_ref is negative");
-	if ((skip->flag & (0x001 | 0x002)) && (!skip->ref_len || (n_reads > 0 && (!skip->q_lo || !skip->q_eq))))
-		return fail(MM2C_E_ARG, "NO_DIAG / NO_DUAL with ref_rank need ref_len, q_lo and q_eq");
-	if (n_reads <= 0) return 0;
-	int64_t max_rid = -1;
-	if (pool) max_rid = pool->max_rid;
-	else {
-		int64_t lo = INT64_MAX, hi = 0;
-		for (int64_t i = h_match_off[0]; i < h_match_off[n_reads]; ++i) {
-			const int64_t c0 = h_matches[i].cr_off, c1 = c0 + (int64_t)h_matches[i].n;
-			if (c0 < 0 || c1 > n_hits) return fail(MM2C_E_ARG, "match %lld reaches beyond the hit pool", (long long)i);
-			if (h_matches[i].n) { lo = std::min(lo, c0); hi = std::max(hi, c1); }
-		}
-		if (hi > lo && !h_hits) return fail(MM2C_E_ARG, "host pointer is NULL");
-		for (int64_t i = lo; i < hi; ++i) max_rid = std::max(max_rid, (int64_t)(h_hits[i] >> 32));
-	}
-	if (max_rid >= skip->n_ref) return fail(MM2C_E_ARG, "a hit names reference %lld, beyond the %d of ref_rank", (long long)max_rid, (int)skip->n_ref);
-	return 0;
+	return seed_hits_impl(n_reads, h_match_off, h_matches, h_hits, n_hits, h_qlen, nullptr, false, anchor_off, anchors);
 }
 
 int mm2c_seed_hits_batch_host_skip(int64_t n_reads, const int64_t *h_match_off, const mm2c_match_t *h_matches, const uint64_t *h_hits,
                                    int64_t n_hits, const int32_t *h_qlen, const mm2c_seed_skip_host_t *skip, int64_t *anchor_off, mm2c_anchor_t *anchors)
 {
-	if (n_reads < 0 || !anchor_off) return fail(MM2C_E_ARG, "bad argument");
-	anchor_off[0] = 0;
-	if (n_reads == 0) return skip ? 0 : fail(MM2C_E_ARG, "skip description is NULL");
-	if (!h_match_off || !h_qlen) return fail(MM2C_E_ARG, "host pointer is NULL");
-	const int64_t mb = h_match_off[0], n_m = h_match_off[n_reads] - mb;
-	if (n_m > 0 && !h_matches) return fail(MM2C_E_ARG, "matches is NULL");
-	std::vector<int64_t> cap((size_t)n_reads + 1, 0);                 // the plan's offsets: capacities (every hit); the caller's get the packed ones
-	for (int64_t r = 0; r < n_reads; ++r) {
-		int64_t sum = 0;
-		if (h_match_off[r + 1] < h_match_off[r]) return fail(MM2C_E_ARG, "match offsets not monotone at read %lld", (long long)r);
-		for (int64_t i = h_match_off[r]; i < h_match_off[r + 1]; ++i) {
-			if (h_matches[i].cr_off < 0 || h_matches[i].cr_off + (int64_t)h_matches[i].n > n_hits)
-				return fail(MM2C_E_ARG, "match %lld reaches beyond the hit pool", (long long)i);
-			sum += h_matches[i].n;
-		}
-		cap[(size_t)r + 1] = cap[(size_t)r] + sum;
-	}
-	int rc;
-	if ((rc = check_skip(skip, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr))) return rc;
-	const int64_t total = cap[(size_t)n_reads];
-	if (total == 0) { for (int64_t r = 1; r <= n_reads; ++r) anchor_off[r] = 0; return 0; }
-	if (!h_hits || !anchors) return fail(MM2C_E_ARG, "host pointer is NULL");
-	mm2c_seedplan_t *pl = mm2c_seedplan_create(n_reads, h_match_off, cap.data());
-	if (!pl) return MM2C_E_HIP;
-	const bool names = skip->ref_rank != nullptr, per_read = names && skip->q_lo && skip->q_eq;
-	const int64_t n_ref = names ? std::max<int32_t>(skip->n_ref, 1) : 1;
-	char *d = nullptr;
-	size_t at = 0;
-	auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-	const size_t o_m = take((size_t)n_m * sizeof(mm2c_match_t)), o_h = take((size_t)n_hits * 8), o_q = take((size_t)n_reads * 4), o_a = take((size_t)total * 16),
-	             o_rr = take((size_t)n_ref * 4), o_rl = take((size_t)n_ref * 4), o_lo = take((size_t)n_reads * 4), o_eq = take((size_t)n_reads * 4),
-	             o_ao = take(((size_t)n_reads + 1) * 8);
-	auto body = [&]() -> int {
-		int r;
-		HIP_TRY(dev_alloc((void **)&d, at));
-		HIP_TRY(hipMemcpyAsync(d + o_m, h_matches + mb, (size_t)n_m * sizeof(mm2c_match_t), hipMemcpyHostToDevice, G.stream));
-		HIP_TRY(hipMemcpyAsync(d + o_h, h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice, G.stream));
-		HIP_TRY(hipMemcpyAsync(d + o_q, h_qlen, (size_t)n_reads * 4, hipMemcpyHostToDevice, G.stream));
-		mm2c_seed_skip_t sk = { skip->flag, nullptr, nullptr, nullptr, nullptr };
-		if (names) {
-			if (skip->n_ref > 0) HIP_TRY(hipMemcpyAsync(d + o_rr, skip->ref_rank, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, G.stream));
-			if (skip->n_ref > 0 && skip->ref_len) HIP_TRY(hipMemcpyAsync(d + o_rl, skip->ref_len, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, G.stream));
-			sk.d_ref_rank = (const int32_t *)(d + o_rr); sk.d_ref_len = skip->ref_len ? (const int32_t *)(d + o_rl) : nullptr;
-		}
-		if (per_read) {
-			HIP_TRY(hipMemcpyAsync(d + o_lo, skip->q_lo, (size_t)n_reads * 4, hipMemcpyHostToDevice, G.stream));
-			HIP_TRY(hipMemcpyAsync(d + o_eq, skip->q_eq, (size_t)n_reads * 4, hipMemcpyHostToDevice, G.stream));
-			sk.d_q_lo = (const int32_t *)(d + o_lo); sk.d_q_eq = (const int32_t *)(d + o_eq);
-		}
-		if ((r = mm2c_seedplan_run_device_skip(pl, (const mm2c_match_t *)(d + o_m), n_m, (const uint64_t *)(d + o_h), n_hits, (const int32_t *)(d + o_q), n_reads, &sk,
-		                                       d + o_a, total, (int64_t *)(d + o_ao), G.stream))) return r;
-		HIP_TRY(hipMemcpyAsync(anchor_off, d + o_ao, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, G.stream));
-		HIP_TRY(hipStreamSynchronize(G.stream));
-		if ((r = mm2c_seedplan_check(pl, nullptr))) return r;
-		if (anchor_off[n_reads] > 0) HIP_TRY(hipMemcpy(anchors, d + o_a, (size_t)anchor_off[n_reads] * 16, hipMemcpyDeviceToHost));
-		return 0;
-	};
-	const int rc2 = body();
-	dev_free(d);
-	mm2c_seedplan_destroy(pl);
-	return rc2;
+	return seed_hits_impl(n_reads, h_match_off, h_matches, h_hits, n_hits, h_qlen, skip, true, anchor_off, anchors);
 }
 
 // matches in, chains out: collect_seed_hits + mm_chain_dp for a batch of reads (map.c:295-316) without the anchors leaving the GPU.
@@ -483,12 +502,13 @@ int mm2c_seed_hits_batch_host_skip(int64_t n_reads, const int64_t *h_match_off, 
 // uploads and the chains of chunk k-1 download.  Per chunk: a seed plan and a chain plan (workspace from the device cache: chunks are of
 // similar size, so after the first ones nothing is allocated) and one grow-only arena per slot.  hits come from the caller's host pool
 // (only the range the chunk's matches point into is uploaded; a pool that is shared by all chunks is uploaded once) or from a resident pool.
-// skip (checked by the caller, check_skip): skip_seed -- the reads keep fewer anchors than they have hits.  Chunks, arenas and plans are then sized by the
+// skip (its description checked by the caller, check_skip; with check_rids its hits' reference ids here, once the scan knows which hits of a host pool are
+// meant): skip_seed -- the reads keep fewer anchors than they have hits.  Chunks, arenas and plans are then sized by the
 // capacities (every hit, kept in `cap`), the seed plans run with the skip description and pack each read's kept anchors, the chain plans take those packed
 // offsets from the device, and the caller's anchor_off receives them chunk by chunk, placed behind the chunks before.
 static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
                            const mm2c_match_t *h_matches, const uint64_t *h_hits, int64_t n_hits, const mm2c_hitpool_t *pool, const int32_t *h_qlen,
-                           const mm2c_seed_skip_host_t *skip, int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
+                           const mm2c_seed_skip_host_t *skip, bool check_rids, int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
 {
 	int rc;
 	ScopedNs timed_total(SS.total_ns);
@@ -498,28 +518,15 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 	if (n_reads == 0) return 0;
 	if (!h_match_off || !h_qlen) return fail(MM2C_E_ARG, "host pointer is NULL");
 	if (pool) n_hits = pool->n;
-	const int64_t mb = h_match_off[0], n_m = h_match_off[n_reads] - mb;
-	if (n_m > 0 && !h_matches) return fail(MM2C_E_ARG, "matches is NULL");
-	std::vector<int64_t> cr_lo, cr_hi;                      // per read: the range of the hit pool its matches point into
-	std::vector<int64_t> cap_off;                           // skip_seed: the capacities' prefix sums (without it anchor_off holds them, exact)
-	if (skip) cap_off.assign((size_t)n_reads + 1, 0);
+	std::vector<int64_t> cr_lo((size_t)n_reads), cr_hi((size_t)n_reads);   // per read: the range of the hit pool its matches point into
+	std::vector<int64_t> cap_off(skip ? (size_t)n_reads + 1 : 0);   // skip_seed: the capacities' prefix sums (without it anchor_off holds them, exact)
 	int64_t *cap = skip ? cap_off.data() : anchor_off;
+	int64_t range[2];
 	{
 		ScopedNs timed(SS.setup_ns);
-		cr_lo.resize((size_t)n_reads); cr_hi.resize((size_t)n_reads);
-		for (int64_t r = 0; r < n_reads; ++r) {
-			int64_t sum = 0, lo = INT64_MAX, hi = 0;
-			if (h_match_off[r + 1] < h_match_off[r]) return fail(MM2C_E_ARG, "match offsets not monotone at read %lld", (long long)r);
-			for (int64_t i = h_match_off[r]; i < h_match_off[r + 1]; ++i) {
-				const int64_t c0 = h_matches[i].cr_off, c1 = c0 + (int64_t)h_matches[i].n;
-				if (c0 < 0 || c1 > n_hits) return fail(MM2C_E_ARG, "match %lld reaches beyond the hit pool", (long long)i);
-				sum += h_matches[i].n;
-				if (h_matches[i].n) { lo = std::min(lo, c0); hi = std::max(hi, c1); }
-			}
-			cr_lo[(size_t)r] = lo; cr_hi[(size_t)r] = hi;
-			cap[r + 1] = cap[r] + sum;
-		}
+		if ((rc = scan_matches(n_reads, h_match_off, h_matches, n_hits, cap, cr_lo.data(), cr_hi.data(), range))) return rc;
 	}
+	if (check_rids && (rc = check_skip_rids(skip, n_reads, nullptr, h_hits, range[0], range[1]))) return rc;
 	const int64_t total = cap[n_reads];
 	if (total == 0) { for (int64_t r = 1; r <= n_reads; ++r) anchor_off[r] = u_off[r] = b_off[r] = 0; return 0; }
 	if ((!pool && !h_hits) || !u || !b) return fail(MM2C_E_ARG, "host pointer is NULL");
@@ -535,7 +542,7 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 			const int64_t at = cap[k0];
 			mm2c_seed_skip_host_t sk;                                      // the part's reads: their per-read arrays from k0 on
 			if (skip) { sk = *skip; if (sk.q_lo) sk.q_lo += k0; if (sk.q_eq) sk.q_eq += k0; }
-			return seed_chain_impl(par, min_cnt, min_sc, k1 - k0, h_match_off + k0, h_matches, h_hits, n_hits, pool, h_qlen + k0, skip ? &sk : nullptr,
+			return seed_chain_impl(par, min_cnt, min_sc, k1 - k0, h_match_off + k0, h_matches, h_hits, n_hits, pool, h_qlen + k0, skip ? &sk : nullptr, false,
 			                       ao[(size_t)part].data(), uo[(size_t)part].data(), u + at, bo[(size_t)part].data(), b + at);
 		});
 		if (rc != 0) return rc;
@@ -563,7 +570,7 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 	DeviceScope on(device);
 	HIP_TRY(on.err);
 	const uint64_t *d_pool = nullptr;
-	if (pool && !(d_pool = pool_on(pool, device))) return fail(MM2C_E_ARG, "the hit pool has no copy on device %d (created before mm2c_init_devices?)", device);
+	if (pool && !(d_pool = hitpool_on(pool, device))) return fail(MM2C_E_ARG, "the hit pool has no copy on device %d (created before mm2c_init_devices?)", device);
 	// chunks of whole reads
 	const int64_t chunk_anchors = total >= 2 * G.pipeline_chunk_anchors ? G.pipeline_chunk_anchors.load() : std::min<int64_t>(total, (int64_t)INT32_MAX - 1);
 	std::vector<int64_t> cuts(1, 0);
@@ -590,11 +597,9 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 		whole_pool = n_chunks > 1 && span > n_hits + n_hits / 2;
 	}
 	int64_t base_u = 0, base_b = 0, base_a = 0;
-	int nl = 0;
 	// skip_seed: the reference arrays go up once per call (on this device), the per-read ones with each chunk
-	const bool names = skip && skip->ref_rank, per_read = names && skip->q_lo && skip->q_eq;
-	char *d_ref = nullptr;
-	const size_t n_ref = names ? (size_t)std::max<int32_t>(skip->n_ref, 1) : 0;
+	int32_t *d_ref = nullptr;
+	const size_t n_ref = skip_n_ref(skip);
 
 	auto drop_plans = [&](SeedSlot &w, bool waited) {           // the chunk's kernels are done (waited) or the call failed (wait inside)
 		if (w.seedplan) { if (waited) seedplan_destroy_synced((mm2c_seedplan_t *)w.seedplan); else mm2c_seedplan_destroy((mm2c_seedplan_t *)w.seedplan); w.seedplan = nullptr; }
@@ -619,12 +624,11 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 			w.plan = mm2c_plan_create(par, (int64_t)nr, cap + k0);
 			if (!w.plan) return MM2C_E_HIP;
 		}
-		size_t at = 0;
-		auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-		const size_t o_m = take(nm * sizeof(mm2c_match_t)), o_h = take(nh * 8), o_q = take(nr * 4), o_lo = take(per_read ? nr * 4 : 0), o_eq = take(per_read ? nr * 4 : 0),
-		             o_a = take(tot * 16), o_f = take(tot * 4), o_p = take(tot * 4);
-		w.o_uo = take((nr + 1) * 8); w.o_bo = take((nr + 1) * 8); w.o_u = take(tot * 8); w.o_b = take(tot * 16); w.o_ao = take(skip ? (nr + 1) * 8 : 0);
-		const size_t n_meta = skip ? 3 : 2;                            // pinned: u_off, b_off (and the packed anchor offsets)
+		Layout L;
+		const size_t o_m = L.take(nm * sizeof(mm2c_match_t)), o_h = L.take(nh * 8);
+		const ChunkLayout o = chunk_layout(L, nr, tot, skip_per_read(skip), skip != nullptr);
+		w.o_u = o.o_u; w.o_b = o.o_b;
+		const size_t at = L.at, n_meta = skip ? 3 : 2;                 // pinned: u_off, b_off (and the packed anchor offsets)
 		if (at > w.cap_buf || n_meta * (nr + 1) * 8 > w.cap_hmeta) {  // the arena moves: the chains of the slot's last chunk may still be on their way out of it
 			ScopedNs timed(SS.wait_ns);
 			HIP_TRY(hipStreamSynchronize(w.st));
@@ -636,32 +640,16 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 		HIP_TRY(hipEventRecord(w.ev[0], st));
 		HIP_TRY(hipMemcpyAsync(d + o_m, h_matches + m0, nm * sizeof(mm2c_match_t), hipMemcpyHostToDevice, st));
 		if (nh) HIP_TRY(hipMemcpyAsync(d + o_h, h_hits + h_lo[(size_t)ck], nh * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_q, h_qlen + k0, nr * 4, hipMemcpyHostToDevice, st));
-		if (per_read) {
-			HIP_TRY(hipMemcpyAsync(d + o_lo, skip->q_lo + k0, nr * 4, hipMemcpyHostToDevice, st));
-			HIP_TRY(hipMemcpyAsync(d + o_eq, skip->q_eq + k0, nr * 4, hipMemcpyHostToDevice, st));
-		}
+		HIP_TRY(hipMemcpyAsync(d + o.o_q, h_qlen + k0, nr * 4, hipMemcpyHostToDevice, st));
+		mm2c_seed_skip_t sk;
+		if (skip) HIP_TRY(skip_upload_reads(skip, k0, k1, d_ref, d_ref + n_ref, (int32_t *)(d + o.o_lo), (int32_t *)(d + o.o_eq), st, &sk));
 		HIP_TRY(hipEventRecord(w.ev[1], st));
 		// the matches keep their pool-relative cr_off: the kernels get the pool's base, i.e. the chunk's range shifted back by its start
 		const uint64_t *d_hits = pool ? d_pool : whole_pool ? (const uint64_t *)d_whole : (const uint64_t *)(d + o_h) - h_lo[(size_t)ck];
-		if (skip) {
-			// the hits the kernels may read end at the pool's end, or at the end of the chunk's range (the host has checked every match against them)
-			const int64_t hits_end = pool || whole_pool ? n_hits : h_hi[(size_t)ck];
-			mm2c_seed_skip_t sk = { skip->flag, names ? (const int32_t *)d_ref : nullptr, names && skip->ref_len ? (const int32_t *)d_ref + n_ref : nullptr,
-			                        per_read ? (const int32_t *)(d + o_lo) : nullptr, per_read ? (const int32_t *)(d + o_eq) : nullptr };
-			if ((r = mm2c_seedplan_run_device_skip((mm2c_seedplan_t *)w.seedplan, (const mm2c_match_t *)(d + o_m), (int64_t)nm, d_hits, hits_end, (const int32_t *)(d + o_q),
-			                                       (int64_t)nr, &sk, d + o_a, (int64_t)tot, (int64_t *)(d + w.o_ao), st))) return r;
-			if ((r = mm2c_plan_set_device_offsets((mm2c_plan_t *)w.plan, (const int64_t *)(d + w.o_ao)))) return r;   // the chains go by the packed offsets
-		} else if ((r = mm2c_seedplan_run_device((mm2c_seedplan_t *)w.seedplan, (const mm2c_match_t *)(d + o_m), d_hits, (const int32_t *)(d + o_q), d + o_a, st))) return r;
-		HIP_TRY(hipEventRecord(w.ev[2], st));
-		if ((r = mm2c_plan_run_device((mm2c_plan_t *)w.plan, d + o_a, nullptr, (int32_t *)(d + o_f), (int32_t *)(d + o_p), st))) return r;
-		HIP_TRY(hipEventRecord(w.ev[3], st));
-		if ((r = mm2c_plan_chains_device((mm2c_plan_t *)w.plan, d + o_a, (int32_t *)(d + o_f), (int32_t *)(d + o_p), min_cnt, min_sc, (int64_t *)(d + w.o_uo),
-		                                 (uint64_t *)(d + w.o_u), (int64_t *)(d + w.o_bo), d + w.o_b, st))) return r;
-		HIP_TRY(hipEventRecord(w.ev[4], st));
-		HIP_TRY(hipMemcpyAsync(w.h_meta, d + w.o_uo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(w.h_meta + (nr + 1) * 8, d + w.o_bo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-		if (skip) HIP_TRY(hipMemcpyAsync(w.h_meta + 2 * (nr + 1) * 8, d + w.o_ao, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+		// the hits the kernels of a skip_seed run may read end at the pool's end, or at the end of the chunk's range (the host has checked every match against them)
+		const int64_t hits_end = pool || whole_pool ? n_hits : h_hi[(size_t)ck];
+		if ((r = chunk_step((mm2c_seedplan_t *)w.seedplan, (mm2c_plan_t *)w.plan, (const mm2c_match_t *)(d + o_m), d_hits, hits_end, skip ? &sk : nullptr, d, o, min_cnt, min_sc,
+		                    st, w.ev[2], w.ev[3], w.ev[4], (int64_t *)w.h_meta))) return r;
 		HIP_TRY(hipEventRecord(w.ev[5], st));
 		++SS.chunks;
 		return 0;
@@ -699,10 +687,10 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 		if (e == hipSuccess) e = hipMemcpy(d_whole, h_hits, (size_t)n_hits * 8, hipMemcpyHostToDevice);   // before either stream starts
 		if (e != hipSuccess) rc = fail(MM2C_E_HIP, "uploading the hit pool: %s", hipGetErrorString(e));
 	}
-	if (names && rc == 0) {                                         // [ref_rank | ref_len], before either stream starts
+	if (n_ref && rc == 0) {                                         // [ref_rank | ref_len], landed before either slot's stream (non-blocking, both) starts
 		hipError_t e = dev_alloc((void **)&d_ref, 2 * n_ref * 4);
-		if (e == hipSuccess && skip->n_ref > 0) e = hipMemcpy(d_ref, skip->ref_rank, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice);
-		if (e == hipSuccess && skip->n_ref > 0 && skip->ref_len) e = hipMemcpy(d_ref + n_ref * 4, skip->ref_len, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice);
+		if (e == hipSuccess) e = skip_upload_refs(skip, d_ref, d_ref + n_ref, nullptr);
+		if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
 		if (e != hipSuccess) rc = fail(MM2C_E_HIP, "uploading the reference ranks: %s", hipGetErrorString(e));
 	}
 	for (int ck = 0; ck < n_chunks && rc == 0; ++ck) {
@@ -720,7 +708,7 @@ static int seed_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, in
 	}
 	if (d_whole) dev_free(d_whole);
 	if (d_ref) dev_free(d_ref);
-	G.tasks += (uint64_t)n_reads; G.anchors += (uint64_t)total; G.launches += (uint64_t)nl; G.passes += (uint64_t)n_chunks;
+	G.tasks += (uint64_t)n_reads; G.anchors += (uint64_t)total; G.passes += (uint64_t)n_chunks;
 	return rc;
 }
 
@@ -728,7 +716,7 @@ int mm2c_seed_chain_batch_host(const mm2c_params_t *par, int min_cnt, int min_sc
                                const mm2c_match_t *h_matches, const uint64_t *h_hits, int64_t n_hits, const int32_t *h_qlen,
                                int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
 {
-	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr, h_qlen, nullptr, anchor_off, u_off, u, b_off, b);
+	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr, h_qlen, nullptr, false, anchor_off, u_off, u, b_off, b);
 }
 
 int mm2c_seed_chain_batch_pool(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
@@ -736,7 +724,7 @@ int mm2c_seed_chain_batch_pool(const mm2c_params_t *par, int min_cnt, int min_sc
                                int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
 {
 	if (!pool) return fail(MM2C_E_ARG, "pool is NULL");
-	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, nullptr, 0, pool, h_qlen, nullptr, anchor_off, u_off, u, b_off, b);
+	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, nullptr, 0, pool, h_qlen, nullptr, false, anchor_off, u_off, u, b_off, b);
 }
 
 int mm2c_seed_chain_batch_host_skip(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
@@ -744,8 +732,8 @@ int mm2c_seed_chain_batch_host_skip(const mm2c_params_t *par, int min_cnt, int m
                                     const mm2c_seed_skip_host_t *skip, int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
 {
 	if (n_reads < 0 || (n_reads > 0 && (!h_match_off || (h_match_off[n_reads] > h_match_off[0] && !h_matches)))) return fail(MM2C_E_ARG, "bad argument");
-	if (const int rc = check_skip(skip, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr)) return rc;
-	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr, h_qlen, skip, anchor_off, u_off, u, b_off, b);
+	if (const int rc = check_skip(skip, n_reads)) return rc;
+	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, h_hits, n_hits, nullptr, h_qlen, skip, true, anchor_off, u_off, u, b_off, b);
 }
 
 int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int min_sc, int64_t n_reads, const int64_t *h_match_off,
@@ -753,14 +741,12 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
                                     const mm2c_seed_skip_host_t *skip, int64_t *anchor_off, int64_t *u_off, uint64_t *u, int64_t *b_off, mm2c_anchor_t *b)
 {
 	if (!pool) return fail(MM2C_E_ARG, "pool is NULL");
-	if (const int rc = check_skip(skip, n_reads, h_match_off, h_matches, nullptr, pool->n, pool)) return rc;
-	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, nullptr, 0, pool, h_qlen, skip, anchor_off, u_off, u, b_off, b);
+	if (const int rc = check_skip_pool(skip, n_reads, pool)) return rc;
+	return seed_chain_impl(par, min_cnt, min_sc, n_reads, h_match_off, h_matches, nullptr, 0, pool, h_qlen, skip, false, anchor_off, u_off, u, b_off, b);
 }
 
 } // extern "C"
 
 namespace mm2c_api {
 void seedplan_destroy_synced(mm2c_seedplan_t *pl) { seedplan_destroy_impl(pl, false); }
-const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device) { return hp ? pool_on(hp, device) : nullptr; }   // the reads-in entries (mm2chain_sketch.cpp)
-int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool) { return check_skip(skip, n_reads, nullptr, nullptr, nullptr, pool->n, pool); }
 }

@@ -17,8 +17,6 @@ size_t sketch_scan_bytes(int64_t n_chunks, int64_t n_sc);
 size_t lookup_scan_bytes(int64_t n_mini);
 size_t sketch_push_bytes();
 size_t sketch_lsum_bytes();
-const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device);          // mm2chain_seeds.cpp
-int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool);
 int minidx_image(const uint64_t *h_keys, const int64_t *h_cr, const uint32_t *h_n, int64_t n, int key_bits, char *d_img, int *h_dup, hipStream_t st);
 std::atomic<int64_t> read_chunk_bases{1 << 27};                             // mm2c_tune("read_chunk_bases")
 }
@@ -136,14 +134,13 @@ struct Run {
 		}
 		const int64_t n_chunks = chunk_off[(size_t)nr], n_sc = sc_off[(size_t)nr];
 		const size_t scan_bytes = sketch_scan_bytes(n_chunks, n_sc);
-		size_t at = 0;
-		auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-		const size_t o_seq = lay((size_t)nb), o_so = lay(((size_t)nr + 1) * 8), o_co = lay(((size_t)nr + 1) * 8), o_sco = lay(((size_t)nr + 1) * 8),
-		             o_push = lay(2 * (size_t)n_chunks * sketch_push_bytes()), o_lsum = lay(2 * (size_t)n_chunks * sketch_lsum_bytes()),
-		             o_sx = lay((size_t)nb * 8), o_sy = lay((size_t)nb * 8), o_sl = lay((size_t)nb * 2), o_ns = lay(((size_t)nr + 1) * 8),
-		             o_cnt = lay(2 * ((size_t)n_sc + 1) * 8), o_mo = lay(((size_t)nr + 1) * 8), o_tmp = lay(scan_bytes);
+		Layout L;
+		const size_t o_seq = L.take((size_t)nb), o_so = L.take(((size_t)nr + 1) * 8), o_co = L.take(((size_t)nr + 1) * 8), o_sco = L.take(((size_t)nr + 1) * 8),
+		             o_push = L.take(2 * (size_t)n_chunks * sketch_push_bytes()), o_lsum = L.take(2 * (size_t)n_chunks * sketch_lsum_bytes()),
+		             o_sx = L.take((size_t)nb * 8), o_sy = L.take((size_t)nb * 8), o_sl = L.take((size_t)nb * 2), o_ns = L.take(((size_t)nr + 1) * 8),
+		             o_cnt = L.take(2 * ((size_t)n_sc + 1) * 8), o_mo = L.take(((size_t)nr + 1) * 8), o_tmp = L.take(scan_bytes);
 		char *d = nullptr;
-		HIP_TRY(take((void **)&d, at));
+		HIP_TRY(take((void **)&d, L.at));
 		if (int rc0 = ev.make()) return rc0;
 		HIP_TRY(hipEventRecord(ev.e[0], st));
 		if (nb > 0) HIP_TRY(hipMemcpyAsync(d + o_seq, seq + b0, (size_t)nb, hipMemcpyHostToDevice, st));
@@ -182,28 +179,19 @@ struct mm2c_minidx {
 	int k = 0, w = 0, hpc = 0;
 	int64_t n = 0;
 	const mm2c_hitpool_t *pool = nullptr;
-	int n_dev = 0;
-	int dev[64] = {};
-	char *d[64] = {};                            // [keys sorted (8 B) | cr_off (8 B) | n (4 B)] per device
+	PerDevice copies;                            // [keys sorted (8 B) | cr_off (8 B) | n (4 B)] per device
 };
-
-static const char *minidx_on(const mm2c_minidx_t *ix, int device)
-{
-	for (int j = 0; j < ix->n_dev; ++j) if (ix->dev[j] == device) return ix->d[j];
-	return nullptr;
-}
 
 int Run::lookup(const mm2c_minidx_t *idx, int device, int mid_occ)
 {
-	const char *dk = minidx_on(idx, device);
+	const char *dk = (const char *)idx->copies.on(device);
 	if (!dk) return fail(MM2C_E_ARG, "the minimizer index has no copy on device %d (created before mm2c_init_devices?)", device);
 	const size_t nk = (size_t)idx->n, scan_bytes = lookup_scan_bytes(n_mini), nm = (size_t)n_mini;
-	size_t at = 0;
-	auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-	const size_t o_t = lay(nm * 4), o_cr = lay((nm + 1) * 8), o_keep = lay(2 * (nm + 1) * 8), o_acnt = lay(2 * (nm + 1) * 8), o_m = lay(nm * sizeof(mm2c_match_t)),
-	             o_mp = lay(nm * 8), o_mo = lay(((size_t)nr + 1) * 8), o_ao = lay(((size_t)nr + 1) * 8), o_rl = lay((size_t)nr * 4), o_tmp = lay(scan_bytes);
+	Layout L;
+	const size_t o_t = L.take(nm * 4), o_cr = L.take((nm + 1) * 8), o_keep = L.take(2 * (nm + 1) * 8), o_acnt = L.take(2 * (nm + 1) * 8), o_m = L.take(nm * sizeof(mm2c_match_t)),
+	             o_mp = L.take(nm * 8), o_mo = L.take(((size_t)nr + 1) * 8), o_ao = L.take(((size_t)nr + 1) * 8), o_rl = L.take((size_t)nr * 4), o_tmp = L.take(scan_bytes);
 	char *d = nullptr;
-	HIP_TRY(take((void **)&d, at));
+	HIP_TRY(take((void **)&d, L.at));
 	d_matches = (mm2c_match_t *)(d + o_m); d_mini_pos = (uint64_t *)(d + o_mp);
 	d_match_off = (int64_t *)(d + o_mo); d_anchor_off = (int64_t *)(d + o_ao); d_rep_len = (int32_t *)(d + o_rl);
 	int rc;
@@ -245,18 +233,13 @@ mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int 
 	std::vector<char> img;                                    // the sorted image, downloaded once when a second device needs a copy
 	mm2c_minidx *ix = new mm2c_minidx();
 	ix->k = k; ix->w = w; ix->hpc = is_hpc ? 1 : 0; ix->n = n_keys; ix->pool = pool;
-	for (size_t q = 0; q < G.devices.size() && ix->n_dev < 64; ++q) {
-		const int dv = G.devices[q];
-		bool seen = false;
-		for (int j = 0; j < ix->n_dev; ++j) seen = seen || ix->dev[j] == dv;
-		if (seen) continue;
+	for (int dv : distinct_devices(G.devices)) {
 		DeviceScope on(dv);
-		void *p = nullptr;
 		hipError_t e = on.err;
-		{ ScopedNs timed(SS.alloc_ns); ++SS.n_alloc; if (e == hipSuccess) e = hipMalloc(&p, img_bytes); }
+		if (e == hipSuccess) e = ix->copies.add(dv, img_bytes);
 		if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_minidx_create: %s", hipGetErrorString(e)); mm2c_minidx_destroy(ix); return nullptr; }
-		ix->dev[ix->n_dev] = dv; ix->d[ix->n_dev] = (char *)p; ++ix->n_dev;
-		if (ix->n_dev == 1) {                                  // sorted on the first device
+		void *p = ix->copies.d.back();
+		if (ix->copies.d.size() == 1) {                        // sorted on the first device
 			OwnStream os;
 			int dup = 0, rc = os.make();
 			if (rc == 0) rc = minidx_image(keys, cr_off, n, n_keys, 2 * k, (char *)p, &dup, os.st);
@@ -266,9 +249,9 @@ mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int 
 		}
 		if (img.empty()) {
 			img.resize(img_bytes);
-			DeviceScope first(ix->dev[0]);
+			DeviceScope first(ix->copies.dev[0]);
 			e = first.err;
-			if (e == hipSuccess) e = hipMemcpy(img.data(), ix->d[0], img_bytes, hipMemcpyDeviceToHost);
+			if (e == hipSuccess) e = hipMemcpy(img.data(), ix->copies.d[0], img_bytes, hipMemcpyDeviceToHost);
 		}
 		if (e == hipSuccess) e = hipMemcpy(p, img.data(), img_bytes, hipMemcpyHostToDevice);
 		if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_minidx_create: %s", hipGetErrorString(e)); mm2c_minidx_destroy(ix); return nullptr; }
@@ -279,7 +262,7 @@ mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int 
 void mm2c_minidx_destroy(mm2c_minidx_t *ix)
 {
 	if (!ix) return;
-	for (int j = 0; j < ix->n_dev; ++j) { DeviceScope on(ix->dev[j]); ScopedNs timed(SS.free_ns); ++SS.n_free; (void)hipDeviceSynchronize(); (void)hipFree(ix->d[j]); }
+	ix->copies.destroy();
 	delete ix;
 }
 
@@ -419,14 +402,12 @@ int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 	if ((rc = os.make())) return rc;
 	hipStream_t st = os.st;
 	++SS.calls;
-	const bool names = skip && skip->ref_rank, per_read = names && skip->q_lo && skip->q_eq;
-	const size_t n_ref = names ? (size_t)std::max<int32_t>(skip->n_ref, 1) : 0;
+	const size_t n_ref = skip_n_ref(skip);
 	Run refs; refs.st = st;                                    // [ref_rank | ref_len] once per call
 	int32_t *d_ref = nullptr;
-	if (names) {
+	if (n_ref) {
 		HIP_TRY(refs.take((void **)&d_ref, 2 * n_ref * 4));
-		if (skip->n_ref > 0) HIP_TRY(hipMemcpyAsync(d_ref, skip->ref_rank, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st));
-		if (skip->n_ref > 0 && skip->ref_len) HIP_TRY(hipMemcpyAsync(d_ref + n_ref, skip->ref_len, (size_t)skip->n_ref * 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(skip_upload_refs(skip, d_ref, d_ref + n_ref, st));
 	}
 	const int64_t chunk_bases = std::max<int64_t>(read_chunk_bases.load(), 1);
 	int64_t A = 0, U = 0, B = 0, M = 0;
@@ -457,46 +438,25 @@ int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 			if (!pl) { mm2c_seedplan_destroy(sp); return MM2C_E_HIP; }
 			auto body = [&]() -> int {
 				int r;
-				size_t at = 0;
-				auto lay = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
-				const size_t o_q = lay(nr * 4), o_lo = lay(per_read ? nr * 4 : 0), o_eq = lay(per_read ? nr * 4 : 0), o_a = lay((size_t)tot * 16), o_f = lay((size_t)tot * 4),
-				             o_p = lay((size_t)tot * 4), o_uo = lay((nr + 1) * 8), o_bo = lay((nr + 1) * 8), o_u = lay((size_t)tot * 8), o_b = lay((size_t)tot * 16),
-				             o_ao = lay((nr + 1) * 8);
+				Layout L;
+				const ChunkLayout o = chunk_layout(L, nr, (size_t)tot, skip_per_read(skip), true);   // (room for the packed anchor_off with or without skip_seed)
 				char *d = nullptr;
-				HIP_TRY(R.take((void **)&d, at));
-				HIP_TRY(hipMemcpyAsync(d + o_q, qlen.data(), nr * 4, hipMemcpyHostToDevice, st));
-				if (per_read) {
-					HIP_TRY(hipMemcpyAsync(d + o_lo, skip->q_lo + r0, nr * 4, hipMemcpyHostToDevice, st));
-					HIP_TRY(hipMemcpyAsync(d + o_eq, skip->q_eq + r0, nr * 4, hipMemcpyHostToDevice, st));
-				}
-				hipEvent_t e0, e1;
-				HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-				struct EvDrop { hipEvent_t a, b; ~EvDrop() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } drop{ e0, e1 };
-				HIP_TRY(hipEventRecord(e0, st));
-				if (skip) {
-					mm2c_seed_skip_t sk = { skip->flag, names ? d_ref : nullptr, names && skip->ref_len ? d_ref + n_ref : nullptr,
-					                        per_read ? (const int32_t *)(d + o_lo) : nullptr, per_read ? (const int32_t *)(d + o_eq) : nullptr };
-					if ((r = mm2c_seedplan_run_device_skip(sp, R.d_matches, R.n_matches, d_pool, n_hits, (const int32_t *)(d + o_q), (int64_t)nr, &sk, d + o_a, tot,
-					                                       (int64_t *)(d + o_ao), st))) return r;
-					if ((r = mm2c_plan_set_device_offsets(pl, (const int64_t *)(d + o_ao)))) return r;
-				} else if ((r = mm2c_seedplan_run_device(sp, R.d_matches, d_pool, (const int32_t *)(d + o_q), d + o_a, st))) return r;
-				HIP_TRY(hipEventRecord(e1, st));
-				if ((r = mm2c_plan_run_device(pl, d + o_a, nullptr, (int32_t *)(d + o_f), (int32_t *)(d + o_p), st))) return r;
-				if ((r = mm2c_plan_chains_device(pl, d + o_a, (int32_t *)(d + o_f), (int32_t *)(d + o_p), min_cnt, min_sc, (int64_t *)(d + o_uo), (uint64_t *)(d + o_u),
-				                                 (int64_t *)(d + o_bo), d + o_b, st))) return r;
-				std::vector<int64_t> uo(nr + 1), bo(nr + 1), ao(nr + 1);
-				HIP_TRY(hipMemcpyAsync(uo.data(), d + o_uo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-				HIP_TRY(hipMemcpyAsync(bo.data(), d + o_bo, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-				if (skip) HIP_TRY(hipMemcpyAsync(ao.data(), d + o_ao, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+				HIP_TRY(R.take((void **)&d, L.at));
+				HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen.data(), nr * 4, hipMemcpyHostToDevice, st));
+				mm2c_seed_skip_t sk;
+				if (skip) HIP_TRY(skip_upload_reads(skip, r0, r1, d_ref, d_ref + n_ref, (int32_t *)(d + o.o_lo), (int32_t *)(d + o.o_eq), st, &sk));
+				Evts seed;                                                // [0], [1]: around the seed hits
+				if ((r = seed.make())) return r;
+				HIP_TRY(hipEventRecord(seed.e[0], st));
+				std::vector<int64_t> off(3 * (nr + 1));
+				if ((r = chunk_step(sp, pl, R.d_matches, d_pool, n_hits, skip ? &sk : nullptr, d, o, min_cnt, min_sc, st, seed.e[1], nullptr, nullptr, off.data()))) return r;
+				const int64_t *uo = off.data(), *bo = uo + nr + 1, *ao = skip ? bo + nr + 1 : cap.data();
 				HIP_TRY(hipStreamSynchronize(st));
 				if ((r = mm2c_seedplan_check(sp, nullptr))) return r;
-				float ms = 0;
-				(void)hipEventElapsedTime(&ms, e0, e1);
-				SS.seed_ns += (uint64_t)(ms * 1e6f);
-				if (!skip) ao = cap;
+				SS.seed_ns += (uint64_t)(seed.ms(0, 1) * 1e6f);
 				P.u.resize((size_t)(U + uo[nr])); P.b.resize((size_t)(B + bo[nr]));
-				if (uo[nr]) HIP_TRY(hipMemcpyAsync(P.u.data() + U, d + o_u, (size_t)uo[nr] * 8, hipMemcpyDeviceToHost, st));
-				if (bo[nr]) HIP_TRY(hipMemcpyAsync(P.b.data() + B, d + o_b, (size_t)bo[nr] * 16, hipMemcpyDeviceToHost, st));
+				if (uo[nr]) HIP_TRY(hipMemcpyAsync(P.u.data() + U, d + o.o_u, (size_t)uo[nr] * 8, hipMemcpyDeviceToHost, st));
+				if (bo[nr]) HIP_TRY(hipMemcpyAsync(P.b.data() + B, d + o.o_b, (size_t)bo[nr] * 16, hipMemcpyDeviceToHost, st));
 				HIP_TRY(hipStreamSynchronize(st));
 				for (size_t k = 1; k <= nr; ++k) {
 					P.u_off[(size_t)r0 + k] = U + uo[k]; P.b_off[(size_t)r0 + k] = B + bo[k]; P.anchor_off[(size_t)r0 + k] = A + ao[k];
