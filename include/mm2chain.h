@@ -396,9 +396,10 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
  * Out of scope here -- a host that needs one of these keeps its own sketching for those reads:
  *   - SDUST masking (sdust_thres > 0, map.c:73-74; no preset sets it, options.c:22);
  *   - reads of several segments (n_segs > 1, --frag);
- *   - building the index (the host builds it and hands its key table to mm2c_minidx_create);
  *   - alignment;
- *   - the max_occ re-chaining of map.c:318-340 (max_occ is never set by this reference's options). */
+ *   - the max_occ re-chaining of map.c:318-340 (max_occ is never set by this reference's options).
+ * The index itself is built here too (mm2c_minidx_build, below).  Two parts of mm_idx_t stay with the host: the packed reference sequence mi->S with the
+ * sequence names (a host that aligns or prints names keeps its own), and .mmi files (mm_idx_dump / mm_idx_load); multi-part indices (-I) are not built. */
 
 /* A minimizer index resident on every configured device (as mm2c_hitpool_create keeps the pool): one row per indexed minimizer, keys[i] = the minimizer
  * (mm128_t.x >> 8), its hits pool[cr_off[i] .. cr_off[i] + n[i]).  A lookup returns exactly what mm_idx_get (index.c:81-98) returns: (cr_off, n) for a key that
@@ -411,6 +412,35 @@ mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int 
 void mm2c_minidx_destroy(mm2c_minidx_t *idx);                                    /* not while a call that uses it is running */
 /* the lookups on their own (tests): n_q keys in, (cr_off, n) out, on the primary device */
 int mm2c_minidx_lookup(const mm2c_minidx_t *idx, int64_t n_q, const uint64_t *keys, int64_t *cr_off, uint32_t *n);
+
+/* The index built on the device from the sequences themselves: what mm_idx_gen + worker_post (index.c:191-233) yield, as the rows
+ * above -- keys = x >> 8 ascending, each once (the span in x's low 8 bits is dropped: two minimizers that differ only in span are one key); a key's hits
+ * are its y values ascending, y = rid << 32 | pos << 1 | strand with rid = the sequence's number; one pool slot per hit, singletons included.  Sequences
+ * are laid out as the reads of the reads-in entries (seq_off: n_seqs + 1 entries); a sequence of length 0 is legal and contributes nothing; every byte
+ * value is legal.  They are sketched in chunks of whole sequences of up to mm2c_tune("index_chunk_bases", default 2^27) bases -- a longer sequence is a
+ * chunk of its own -- at about 20 bytes of device memory per base of a chunk, plus about 50 bytes per minimizer of the whole list while it is sorted.
+ * The index owns its pool (mm2c_minidx_pool; mm2c_minidx_destroy frees it, which it does NOT do for the caller's pool of mm2c_minidx_create), and both
+ * are replicated to every configured device.  *mid_occ (may be NULL) = mm2c_minidx_cal_max_occ(idx, mid_occ_frac).
+ * NULL on failure; mm2c_last_error then starts with the code's name.  Refused before any device work: k outside 1..28, w outside 1..255, seq_off[0] != 0 or
+ * seq_off not monotone (MM2C_E_ARG); a sequence of 2^31 bases or more (pos << 1 must fit 32 bits), more than 2^31 - 1 sequences (MM2C_E_TOOBIG).  More
+ * than 2^32 - 1 keys: MM2C_E_TOOBIG, as mm2c_minidx_create. */
+mm2c_minidx_t *mm2c_minidx_build(int k, int w, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const uint8_t *seq,
+                                 float mid_occ_frac, int *mid_occ);
+int64_t mm2c_minidx_n_keys(const mm2c_minidx_t *idx);
+int64_t mm2c_minidx_n_hits(const mm2c_minidx_t *idx);                  /* sum of n over the rows (a built index: the size of its pool) */
+const mm2c_hitpool_t *mm2c_minidx_pool(const mm2c_minidx_t *idx);      /* for mm2c_seed_chain_batch_pool(_skip); never destroy the pool of a built index */
+/* mm_idx_cal_max_occ (index.c:164-185) on the device, also for an index made by mm2c_minidx_create: the (uint32_t)((1. - f) * n_keys)-th smallest n
+ * (from 0) plus 1, f the float widened to double; INT32_MAX for f <= 0.  An index without keys gives INT32_MAX (the reference is undefined there: it
+ * reads a[0] of an empty array).  A negative MM2C_E_* code on failure. */
+int mm2c_minidx_cal_max_occ(const mm2c_minidx_t *idx, float frac);
+/* download: keys / cr_off / n (mm2c_minidx_n_keys entries each) and pool (mm2c_minidx_n_hits entries); any pointer may be NULL.  For an index made by
+ * mm2c_minidx_create this is the caller's table sorted by key, and `pool` is left untouched (the pool is the caller's). */
+int mm2c_minidx_export(const mm2c_minidx_t *idx, uint64_t *keys, int64_t *cr_off, uint32_t *n, uint64_t *pool);
+/* what mm2c_minidx_build processed and where its time went, summed since mm2c_init or the last reset.  h2d_ns and sketch_ns (sketch and tagging) are device
+ * time between HIP events; sort_ns, group_ns, occ_ns and replicate_ns are host time around stages that end in a stream synchronise */
+typedef struct { uint64_t calls, chunks, bases, minimizers, keys, h2d_ns, sketch_ns, sort_ns, group_ns, occ_ns, replicate_ns; } mm2c_index_stats_t;
+void mm2c_get_index_stats(mm2c_index_stats_t *out);
+void mm2c_reset_index_stats(void);
 
 /* Results of the reads-in entries: LIBRARY-OWNED and reusable (the counts are only known once the device has run).  Create one, hand it to as many calls
  * as you like (each overwrites it; the arrays stay valid until the next call on the same object or mm2c_read_result_free).  Fields an entry does not fill

@@ -83,6 +83,7 @@ struct Global {
 };
 extern Global G;
 extern std::atomic<int64_t> read_chunk_bases;   // mm2c_read_chain_batch: bases per chunk of whole reads (mm2c_tune("read_chunk_bases"); mm2chain_sketch.cpp)
+extern std::atomic<int64_t> index_chunk_bases;  // mm2c_minidx_build: bases per chunk of whole sequences (mm2c_tune("index_chunk_bases"); mm2chain_sketch.cpp)
 // mm2c_init_async: the initialisation runs on a thread of its own while the host does something else (a minimap2 host loads its index, main.c:371-399, before the
 // first chaining call); every entry that needs the device joins that thread first.  async_init_join is a no-op when none is pending and on the thread itself.
 void async_init_join();
@@ -278,6 +279,8 @@ void seedplan_destroy_synced(mm2c_seedplan_t *pl);  // mm2chain_seeds.cpp
 
 // ---- shared by the matches-in entries (mm2chain_seeds.cpp, where all of this lives) and the reads-in entries (mm2chain_sketch.cpp)
 const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device);
+// a pool from copies that are on the devices already (mm2c_minidx_build: the sorted y column); the pool takes them over.  max_rid: the largest rid among the hits, -1 without hits
+mm2c_hitpool_t *hitpool_adopt(int64_t n_hits, int64_t max_rid, PerDevice &copies);
 int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool);   // skip_seed against a resident pool, before any kernel runs
 // skip_seed from the host description to the device.  The rules, written once: without ref_rank no name is compared and nothing goes up; the two reference arrays
 // hold max(n_ref, 1) entries each; ref_len may be NULL (only NO_DIAG / NO_DUAL read it, and check_skip refuses them without); q_lo / q_eq go up when both are given.

@@ -803,6 +803,11 @@ int mm2c_tune(const char *key, int value)
 		read_chunk_bases = value;
 		return 0;
 	}
+	if (strcmp(key, "index_chunk_bases") == 0) {             // mm2c_minidx_build: bases per chunk of whole sequences
+		if (value < 1) return fail(MM2C_E_ARG, "index_chunk_bases must be >= 1");
+		index_chunk_bases = value;
+		return 0;
+	}
 	if (strcmp(key, "heap_sort") == 0) {
 		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "heap_sort must be 0 or 1");
 		G.heap_sort = value;

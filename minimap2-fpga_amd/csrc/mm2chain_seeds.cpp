@@ -140,6 +140,14 @@ int check_skip_rids(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm
 
 const uint64_t *hitpool_on(const mm2c_hitpool_t *hp, int device) { return hp ? (const uint64_t *)hp->copies.on(device) : nullptr; }
 
+mm2c_hitpool_t *hitpool_adopt(int64_t n_hits, int64_t max_rid, PerDevice &copies)
+{
+	mm2c_hitpool *hp = new mm2c_hitpool();
+	hp->n = n_hits; hp->max_rid = max_rid;
+	std::swap(hp->copies, copies);
+	return hp;
+}
+
 int check_skip_pool(const mm2c_seed_skip_host_t *skip, int64_t n_reads, const mm2c_hitpool_t *pool)
 {
 	const int rc = check_skip(skip, n_reads);

@@ -18,12 +18,22 @@ size_t lookup_scan_bytes(int64_t n_mini);
 size_t sketch_push_bytes();
 size_t sketch_lsum_bytes();
 int minidx_image(const uint64_t *h_keys, const int64_t *h_cr, const uint32_t *h_n, int64_t n, int key_bits, char *d_img, int *h_dup, hipStream_t st);
+// index_build.hip
+int index_tag(const mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_seqs, int64_t n_mini, int64_t rid0, uint64_t *key, uint64_t *y, hipStream_t st);
+size_t index_tmp_bytes(int64_t n, int key_bits, int y_bits);
+int index_sort(uint64_t *key, const uint64_t *y, uint64_t *key_tmp, uint64_t *y_tmp, uint64_t *pool, int64_t n, int key_bits, int y_bits, void *tmp, size_t tmp_bytes,
+               hipStream_t st);
+int index_heads(const uint64_t *key, const uint64_t *y, int64_t n, int64_t *head, int64_t *row, int *bad, void *tmp, size_t tmp_bytes, hipStream_t st);
+int index_rows(const uint64_t *key, const int64_t *head, const int64_t *row, int64_t n, int64_t n_keys, char *img, int *bad, hipStream_t st);
+int index_count_select(const uint32_t *d_n, int64_t n_keys, int64_t i, uint32_t *h_val, hipStream_t st);
 std::atomic<int64_t> read_chunk_bases{1 << 27};                             // mm2c_tune("read_chunk_bases")
+std::atomic<int64_t> index_chunk_bases{1 << 27};                            // mm2c_tune("index_chunk_bases")
 }
 
 namespace {
 
 struct SketchStats { std::atomic<uint64_t> calls{0}, chunks{0}, bases{0}, minimizers{0}, matches{0}, h2d_ns{0}, sketch_ns{0}, lookup_ns{0}; } SK;
+struct IndexStats { std::atomic<uint64_t> calls{0}, chunks{0}, bases{0}, minimizers{0}, keys{0}, h2d_ns{0}, sketch_ns{0}, sort_ns{0}, group_ns{0}, occ_ns{0}, replicate_ns{0}; } IX;
 
 // grow-only host arrays: a result object that serves many calls keeps its pages (no zeroing, no page faults on the next call)
 template <class T> struct Buf {
@@ -115,6 +125,7 @@ struct Run {
 	int32_t *d_rep_len = nullptr;
 	std::vector<int64_t> h_seq_off;
 	Evts ev;
+	bool for_index = false;                    // a chunk of mm2c_minidx_build: counted in the index statistics, not in the sketch's
 
 	hipError_t take(void **p, size_t bytes) { hipError_t e = dev_alloc(p, bytes); if (e == hipSuccess) blocks.push_back(*p); return e; }
 	void release() { for (void *p : blocks) dev_free(p); blocks.clear(); }
@@ -160,7 +171,7 @@ struct Run {
 		if ((rc = sketch_write(d_seq, d_seq_off, d_sc_off, nr, n_sc, k, w, (const uint64_t *)(d + o_sx), (const uint64_t *)(d + o_sy), (const uint16_t *)(d + o_sl),
 		                       (const int64_t *)(d + o_ns), (const int64_t *)(d + o_cnt), d_mini, st))) return rc;
 		HIP_TRY(hipEventRecord(ev.e[2], st));
-		SK.bases += (uint64_t)nb; SK.minimizers += (uint64_t)n_mini;
+		if (!for_index) { SK.bases += (uint64_t)nb; SK.minimizers += (uint64_t)n_mini; }
 		return 0;
 	}
 
@@ -177,8 +188,9 @@ struct Run {
 
 struct mm2c_minidx {
 	int k = 0, w = 0, hpc = 0;
-	int64_t n = 0;
+	int64_t n = 0, n_hits = 0;                   // rows; the hits they hold (sum of n)
 	const mm2c_hitpool_t *pool = nullptr;
+	bool owns_pool = false;                      // mm2c_minidx_build: the pool was made with the index and goes with it
 	PerDevice copies;                            // [keys sorted (8 B) | cr_off (8 B) | n (4 B)] per device
 };
 
@@ -213,6 +225,207 @@ struct OwnStream {                               // a private stream of the call
 };
 }
 
+// ---- mm2c_minidx_build: the index made on the device from the sequences (kernels in index_build.hip)
+namespace {
+
+const char *code_name(int rc)
+{
+	return rc == MM2C_E_NODEVICE ? "MM2C_E_NODEVICE" : rc == MM2C_E_ARG ? "MM2C_E_ARG" : rc == MM2C_E_TOOBIG ? "MM2C_E_TOOBIG" : "MM2C_E_HIP";
+}
+
+// mm2c_minidx_build returns a pointer, so the code of a failure goes in front of the message
+int named(int rc)
+{
+	if (rc) {
+		char t[sizeof(g_err)];
+		snprintf(t, sizeof(t), "%s: %s", code_name(rc), g_err);
+		memcpy(g_err, t, sizeof(t));
+	}
+	return rc;
+}
+
+// everything that can be refused without a device
+int check_build_args(int k, int w, int64_t n_seqs, const int64_t *seq_off, const uint8_t *seq)
+{
+	if (int rc = check_kw(k, w)) return rc;
+	if (n_seqs < 0 || (n_seqs > 0 && !seq_off)) return fail(MM2C_E_ARG, "bad argument");
+	if (n_seqs > (int64_t)INT32_MAX) return fail(MM2C_E_TOOBIG, "%lld sequences: more than 2^31 - 1 (rid is 31 bits wide where the hits are used)", (long long)n_seqs);
+	if (n_seqs > 0 && seq_off[0] != 0) return fail(MM2C_E_ARG, "seq_off[0] must be 0");
+	for (int64_t r = 0; r < n_seqs; ++r)
+		if (seq_off[r + 1] < seq_off[r]) return fail(MM2C_E_ARG, "sequence offsets not monotone at sequence %lld", (long long)r);
+		else if (seq_off[r + 1] - seq_off[r] > (int64_t)INT32_MAX) return fail(MM2C_E_TOOBIG, "sequence %lld has 2^31 bases or more (pos << 1 must fit 32 bits)", (long long)r);
+	if (n_seqs > 0 && seq_off[n_seqs] > 0 && !seq) return fail(MM2C_E_ARG, "seq is NULL");
+	return 0;
+}
+
+// the growing (key, y) list of the sequences sketched so far
+struct PairList {
+	uint64_t *key = nullptr, *y = nullptr;
+	int64_t n = 0, cap = 0;
+	~PairList() { if (key) dev_free(key); if (y) dev_free(y); }
+	int reserve(int64_t need, int64_t hint, hipStream_t st)
+	{
+		if (need <= cap) return 0;
+		const int64_t c = std::max(std::max(need, hint), cap + cap / 2);
+		uint64_t *k2 = nullptr, *y2 = nullptr;
+		HIP_TRY(dev_alloc((void **)&k2, (size_t)c * 8));
+		if (hipError_t e = dev_alloc((void **)&y2, (size_t)c * 8)) { dev_free(k2); return fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)); }
+		hipError_t e = hipSuccess;
+		if (n > 0) {
+			e = hipMemcpyAsync(k2, key, (size_t)n * 8, hipMemcpyDeviceToDevice, st);
+			if (e == hipSuccess) e = hipMemcpyAsync(y2, y, (size_t)n * 8, hipMemcpyDeviceToDevice, st);
+			if (e == hipSuccess) e = hipStreamSynchronize(st);
+		}
+		if (e != hipSuccess) { dev_free(k2); dev_free(y2); return fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)); }
+		if (key) dev_free(key); if (y) dev_free(y);
+		key = k2; y = y2; cap = c;
+		return 0;
+	}
+};
+
+struct Block {                                   // one cached device block for the length of a scope
+	void *p = nullptr;
+	~Block() { if (p) dev_free(p); }
+	hipError_t take(size_t bytes) { return dev_alloc(&p, bytes); }
+};
+
+inline int bits_for(uint64_t v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
+
+// mm_idx_cal_max_occ over the counts of the index's image on its first device
+int cal_max_occ(const mm2c_minidx *ix, float frac, int *out)
+{
+	*out = INT32_MAX;
+	if (!(frac > 0.f) || ix->n == 0) return 0;
+	const double v = (1. - (double)frac) * (double)ix->n;           // f is a float widened to double (index.c:164-185)
+	int64_t i = v > 0. ? (int64_t)(uint32_t)v : 0;
+	if (i >= ix->n) i = ix->n - 1;
+	DeviceScope on(ix->copies.dev[0]);
+	HIP_TRY(on.err);
+	OwnStream os;
+	if (int rc = os.make()) return rc;
+	uint32_t c = 0;
+	if (int rc = index_count_select((const uint32_t *)((const char *)ix->copies.d[0] + (size_t)ix->n * 16), ix->n, i, &c, os.st)) return rc;
+	*out = (int)std::min<int64_t>((int64_t)c + 1, INT32_MAX);
+	return 0;
+}
+
+// one more copy of `bytes` at src (device src_dev) on the current device dst_dev: device to device, through the host where that is refused
+hipError_t replicate(void *dst, int dst_dev, const void *src, int src_dev, size_t bytes)
+{
+	if (bytes == 0) return hipSuccess;
+	if (hipMemcpyPeer(dst, dst_dev, src, src_dev, bytes) == hipSuccess) return hipSuccess;
+	(void)hipGetLastError();
+	std::vector<char> h(bytes);
+	hipError_t e;
+	{ DeviceScope from(src_dev); e = from.err; if (e == hipSuccess) e = hipMemcpy(h.data(), src, bytes, hipMemcpyDeviceToHost); }
+	if (e == hipSuccess) e = hipMemcpy(dst, h.data(), bytes, hipMemcpyHostToDevice);
+	return e;
+}
+
+int build_index(mm2c_minidx *ix, int64_t n_seqs, const int64_t *seq_off, const uint8_t *seq, float frac, int *occ)
+{
+	int rc;
+	const std::vector<int> devs = distinct_devices(G.devices);
+	const int dev0 = devs[0];
+	DeviceScope on(dev0);
+	HIP_TRY(on.err);
+	OwnStream os;
+	if ((rc = os.make())) return rc;
+	hipStream_t st = os.st;
+	const int64_t total_bases = n_seqs > 0 ? seq_off[n_seqs] : 0;
+	++IX.calls; IX.bases += (uint64_t)total_bases;
+
+	// 1. sketch in chunks of whole sequences, tag, append
+	PairList P;
+	const int64_t chunk_bases = std::max<int64_t>(index_chunk_bases.load(), 1);
+	for (int64_t r0 = 0; r0 < n_seqs;) {
+		int64_t r1 = r0 + 1;
+		while (r1 < n_seqs && seq_off[r1 + 1] - seq_off[r0] <= chunk_bases) ++r1;
+		Run R; R.st = st; R.for_index = true;
+		if ((rc = R.sketch(ix->k, ix->w, ix->hpc, seq_off, seq, r0, r1))) return rc;
+		// room for the rest at this chunk's density, with a margin: most builds then grow the list once
+		const int64_t done = seq_off[r1], left = total_bases - done;
+		const int64_t hint = P.n + R.n_mini + (done > 0 ? (int64_t)((double)(P.n + R.n_mini) / (double)done * (double)left * 1.05) + 1024 : 0);
+		if ((rc = P.reserve(P.n + R.n_mini, r1 < n_seqs ? hint : 0, st))) return rc;
+		if ((rc = index_tag(R.d_mini, R.d_mini_off, r1 - r0, R.n_mini, r0, P.key + P.n, P.y + P.n, st))) return rc;
+		HIP_TRY(hipEventRecord(R.ev.e[3], st));
+		HIP_TRY(hipEventSynchronize(R.ev.e[3]));
+		IX.h2d_ns += (uint64_t)(R.ev.ms(0, 1) * 1e6f); IX.sketch_ns += (uint64_t)(R.ev.ms(1, 3) * 1e6f);
+		P.n += R.n_mini;
+		++IX.chunks;
+		r0 = r1;
+	}
+	const int64_t N = P.n;
+	IX.minimizers += (uint64_t)N;
+
+	// 2. order by (key, y): the y column goes straight into the pool's copy on this device
+	PerDevice pool;
+	hipError_t e = pool.add(dev0, (size_t)std::max<int64_t>(N, 1) * 8);
+	auto guard = [&](int code) { pool.destroy(); return code; };   // until the pool object owns the copies
+	if (e != hipSuccess) return fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e));
+	int64_t n_keys = 0, max_rid = -1;
+	if (N > 0) {
+		const int key_bits = 2 * ix->k, y_bits = 32 + std::max(bits_for((uint64_t)(n_seqs - 1)), 1);
+		const size_t tmp_bytes = index_tmp_bytes(N, key_bits, y_bits);
+		Layout L;                                                  // key_tmp / y_tmp (the sort's other halves) are head / row afterwards: N + 1 entries each
+		const size_t o_kt = L.take(((size_t)N + 1) * 8), o_yt = L.take(((size_t)N + 1) * 8), o_bad = L.take(4), o_tmp = L.take(tmp_bytes);
+		Block W;
+		if ((e = W.take(L.at)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+		char *d = (char *)W.p;
+		uint64_t *d_pool = (uint64_t *)pool.d[0];
+		{
+			ScopedNs timed(IX.sort_ns);
+			if ((rc = index_sort(P.key, P.y, (uint64_t *)(d + o_kt), (uint64_t *)(d + o_yt), d_pool, N, key_bits, y_bits, d + o_tmp, tmp_bytes, st))) return guard(rc);
+			uint64_t last = 0;                                     // sorted by y, the last one has the largest rid
+			if ((e = hipMemcpyAsync(&last, (uint64_t *)(d + o_yt) + (N - 1), 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+			    (e = hipStreamSynchronize(st)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+			max_rid = (int64_t)(last >> 32);
+		}
+		// 3. group
+		ScopedNs timed(IX.group_ns);
+		int64_t *head = (int64_t *)(d + o_kt), *row = (int64_t *)(d + o_yt);
+		int *d_bad = (int *)(d + o_bad), bad = 0;
+		if ((rc = index_heads(P.key, d_pool, N, head, row, d_bad, d + o_tmp, tmp_bytes, st))) return guard(rc);
+		if ((e = hipMemcpyAsync(&n_keys, row + N, 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+		    (e = hipStreamSynchronize(st)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+		if (n_keys > (int64_t)UINT32_MAX) return guard(fail(MM2C_E_TOOBIG, "more than 2^32 - 1 keys"));
+		if ((e = ix->copies.add(dev0, (size_t)n_keys * 20)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+		if ((rc = index_rows(P.key, head, row, N, n_keys, (char *)ix->copies.d[0], d_bad, st))) return guard(rc);
+		if ((e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+		    (e = hipStreamSynchronize(st)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+		if (bad & 1) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: the sorted minimizers are not in (key, y) order"));
+		if (bad & 2) return guard(fail(MM2C_E_TOOBIG, "a key with 2^32 hits or more"));
+	} else if ((e = ix->copies.add(dev0, 1)) != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+	ix->n = n_keys; ix->n_hits = N;
+	IX.keys += (uint64_t)n_keys;
+
+	// 4. mid_occ
+	{
+		ScopedNs timed(IX.occ_ns);
+		if ((rc = cal_max_occ(ix, frac, occ))) return guard(rc);
+	}
+
+	// 5. a copy of the image and of the pool on every other device
+	{
+		ScopedNs timed(IX.replicate_ns);
+		const size_t img_bytes = (size_t)n_keys * 20, pool_bytes = (size_t)N * 8;
+		for (size_t j = 1; j < devs.size(); ++j) {
+			DeviceScope there(devs[j]);
+			e = there.err;
+			if (e == hipSuccess) e = ix->copies.add(devs[j], std::max<size_t>(img_bytes, 1));
+			if (e == hipSuccess) e = replicate(ix->copies.d.back(), devs[j], ix->copies.d[0], dev0, img_bytes);
+			if (e == hipSuccess) e = pool.add(devs[j], std::max<size_t>(pool_bytes, 8));
+			if (e == hipSuccess) e = replicate(pool.d.back(), devs[j], pool.d[0], dev0, pool_bytes);
+			if (e != hipSuccess) return guard(fail(MM2C_E_HIP, "mm2c_minidx_build: %s", hipGetErrorString(e)));
+		}
+	}
+	ix->pool = hitpool_adopt(N, max_rid, pool);
+	ix->owns_pool = true;
+	return 0;
+}
+
+} // namespace
+
 extern "C" {
 
 mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int is_hpc, int64_t n_keys, const uint64_t *keys,
@@ -233,6 +446,7 @@ mm2c_minidx_t *mm2c_minidx_create(const mm2c_hitpool_t *pool, int k, int w, int 
 	std::vector<char> img;                                    // the sorted image, downloaded once when a second device needs a copy
 	mm2c_minidx *ix = new mm2c_minidx();
 	ix->k = k; ix->w = w; ix->hpc = is_hpc ? 1 : 0; ix->n = n_keys; ix->pool = pool;
+	for (int64_t i = 0; i < n_keys; ++i) ix->n_hits += (int64_t)n[i];
 	for (int dv : distinct_devices(G.devices)) {
 		DeviceScope on(dv);
 		hipError_t e = on.err;
@@ -263,7 +477,66 @@ void mm2c_minidx_destroy(mm2c_minidx_t *ix)
 {
 	if (!ix) return;
 	ix->copies.destroy();
+	if (ix->owns_pool) mm2c_hitpool_destroy(const_cast<mm2c_hitpool_t *>(ix->pool));
 	delete ix;
+}
+
+mm2c_minidx_t *mm2c_minidx_build(int k, int w, int is_hpc, int64_t n_seqs, const int64_t *seq_off, const uint8_t *seq, float mid_occ_frac, int *mid_occ)
+{
+	if (named(check_build_args(k, w, n_seqs, seq_off, seq))) return nullptr;   // before any device work
+	if (!lib_ready()) { named(fail_not_ready()); return nullptr; }
+	mm2c_minidx *ix = new mm2c_minidx();
+	ix->k = k; ix->w = w; ix->hpc = is_hpc ? 1 : 0;
+	int occ = INT32_MAX, rc;
+	try { rc = build_index(ix, n_seqs, seq_off, seq, mid_occ_frac, &occ); }
+	catch (const std::bad_alloc &) { rc = fail(MM2C_E_HIP, "mm2c_minidx_build: out of host memory"); }
+	if (named(rc)) { mm2c_minidx_destroy(ix); return nullptr; }
+	if (mid_occ) *mid_occ = occ;
+	return ix;
+}
+
+int64_t mm2c_minidx_n_keys(const mm2c_minidx_t *idx) { return idx ? idx->n : 0; }
+int64_t mm2c_minidx_n_hits(const mm2c_minidx_t *idx) { return idx ? idx->n_hits : 0; }
+const mm2c_hitpool_t *mm2c_minidx_pool(const mm2c_minidx_t *idx) { return idx ? idx->pool : nullptr; }
+
+int mm2c_minidx_cal_max_occ(const mm2c_minidx_t *idx, float frac)
+{
+	if (!lib_ready()) return fail_not_ready();
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	int occ = INT32_MAX;
+	if (int rc = cal_max_occ(idx, frac, &occ)) return rc;
+	return occ;
+}
+
+int mm2c_minidx_export(const mm2c_minidx_t *idx, uint64_t *keys, int64_t *cr_off, uint32_t *n, uint64_t *pool)
+{
+	if (!lib_ready()) return fail_not_ready();
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	const int dev = idx->copies.dev[0];
+	DeviceScope on(dev);
+	HIP_TRY(on.err);
+	const char *img = (const char *)idx->copies.d[0];
+	const size_t nk = (size_t)idx->n;
+	if (nk && keys) HIP_TRY(hipMemcpy(keys, img, nk * 8, hipMemcpyDeviceToHost));
+	if (nk && cr_off) HIP_TRY(hipMemcpy(cr_off, img + nk * 8, nk * 8, hipMemcpyDeviceToHost));
+	if (nk && n) HIP_TRY(hipMemcpy(n, img + nk * 16, nk * 4, hipMemcpyDeviceToHost));
+	if (pool && idx->owns_pool && idx->n_hits > 0) {
+		const uint64_t *d_pool = hitpool_on(idx->pool, dev);
+		if (!d_pool) return fail(MM2C_E_ARG, "the hit pool has no copy on device %d", dev);
+		HIP_TRY(hipMemcpy(pool, d_pool, (size_t)idx->n_hits * 8, hipMemcpyDeviceToHost));
+	}
+	return 0;
+}
+
+void mm2c_get_index_stats(mm2c_index_stats_t *out)
+{
+	if (!out) return;
+	*out = mm2c_index_stats_t{ IX.calls, IX.chunks, IX.bases, IX.minimizers, IX.keys, IX.h2d_ns, IX.sketch_ns, IX.sort_ns, IX.group_ns, IX.occ_ns, IX.replicate_ns };
+}
+
+void mm2c_reset_index_stats(void)
+{
+	for (auto *a : { &IX.calls, &IX.chunks, &IX.bases, &IX.minimizers, &IX.keys, &IX.h2d_ns, &IX.sketch_ns, &IX.sort_ns, &IX.group_ns, &IX.occ_ns, &IX.replicate_ns }) *a = 0;
 }
 
 mm2c_read_result_t *mm2c_read_result_create(void)

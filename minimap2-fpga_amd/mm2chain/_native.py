@@ -55,6 +55,11 @@ class SketchStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "matches", "h2d_ns", "sketch_ns", "lookup_ns")]
 
 
+class IndexStats(C.Structure):
+    """mm2c_index_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "keys", "h2d_ns", "sketch_ns", "sort_ns", "group_ns", "occ_ns", "replicate_ns")]
+
+
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
     "mm2c_init_devices": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
@@ -132,6 +137,14 @@ C_SYMBOLS = {
     "mm2c_minidx_create": (C.c_void_p, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_minidx_destroy": (None, [C.c_void_p]),
     "mm2c_minidx_lookup": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_minidx_build": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(C.c_int)]),
+    "mm2c_minidx_n_keys": (C.c_int64, [C.c_void_p]),
+    "mm2c_minidx_n_hits": (C.c_int64, [C.c_void_p]),
+    "mm2c_minidx_pool": (C.c_void_p, [C.c_void_p]),
+    "mm2c_minidx_cal_max_occ": (C.c_int, [C.c_void_p, C.c_float]),
+    "mm2c_minidx_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_get_index_stats": (None, [C.POINTER(IndexStats)]),
+    "mm2c_reset_index_stats": (None, []),
     "mm2c_read_result_create": (C.POINTER(ReadResult), []),
     "mm2c_read_result_free": (None, [C.POINTER(ReadResult)]),
     "mm2c_sketch_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),

@@ -511,10 +511,19 @@ class HitPool:
             N.check(-4, "mm2c_hitpool_create")
         self.size = h.size
 
+    _owned = True
+
+    @classmethod
+    def _view(cls, handle, size):
+        """a pool that belongs to something else (the pool of MinimizerIndex.build): never destroyed from here"""
+        self = cls.__new__(cls)
+        self.lib, self.handle, self.size, self._owned = N.load(), handle, int(size), False
+        return self
+
     def close(self):
-        if self.handle:
+        if self.handle and self._owned:
             self.lib.mm2c_hitpool_destroy(self.handle)
-            self.handle = None
+        self.handle = None
 
     def __del__(self):
         try:
@@ -609,6 +618,49 @@ class MinimizerIndex:
             N.check(-2, "mm2c_minidx_create")
         self.size = kk.size
 
+    @classmethod
+    def build(cls, seqs, k, w, is_hpc=False, mid_occ_frac=2e-4):
+        """mm2c_minidx_build: the index of `seqs` (a list of bytes / str / uint8 arrays, or (seq_off, seq)) made on the device, as mm_idx_gen makes it.
+        The index owns its pool: .pool is a view that does not free it.  .mid_occ = mm_idx_cal_max_occ(mid_occ_frac)"""
+        off, seq = _reads_args(seqs)
+        self = cls.__new__(cls)
+        self.lib = N.load()
+        self.k, self.w, self.is_hpc = int(k), int(w), int(bool(is_hpc))
+        occ = C.c_int(0)
+        self.handle = self.lib.mm2c_minidx_build(self.k, self.w, self.is_hpc, off.size - 1, _np_ptr(off), _np_ptr(seq), float(mid_occ_frac), C.byref(occ))
+        if not self.handle:
+            msg = (self.lib.mm2c_last_error() or b"").decode()
+            code = {"MM2C_E_NODEVICE": -1, "MM2C_E_ARG": -2, "MM2C_E_TOOBIG": -3}.get(msg.split(":")[0], -4)
+            N.check(code, "mm2c_minidx_build")
+        self.mid_occ = int(occ.value)
+        self.size = self.n_keys
+        self.pool = HitPool._view(self.lib.mm2c_minidx_pool(self.handle), self.n_hits)
+        return self
+
+    @property
+    def n_keys(self):
+        return int(self.lib.mm2c_minidx_n_keys(self.handle))
+
+    @property
+    def n_hits(self):
+        return int(self.lib.mm2c_minidx_n_hits(self.handle))
+
+    def cal_max_occ(self, frac=2e-4):
+        """mm_idx_cal_max_occ on the device"""
+        occ = self.lib.mm2c_minidx_cal_max_occ(self.handle, float(frac))
+        if occ < 0:
+            N.check(occ, "mm2c_minidx_cal_max_occ")
+        return int(occ)
+
+    def export(self):
+        """(keys uint64, cr_off int64, n uint32, pool uint64) downloaded; pool is empty for an index made over a caller's HitPool"""
+        nk = self.n_keys
+        built = not self.pool._owned
+        keys = np.zeros(nk, np.uint64); cr = np.zeros(nk, np.int64); n = np.zeros(nk, np.uint32)
+        pool = np.zeros(self.n_hits if built else 0, np.uint64)
+        N.check(self.lib.mm2c_minidx_export(self.handle, _np_ptr(keys), _np_ptr(cr), _np_ptr(n), _np_ptr(pool) if pool.size else None), "mm2c_minidx_export")
+        return keys, cr, n, pool
+
     def lookup(self, keys):
         """(cr_off int64, n uint32) per key"""
         q = np.ascontiguousarray(keys, dtype=np.uint64)
@@ -620,6 +672,8 @@ class MinimizerIndex:
         if self.handle:
             self.lib.mm2c_minidx_destroy(self.handle)
             self.handle = None
+            if not self.pool._owned:                    # a built index took its pool with it
+                self.pool.handle = None
 
     def __del__(self):
         try:
@@ -673,6 +727,16 @@ def sketch_stats(reset=False):
     lib.mm2c_get_sketch_stats(C.byref(st))
     if reset:
         lib.mm2c_reset_sketch_stats()
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def index_stats(reset=False):
+    """mm2c_get_index_stats as a dict (ns and counts); reset=True clears the counters afterwards"""
+    lib = N.load()
+    st = N.IndexStats()
+    lib.mm2c_get_index_stats(C.byref(st))
+    if reset:
+        lib.mm2c_reset_index_stats()
     return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
 
