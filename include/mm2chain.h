@@ -391,13 +391,13 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
 
 /* ---- reads in: mm_sketch (sketch.c:77-143) and collect_matches (map.c:90-123) on the device ------------------------------
  * Reads are raw bytes, concatenated: read r is seq[seq_off[r] .. seq_off[r+1]) (seq_off: n_reads + 1 entries, seq_off[0] = 0, monotone).  Every byte value is
- * legal; the nucleotide table of sketch.c:9-26 applies.  A read of length 0 has no minimizers.  Every read is ONE segment with rid 0, as collect_minimizers
- * (map.c:64-77) with n_segs = 1.  Results are bit for bit those of the reference, in its order (minimizers, matches, mini_pos).
+ * legal; the nucleotide table of sketch.c:9-26 applies.  A read of length 0 has no minimizers.  In the three entries mm2c_sketch_batch, mm2c_sketch_match_batch and
+ * mm2c_read_chain_batch every read is ONE segment with rid 0, as collect_minimizers (map.c:64-77) with n_segs = 1; paired and multi-segment reads (n_segs > 1,
+ * --frag, -x sr) and the max_occ re-chaining of map.c:318-340 (-x sr sets mid_occ = 1000, max_occ = 5000, options.c:138-139) go through the fragment entries
+ * further down.  Results are bit for bit those of the reference, in its order (minimizers, matches, mini_pos).
  * Out of scope here -- a host that needs one of these keeps its own sketching for those reads:
  *   - SDUST masking (sdust_thres > 0, map.c:73-74; no preset sets it, options.c:22);
- *   - reads of several segments (n_segs > 1, --frag);
- *   - alignment;
- *   - the max_occ re-chaining of map.c:318-340 (max_occ is never set by this reference's options).
+ *   - alignment.
  * The index itself is built here too (mm2c_minidx_build, below).  Two parts of mm_idx_t stay with the host: the packed reference sequence mi->S with the
  * sequence names (a host that aligns or prints names keeps its own), and .mmi files (mm_idx_dump / mm_idx_load); multi-part indices (-I) are not built. */
 
@@ -459,6 +459,9 @@ typedef struct {
 	/* mm2c_read_chain_batch: what mm_chain_dp returns per read, as mm2c_mm_chain_dp_batch_host lays it out */
 	int64_t n_u, n_b; int64_t *u_off; uint64_t *u; int64_t *b_off; mm2c_anchor_t *b;
 	void *priv;
+	/* mm2c_frag_chain_batch (behind priv: every field above keeps its offset): the fragments whose chains come from the second pass with max_occ, and one
+	 * byte per fragment saying so.  0 / NULL after every other entry */
+	int64_t n_rechained; uint8_t *rechained;
 } mm2c_read_result_t;
 mm2c_read_result_t *mm2c_read_result_create(void);
 void mm2c_read_result_free(mm2c_read_result_t *res);
@@ -476,6 +479,43 @@ int mm2c_sketch_match_batch(const mm2c_minidx_t *idx, int mid_occ, int64_t n_rea
  * mini_off / mini_pos; the results equal mm2c_seed_chain_batch_pool(_skip) fed the matches of mm2c_sketch_match_batch. */
 int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads,
                           const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip, mm2c_read_result_t *res);
+
+/* ---- fragments: paired and multi-segment reads (mm_map_frag with n_segs > 1, map.c:272-340) ----
+ * The batch is laid out as above -- n_reads SEGMENTS concatenated, with seq_off -- and frag_off (n_frags + 1 entries, frag_off[0] = 0, monotone, last = n_reads)
+ * groups consecutive segments into fragments: fragment g holds the segments frag_off[g] .. frag_off[g+1]), with the segment ids 0 .. n - 1 in that order.
+ * As collect_minimizers (map.c:64-77) does, each segment is sketched with rid = its id and its positions are shifted by the lengths of the segments before it
+ * (y += (uint64_t)seg << 32 | sum << 1); the fragment's minimizer list is its segments' lists one after another, and collect_matches runs over that one list:
+ * is_tandem compares neighbours across a segment boundary too, the rep_len recurrence runs on through it, seg_id = y >> 32 goes into seg_tandem, and qlen is the
+ * sum of the segment lengths.  A segment of length 0 contributes nothing but keeps its id; a fragment whose total length is 0 yields nothing (map.c:287).
+ * RESULTS ARE PER FRAGMENT: res->n_reads is n_frags and every offset array has n_frags + 1 entries.
+ * Refused before any device work: a malformed frag_off, an empty fragment, a fragment of more than MM_MAX_SEG = 255 segments (MM2C_E_ARG); a fragment whose total
+ * length does not fit 31 bits, or a non-empty segment that starts 2^30 bases or more into its fragment -- `sum << 1` (map.c:72) overflows the reference's int there
+ * and would spill into the segment id (MM2C_E_TOOBIG). */
+/* collect_minimizers for every fragment -> res->sketch_off / sketch */
+int mm2c_sketch_frag_batch(int k, int w, int is_hpc, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
+                           mm2c_read_result_t *res);
+/* fragments in, matches out: collect_matches with max_occ = occ over every fragment's joined list; fills what mm2c_sketch_match_batch fills */
+int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off,
+                                 const uint8_t *seq, mm2c_read_result_t *res);
+/* fragments in, chains out, with the re-chain of map.c:318-340: every fragment is chained with mid_occ; a kernel then decides per fragment, from the chains on the
+ * device, rechain = (max_occ > mid_occ && rep_len > 0) && (no chain || the best chain -- the FIRST with the strictly largest score -- does not span all n_segs
+ * segments); the flagged fragments' minimizers are compacted on the device (the sketch is not redone) and run through lookups, seed hits, DP and epilogue a second
+ * time with max_occ.  For exactly those fragments anchor_off, rep_len, mini_pos, u and b are the second pass's; the output is in fragment order, as if one pass
+ * had made it.  max_occ <= mid_occ switches the second pass off.  Chunks of "read_chunk_bases" bases are cut between fragments, never inside one.
+ * Every fragment must have exactly par->n_segs segments (mm_chain_dp gets the fragment's own n_segs, chain.c:206; MM2C_E_ARG otherwise): a host with fragments of
+ * different segment counts makes one call per count.  par->max_dist_x / max_dist_y are the call's: under -x sr they depend on the fragment's total length
+ * (max_dist_y = max(qlen_sum, max_gap), max_dist_x = max(max_frag_len - qlen_sum, max_gap), map.c:306-314), so such a host makes one call per total length --
+ * fixed-length pairs are one call.  skip: its per-read arrays are per fragment.  mm2c_tune("heap_sort", 1) applies (-x sr sets MM_F_HEAP_SORT). */
+int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, int64_t n_frags,
+                          const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
+                          mm2c_read_result_t *res);
+/* the fragment entries since mm2c_init or the last reset: calls, fragments processed, fragments re-chained, and the time of the second pass on the call's
+ * stream.  rechain_ns is the time ELAPSED between two HIP events, one in front of the decision kernel and one behind the second pass's epilogue: it holds the
+ * decision, the compaction, the second lookups -> epilogue AND the gaps in which the stream waits for the host (the counts coming down, the second pass's seed
+ * and chain plans being set up).  It is what the second pass adds to a call, not the busy time of its kernels. */
+typedef struct { uint64_t calls, fragments, rechained, rechain_ns; } mm2c_frag_stats_t;
+void mm2c_get_frag_stats(mm2c_frag_stats_t *out);
+void mm2c_reset_frag_stats(void);
 /* device time of the sketch and of the lookups (HIP events around them, summed since mm2c_init or the last reset), and what they processed */
 typedef struct { uint64_t calls, chunks, bases, minimizers, matches, h2d_ns, sketch_ns, lookup_ns; } mm2c_sketch_stats_t;
 void mm2c_get_sketch_stats(mm2c_sketch_stats_t *out);

@@ -17,6 +17,14 @@ size_t sketch_scan_bytes(int64_t n_chunks, int64_t n_sc);
 size_t lookup_scan_bytes(int64_t n_mini);
 size_t sketch_push_bytes();
 size_t sketch_lsum_bytes();
+int frag_tag(mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_segs, int64_t n_mini, const uint64_t *seg_tag, const int64_t *frag_off, int64_t n_frags,
+             int64_t *frag_mini_off, hipStream_t st);
+size_t rechain_scan_bytes(int64_t n_frags);
+int rechain_decide(const int64_t *u_off, const uint64_t *u, const int64_t *b_off, const mm2c_anchor_t *b, const int32_t *rep_len, const int64_t *mini_off,
+                   int64_t n_frags, int n_segs, uint8_t *flag, int64_t *cnt, int64_t *sel, int64_t *mini_off2, void *scan_tmp, size_t scan_bytes, int64_t h_n[2],
+                   hipStream_t st);
+int rechain_gather(const mm2c_anchor_t *mini, const int64_t *mini_off, const int64_t *sel, const int64_t *mini_off2, int64_t n_sel, int64_t n_mini2, mm2c_anchor_t *mini2,
+                   hipStream_t st);
 int minidx_image(const uint64_t *h_keys, const int64_t *h_cr, const uint32_t *h_n, int64_t n, int key_bits, char *d_img, int *h_dup, hipStream_t st);
 // index_build.hip
 int index_tag(const mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_seqs, int64_t n_mini, int64_t rid0, uint64_t *key, uint64_t *y, hipStream_t st);
@@ -33,6 +41,7 @@ std::atomic<int64_t> index_chunk_bases{1 << 27};                            // m
 namespace {
 
 struct SketchStats { std::atomic<uint64_t> calls{0}, chunks{0}, bases{0}, minimizers{0}, matches{0}, h2d_ns{0}, sketch_ns{0}, lookup_ns{0}; } SK;
+struct FragStats { std::atomic<uint64_t> calls{0}, fragments{0}, rechained{0}, rechain_ns{0}; } FR;
 struct IndexStats { std::atomic<uint64_t> calls{0}, chunks{0}, bases{0}, minimizers{0}, keys{0}, h2d_ns{0}, sketch_ns{0}, sort_ns{0}, group_ns{0}, occ_ns{0}, replicate_ns{0}; } IX;
 
 // grow-only host arrays: a result object that serves many calls keeps its pages (no zeroing, no page faults on the next call)
@@ -63,6 +72,7 @@ struct ResPriv {
 	Buf<mm2c_match_t> matches;
 	Buf<int32_t> rep_len;
 	Buf<uint64_t> mini_pos, u;
+	Buf<uint8_t> rechained;
 };
 
 void publish(mm2c_read_result_t *res, int64_t n_reads)
@@ -77,13 +87,14 @@ void publish(mm2c_read_result_t *res, int64_t n_reads)
 	res->mini_off = off(P.mini_off); res->n_mini_pos = P.mini_off.empty() ? 0 : P.mini_off.back(); res->mini_pos = P.mini_pos.data();
 	res->u_off = off(P.u_off); res->n_u = P.u_off.empty() ? 0 : P.u_off.back(); res->u = P.u.data();
 	res->b_off = off(P.b_off); res->n_b = P.b_off.empty() ? 0 : P.b_off.back(); res->b = P.b.data();
+	res->n_rechained = 0; res->rechained = nullptr;            // mm2c_frag_chain_batch fills them after this
 }
 
 void clear(mm2c_read_result_t *res)
 {
 	ResPriv &P = *(ResPriv *)res->priv;
 	for (auto *v : { &P.sketch_off, &P.match_off, &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->clear();
-	P.sketch.clear(); P.b.clear(); P.matches.clear(); P.rep_len.clear(); P.mini_pos.clear(); P.u.clear();
+	P.sketch.clear(); P.b.clear(); P.matches.clear(); P.rep_len.clear(); P.mini_pos.clear(); P.u.clear(); P.rechained.clear();
 }
 
 int check_reads(int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
@@ -95,6 +106,30 @@ int check_reads(int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2
 		if (seq_off[r + 1] < seq_off[r]) return fail(MM2C_E_ARG, "sequence offsets not monotone at read %lld", (long long)r);
 		else if (seq_off[r + 1] - seq_off[r] > INT32_MAX) return fail(MM2C_E_TOOBIG, "read %lld is longer than 2^31 - 1 bases", (long long)r);
 	if (n_reads > 0 && seq_off[n_reads] > 0 && !seq) return fail(MM2C_E_ARG, "seq is NULL");
+	return 0;
+}
+
+// the fragments of a batch whose segments check_reads has accepted: frag_off runs from 0 to n_reads, 1 .. MM_MAX_SEG segments each, a total length of 31 bits
+int check_frags(int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off)
+{
+	if (n_frags < 0 || (n_frags > 0 && !frag_off)) return fail(MM2C_E_ARG, "bad argument");
+	if (n_frags == 0) return n_reads == 0 && (!frag_off || frag_off[0] == 0) ? 0 : fail(MM2C_E_ARG, "frag_off must run from 0 to n_reads");
+	if (frag_off[0] != 0 || frag_off[n_frags] != n_reads) return fail(MM2C_E_ARG, "frag_off must run from 0 to n_reads");
+	for (int64_t g = 0; g < n_frags; ++g) {
+		const int64_t n = frag_off[g + 1] - frag_off[g];
+		if (n < 0) return fail(MM2C_E_ARG, "fragment offsets not monotone at fragment %lld", (long long)g);
+		if (n == 0) return fail(MM2C_E_ARG, "fragment %lld has no segment", (long long)g);
+		if (n > 255) return fail(MM2C_E_ARG, "fragment %lld has %lld segments: more than MM_MAX_SEG = 255 (map.c:287)", (long long)g, (long long)n);
+	}
+	for (int64_t g = 0; g < n_frags; ++g)                      // monotone from 0 to n_reads: every entry indexes seq_off
+		if (seq_off[frag_off[g + 1]] - seq_off[frag_off[g]] > (int64_t)INT32_MAX)
+			return fail(MM2C_E_TOOBIG, "fragment %lld is longer than 2^31 - 1 bases in all (qlen_sum is an int)", (long long)g);
+	// `y += sum << 1` (map.c:72) overflows the reference's int once the segments before a non-empty one hold 2^30 bases, and would spill into the segment id
+	for (int64_t g = 0; g < n_frags; ++g)
+		for (int64_t s = frag_off[g]; s < frag_off[g + 1]; ++s)
+			if (seq_off[s + 1] > seq_off[s] && seq_off[s] - seq_off[frag_off[g]] >= ((int64_t)1 << 30))
+				return fail(MM2C_E_TOOBIG, "fragment %lld: segment %lld starts 2^30 bases or more into the fragment (sum << 1 must fit an int, map.c:72)",
+				            (long long)g, (long long)(s - frag_off[g]));
 	return 0;
 }
 
@@ -123,7 +158,8 @@ struct Run {
 	uint64_t *d_mini_pos = nullptr;
 	int64_t *d_match_off = nullptr, *d_anchor_off = nullptr;
 	int32_t *d_rep_len = nullptr;
-	std::vector<int64_t> h_seq_off;
+	std::vector<int64_t> h_seq_off, h_frag_off;
+	std::vector<uint64_t> h_seg_tag;
 	Evts ev;
 	bool for_index = false;                    // a chunk of mm2c_minidx_build: counted in the index statistics, not in the sketch's
 
@@ -175,6 +211,32 @@ struct Run {
 		return 0;
 	}
 
+	// after sketch() over the segments [frag_off[g0], frag_off[g1]): collect_minimizers' tagging (rid = segment number, positions shifted by the lengths of the
+	// segments before, map.c:70-72), and from here on the run's "reads" are the fragments [g0, g1) with their segments' lists joined
+	int to_frags(const int64_t *frag_off, int64_t g0, int64_t g1)
+	{
+		const int64_t ns = nr, nf = g1 - g0, s0 = frag_off[g0];
+		h_frag_off.resize((size_t)nf + 1); h_seg_tag.resize((size_t)std::max<int64_t>(ns, 1));
+		for (int64_t g = 0; g <= nf; ++g) h_frag_off[(size_t)g] = frag_off[g0 + g] - s0;
+		for (int64_t g = 0; g < nf; ++g) {
+			int sum = 0;                                           // the reference's int (map.c:66)
+			for (int64_t s = h_frag_off[(size_t)g], i = 0; s < h_frag_off[(size_t)g + 1]; ++s, ++i) {
+				h_seg_tag[(size_t)s] = (uint64_t)i << 32;
+				h_seg_tag[(size_t)s] += (uint64_t)sum << 1;           // y += sum << 1 (check_frags: no overflow of the reference's int)
+				sum += (int)(h_seq_off[(size_t)s + 1] - h_seq_off[(size_t)s]);
+			}
+		}
+		Layout L;
+		const size_t o_tag = L.take((size_t)std::max<int64_t>(ns, 1) * 8), o_fo = L.take(((size_t)nf + 1) * 8), o_fmo = L.take(((size_t)nf + 1) * 8);
+		char *d = nullptr;
+		HIP_TRY(take((void **)&d, L.at));
+		HIP_TRY(hipMemcpyAsync(d + o_tag, h_seg_tag.data(), (size_t)std::max<int64_t>(ns, 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d + o_fo, h_frag_off.data(), ((size_t)nf + 1) * 8, hipMemcpyHostToDevice, st));
+		if (int rc = frag_tag(d_mini, d_mini_off, ns, n_mini, (const uint64_t *)(d + o_tag), (const int64_t *)(d + o_fo), nf, (int64_t *)(d + o_fmo), st)) return rc;
+		d_mini_off = (int64_t *)(d + o_fmo); nr = nf;
+		return 0;
+	}
+
 	int lookup(const mm2c_minidx_t *idx, int device, int mid_occ);   // after sketch(); below
 	void time_it(bool looked_up)
 	{
@@ -223,6 +285,86 @@ struct OwnStream {                               // a private stream of the call
 	int make() { HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); return 0; }
 	~OwnStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
 };
+
+// One pass of seed hits -> DP -> epilogue over the reads (or fragments) of a Run that has looked its minimizers up: the per-chunk step of mm2c_read_chain_batch and
+// of both passes of mm2c_frag_chain_batch.  The chains stay in the pass's arena on the device (u_off / b_off / u / b, where the re-chain decision reads them)
+// until fetch_pass() brings them down.
+struct ChainPass {
+	size_t nr = 0;
+	int64_t tot = 0;
+	std::vector<int64_t> mo, cap, off;                     // match offsets, anchor capacities; [u_off | b_off | packed anchor_off]
+	const int64_t *uo = nullptr, *bo = nullptr, *ao = nullptr;
+	char *d = nullptr;
+	ChunkLayout o{};
+
+	// qlen / skip: of exactly these nr reads (skip's per-read arrays start at the first of them).  on_device: u_off / b_off are wanted on the device even when
+	// the chunk has no anchor at all (the re-chain decision reads them)
+	int run(Run &R, const mm2c_params_t *par, int min_cnt, int min_sc, const uint64_t *d_pool, int64_t n_hits, const int32_t *qlen, const mm2c_seed_skip_host_t *skip,
+	        const int32_t *d_ref, size_t n_ref, hipEvent_t ev_epi, bool on_device)
+	{
+		hipStream_t st = R.st;
+		nr = (size_t)R.nr;
+		mo.resize(nr + 1); cap.resize(nr + 1); off.assign(3 * (nr + 1), 0);
+		HIP_TRY(hipMemcpyAsync(mo.data(), R.d_match_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(cap.data(), R.d_anchor_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		tot = cap[nr];
+		if (tot >= (int64_t)INT32_MAX) return fail(MM2C_E_TOOBIG, "a chunk of reads with 2^31 anchors or more (lower read_chunk_bases)");
+		uo = off.data(); bo = uo + nr + 1; ao = skip ? bo + nr + 1 : cap.data();
+		if (tot == 0 && !on_device) return 0;                  // no anchors at all: no read has a chain
+		Layout L;
+		o = chunk_layout(L, nr, (size_t)tot, skip_per_read(skip), true);   // (room for the packed anchor_off with or without skip_seed)
+		HIP_TRY(R.take((void **)&d, L.at));
+		if (tot == 0) {
+			HIP_TRY(hipMemsetAsync(d + o.o_uo, 0, (nr + 1) * 8, st));
+			HIP_TRY(hipMemsetAsync(d + o.o_bo, 0, (nr + 1) * 8, st));
+			if (ev_epi) HIP_TRY(hipEventRecord(ev_epi, st));
+			return 0;
+		}
+		mm2c_seedplan_t *sp = mm2c_seedplan_create((int64_t)nr, mo.data(), cap.data());
+		if (!sp) return MM2C_E_HIP;
+		mm2c_plan_t *pl = mm2c_plan_create(par, (int64_t)nr, cap.data());
+		if (!pl) { mm2c_seedplan_destroy(sp); return MM2C_E_HIP; }
+		auto body = [&]() -> int {
+			int r;
+			HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
+			mm2c_seed_skip_t sk;
+			if (skip) HIP_TRY(skip_upload_reads(skip, 0, (int64_t)nr, d_ref, d_ref + n_ref, (int32_t *)(d + o.o_lo), (int32_t *)(d + o.o_eq), st, &sk));
+			Evts seed;                                                // [0], [1]: around the seed hits
+			if ((r = seed.make())) return r;
+			HIP_TRY(hipEventRecord(seed.e[0], st));
+			if ((r = chunk_step(sp, pl, R.d_matches, d_pool, n_hits, skip ? &sk : nullptr, d, o, min_cnt, min_sc, st, seed.e[1], nullptr, ev_epi, off.data()))) return r;
+			HIP_TRY(hipStreamSynchronize(st));
+			if ((r = mm2c_seedplan_check(sp, nullptr))) return r;
+			SS.seed_ns += (uint64_t)(seed.ms(0, 1) * 1e6f);
+			return 0;
+		};
+		const int rc = body();
+		mm2c_plan_destroy(pl);
+		mm2c_seedplan_destroy(sp);
+		return rc;
+	}
+};
+
+// the chains of a pass, the mini_pos and the rep_len of its run, down to the host (room for C.uo[nr] / C.bo[nr] / R.n_matches / nr entries); waits
+int fetch_pass(Run &R, const ChainPass &C, uint64_t *u, mm2c_anchor_t *b, uint64_t *mini_pos, int32_t *rep_len)
+{
+	const size_t nr = C.nr;
+	if (C.uo[nr]) HIP_TRY(hipMemcpyAsync(u, C.d + C.o.o_u, (size_t)C.uo[nr] * 8, hipMemcpyDeviceToHost, R.st));
+	if (C.bo[nr]) HIP_TRY(hipMemcpyAsync(b, C.d + C.o.o_b, (size_t)C.bo[nr] * 16, hipMemcpyDeviceToHost, R.st));
+	if (R.n_matches) HIP_TRY(hipMemcpyAsync(mini_pos, R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, R.st));
+	HIP_TRY(hipMemcpyAsync(rep_len, R.d_rep_len, nr * 4, hipMemcpyDeviceToHost, R.st));
+	HIP_TRY(hipStreamSynchronize(R.st));
+	return 0;
+}
+
+// the per-read arrays of a skip description from read r0 on
+inline mm2c_seed_skip_host_t skip_from(const mm2c_seed_skip_host_t *skip, int64_t r0)
+{
+	mm2c_seed_skip_host_t s{};
+	if (skip) { s = *skip; if (s.q_lo) s.q_lo += r0; if (s.q_eq) s.q_eq += r0; }
+	return s;
+}
 }
 
 // ---- mm2c_minidx_build: the index made on the device from the sequences (kernels in index_build.hip)
@@ -690,59 +832,19 @@ int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 		const size_t nr = (size_t)(r1 - r0);
 		Run R; R.st = st;
 		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, r0, r1)) || (rc = R.lookup(idx, device, mid_occ))) return rc;
-		std::vector<int64_t> mo(nr + 1), cap(nr + 1);
+		R.time_it(true);
 		std::vector<int32_t> qlen(nr);
 		for (size_t r = 0; r < nr; ++r) qlen[r] = (int32_t)(seq_off[r0 + (int64_t)r + 1] - seq_off[r0 + (int64_t)r]);
-		P.mini_pos.resize((size_t)(M + R.n_matches));
-		HIP_TRY(hipMemcpyAsync(mo.data(), R.d_match_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(cap.data(), R.d_anchor_off, (nr + 1) * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(P.rep_len.data() + r0, R.d_rep_len, nr * 4, hipMemcpyDeviceToHost, st));
-		if (R.n_matches) HIP_TRY(hipMemcpyAsync(P.mini_pos.data() + M, R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		R.time_it(true);
-		for (size_t r = 1; r <= nr; ++r) P.mini_off[(size_t)r0 + r] = M + mo[r];
-		M += R.n_matches;
-		const int64_t tot = cap[nr];
-		if (tot >= (int64_t)INT32_MAX) return fail(MM2C_E_TOOBIG, "a chunk of reads with 2^31 anchors or more (lower read_chunk_bases)");
-		if (tot > 0) {
-			mm2c_seedplan_t *sp = mm2c_seedplan_create((int64_t)nr, mo.data(), cap.data());
-			if (!sp) return MM2C_E_HIP;
-			mm2c_plan_t *pl = mm2c_plan_create(par, (int64_t)nr, cap.data());
-			if (!pl) { mm2c_seedplan_destroy(sp); return MM2C_E_HIP; }
-			auto body = [&]() -> int {
-				int r;
-				Layout L;
-				const ChunkLayout o = chunk_layout(L, nr, (size_t)tot, skip_per_read(skip), true);   // (room for the packed anchor_off with or without skip_seed)
-				char *d = nullptr;
-				HIP_TRY(R.take((void **)&d, L.at));
-				HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen.data(), nr * 4, hipMemcpyHostToDevice, st));
-				mm2c_seed_skip_t sk;
-				if (skip) HIP_TRY(skip_upload_reads(skip, r0, r1, d_ref, d_ref + n_ref, (int32_t *)(d + o.o_lo), (int32_t *)(d + o.o_eq), st, &sk));
-				Evts seed;                                                // [0], [1]: around the seed hits
-				if ((r = seed.make())) return r;
-				HIP_TRY(hipEventRecord(seed.e[0], st));
-				std::vector<int64_t> off(3 * (nr + 1));
-				if ((r = chunk_step(sp, pl, R.d_matches, d_pool, n_hits, skip ? &sk : nullptr, d, o, min_cnt, min_sc, st, seed.e[1], nullptr, nullptr, off.data()))) return r;
-				const int64_t *uo = off.data(), *bo = uo + nr + 1, *ao = skip ? bo + nr + 1 : cap.data();
-				HIP_TRY(hipStreamSynchronize(st));
-				if ((r = mm2c_seedplan_check(sp, nullptr))) return r;
-				SS.seed_ns += (uint64_t)(seed.ms(0, 1) * 1e6f);
-				P.u.resize((size_t)(U + uo[nr])); P.b.resize((size_t)(B + bo[nr]));
-				if (uo[nr]) HIP_TRY(hipMemcpyAsync(P.u.data() + U, d + o.o_u, (size_t)uo[nr] * 8, hipMemcpyDeviceToHost, st));
-				if (bo[nr]) HIP_TRY(hipMemcpyAsync(P.b.data() + B, d + o.o_b, (size_t)bo[nr] * 16, hipMemcpyDeviceToHost, st));
-				HIP_TRY(hipStreamSynchronize(st));
-				for (size_t k = 1; k <= nr; ++k) {
-					P.u_off[(size_t)r0 + k] = U + uo[k]; P.b_off[(size_t)r0 + k] = B + bo[k]; P.anchor_off[(size_t)r0 + k] = A + ao[k];
-				}
-				U += uo[nr]; B += bo[nr]; A += ao[nr];
-				return 0;
-			};
-			rc = body();
-			mm2c_plan_destroy(pl);
-			mm2c_seedplan_destroy(sp);
-			if (rc) return rc;
-		} else
-			for (size_t k = 1; k <= nr; ++k) { P.u_off[(size_t)r0 + k] = U; P.b_off[(size_t)r0 + k] = B; P.anchor_off[(size_t)r0 + k] = A; }
+		const mm2c_seed_skip_host_t sk = skip_from(skip, r0);
+		ChainPass C;
+		if ((rc = C.run(R, par, min_cnt, min_sc, d_pool, n_hits, qlen.data(), skip ? &sk : nullptr, d_ref, n_ref, nullptr, false))) return rc;
+		P.u.resize((size_t)(U + C.uo[nr])); P.b.resize((size_t)(B + C.bo[nr])); P.mini_pos.resize((size_t)(M + R.n_matches));
+		if ((rc = fetch_pass(R, C, P.u.data() + U, P.b.data() + B, P.mini_pos.data() + M, P.rep_len.data() + r0))) return rc;
+		for (size_t k = 1; k <= nr; ++k) {
+			P.mini_off[(size_t)r0 + k] = M + C.mo[k];
+			P.u_off[(size_t)r0 + k] = U + C.uo[k]; P.b_off[(size_t)r0 + k] = B + C.bo[k]; P.anchor_off[(size_t)r0 + k] = A + C.ao[k];
+		}
+		M += R.n_matches; U += C.uo[nr]; B += C.bo[nr]; A += C.ao[nr];
 		++SK.chunks; ++SS.chunks;
 		r0 = r1;
 	}
@@ -750,6 +852,239 @@ int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 	G.tasks += (uint64_t)n_reads; G.anchors += (uint64_t)A;
 	publish(res, n_reads);
 	return 0;
+}
+
+// ---- fragments of several segments and the max_occ re-chain
+} // extern "C"
+
+namespace {
+
+// what one pass left for its fragments, on the host
+struct PassHost {
+	std::vector<uint64_t> u, mini_pos;
+	std::vector<mm2c_anchor_t> b;
+	std::vector<int32_t> rep_len;
+	int fetch(Run &R, ChainPass &C)
+	{
+		u.resize((size_t)C.uo[C.nr]); b.resize((size_t)C.bo[C.nr]); mini_pos.resize((size_t)R.n_matches); rep_len.resize(C.nr);
+		return fetch_pass(R, C, u.data(), b.data(), mini_pos.data(), rep_len.data());
+	}
+};
+
+// the checks the three fragment entries share, before any device work
+int check_frag_call(int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	if (int rc = check_reads(n_reads, seq_off, seq, res)) return rc;
+	return check_frags(n_frags, frag_off, n_reads, seq_off);
+}
+
+} // namespace
+
+extern "C" {
+
+int mm2c_sketch_frag_batch(int k, int w, int is_hpc, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
+                           mm2c_read_result_t *res)
+{
+	int rc;
+	if ((rc = check_kw(k, w)) || (rc = check_frag_call(n_frags, frag_off, n_reads, seq_off, seq, res))) return rc;   // before any device work
+	if (!lib_ready()) return fail_not_ready();
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	P.sketch_off.assign((size_t)n_frags + 1, 0);
+	if (n_frags > 0) {
+		DeviceScope on(cur_device());
+		HIP_TRY(on.err);
+		OwnStream os;
+		if ((rc = os.make())) return rc;
+		Run R; R.st = os.st;
+		if ((rc = R.sketch(k, w, is_hpc ? 1 : 0, seq_off, seq, 0, n_reads)) || (rc = R.to_frags(frag_off, 0, n_frags))) return rc;
+		P.sketch.resize((size_t)R.n_mini);
+		HIP_TRY(hipMemcpyAsync(P.sketch_off.data(), R.d_mini_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		if (R.n_mini) HIP_TRY(hipMemcpyAsync(P.sketch.data(), R.d_mini, (size_t)R.n_mini * 16, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipStreamSynchronize(os.st));
+		R.time_it(false);
+		++SK.calls; ++SK.chunks;
+		FR.fragments += (uint64_t)n_frags;
+	}
+	++FR.calls;
+	publish(res, n_frags);
+	return 0;
+}
+
+int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off,
+                                 const uint8_t *seq, mm2c_read_result_t *res)
+{
+	int rc;
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	if ((rc = check_frag_call(n_frags, frag_off, n_reads, seq_off, seq, res))) return rc;                             // before any device work
+	if (!lib_ready()) return fail_not_ready();
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	P.match_off.assign((size_t)n_frags + 1, 0); P.anchor_off.assign((size_t)n_frags + 1, 0); P.mini_off.assign((size_t)n_frags + 1, 0);
+	P.rep_len.assign((size_t)n_frags, 0);
+	if (n_frags > 0) {
+		const int device = cur_device();
+		DeviceScope on(device);
+		HIP_TRY(on.err);
+		OwnStream os;
+		if ((rc = os.make())) return rc;
+		Run R; R.st = os.st;
+		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, 0, n_reads)) || (rc = R.to_frags(frag_off, 0, n_frags)) || (rc = R.lookup(idx, device, occ))) return rc;
+		P.matches.resize((size_t)R.n_matches); P.mini_pos.resize((size_t)R.n_matches);
+		HIP_TRY(hipMemcpyAsync(P.match_off.data(), R.d_match_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.anchor_off.data(), R.d_anchor_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.rep_len.data(), R.d_rep_len, (size_t)n_frags * 4, hipMemcpyDeviceToHost, os.st));
+		if (R.n_matches) {
+			HIP_TRY(hipMemcpyAsync(P.matches.data(), R.d_matches, (size_t)R.n_matches * sizeof(mm2c_match_t), hipMemcpyDeviceToHost, os.st));
+			HIP_TRY(hipMemcpyAsync(P.mini_pos.data(), R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, os.st));
+		}
+		HIP_TRY(hipStreamSynchronize(os.st));
+		std::copy(P.match_off.p, P.match_off.p + P.match_off.n, P.mini_off.p);   // one mini_pos per kept match
+		R.time_it(true);
+		++SK.calls; ++SK.chunks;
+		FR.fragments += (uint64_t)n_frags;
+	}
+	++FR.calls;
+	publish(res, n_frags);
+	return 0;
+}
+
+int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, int64_t n_frags,
+                          const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
+                          mm2c_read_result_t *res)
+{
+	int rc;
+	if ((rc = check_params(par))) return rc;
+	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
+	if ((rc = check_frag_call(n_frags, frag_off, n_reads, seq_off, seq, res))) return rc;
+	for (int64_t g = 0; g < n_frags; ++g)
+		if (frag_off[g + 1] - frag_off[g] != (int64_t)par->n_segs)
+			return fail(MM2C_E_ARG, "fragment %lld has %lld segments, par->n_segs is %d (mm_chain_dp gets the fragment's own n_segs: one call per segment count)",
+			            (long long)g, (long long)(frag_off[g + 1] - frag_off[g]), (int)par->n_segs);
+	if (skip && (rc = check_skip_pool(skip, n_frags, idx->pool))) return rc;
+	if (!lib_ready()) return fail_not_ready();
+	ScopedNs timed_total(SS.total_ns);
+	clear(res);
+	ResPriv &P = *(ResPriv *)res->priv;
+	for (auto *v : { &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->assign((size_t)n_frags + 1, 0);
+	P.rep_len.assign((size_t)n_frags, 0); P.rechained.assign((size_t)n_frags, 0);
+	++FR.calls;
+	if (n_frags == 0) { publish(res, 0); return 0; }
+	const int device = cur_device();
+	DeviceScope on(device);
+	HIP_TRY(on.err);
+	const uint64_t *d_pool = hitpool_on(idx->pool, device);
+	if (!d_pool) return fail(MM2C_E_ARG, "the hit pool has no copy on device %d", device);
+	const int64_t n_hits = mm2c_hitpool_size(idx->pool);
+	OwnStream os;
+	if ((rc = os.make())) return rc;
+	hipStream_t st = os.st;
+	++SS.calls;
+	const size_t n_ref = skip_n_ref(skip);
+	Run refs; refs.st = st;                                    // [ref_rank | ref_len] once per call
+	int32_t *d_ref = nullptr;
+	if (n_ref) {
+		HIP_TRY(refs.take((void **)&d_ref, 2 * n_ref * 4));
+		HIP_TRY(skip_upload_refs(skip, d_ref, d_ref + n_ref, st));
+	}
+	const bool two_pass = max_occ > mid_occ;                   // map.c:318
+	const int64_t chunk_bases = std::max<int64_t>(read_chunk_bases.load(), 1);
+	auto bases = [&](int64_t g0, int64_t g1) { return seq_off[frag_off[g1]] - seq_off[frag_off[g0]]; };
+	int64_t A = 0, U = 0, B = 0, M = 0, n_rechained = 0;
+	for (int64_t g0 = 0; g0 < n_frags;) {                      // chunks of whole fragments
+		int64_t g1 = g0 + 1;
+		while (g1 < n_frags && bases(g0, g1 + 1) <= chunk_bases) ++g1;
+		const size_t nf = (size_t)(g1 - g0);
+		Run R; R.st = st;
+		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, frag_off[g0], frag_off[g1])) || (rc = R.to_frags(frag_off, g0, g1)) ||
+		    (rc = R.lookup(idx, device, mid_occ))) return rc;
+		R.time_it(true);
+		std::vector<int32_t> qlen(nf);
+		for (size_t g = 0; g < nf; ++g) qlen[g] = (int32_t)bases(g0 + (int64_t)g, g0 + (int64_t)g + 1);   // qlen_sum
+		const mm2c_seed_skip_host_t sk1 = skip_from(skip, g0);
+		ChainPass C1, C2;
+		if ((rc = C1.run(R, par, min_cnt, min_sc, d_pool, n_hits, qlen.data(), skip ? &sk1 : nullptr, d_ref, n_ref, nullptr, true))) return rc;
+
+		// the second pass: decided and compacted on the device, looked up with max_occ, chained like the first
+		Run R2; R2.st = st;
+		int64_t n2[2] = { 0, 0 };
+		std::vector<int64_t> sel;
+		uint8_t *flags = P.rechained.data() + g0;
+		if (two_pass) {
+			Evts ev;
+			if ((rc = ev.make())) return rc;
+			HIP_TRY(hipEventRecord(ev.e[0], st));
+			const size_t scan_bytes = rechain_scan_bytes((int64_t)nf);
+			Layout L;
+			const size_t o_flag = L.take(nf), o_cnt = L.take(4 * (nf + 1) * 8), o_sel = L.take(nf * 8), o_mo2 = L.take((nf + 1) * 8), o_tmp = L.take(scan_bytes);
+			char *d = nullptr;
+			HIP_TRY(R.take((void **)&d, L.at));
+			if ((rc = rechain_decide((const int64_t *)(C1.d + C1.o.o_uo), (const uint64_t *)(C1.d + C1.o.o_u), (const int64_t *)(C1.d + C1.o.o_bo),
+			                         (const mm2c_anchor_t *)(C1.d + C1.o.o_b), R.d_rep_len, R.d_mini_off, (int64_t)nf, par->n_segs, (uint8_t *)(d + o_flag),
+			                         (int64_t *)(d + o_cnt), (int64_t *)(d + o_sel), (int64_t *)(d + o_mo2), d + o_tmp, scan_bytes, n2, st))) return rc;
+			if (n2[0] > 0) {
+				sel.resize((size_t)n2[0]);
+				HIP_TRY(hipMemcpyAsync(flags, d + o_flag, nf, hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipMemcpyAsync(sel.data(), d + o_sel, sel.size() * 8, hipMemcpyDeviceToHost, st));
+				R2.nr = n2[0]; R2.n_mini = n2[1]; R2.d_mini_off = (int64_t *)(d + o_mo2);
+				HIP_TRY(R2.take((void **)&R2.d_mini, (size_t)std::max<int64_t>(n2[1], 1) * 16));
+				if ((rc = rechain_gather(R.d_mini, R.d_mini_off, (const int64_t *)(d + o_sel), R2.d_mini_off, n2[0], n2[1], R2.d_mini, st))) return rc;
+				if ((rc = R2.ev.make())) return rc;
+				if ((rc = R2.lookup(idx, device, max_occ))) return rc;       // (waits for the stream: flags and sel are down)
+				std::vector<int32_t> qlen2(sel.size()), lo2, eq2;
+				for (size_t j = 0; j < sel.size(); ++j) qlen2[j] = qlen[(size_t)sel[j]];
+				mm2c_seed_skip_host_t sk2{};
+				if (skip) {
+					sk2 = sk1;
+					if (sk1.q_lo) { lo2.resize(sel.size()); for (size_t j = 0; j < sel.size(); ++j) lo2[j] = sk1.q_lo[sel[j]]; sk2.q_lo = lo2.data(); }
+					if (sk1.q_eq) { eq2.resize(sel.size()); for (size_t j = 0; j < sel.size(); ++j) eq2[j] = sk1.q_eq[sel[j]]; sk2.q_eq = eq2.data(); }
+				}
+				if ((rc = C2.run(R2, par, min_cnt, min_sc, d_pool, n_hits, qlen2.data(), skip ? &sk2 : nullptr, d_ref, n_ref, ev.e[1], true))) return rc;
+			} else HIP_TRY(hipEventRecord(ev.e[1], st));
+			HIP_TRY(hipEventSynchronize(ev.e[1]));
+			FR.rechain_ns += (uint64_t)(ev.ms(0, 1) * 1e6f);
+		}
+
+		// down, in fragment order: a re-chained fragment's second-pass results in the place of its first-pass ones
+		PassHost H1, H2;
+		if ((rc = H1.fetch(R, C1)) || (n2[0] > 0 && (rc = H2.fetch(R2, C2)))) return rc;
+		size_t j = 0;
+		for (size_t g = 0; g < nf; ++g) {
+			const bool second = n2[0] > 0 && flags[g];
+			const ChainPass &C = second ? C2 : C1;
+			const PassHost &H = second ? H2 : H1;
+			const size_t q = second ? j++ : g;
+			const int64_t nu = C.uo[q + 1] - C.uo[q], nb = C.bo[q + 1] - C.bo[q], nm = C.mo[q + 1] - C.mo[q], na = C.ao[q + 1] - C.ao[q];
+			P.u.resize((size_t)(U + nu)); P.b.resize((size_t)(B + nb)); P.mini_pos.resize((size_t)(M + nm));
+			if (nu) memcpy(P.u.data() + U, H.u.data() + C.uo[q], (size_t)nu * 8);
+			if (nb) memcpy(P.b.data() + B, H.b.data() + C.bo[q], (size_t)nb * 16);
+			if (nm) memcpy(P.mini_pos.data() + M, H.mini_pos.data() + C.mo[q], (size_t)nm * 8);
+			U += nu; B += nb; M += nm; A += na;
+			const size_t at = (size_t)g0 + g;
+			P.rep_len[at] = H.rep_len[q];
+			P.u_off[at + 1] = U; P.b_off[at + 1] = B; P.mini_off[at + 1] = M; P.anchor_off[at + 1] = A;
+		}
+		n_rechained += n2[0];
+		++SK.chunks; ++SS.chunks;
+		g0 = g1;
+	}
+	++SK.calls;
+	FR.fragments += (uint64_t)n_frags; FR.rechained += (uint64_t)n_rechained;
+	G.tasks += (uint64_t)n_frags; G.anchors += (uint64_t)A;
+	publish(res, n_frags);
+	res->n_rechained = n_rechained; res->rechained = P.rechained.data();
+	return 0;
+}
+
+void mm2c_get_frag_stats(mm2c_frag_stats_t *out)
+{
+	if (!out) return;
+	*out = mm2c_frag_stats_t{ FR.calls, FR.fragments, FR.rechained, FR.rechain_ns };
+}
+
+void mm2c_reset_frag_stats(void)
+{
+	for (auto *a : { &FR.calls, &FR.fragments, &FR.rechained, &FR.rechain_ns }) *a = 0;
 }
 
 void mm2c_get_sketch_stats(mm2c_sketch_stats_t *out)

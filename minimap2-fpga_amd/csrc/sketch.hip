@@ -15,6 +15,9 @@
 //      place them.
 //   4. lookups.  A minimizer index is a sorted key array with the (pool offset, n) of every key (mm_idx_get, index.c:81-98: n = 0 when absent); matches,
 //      is_tandem against the unfiltered neighbours, rep_len (map.c:104-110,120, one wave per read folding the repetitive minimizers in order) and mini_pos.
+//   5. fragments.  Reads of several segments (collect_minimizers with n_segs > 1, map.c:64-77) are the segments' sketches tagged with seg << 32 | sum << 1 and
+//      joined; the lookups then run per fragment.  The max_occ re-chain (map.c:318-340) is decided per fragment from the chains on the device, and the flagged
+//      fragments' minimizers are compacted for a second pass.  DESIGN.md section 3.11.
 #include "api_internal.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -25,6 +28,7 @@ constexpr int CH = 64;        // positions per lane in the push / slot passes
 constexpr int SC = 256;       // slots per lane in the selection passes
 constexpr int TPB = 256;
 constexpr uint64_t ALL1 = ~(uint64_t)0;
+constexpr uint64_t SEG_MASK = 0xffULL << 48;   // MM_SEED_SEG_MASK (mmpriv.h:22-23)
 
 __device__ __forceinline__ int nt4(uint8_t b)                  // seq_nt4_table (sketch.c:9-26): bytes 0-3 and A C G T U in either case
 {
@@ -300,6 +304,89 @@ __global__ void __launch_bounds__(TPB) lk_reads(LkArgs A)
 	if (lane == 0) A.rep_len[r] = acc + (rep_en - rep_st);
 }
 
+// ---- fragments of several segments (collect_minimizers with n_segs > 1, map.c:64-77) and the max_occ re-chain (map.c:318-340); DESIGN.md section 3.11
+
+// y += seg << 32 | sum << 1 for every minimizer of a segment (seg_tag[s], made by the host from the segment lengths)
+__global__ void __launch_bounds__(TPB) fr_tag(mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_segs, int64_t n_mini, const uint64_t *seg_tag)
+{
+	const int64_t m = (int64_t)blockIdx.x * TPB + threadIdx.x;
+	if (m >= n_mini) return;
+	mini[m].y += seg_tag[owner(mini_off, n_segs, m)];
+}
+
+// a fragment's list is its segments' lists one after another: its offset is that of its first segment
+__global__ void fr_mini_off(const int64_t *mini_off, const int64_t *frag_off, int64_t n_frags, int64_t *frag_mini_off)
+{
+	const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g <= n_frags) frag_mini_off[g] = mini_off[frag_off[g]];
+}
+
+struct RcArgs {
+	const int64_t *u_off, *b_off; const uint64_t *u; const mm2c_anchor_t *b;   // what the epilogue left: chains per fragment, anchors in chain order
+	const int32_t *rep_len; const int64_t *mini_off;
+	int64_t n_frags; int n_segs;
+	uint8_t *flag; int64_t *sel_cnt, *mini_cnt;                // per fragment (n_frags + 1, the last 0): 1 / its minimizers when flagged, then their exclusive scans
+};
+
+template <class T> __device__ __forceinline__ T wave_sum(T v)
+{
+	for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+	return v;
+}
+
+// one wave per fragment: rechain = rep_len > 0 && (no chain || the best chain misses a segment), map.c:318-331 (the caller has tested max_occ > mid_occ)
+__global__ void __launch_bounds__(TPB) rc_decide(RcArgs A)
+{
+	const int64_t g = ((int64_t)blockIdx.x * TPB + threadIdx.x) / 64;
+	const int lane = threadIdx.x & 63;
+	if (g > A.n_frags) return;
+	if (g == A.n_frags) { if (lane == 0) { A.sel_cnt[g] = 0; A.mini_cnt[g] = 0; } return; }
+	bool rechain = false;
+	if (A.rep_len[g] > 0) {
+		const int64_t u0 = A.u_off[g], n_u = A.u_off[g + 1] - u0;
+		if (n_u == 0) rechain = true;
+		else {
+			// the FIRST chain with the strictly largest score above 0 (`max < (int)(u[i] >> 32)` from max = 0)
+			int best = 0; int64_t best_i = -1;
+			for (int64_t i = lane; i < n_u; i += 64) { const int sc = (int)(A.u[u0 + i] >> 32); if (sc > best) { best = sc; best_i = i; } }
+			for (int d = 32; d > 0; d >>= 1) {
+				const int sc = __shfl_xor(best, d); const int64_t oi = __shfl_xor(best_i, d);
+				if (sc > best || (sc == best && oi >= 0 && (best_i < 0 || oi < best_i))) { best = sc; best_i = oi; }
+			}
+			int n_chained_segs = 1;                              // no chain scores above 0: the reference reads u[-1] there; here the chain counts as one segment
+			if (best_i >= 0) {
+				int64_t off = 0;
+				for (int64_t i = lane; i < best_i; i += 64) off += (int64_t)(uint32_t)A.u[u0 + i];
+				off = A.b_off[g] + wave_sum(off);
+				const int64_t cnt = (int64_t)(int32_t)A.u[u0 + best_i];
+				int diff = 0;
+				for (int64_t i = 1 + lane; i < cnt; i += 64) diff += (A.b[off + i].y & SEG_MASK) != (A.b[off + i - 1].y & SEG_MASK);
+				n_chained_segs += wave_sum(diff);
+			}
+			rechain = n_chained_segs < A.n_segs;
+		}
+	}
+	if (lane == 0) { A.flag[g] = rechain; A.sel_cnt[g] = rechain; A.mini_cnt[g] = rechain ? A.mini_off[g + 1] - A.mini_off[g] : 0; }
+}
+
+// the flagged fragments, in order: which they are and where their minimizers go
+__global__ void rc_select(const uint8_t *flag, const int64_t *sel_scan, const int64_t *mini_scan, int64_t n_frags, int64_t *sel, int64_t *mini_off2)
+{
+	const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g > n_frags) return;
+	if (g == n_frags) mini_off2[sel_scan[g]] = mini_scan[g];
+	else if (flag[g]) { sel[sel_scan[g]] = g; mini_off2[sel_scan[g]] = mini_scan[g]; }
+}
+
+__global__ void __launch_bounds__(TPB) rc_gather(const mm2c_anchor_t *mini, const int64_t *mini_off, const int64_t *sel, const int64_t *mini_off2, int64_t n_sel, int64_t n_mini2,
+                                                 mm2c_anchor_t *mini2)
+{
+	const int64_t m = (int64_t)blockIdx.x * TPB + threadIdx.x;
+	if (m >= n_mini2) return;
+	const int64_t j = owner(mini_off2, n_sel, m);
+	mini2[m] = mini[mini_off[sel[j]] + (m - mini_off2[j])];
+}
+
 inline unsigned blocks(int64_t n, int per = TPB) { return (unsigned)((n + per - 1) / per); }
 
 } // namespace
@@ -402,6 +489,58 @@ int lookup_run(const mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_rea
 		HIP_TRY(hipGetLastError());
 	}
 	lk_reads<<<blocks((n_reads + 1) * 64), TPB, 0, st>>>(A);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// Fragments: tags the minimizers of every segment with seg_tag (n_segs entries, device) and writes the fragments' offsets into the joined list
+// (frag_mini_off, n_frags + 1).  mini_off: the segments' offsets as sketch_count left them; frag_off: n_frags + 1 segment numbers (device).
+int frag_tag(mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_segs, int64_t n_mini, const uint64_t *seg_tag, const int64_t *frag_off, int64_t n_frags,
+             int64_t *frag_mini_off, hipStream_t st)
+{
+	if (n_mini > 0) {
+		fr_tag<<<blocks(n_mini), TPB, 0, st>>>(mini, mini_off, n_segs, n_mini, seg_tag);
+		HIP_TRY(hipGetLastError());
+	}
+	fr_mini_off<<<blocks(n_frags + 1), TPB, 0, st>>>(mini_off, frag_off, n_frags, frag_mini_off);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+size_t rechain_scan_bytes(int64_t n_frags) { return lookup_scan_bytes(n_frags); }
+
+// The re-chain decision of map.c:318-331 for every fragment of a chunk and the compaction of the flagged ones.  u_off / u / b_off / b: the epilogue's output on the
+// device; mini_off: the fragments' offsets into the minimizers.  flag: n_frags bytes; cnt: 4 (n_frags + 1) (flags and minimizer counts, then their scans);
+// sel: n_frags; mini_off2: n_frags + 1.  h_n: the number of flagged fragments and of their minimizers, downloaded (the call waits for the stream).
+int rechain_decide(const int64_t *u_off, const uint64_t *u, const int64_t *b_off, const mm2c_anchor_t *b, const int32_t *rep_len, const int64_t *mini_off,
+                   int64_t n_frags, int n_segs, uint8_t *flag, int64_t *cnt, int64_t *sel, int64_t *mini_off2, void *scan_tmp, size_t scan_bytes, int64_t h_n[2],
+                   hipStream_t st)
+{
+	RcArgs A{};
+	const size_t n1 = (size_t)n_frags + 1;
+	A.u_off = u_off; A.u = u; A.b_off = b_off; A.b = b; A.rep_len = rep_len; A.mini_off = mini_off; A.n_frags = n_frags; A.n_segs = n_segs;
+	A.flag = flag; A.sel_cnt = cnt; A.mini_cnt = cnt + n1;
+	int64_t *sel_scan = cnt + 2 * n1, *mini_scan = cnt + 3 * n1;
+	rc_decide<<<blocks((n_frags + 1) * 64), TPB, 0, st>>>(A);
+	HIP_TRY(hipGetLastError());
+	size_t bytes = scan_bytes;
+	HIP_TRY(rocprim::exclusive_scan(scan_tmp, bytes, A.sel_cnt, sel_scan, (int64_t)0, n1, rocprim::plus<int64_t>(), st));
+	bytes = scan_bytes;
+	HIP_TRY(rocprim::exclusive_scan(scan_tmp, bytes, A.mini_cnt, mini_scan, (int64_t)0, n1, rocprim::plus<int64_t>(), st));
+	rc_select<<<blocks(n_frags + 1), TPB, 0, st>>>(flag, sel_scan, mini_scan, n_frags, sel, mini_off2);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(&h_n[0], sel_scan + n_frags, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&h_n[1], mini_scan + n_frags, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
+// the minimizers of the flagged fragments, one after another (the sketch is not redone: the reference keeps mv)
+int rechain_gather(const mm2c_anchor_t *mini, const int64_t *mini_off, const int64_t *sel, const int64_t *mini_off2, int64_t n_sel, int64_t n_mini2, mm2c_anchor_t *mini2,
+                   hipStream_t st)
+{
+	if (n_mini2 == 0) return 0;
+	rc_gather<<<blocks(n_mini2), TPB, 0, st>>>(mini, mini_off, sel, mini_off2, n_sel, n_mini2, mini2);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

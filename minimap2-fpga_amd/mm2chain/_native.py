@@ -47,12 +47,17 @@ class ReadResult(C.Structure):
                 ("n_anchors", C.c_int64), ("anchor_off", C.c_void_p), ("rep_len", C.c_void_p),
                 ("n_mini_pos", C.c_int64), ("mini_off", C.c_void_p), ("mini_pos", C.c_void_p),
                 ("n_u", C.c_int64), ("n_b", C.c_int64), ("u_off", C.c_void_p), ("u", C.c_void_p), ("b_off", C.c_void_p), ("b", C.c_void_p),
-                ("priv", C.c_void_p)]
+                ("priv", C.c_void_p), ("n_rechained", C.c_int64), ("rechained", C.c_void_p)]
 
 
 class SketchStats(C.Structure):
     """mm2c_sketch_stats_t"""
     _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "matches", "h2d_ns", "sketch_ns", "lookup_ns")]
+
+
+class FragStats(C.Structure):
+    """mm2c_frag_stats_t"""
+    _fields_ = [(k, C.c_uint64) for k in ("calls", "fragments", "rechained", "rechain_ns")]
 
 
 class IndexStats(C.Structure):
@@ -151,6 +156,12 @@ C_SYMBOLS = {
     "mm2c_sketch_match_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
     "mm2c_read_chain_batch": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.POINTER(ReadResult)]),
+    "mm2c_sketch_frag_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_sketch_match_frag_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_frag_chain_batch": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_get_frag_stats": (None, [C.POINTER(FragStats)]),
+    "mm2c_reset_frag_stats": (None, []),
     "mm2c_get_sketch_stats": (None, [C.POINTER(SketchStats)]),
     "mm2c_reset_sketch_stats": (None, []),
     "mm2c_get_stats": (None, [C.POINTER(Stats)]),

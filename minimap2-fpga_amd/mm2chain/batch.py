@@ -720,6 +720,77 @@ def read_chain_batch(params: Params, min_cnt, min_sc, seqs, idx: MinimizerIndex,
     return out
 
 
+def _frags_args(frags):
+    """fragments as (frag_off int64 [n_frags+1], seq_off, seq): a list of fragments, each a list of segments (bytes / str / uint8 arrays), or (frag_off, seq_off, seq)"""
+    def offsets(x):
+        """a 1-D array of integers, which no fragment (a list of segments) is"""
+        if isinstance(x, (bytes, str)):
+            return False
+        try:
+            a = np.asarray(x)
+        except ValueError:                                     # segments of different lengths
+            return False
+        return a.ndim == 1 and a.dtype.kind in "iu" and a.dtype != np.uint8
+    if isinstance(frags, tuple) and len(frags) == 3 and offsets(frags[0]) and offsets(frags[1]):
+        off, seq = _reads_args((frags[1], frags[2]))
+        return np.ascontiguousarray(np.asarray(frags[0], dtype=np.int64)), off, seq
+    fo = np.zeros(len(frags) + 1, np.int64)
+    fo[1:] = np.cumsum([len(f) for f in frags]) if len(frags) else []
+    off, seq = _reads_args([s for f in frags for s in f])
+    return fo, off, seq
+
+
+def sketch_frag_batch(frags, k, w, is_hpc=False):
+    """mm2c_sketch_frag_batch: collect_minimizers per fragment (segment ids in y's high word, positions shifted by the earlier segments' lengths).
+    Returns (off int64 [n_frags+1], minimizers uint64 [m, 2])"""
+    fo, off, seq = _frags_args(frags)
+    R = _Result()
+    N.check(R.lib.mm2c_sketch_frag_batch(int(k), int(w), int(bool(is_hpc)), fo.size - 1, _np_ptr(fo), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p),
+            "mm2c_sketch_frag_batch")
+    r = R.p.contents
+    return _arr(r.sketch_off, fo.size, np.int64), _arr(r.sketch, 2 * r.n_sketch, np.uint64).reshape(-1, 2)
+
+
+def sketch_match_frag_batch(frags, idx: MinimizerIndex, occ):
+    """mm2c_sketch_match_frag_batch: fragments in, matches out; the dict of sketch_match_batch, per fragment"""
+    fo, off, seq = _frags_args(frags)
+    R = _Result()
+    N.check(R.lib.mm2c_sketch_match_frag_batch(idx.handle, int(occ), fo.size - 1, _np_ptr(fo), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p),
+            "mm2c_sketch_match_frag_batch")
+    r, nf = R.p.contents, fo.size - 1
+    return {"match_off": _arr(r.match_off, nf + 1, np.int64), "matches": _arr(r.matches, r.n_matches, MATCH_DTYPE),
+            "anchor_off": _arr(r.anchor_off, nf + 1, np.int64), "rep_len": _arr(r.rep_len, nf, np.int32),
+            "mini_off": _arr(r.mini_off, nf + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+
+
+def frag_chain_batch(params: Params, min_cnt, min_sc, frags, idx: MinimizerIndex, mid_occ, max_occ, skip: SeedSkip = None):
+    """mm2c_frag_chain_batch: fragments of params.n_segs segments in, chains out, with the max_occ re-chain of map.c:318-340.  Returns the dict of
+    read_chain_batch per fragment, plus rechained (uint8 per fragment) and n_rechained"""
+    fo, off, seq = _frags_args(frags)
+    nf = fo.size - 1
+    sk = skip._native(nf) if skip is not None else None
+    R = _Result()
+    N.check(R.lib.mm2c_frag_chain_batch(C.byref(params), int(min_cnt), int(min_sc), idx.handle, int(mid_occ), int(max_occ), nf, _np_ptr(fo), off.size - 1,
+                                        _np_ptr(off), _np_ptr(seq), C.byref(sk) if sk is not None else None, R.p), "mm2c_frag_chain_batch")
+    r = R.p.contents
+    out = {"anchor_off": _arr(r.anchor_off, nf + 1, np.int64), "u_off": _arr(r.u_off, nf + 1, np.int64), "u": _arr(r.u, r.n_u, np.uint64),
+           "b_off": _arr(r.b_off, nf + 1, np.int64), "b": _arr(r.b, 2 * r.n_b, np.uint64).reshape(-1, 2), "rep_len": _arr(r.rep_len, nf, np.int32),
+           "mini_off": _arr(r.mini_off, nf + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64),
+           "rechained": _arr(r.rechained, nf, np.uint8), "n_rechained": int(r.n_rechained)}
+    out["chains"] = _split_chains(nf, out["u_off"], out["u"], out["b_off"], out["b"])
+    return out
+
+
+def frag_stats(reset=False):
+    """mm2c_get_frag_stats as a dict (ns and counts); reset=True clears the counters afterwards"""
+    lib = N.load()
+    st = N.FragStats()
+    lib.mm2c_get_frag_stats(C.byref(st))
+    if reset:
+        lib.mm2c_reset_frag_stats()
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
 def sketch_stats(reset=False):
     """mm2c_get_sketch_stats as a dict (ns and counts); reset=True clears the counters afterwards"""
     lib = N.load()
