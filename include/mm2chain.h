@@ -107,7 +107,9 @@ int  mm2c_device_identity(int *ordinal, char *pci_bus_id, size_t bus_len, char *
  * devices of mm2c_init_devices (default 2^20); "trim" = give the cached device memory back to the runtime.  Results never depend on a knob.  "coop_waves" > 1 (default 16, the only width built: any value above 1 means 16) = a host-buffer pass of at most "coop_max_tasks" (1024) pieces gives every piece a workgroup of
  * 16 waves that share its LDS rings (csrc/chain_dp_coop.h: candidates counted and the older tiles reduced in parallel, the exact scan only where the early exit of chain.c:231 can fire;
  * env MM2C_COOP_WAVES), 0 = one wave per piece always; "coop_plans" 1 = plans of few tasks take that kernel too (tests); "combiner_lanes" 1..16 = passes the call combiner of the per-read
- * entries may have in flight at once on each device (default 4; env MM2C_COMBINER_LANES), "combine_max_anchors" = a call of more anchors than this runs alone (env MM2C_COMBINE_MAX). */
+ * entries may have in flight at once on each device (default 4; env MM2C_COMBINER_LANES), "combine_max_anchors" = a call of more anchors than this runs alone (env MM2C_COMBINE_MAX);
+ * "packed_fp" 1 = plan tasks of the compact ring with at most 8192 anchors and a span sum of at most 131071 run an instantiation that keeps f and p of a ring anchor in one word
+ * (four tiles of f / p in the LDS of two, deeper ones from a side array with one load; default; a plan that holds a task of more than 8192 anchors runs without it, and mm2c_plan_last_variant says so), 0 = never. */
 int  mm2c_tune(const char *key, int value);
 
 /* HW/SW split model of the reference for this hardware (chain.c:80-81,101; constants in the form of chain_hardware.h:19-30 live in
@@ -174,6 +176,9 @@ int mm2c_route_pieces(int64_t pieces, int64_t longest, int64_t total);
  * "chain_dp_tile<NX=8,NF=2,SKIP=1,GEN=0,GS1=1,FAR=1,TAB=0> loop=asm classes=1 cut=0" (loop=asm: the hand-written per-tile loop, loop=c++: its
  * C++ restatement; chain_dp_wave<...>: the first-generation kernel).  For tests and logs: results never depend on the instantiation. */
 int mm2c_plan_last_variant(mm2c_plan_t *plan, char *buf, size_t len);
+/* the class byte the prepass of the last run gave each task of the plan (n = its number of tasks): bit 0 the long LDS ring, bit 1 the 32-bit x / q ring,
+ * bit 2 a query position beyond the q24 ring, bit 3 the task fits the packed f / p ring ("packed_fp") -- which instantiation took which task (tests) */
+int mm2c_plan_last_classes(mm2c_plan_t *plan, unsigned char *cls, int64_t n);
 /* the same text for the last DP launch of a host-buffer entry (mm2c_chain_task_host, mm2c_chain_batch_host, mm2c_mm_chain_dp_batch_host), process-wide:
  * those entries give their passes the prepass classes too, so tasks whose q values allow it take the compact ring there as in plans */
 int  mm2c_last_host_variant(char *buf, size_t len);

@@ -89,21 +89,37 @@ __device__ __forceinline__ void write_lane2(int &v0, int &v1, int a0, int a1, in
 // in 32 bits: exact for every task whose q values are below 2^24 (reads of up to 16.7 Mb: the prepass clears the long-ring class of any other task).  It is the form of
 // the LONG ring (ring-size class 1: tasks whose scans leave the short ring -- long noisy reads, all-vs-all overlaps): 16 tiles in 7 KB instead of 10 KB, 22 waves per CU
 // instead of 16, which is what bounded those streams (16 384 reads of 20 000 anchors were exactly four rounds of 16 x 256 wave slots).
+// RING 3 (packed f / p ring): the compact x / q ring with 4-BYTE f / p slots -- one word per ring anchor holds f - FBIAS in its low PK_FBITS bits and the
+// piece-relative p (-1: none) in the 14 bits above, both signed (pack_fp below), so the 1 KB that held two tiles of pairs holds four tiles of words and a scored tile
+// is one ds_read_b32 + two unpack instructions.  The same word goes to a side array in memory (4 B per anchor, beside st[] and t[]) when the tile is finished: a
+// scored tile deeper than the f / p ring loads that one word instead of f[] and p[] and needs none of their fix-ups.  Limits, checked per task by the prepass
+// (chain_window_start_t: bit 3 of the class byte marks the tasks that fit; every other task runs the RING 1 instantiation): p <= 8191, so a piece of at most
+// PK_MAX_N = 8192 anchors (a device-cut piece is never longer than its task, whose length is what is tested); f - FBIAS < 2^17, and f[i] is at most the sum of
+// the spans of the task (a score adds at most the anchor's span to f[j], chain.c:207-220), so tasks whose span sum is at most PK_MAX_F = 2^17 - 1.  f >= 0 always
+// (it starts at the anchor's span), so f - FBIAS >= -14 fits the signed field.
 template <int NX, int NF, bool GEN, bool TAB, int RING = 0>
 struct Lds {
 	static constexpr int SN = 64 * NX;           // anchors with a stamp slot = anchors in the x / q ring
 	static constexpr int XS = RING ? 4 : 8;      // bytes of an x / q slot
+	static constexpr int FS = RING == 3 ? 4 : 8; // bytes of an f / p slot
 	static constexpr int TILE = 64 * XS;         // ... of a tile in the x / q ring
 	static constexpr int RB = SN * XS;           // ... of the x / q ring
-	static constexpr int XQ = 0, FP = RB, ST = FP + NF * 512, QH = ST + SN, GAP = QH + (RING == 2 ? SN : 0),
+	static constexpr int XQ = 0, FP = RB, ST = FP + NF * 64 * FS, QH = ST + SN, GAP = QH + (RING == 2 ? SN : 0),
 	                     G = GAP + (TAB ? 1024 : 0), BYTES = G + (GEN ? NX * 64 : 0);
-	static constexpr int FMASK = NF * 512 - 1;   // slot of a tile in the f / p ring = its x / q slot mod NF (NF a power of two dividing NX)
+	static constexpr int FMASK = NF * 64 * FS - 1;   // slot of a tile in the f / p ring = its x / q slot mod NF (NF a power of two dividing NX)
 	static constexpr int SBITS = __builtin_ctz(SN);
 };
 
+constexpr int PK_FBITS = 18;                         // packed f / p word: bits 0-17 f - FBIAS (signed), bits 18-31 p (signed, piece-relative)
+// (PK_MAX_N = 8192, the longest task whose p values fit, is in chain_kernel.h: the host looks at it too)
+constexpr int PK_MAX_F = (1 << (PK_FBITS - 1)) - 1;  // largest span sum of a task whose f values fit
 constexpr int FBIAS = 14;   // min(dq, dr, span) - gap cost = min3(dq - 1, dr - 1, span - 1) - linear part + (clz(dd | 1) >> 1) - 14 (chain.c:207-209,218)
 
 // what the chunks of one anchor share (wave-uniform unless noted)
+__device__ __forceinline__ int pack_fp(int f_biased, int p) { return (int)(((unsigned)p << PK_FBITS) | ((unsigned)f_biased & ((1u << PK_FBITS) - 1))); }
+__device__ __forceinline__ int packed_f(int w) { return (int)((unsigned)w << (32 - PK_FBITS)) >> (32 - PK_FBITS); }   // f - FBIAS
+__device__ __forceinline__ int packed_p(int w) { return w >> PK_FBITS; }
+
 struct AnchorCtx {
 	int xi1, qi1;            // x_i - 1, q_i - 1 (so that dr - 1 and dq - 1 come out of one subtraction each)
 	int span_i, seg_i;
@@ -119,6 +135,7 @@ struct AnchorCtx {
 struct TileMem {
 	char *lds;               // the wave's LDS (layout: Lds<>)
 	const uint4 *a; const int32_t *f, *p; int32_t *t;   // global arrays of the task
+	const int32_t *w;        // packed f / p words of the task's finished tiles (RING 3 only)
 	int pbase;
 };
 
@@ -180,7 +197,12 @@ __device__ __forceinline__ bool chunk_finish(const KParams &P, const AnchorCtx &
 template <class LY, int NF>
 __device__ __forceinline__ void ring_fp(const TileMem &M, int addr, int depth, int base, int rl, int &fj, int &pj)
 {
-	if (depth <= NF) {
+	if (LY::FS == 4) {
+		int v;
+		if (depth <= NF) v = *(const int *)(M.lds + LY::FP + (addr & LY::FMASK));   // (j mod 64 NF) * 4: the x / q slots are 4 bytes too
+		else v = __hip_atomic_load(&M.w[max(base + rl, 0)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		fj = packed_f(v) + FBIAS; pj = packed_p(v);
+	} else if (depth <= NF) {
 		const int o = (LY::XS == 4 ? addr << 1 : addr) & LY::FMASK;   // (j mod 64 NF) * 8
 		const int2 fp = *(const int2 *)(M.lds + LY::FP + o);      // the ring holds f - FBIAS and p (piece-relative), see the end of the tile loop
 		fj = fp.x + FBIAS; pj = fp.y;
@@ -403,6 +425,15 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"v_perm_b32 %[u1], " MM2C_R_Q ", " MM2C_R_X ", %[selq]\n\t" "v_sub_u32 %[dq], %[qi1], %[u1]\n\t"
 #define MM2C_OLDADDR_W "v_add_u32 %[vb], 0x400, %[addr]\n\t"
 #define MM2C_OLDADDR_C "v_add_lshl_u32 %[vb], %[addr], %[c200], 1\n\t"
+#define MM2C_OLDADDR_P "v_add_u32 %[vb], 0x200, %[addr]\n\t"          /* packed f / p ring: x / q, f / p and (times 4) stamp slots share one address */
+// ---- what depends on the slot size of the f / p ring (Lds<>::FS): the request of a scored ring tile's f / p, what follows its arrival, the bit at which the
+// stamp slot starts in the address OLDADDR made, and what a deep tile's values from memory need before they join the ring path
+#define MM2C_RDFP_8 "ds_read_b64 " MM2C_R_FP ", %[u2] offset:%[FPOFF]\n\t"
+#define MM2C_RDFP_4 "ds_read_b32 " MM2C_R_F ", %[u2] offset:%[FPOFF]\n\t"
+#define MM2C_UNPACK_8 ""
+#define MM2C_UNPACK_4 "v_ashrrev_i32 " MM2C_R_P ", %[FBITS], " MM2C_R_F "\n\t" "v_bfe_i32 " MM2C_R_F ", " MM2C_R_F ", 0, %[FBITS]\n\t"
+#define MM2C_FGFIX_8 "v_subrev_u32 " MM2C_R_P ", %[pbase], " MM2C_R_P "\n\t" "v_max_i32 " MM2C_R_P ", -1, " MM2C_R_P "\n\t" "v_add_u32 " MM2C_R_F ", -14, " MM2C_R_F "\n\t"
+#define MM2C_FGFIX_4 MM2C_UNPACK_4
 // x / q of the tile with first anchor fb from memory (anchors are 16 bytes: x low word at 0, q at 8), fb one tile back afterwards
 #define MM2C_FAR_REQ "v_add_u32 %[u2], %[fb], %[rl]\n\t" "v_max_i32 %[u2], 0, %[u2]\n\t" "v_lshlrev_b32 %[u2], 4, %[u2]\n\t" \
 	"global_load_dword %[fx], %[u2], %[aptr]\n\t" "global_load_dword %[fq], %[u2], %[aptr] offset:8\n\t" "s_sub_i32 %[fb], %[fb], 64\n\t"
@@ -621,6 +652,17 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"global_load_dword " MM2C_R_F ", %[u2], %[fptr] sc0\n\t" \
 	SCORE \
 	"s_waitcnt vmcnt(0)\n\t"
+// packed f / p: the tile's words from the side array -- one load, and the values are the ring's own (piece-relative p, biased f).  (wptr is an input operand of
+// every instantiation of the block -- the others are handed f -- which costs those two SGPRs and nothing else: VGPRs, LDS and waves per SIMD are what they were.)
+#define MM2C_FG_PACKED(SCORE) \
+	"s_lshl_b32 %[t0], %[d], 6\n\t" \
+	"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+	"v_add_u32 %[u2], %[base], %[rl]\n\t" \
+	"v_max_i32 %[u2], 0, %[u2]\n\t" \
+	"v_lshlrev_b32 %[u2], 2, %[u2]\n\t" \
+	"global_load_dword " MM2C_R_F ", %[u2], %[wptr] sc0\n\t" \
+	SCORE \
+	"s_waitcnt vmcnt(0)\n\t"
 #if MM2C_DEEP_PREFETCH
 #define MM2C_FG_W(SCORE) \
 	"s_lshl_b32 %[t0], %[d], 6\n\t" \
@@ -704,9 +746,9 @@ __device__ unsigned long long g_label_hits[8 * 32];   // row = compact << 2 | ta
 #define MM2C_LB_FOLD "0x10000000"
 #define MM2C_LB_DONE "0x20000000"
 #define MM2C_LB_SPEC "0x40000000"
-#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, SCORE, ADDF, SEG_RD, SEG_LK, SEG_HF, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
+#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, UNPACK, FGFIX, STSH, SCORE, ADDF, SEG_RD, SEG_LK, SEG_HF, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
 template <int NX, int NF> \
-__device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, float avg, const int32_t *f, const int32_t *p, int pbase, const uint4 *a, \
+__device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, float avg, const int32_t *f, const int32_t *p, const int32_t *wq, int pbase, const uint4 *a, \
                                     int32_t *tg, int tx, int tx1, int tq, int tq1, int tspan, int tlo, int tlo0, int tw, int &own_f, int &own_p, \
                                     int addr1, int addr2, int lomc, int ownst, int rl, int mdqbw_v, int bw_v, int sent_v, int addr1q, int selq_v MM2C_LC_PARAM) \
 { \
@@ -767,14 +809,16 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_sub_i32 %[d], %[nfull], %[n]\n" \
 		"Lold_%=:\n\t" \
 		MM2C_LC(MM2C_LB_OLD) \
-		OLDADDR                                        /* the running address is two tiles further on: back to this tile's (in units of 8-byte slots) */ \
+		OLDADDR                                        /* the running address is two tiles further on: back to this tile's (in units of 8-byte slots; of 4-byte slots in the packed form, whose STSH is 2) */ \
 		"v_and_b32 %[u2], %[FMASK], %[vb]\n\t"          /* its slot in the f / p ring */ \
-		"v_bfe_u32 %[vb], %[vb], 3, %[SBITS]\n\t"       /* its slot in the stamp ring */ \
+		"v_bfe_u32 %[vb], %[vb], " STSH ", %[SBITS]\n\t"   /* its slot in the stamp ring */ \
 		"s_cmp_gt_u32 %[d], %[NFI]\n\t" \
 		"s_cbranch_scc1 Lfg_%=\n\t" \
-		"ds_read_b64 " MM2C_R_FP ", %[u2] offset:%[FPOFF]\n\t" \
+		RDFP \
 		SCORE \
-		"s_waitcnt lgkmcnt(0)\n" \
+		"s_waitcnt lgkmcnt(0)\n\t" \
+		UNPACK \
+		"\n" \
 		"Lhf_%=:\n\t" \
 		MM2C_LC(MM2C_LB_HF) \
 		SEG_HF \
@@ -791,9 +835,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"Lfg_%=:\n\t" \
 		MM2C_LC(MM2C_LB_FG) \
 		SEG_FG(SCORE) \
-		"v_subrev_u32 " MM2C_R_P ", %[pbase], " MM2C_R_P "\n\t" \
-		"v_max_i32 " MM2C_R_P ", -1, " MM2C_R_P "\n\t" \
-		"v_add_u32 " MM2C_R_F ", -14, " MM2C_R_F "\n\t" \
+		FGFIX \
 		"s_branch Lhf_%=\n" \
 		"Lpart_%=:\n\t" \
 		MM2C_LC(MM2C_LB_PART) \
@@ -986,20 +1028,21 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		  [dr] "=&v"(dr), [dq] "=&v"(dq), [dd] "=&v"(dd), [u1] "=&v"(u1), [u2] "=&v"(u2), \
 		  [sc] "=&v"(sc), [va] "=&v"(va), [vb] "=&v"(vb), [vc] "=&v"(vc), [addr] "=&v"(addr), [s16v] "=&v"(s16v), [lom1v] "=&v"(lom1v), [fx] "=&v"(fx), [fq] "=&v"(fq), \
 		  [own_f] "+v"(own_f), [own_p] "+v"(own_p) MM2C_PROBE_OPERAND MM2C_LC_OPERAND \
-		: [i0] "s"(i0), [kstart] "s"(k_start), [cnt] "s"(cnt), [icnt1] "s"(i0 + cnt + 1), [i063] "s"(i0 + 63), [c200] "s"(0x200), [maxskip] "s"(max_skip), [avg] "s"(avg), [fptr] "s"(f), [pptr] "s"(p), [pbase] "s"(pbase), [aptr] "s"(a), [tptr] "s"(tg), \
+		: [i0] "s"(i0), [kstart] "s"(k_start), [cnt] "s"(cnt), [icnt1] "s"(i0 + cnt + 1), [i063] "s"(i0 + 63), [c200] "s"(0x200), [maxskip] "s"(max_skip), [avg] "s"(avg), [fptr] "s"(f), [pptr] "s"(p), [wptr] "s"(wq), [pbase] "s"(pbase), [aptr] "s"(a), [tptr] "s"(tg), \
 		  [tx] "v"(tx), [tx1] "v"(tx1), [tq] "v"(tq), [tq1] "v"(tq1), [tspan] "v"(tspan), [tlo] "v"(tlo), [tlo0] "v"(tlo0), [tw] "v"(tw), \
 		  [addr1] "v"(addr1), [addr2] "v"(addr2), [lomc] "v"(lomc), [ownst] "v"(ownst), [rl] "v"(rl), [mdqbw] "v"(mdqbw_v), [bw] "v"(bw_v), [sent] "v"(sent_v), \
 		  [addr1q] "v"(addr1q), [selq] "v"(selq_v), [QHOFF] "n"(LY::QH), \
 		  [XQOFF] "n"(LY::XQ), [FPOFF] "n"(LY::FP), [STOFF] "n"(LY::ST), [RBM1] "n"(LY::RB - 1), [FMASK] "n"(LY::FMASK), \
-		  [SNM1] "n"(LY::SN - 1), [RMASK] "n"(64 * NX - 1), [SBITS] "n"(LY::SBITS), [NFI] "n"(NF), [GAPOFF] "n"(LYT::GAP), [NXM1] "n"(NX - 1), [REACH] "n"(64 * NX) \
+		  [SNM1] "n"(LY::SN - 1), [RMASK] "n"(64 * NX - 1), [SBITS] "n"(LY::SBITS), [NFI] "n"(NF), [GAPOFF] "n"(LYT::GAP), [NXM1] "n"(NX - 1), [REACH] "n"(64 * NX), [FBITS] "n"(PK_FBITS) \
 		: "memory", "vcc", "scc", MM2C_R_X, MM2C_R_Q, MM2C_R_F, MM2C_R_P MM2C_FG_CLOB(CLOB)); \
 	return cnt + c; \
 }
 
 // two instantiations of each: `lean` for tiles in which no window reaches beyond the LDS ring (no test for it anywhere in the loop, stamps written
 // without touching exec), `far` for the others
-#define MM2C_RING_W MM2C_XQ1_W, MM2C_NEXT_XQ_W, MM2C_RFILTER_W, MM2C_OLDADDR_W, MM2C_BACK_W, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_W, PF2
-#define MM2C_RING_C MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PLAIN, PF0
+#define MM2C_RING_W MM2C_XQ1_W, MM2C_NEXT_XQ_W, MM2C_RFILTER_W, MM2C_OLDADDR_W, MM2C_BACK_W, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_W, PF2, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
+#define MM2C_RING_C MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
+#define MM2C_RING_P MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_P, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PACKED, PF0, MM2C_RDFP_4, MM2C_UNPACK_4, MM2C_FGFIX_4, "2"
 #define MM2C_SCAN_TILE_ASM_(...) MM2C_SCAN_TILE_ASM(__VA_ARGS__)
 #define MM2C_LEAN MM2C_RD_LEAN, MM2C_LK_LEAN, MM2C_HF_LEAN, MM2C_TAIL_LEAN, MM2C_END_LEAN, "", "Lloop_%="
 #define MM2C_FARS MM2C_RD_FAR, MM2C_LK_FAR, MM2C_HF_FAR, MM2C_TAIL_FAR, MM2C_END_FAR, MM2C_DONE_FAR, "Lret_%="
@@ -1012,8 +1055,13 @@ MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_c, false, true, MM2C_RING_C, MM2C_SCORE_CM
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_c, false, true, MM2C_RING_C, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
+// ... the compact x / q ring with the packed f / p ring and the one-load deep fetch (Lds<> RING 3)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
 // ... and over the q24 ring (the long ring of class-1 tasks): everything but a ring tile's request and filter is the 32-bit form's or the compact form's
-#define MM2C_RING_Q MM2C_XQ1_Q, MM2C_NEXT_XQ_Q, MM2C_RFILTER_Q, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_PLAIN, PF0
+#define MM2C_RING_Q MM2C_XQ1_Q, MM2C_NEXT_XQ_Q, MM2C_RFILTER_Q, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
@@ -1022,17 +1070,17 @@ MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TA
 // ---------------------------------------------------------------- the kernel: one wave per task
 // LDS rings before the own tile: x / q of NX tiles, f / p of the NF nearest (NF a power of two dividing NX).
 // C16: the compact x / q ring (Lds<>), for the variants with the hand-written loop; the launcher picks it per task (cls bit 1 clear)
-template <int NX, int NF, bool SKIP, bool GEN, bool GS1, bool FAR, bool TAB, int C16 /* the ring form: 0 32-bit slots, 1 compact (16 + 16 bits), 2 q24 (16 + 24 bits) */>
+template <int NX, int NF, bool SKIP, bool GEN, bool GS1, bool FAR, bool TAB, int C16 /* the ring form: 0 32-bit slots, 1 compact (16 + 16 bits), 2 q24 (16 + 24 bits), 3 compact with the packed f / p ring */>
 #ifdef MM2C_LABEL_COUNT
 #define MM2C_WAVES_PER_SIMD(C16V, BYTES) 1
 #else
-#define MM2C_WAVES_PER_SIMD(C16V, BYTES) ((C16V) == 1 && (BYTES) <= 6144 ? 7 : (C16V) == 2 && (BYTES) <= 7424 ? 6 : 1)   /* q24 ring: 22 waves per CU by its LDS, at most 80 VGPRs then */
+#define MM2C_WAVES_PER_SIMD(C16V, BYTES) (((C16V) == 1 || (C16V) == 3) && (BYTES) <= 6144 ? 7 : (C16V) == 2 && (BYTES) <= 7424 ? 6 : 1)   /* q24 ring: 22 waves per CU by its LDS, at most 80 VGPRs then */
 #endif
 __global__ void __launch_bounds__(64, MM2C_WAVES_PER_SIMD(C16, (Lds<NX, NF, GEN, TAB, C16>::BYTES)))   // the compact ring leaves room for 7 waves per SIMD: at most 72 VGPRs then (it came out at 73)
 chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, const int32_t *__restrict__ order,
               const uint4 *__restrict__ a_all, const float *__restrict__ avg_in, const int32_t *__restrict__ pbase_in,
               const int32_t *__restrict__ st_all, int32_t *__restrict__ f_all, int32_t *__restrict__ p_all, int32_t *__restrict__ t_all,
-              int32_t *__restrict__ status, int only_flagged, const int64_t *__restrict__ ends, const int32_t *__restrict__ n_live,
+              int32_t *__restrict__ w_all /* packed f / p words, one per anchor (RING 3 only) */, int32_t *__restrict__ status, int only_flagged, const int64_t *__restrict__ ends, const int32_t *__restrict__ n_live,
               const uint8_t *__restrict__ cls, int my_cls, int cls_mask)
 {
 	static_assert(!C16 || (SKIP && !GEN && (GS1 || TAB)), "the compact and the q24 ring belong to the variants of the hand-written loop");
@@ -1057,6 +1105,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 	const uint4 *a = a_all + base0;        // {x lo, x hi, y lo (= query pos), y hi (span | flags | seg)}
 	const int32_t *st = st_all + base0;
 	int32_t *f = f_all + base0, *p = p_all + base0, *t = FAR ? t_all + base0 : nullptr;
+	int32_t *w = C16 == 3 ? w_all + base0 : f;
 	if (ASMV && (uint32_t)(uintptr_t)(void *)lds != 0) { if (lane == 0) status[task] = 3; return; }   // cannot happen: one LDS object per kernel
 
 	const int pbase = pbase_in ? pbase_in[task] : 0;
@@ -1091,7 +1140,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 	asm volatile("" : "+v"(X.mdq1_v), "+v"(X.bw_v), "+v"(sent_v), "+v"(mdqbw_v));   // per-lane copies: VALU operands from VGPRs issue at the full rate
 	if (C16 == 2) asm volatile("" : "+v"(selq_v));           // (a register of its own only in the instantiation that uses it)
 	TileMem M;
-	M.lds = lds; M.a = a; M.f = f; M.p = p; M.t = t; M.pbase = pbase;
+	M.lds = lds; M.a = a; M.f = f; M.p = p; M.t = t; M.w = w; M.pbase = pbase;
 
 	int own_x = 0, own_q = 0, own_g = 0, own_f = 0, own_p = -1;   // the own tile: lane L = anchor i0 + 63 - L
 	int seg0 = 0;
@@ -1179,7 +1228,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 
 		for (int k = 0; k < cnt; ++k) {
 			if (ASM) {
-#define MM2C_CALL(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, pbase, a, t, own_x, tx1_l, own_q, tq1_l, span_l, lo_c, \
+#define MM2C_CALL(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, w, pbase, a, t, own_x, tx1_l, own_q, tq1_l, span_l, lo_c, \
                                  LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, addr0 >> 2, selq_v MM2C_LC_ARG)
 				if (C16 == 2) {
 					// the q24 forms take what the 32-bit ones take (x, q, x - 1, q - 1 in full) + the byte ring's address of the tile before and the byte selector
@@ -1187,9 +1236,12 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 					else k = TAB ? MM2C_CALL(scan_tile_asm_tab_q, lo_l) : MM2C_CALL(scan_tile_asm_cmp_q, lo_l);
 				} else if (C16) {
 					// the compact forms take packed words where the 32-bit ones take x and q: the tile's own {x, q} halves and the anchors' {x - 1, q - 1} halves
-#define MM2C_CALLC(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, pbase, a, t, own_xq, own_xq1, own_xq, own_xq1, span_l, lo_c, \
+#define MM2C_CALLC(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, w, pbase, a, t, own_xq, own_xq1, own_xq, own_xq1, span_l, lo_c, \
                                  LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, 0, 0 MM2C_LC_ARG)
-					if (FAR && tile_far) k = TAB ? MM2C_CALLC(scan_tile_asm_tab_far_c, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_far_c, lo_l);
+					if (C16 == 3) {
+						if (FAR && tile_far) k = TAB ? MM2C_CALLC(scan_tile_asm_tab_far_p, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_far_p, lo_l);
+						else k = TAB ? MM2C_CALLC(scan_tile_asm_tab_p, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_p, lo_l);
+					} else if (FAR && tile_far) k = TAB ? MM2C_CALLC(scan_tile_asm_tab_far_c, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_far_c, lo_l);
 					else k = TAB ? MM2C_CALLC(scan_tile_asm_tab_c, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_c, lo_l);
 #undef MM2C_CALLC
 				} else if (FAR && tile_far) k = TAB ? MM2C_CALL(scan_tile_asm_tab_far, lo_l) : MM2C_CALL(scan_tile_asm_cmp_far, lo_l);
@@ -1197,7 +1249,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 #undef MM2C_CALL
 #ifdef MM2C_LABEL_COUNT
 				{	// this call's label hits go to the row of the instantiation that ran: compact << 2 | table << 1 | far
-					const int row = (C16 == 1 ? 4 : 0) | (TAB ? 2 : 0) | ((FAR && tile_far) ? 1 : 0);   // (the q24 forms count into the 32-bit rows: the same labels, the same paths)
+					const int row = (C16 == 1 || C16 == 3 ? 4 : 0) | (TAB ? 2 : 0) | ((FAR && tile_far) ? 1 : 0);   // (the q24 forms count into the 32-bit rows, the packed f / p forms into the compact rows: the same labels, the same paths)
 					if (lane < 32 && lc_v != 0) atomicAdd(&g_label_hits[row * 32 + lane], (unsigned long long)(unsigned)lc_v);
 					lc_v = 0;
 				}
@@ -1231,7 +1283,11 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 		}
 		// ---- the finished tile: results leave in coalesced stores ...
 		if (rl < cnt) { f[idx] = own_f; p[idx] = own_p < 0 ? own_p : own_p + pbase; }
-		{
+		if (LY::FS == 4) {
+			const int v = pack_fp(own_f - FBIAS, own_p);   // ... and enters the f / p ring and the side array as one word (lanes beyond the task hold f = 0, p = -1)
+			*(int *)(lds + LY::FP + ((idx << 2) & LY::FMASK)) = v;
+			if (rl < cnt) w[idx] = v;
+		} else {
 			const int o = (idx << 3) & LY::FMASK;    // ... and enters the f / p ring: what the hand-written score adds (f[j] and its constant term in one), and p
 			*(int2 *)(lds + LY::FP + o) = make_int2(own_f - FBIAS, own_p);
 		}

@@ -7,6 +7,7 @@
 namespace mm2c {
 
 enum { KF_IGNORE_SEG = 0x1, KF_FORCE_GENERAL = 0x2 };
+constexpr int PK_MAX_N = 8192;       // packed f / p ring (chain_dp_tile.h, Lds<> RING 3): the longest task whose p values fit the word
 constexpr int CLS_STAT_SLOTS = 64;   // sets of class counters the tasks of a batch spread their atomic additions over (chain_window_start -> chain_cls_settle)
 
 // scalars of one mm_chain_dp call (mmpriv.h:65), passed by value to the kernel
@@ -44,13 +45,16 @@ struct LaunchArgs {
 	const float *d_avg;         // per task or nullptr (computed on the device, chain.c:48-49)
 	float *d_avg_ws = nullptr;  // n_tasks floats of workspace: when d_avg is nullptr the prepass computes avg_qspan_scaled into it
 	uint8_t *d_cls = nullptr;   // n_tasks bytes of workspace, or nullptr: class per task, written by the prepass (tile kernel only): bit 0 long ring, bit 1 the
-	                            // task needs the 32-bit x / q ring (its q values span more than the compact ring can tell apart, chain_dp_tile.h Lds<>)
+	                            // task needs the 32-bit x / q ring (its q values span more than the compact ring can tell apart, chain_dp_tile.h Lds<>), bit 2 a q value beyond the q24 ring,
+	                            // bit 3 the task's p and f fit the packed f / p word
 	hipStream_t side = nullptr; // with ev_fork / ev_join: when the batch is split over the 32-bit and the compact instantiations, the 32-bit ones run on this stream
 	hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // beside the compact one (two launches one after the other each end with the GPU part empty)
 	int noskip_loop = 1;        // calls whose max-skip exit cannot fire (max_skip >= max_iter) run with max_skip = max_iter - 1 through the hand-written loop (0: the instantiations
 	                            // without the max-skip machinery, C++ loop; mm2c_tune("noskip_loop"), the parity tests run both)
 	int compact = 1;            // 0: never the compact x / q ring (mm2c_tune("compact_ring", 0); the parity tests run both)
 	int q24 = 1;                // 0: the long ring of class-1 tasks keeps its 32-bit slots (mm2c_tune("q24_ring", 0); the parity tests run both); 1: the q24 ring (16 + 24 bits, 7 KB)
+	int packed_fp = 1;          // 0: never the packed f / p ring (mm2c_tune("packed_fp", 0): the routing without it); 1: tasks of the compact ring whose p and f fit one word take it (needs d_w)
+	int32_t *d_w = nullptr;     // one word per anchor of workspace, or nullptr: the packed f / p words of finished tiles (chain_dp_tile.h, Lds<> RING 3), read back by scans deeper than the f / p ring
 	unsigned long long *d_cls_stat = nullptr;   // CLS_STAT_SLOTS sets of four counters, zero on entry (chain_cls_settle), or nullptr
 	int wide_pct = 40;          // when the tasks that need the 32-bit x / q ring hold more than this share of the batch's anchors, every task takes it
 	int far_thr10 = 7;          // far_ring 1: a task takes the long ring when it expects more than far_thr10 / 10 tiles beyond the short ring per anchor
@@ -90,6 +94,7 @@ struct LaunchInfo {
 	int classes;     // ring-size classes: class-1 tasks run the instantiation with 2 * nx tiles
 	int c16;         // tasks whose q values allow it run the instantiations with the compact x / q ring (per task: bit 1 of its class clear)
 	int q24;         // class-1 tasks (long ring) run the instantiation with the q24 ring (chain_dp_tile.h, Lds<> RING 2) instead of 32-bit slots
+	int packed;      // tasks of the compact ring whose p and f fit one word (bit 3 of the class) run the instantiation with the packed f / p ring of four tiles and the one-load deep fetch
 	int cut;         // tasks are cut into pieces on the device first
 	int coop;        // waves per task of the cooperative kernel (chain_dp_coop), 0: one wave per task
 	int host_out;    // 1: the cooperative kernel wrote f / p to the caller's buffer and raised the flag itself (LaunchArgs::h_f ...)

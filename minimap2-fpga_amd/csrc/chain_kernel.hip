@@ -63,6 +63,9 @@
 #ifndef MM2C_CNX
 #define MM2C_CNX 16
 #endif
+#ifndef MM2C_PNF
+#define MM2C_PNF 4       // tiles of f / p in the packed ring (4-byte slots: the LDS of MM2C_CNF tiles of pairs)
+#endif
 #ifndef MM2C_CNF
 #define MM2C_CNF 2
 #endif
@@ -259,6 +262,7 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
                    unsigned long long *__restrict__ cls_stat /* CLS_STAT_SLOTS sets of [anchors of class-1 tasks, of all tasks, -, of tasks with the 32-bit ring], or nullptr */,
                    unsigned q_span_max /* compact x / q ring: the widest span of q values a task may have (0: no task takes it) */,
                    int q24 /* the long ring is the q24 ring: a task with a q value of 2^24 or more stays out of class 1 (and carries bit 2) */,
+                   int packed_fp /* the packed f / p ring (chain_dp_tile.h, Lds<> RING 3) is in use: a task it can hold carries bit 3 */,
                    int seg_anchors, unsigned long long *__restrict__ seg_ws)
 {
 	const int lane = threadIdx.x;
@@ -362,6 +366,11 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
 		if (!s_last) return;
 		far_sum = 0; span_sum = 0; q_min = s_qmin; q_max = s_qmax;              // (the tail below adds the lanes' shares to the LDS totals: nothing left to add)
 	}
+	if ((cls_out || avg_out) && n > 0) {
+		// the task's span sum (chain.c:48), for avg_qspan_scaled and for the bound on f below
+		for (int o = 32; o > 0; o >>= 1) span_sum += __shfl_xor(span_sum, o);
+		if ((lane & 63) == 0 && span_sum) atomicAdd(&s_sum, (unsigned long long)span_sum);
+	}
 	if (cls_out && n > 0) {
 		// bit 1: the task's q values span more than the compact x / q ring tells apart (chain_dp_tile.h, Lds<>): it runs with the 32-bit ring
 		for (int o = 32; o > 0; o >>= 1) { q_min = min(q_min, __shfl_xor(q_min, o)); q_max = max(q_max, __shfl_xor(q_max, o)); }
@@ -369,6 +378,10 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
 		__syncthreads();
 		const int wide = (q_span_max == 0 || (unsigned)s_qmax - (unsigned)s_qmin > q_span_max) ? 2 : 0;
 		const int huge = (q24 && (s_qmin < 0 || s_qmax >= (1 << 24))) ? 4 : 0;    // (q as a signed word: a position of 2^31 or more shows as negative)
+		// bit 3: p and f of the task fit the packed f / p word (chain_dp_tile.h, Lds<> RING 3): at most PK_MAX_N anchors, and the sum of the spans the scores add
+		// (the anchors' own, or span_override for each) at most PK_MAX_F -- no f[i] of the task can exceed it.  The task's own, like bits 1 and 2: it takes no part in the ring-size class.
+		const unsigned long long f_bound = P.span_override >= 0 ? (unsigned long long)P.span_override * (unsigned long long)n : s_sum;
+		const int fits = (packed_fp && n <= PK_MAX_N && f_bound <= (unsigned long long)PK_MAX_F) ? 8 : 0;
 		if (far_ring == 1) {
 			for (int o = 32; o > 0; o >>= 1) far_sum += __shfl_xor(far_sum, o);
 			if ((lane & 63) == 0 && far_sum) atomicAdd(&s_far, (unsigned long long)far_sum);
@@ -380,7 +393,7 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
 			// asm20 mixed (0.5) and dense (0.85)
 			if (lane == 0) {
 				const int c = (!huge && n >= 1024 && 10 * s_far > (unsigned long long)far_thr10 * (unsigned long long)n) ? 1 : 0;
-				cls_out[task] = (uint8_t)(c | wide | huge);
+				cls_out[task] = (uint8_t)(c | wide | huge | fits);
 				if (cls_stat) {
 					unsigned long long *cs = cls_stat + 4 * (task & (CLS_STAT_SLOTS - 1));   // 64 sets of counters: 65 536 tasks adding to ONE set cost the dense stream's prepass 0.6 ms
 					atomicAdd(&cs[1], (unsigned long long)n); if (c) atomicAdd(&cs[0], (unsigned long long)n);
@@ -388,14 +401,12 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
 				}
 			}
 		} else if (lane == 0) {
-			cls_out[task] = (uint8_t)((far_ring == 2 && !huge ? 1 : 0) | wide | huge);
+			cls_out[task] = (uint8_t)((far_ring == 2 && !huge ? 1 : 0) | wide | huge | fits);
 			if (cls_stat) { unsigned long long *cs = cls_stat + 4 * (task & (CLS_STAT_SLOTS - 1)); atomicAdd(&cs[1], (unsigned long long)n); if (wide) atomicAdd(&cs[3], (unsigned long long)n); }
 		}
 	}
 	if (avg_out && n > 0) {
 		// avg_qspan_scaled of the task (chain.c:48-49), so that the DP kernel does not sweep the anchors a second time
-		for (int o = 32; o > 0; o >>= 1) span_sum += __shfl_xor(span_sum, o);
-		if ((lane & 63) == 0) atomicAdd(&s_sum, (unsigned long long)span_sum);
 		__syncthreads();
 		if (lane == 0) avg_out[task] = (float)(__dmul_rn(.01, (double)(float)s_sum) / (double)n);
 	}
@@ -492,7 +503,7 @@ chain_cls_settle(int64_t n_tasks, uint8_t *__restrict__ cls, const unsigned long
 	int c = cls[t];
 	if (all_wide) c |= 2;
 	if (settle_ring) {
-		if (4 * far < all) c &= 6;                            // (bit 1, the 32-bit ring, and bit 2, a q value beyond the q24 ring, are the task's own)
+		if (4 * far < all) c &= ~1;                           // (bit 1, the 32-bit ring, bit 2, a q value beyond the q24 ring, and bit 3, the packed f / p word fits, are the task's own)
 		else if (4 * far > 3 * all && !(c & 4)) c |= 1;       // (a task the q24 long ring cannot hold stays in class 0, whatever the batch does)
 	}
 	cls[t] = (uint8_t)c;
@@ -745,12 +756,12 @@ static hipError_t launch_tile_nx(const LaunchArgs &L, const float *d_avg, hipStr
 	if (L.cut.max_pieces > 0) {
 		hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)L.cut.max_pieces), dim3(64), 0, st,
 		                   L.P, L.cut.max_pieces, L.cut.d_start, (const int32_t *)nullptr, (const uint4 *)L.d_anchors, L.cut.d_avg, L.cut.d_pbase, L.d_st, L.d_f, L.d_p,
-		                   L.d_t, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_live ? L.cut.d_live : L.cut.d_count, with_cls ? (const uint8_t *)L.cut.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
+		                   L.d_t, L.d_w, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_live ? L.cut.d_live : L.cut.d_count, with_cls ? (const uint8_t *)L.cut.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
 		return hipGetLastError();
 	}
 	hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)L.n_tasks), dim3(64), 0, st,
 	                   L.P, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, d_avg, L.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t,
-	                   L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, with_cls ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
+	                   L.d_w, L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, with_cls ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
 	return hipGetLastError();
 }
 
@@ -766,6 +777,10 @@ static unsigned compact_q_span(const LaunchArgs &L, bool asm_loop)
 	if (!L.compact || !asm_loop || !have_cls(L) || P.max_dist_x < 0 || P.max_dist_x > 65535 || P.max_dq < 1 || P.max_dq > 32768) return 0;
 	return 65535u - (unsigned)P.max_dq;
 }
+
+// the packed f / p ring (chain_dp_tile.h, Lds<> RING 3): for the tasks of the compact x / q ring whose p and f fit its word (bit 3 of the class, set by the prepass
+// when this says so); needs the side array of one word per anchor, which plans have
+static bool packed_fp_ring(const LaunchArgs &L, bool asm_loop) { return L.packed_fp != 0 && L.d_w != nullptr && compact_q_span(L, asm_loop) != 0; }
 
 // the q24 ring (chain_dp_tile.h, Lds<> RING 2) is the form of the LONG ring (ring-size class 1): dr from the low halves of x needs max_dist_x < 2^16, q is exact for
 // tasks whose q values are below 2^24 -- the prepass keeps every other task out of class 1 (bit 2 of the class byte)
@@ -800,10 +815,21 @@ static hipError_t launch_tile_one(const LaunchArgs &L, const float *d_avg, hipSt
 			if (!done) e = launch_tile_nx<2 * MM2C_NX, MM2C_NF1, SKIP, GEN, GS1, FAR, TAB, 0>(L, d_avg, sw, only_flagged, true, wide | 1, mask);
 			if (n_launches) ++*n_launches;
 		}
+	// the compact ring.  Tasks the packed f / p word can hold (bit 3) take the instantiation with it, the others -- the long ones -- the one with pairs, which goes
+	// FIRST and, where there is a side stream, beside the packed one (two launches one after the other on one stream each end with the GPU part empty, and the
+	// longest tasks started last would make the batch wait for their whole length); without the packed ring bit 3 is not looked at
+	bool pk = false;
+	if constexpr (SKIP && !GEN && (GS1 || TAB)) pk = c16 && packed_fp_ring(L, true);
+	if constexpr (SKIP && !GEN && (GS1 || TAB))
+		if (e == hipSuccess && c16 && pk) { e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, d_avg, sw, only_flagged, true, 0, 2 | 8); if (n_launches) ++*n_launches; }
 	bool joined = false;
 	if (forked) joined = hipEventRecord(L.ev_join, sw) == hipSuccess;
 	if constexpr (SKIP && !GEN && (GS1 || TAB))
-		if (e == hipSuccess && c16) { e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, d_avg, st, only_flagged, true, 0, 2); if (n_launches) ++*n_launches; }
+		if (e == hipSuccess && c16) {
+			if (pk) e = launch_tile_nx<MM2C_CNX, MM2C_PNF, SKIP, GEN, GS1, FAR, TAB, 3>(L, d_avg, st, only_flagged, true, 8, 2 | 8);
+			else e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, d_avg, st, only_flagged, true, 0, 2);
+			if (n_launches) ++*n_launches;
+		}
 	if (forked) {
 		const hipError_t ej = joined ? hipStreamWaitEvent(st, L.ev_join, 0) : hipStreamSynchronize(sw);   // no event to wait on: the host waits for the side stream instead
 		if (e == hipSuccess) e = joined ? ej : hipErrorUnknown;
@@ -975,8 +1001,9 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 		info->classes = t0 && use_classes(L, skip, want_gen);
 		info->c16 = t0 && compact_q_span(L, info->asm_loop != 0) != 0;
 		info->q24 = t0 && info->classes && q24_ring(L, skip, want_gen, gs1, tab);
+		info->packed = t0 && info->c16 && packed_fp_ring(L, info->asm_loop != 0);
 		info->cut = L.cut.max_pieces > 0;
-		if (coop) { info->nx = COOP_NX; info->nf = COOP_NF; info->r = 64 * (COOP_NX - 1); info->far_ = (int64_t)P.max_iter > 64 * (COOP_NX - 1); info->classes = 0; info->c16 = 0; info->q24 = 0; }
+		if (coop) { info->nx = COOP_NX; info->nf = COOP_NF; info->r = 64 * (COOP_NX - 1); info->far_ = (int64_t)P.max_iter > 64 * (COOP_NX - 1); info->classes = 0; info->c16 = 0; info->q24 = 0; info->packed = 0; }
 	}
 	if (L.dry_run) return hipSuccess;                                  // the caller only wanted to know (info)
 	// avg_qspan_scaled per task: the caller's, or computed by the prepass into the workspace (else the DP kernel sweeps the task itself)
@@ -1005,7 +1032,7 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 	                   (const ulonglong2 *)L.d_anchors, L.d_st, L.cut.max_pieces > 0 ? L.cut.d_has_cut : (int32_t *)nullptr, avg_out, \
 	                   tile && !coop ? L.d_cls : (uint8_t *)nullptr, L.far_ring, L.far_thr10, tile && !coop ? L.d_cls_stat : (unsigned long long *)nullptr, \
 	                   coop ? 0u : c16_bound,                     /* (the cooperative kernel has one ring form: no classes to find) */ \
-	                   (!coop && tile && q24_ring(L, skip, want_gen, gs1, tab)) ? 1 : 0, SEGN, WS)
+	                   (!coop && tile && q24_ring(L, skip, want_gen, gs1, tab)) ? 1 : 0, (!coop && c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr) ? 1 : 0, SEGN, WS)
 		if (seg) MM2C_WS(true, dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
 		else MM2C_WS(false, dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
 #undef MM2C_WS

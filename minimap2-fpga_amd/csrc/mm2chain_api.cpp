@@ -484,7 +484,7 @@ struct mm2c_plan {
 	int device = 0;                         // the device the plan's workspace lives on
 	const int64_t *d_off_user = nullptr;    // mm2c_plan_set_device_offsets: task sizes that only the device knows
 	int64_t n_tasks = 0, total = 0;
-	int64_t *d_off = nullptr; int32_t *d_order = nullptr, *d_status = nullptr, *d_t = nullptr, *d_st = nullptr; float *d_avg_ws = nullptr; uint8_t *d_cls = nullptr;
+	int64_t *d_off = nullptr; int32_t *d_order = nullptr, *d_status = nullptr, *d_t = nullptr, *d_st = nullptr, *d_w = nullptr; float *d_avg_ws = nullptr; uint8_t *d_cls = nullptr;
 	unsigned long long *d_seg_ws = nullptr; // plans with long tasks: the words in which the segments of a task add up the prepass's sums (chain_window_start_t<true>; zero between runs)
 	hipEvent_t ev_pre = nullptr, ev0 = nullptr, ev1 = nullptr, ev_e0 = nullptr, ev_e1 = nullptr;
 	mm2c_api::AuxSet aux;                   // helper stream + fork / join events (pooled): taken by the first run that may split its tasks over two instantiations
@@ -882,6 +882,11 @@ int mm2c_tune(const char *key, int value)
 		G.q24_ring = value != 0;
 		return 0;
 	}
+	if (strcmp(key, "packed_fp") == 0) {
+		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "packed_fp must be 0 or 1");
+		G.packed_fp = value;
+		return 0;
+	}
 	if (strcmp(key, "pin_workers") == 0) {
 		G.pin_workers = value != 0;
 		return 0;
@@ -1048,7 +1053,7 @@ static void plan_destroy_impl(mm2c_plan_t *pl, bool wait)
 	{
 		DeviceScope on(pl->device);
 		if (wait && (pl->ran || pl->epi_ran)) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }   // ONE wait, as hipFree would: the blocks go back to the cache and may be reused at once
-		dev_free_synced(pl->d_off); dev_free_synced(pl->d_order); dev_free_synced(pl->d_status); dev_free_synced(pl->d_t); dev_free_synced(pl->d_st);
+		dev_free_synced(pl->d_off); dev_free_synced(pl->d_order); dev_free_synced(pl->d_status); dev_free_synced(pl->d_t); dev_free_synced(pl->d_st); dev_free_synced(pl->d_w);
 		dev_free_synced(pl->d_avg_ws); dev_free_synced(pl->d_seg_ws); dev_free_synced(pl->d_cls); dev_free_synced(pl->d_epi); dev_free_synced(pl->d_cut);
 		if (pl->ev_pre) (void)hipEventDestroy(pl->ev_pre);
 		if (pl->ev0) (void)hipEventDestroy(pl->ev0); if (pl->ev1) (void)hipEventDestroy(pl->ev1);
@@ -1081,8 +1086,16 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::LaunchArgs L;
 	L.P = to_kparams(&pl->par);
+	// the packed f / p words of finished tiles (chain_dp_tile.h, Lds<> RING 3), 4 B per anchor: taken by the first run that can use them (the knobs on, scalars the
+	// compact ring takes); a plan that cannot get them runs without the packed ring
+	// A plan with a task longer than the packed word can hold (PK_MAX_N anchors) runs without the packed ring altogether: its long tasks would run the form with pairs
+	// in a launch of their own beside or after the packed one, and that split costs more than the packed ring returns (ragged mixed stream: 49.0 -> 53.1 ms with the
+	// split, whichever form goes first; profiles/packed_fp.md).  The variant text then says packed_fp=0.
+	const bool packed_ok = G.packed_fp && pl->sizes_desc[0] <= mm2c::PK_MAX_N;
+	if (!pl->d_w && packed_ok && G.compact_ring && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535 && L.P.max_dq >= 1 && L.P.max_dq <= 32768)
+		if (dev_alloc((void **)&pl->d_w, (size_t)std::max<int64_t>(pl->total, 1) * 4) != hipSuccess) { pl->d_w = nullptr; (void)hipGetLastError(); }
 	L.n_tasks = pl->n_tasks; L.d_offsets = pl->d_off_user ? pl->d_off_user : pl->d_off; L.d_order = pl->d_order;
-	L.d_anchors = d_anchors; L.d_avg = d_avg_qspan; L.d_pbase = nullptr; L.d_f = d_f; L.d_p = d_p; L.d_t = pl->d_t; L.d_st = pl->d_st; L.d_status = pl->d_status;
+	L.d_anchors = d_anchors; L.d_avg = d_avg_qspan; L.d_pbase = nullptr; L.d_f = d_f; L.d_p = d_p; L.d_t = pl->d_t; L.d_st = pl->d_st; L.d_w = pl->d_w; L.packed_fp = packed_ok ? 1 : 0; L.d_status = pl->d_status;
 	L.d_avg_ws = pl->d_avg_ws;
 	L.d_cls = pl->d_cls; L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10;
 	L.d_cls_stat = (unsigned long long *)(pl->d_cls + (((size_t)std::max<int64_t>(pl->n_tasks, 1) + 15) & ~(size_t)15));
@@ -1190,6 +1203,19 @@ int mm2c_plan_last_variant(mm2c_plan_t *pl, char *buf, size_t len)
 	if (!pl || !buf || len == 0) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
 	format_variant(pl->info, buf, len);
+	return 0;
+}
+
+int mm2c_plan_last_classes(mm2c_plan_t *pl, unsigned char *cls, int64_t n)
+{
+	if (!pl || !cls) return fail(MM2C_E_ARG, "NULL argument");
+	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
+	if (n != pl->n_tasks) return fail(MM2C_E_ARG, "one byte per task of the plan");
+	if (n == 0) return 0;
+	DeviceScope on(pl->device);
+	HIP_TRY(on.err);
+	HIP_TRY(hipEventSynchronize(pl->ev1));
+	HIP_TRY(hipMemcpy(cls, pl->d_cls, (size_t)n, hipMemcpyDeviceToHost));
 	return 0;
 }
 

@@ -92,6 +92,7 @@ C_SYMBOLS = {
     "mm2c_plan_predict_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_plan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_plan_last_variant": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "mm2c_plan_last_classes": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte), C.c_int64]),
     "mm2c_plan_last_route": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mm2c_route_pieces": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "mm2c_last_host_variant": (C.c_int, [C.c_char_p, C.c_size_t]),

@@ -180,6 +180,12 @@ class ChainPlan:
         N.check(self.lib.mm2c_plan_last_variant(self.handle, buf, len(buf)), "mm2c_plan_last_variant")
         return buf.value.decode()
 
+    def last_classes(self):
+        """class byte per task from the prepass of the last run (mm2c_plan_last_classes): bit 1 the 32-bit ring, bit 3 the packed f / p ring"""
+        buf = (C.c_ubyte * max(self.n_tasks, 1))()
+        N.check(self.lib.mm2c_plan_last_classes(self.handle, buf, self.n_tasks), "mm2c_plan_last_classes")
+        return bytes(buf)[:self.n_tasks]
+
     def last_prepass_ms(self):
         ms = C.c_float(0)
         N.check(self.lib.mm2c_plan_last_prepass_ms(self.handle, C.byref(ms)), "mm2c_plan_last_prepass_ms")

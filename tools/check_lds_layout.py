@@ -20,9 +20,10 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def lds_bytes(nx, nf, gen, tab, ring):
     """Lds<NX, NF, GEN, TAB, RING>::BYTES of csrc/chain_dp_tile.h: x / q ring (NX tiles of 64 slots of 8 bytes; 4 in the compact form, RING 1, and in the
-    q24 form, RING 2, which adds one byte per ring anchor for bits 16-23 of q), f / p ring (NF tiles), one stamp byte per ring anchor, the gap-cost
+    q24 form, RING 2, which adds one byte per ring anchor for bits 16-23 of q), f / p ring (NF tiles of 64 pairs; of 64 packed words in RING 3, the compact
+    x / q ring with the packed f / p ring), one stamp byte per ring anchor, the gap-cost
     table, the segment-id ring"""
-    return nx * 64 * (4 if ring else 8) + 2 * nf * 256 + 64 * nx + (64 * nx if ring == 2 else 0) + (1024 if tab else 0) + (64 * nx if gen else 0)
+    return nx * 64 * (4 if ring else 8) + (1 if ring == 3 else 2) * nf * 256 + 64 * nx + (64 * nx if ring == 2 else 0) + (1024 if tab else 0) + (64 * nx if gen else 0)
 
 
 def elf_sections(elf):
@@ -80,7 +81,7 @@ def check(path, verbose=False):
     for triple, elf in code_objects(data):
         for name, lds in kernels_of(elf):
             # _ZN4mm2c13chain_dp_tileILi8ELi2ELb1ELb0ELb1ELb1ELb0ELi1EEEv...: <NX, NF, SKIP, GEN, GS1, FAR, TAB, RING>
-            m = re.match(r"_ZN4mm2c13chain_dp_tileILi(\d+)ELi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])ELb([01])ELi([012])EEE", name)
+            m = re.match(r"_ZN4mm2c13chain_dp_tileILi(\d+)ELi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])ELb([01])ELi([0123])EEE", name)
             mc = re.match(r"_ZN4mm2c13chain_dp_coopILi(\d+)ELb([01])ELb([01])ELb([01])EEE", name)
             if mc:
                 # chain_dp_coop<W, GS1, FAR, TAB> (csrc/chain_dp_coop.h): the same hand-written loop over Lds<COOP_NX = 16, COOP_NF = 8, false, TAB, false>, with the

@@ -2,7 +2,9 @@
 """How often an anchor of a synthetic stream takes each path of the hand-written loop of chain_dp_tile (own-tile chunk, older tiles from the
 ring, deep f / p, beyond the ring; fold A / B1 / B2; the `break` of chain.c:231), counted by the NumPy model of the kernel's control flow
 (tests/tile_model.py, checked against the CPU oracle in tests/test_cpu_oracle.py).  Together with tools/isa_budget.py this decomposes the
-per-anchor instruction counts of the PMC profiles.   python tools/chunk_stats.py [profile ...] [--reads N] [--anchors M]"""
+per-anchor instruction counts of the PMC profiles.   python tools/chunk_stats.py [profile ...] [--reads N] [--anchors M]
+--fp-depth: how deep the SCORED ring tiles lie (tiles before the own one): 1-2 = the f / p ring of pairs, 3-4 = what the packed f / p ring adds, > 4 = the deep fetch
+either way (profiles/packed_fp.md).  The model counts a scored ring tile beyond NF tiles as deep_fp, so two runs (NF 2 and NF 4) give the three bins."""
 import os
 import sys
 
@@ -32,6 +34,22 @@ if __name__ == "__main__":
         # round 6: what a per-tile bitmap of diagonal buckets would reject (skip_rejects of skip_tested ring-tile visits; skip_missed: visits without a surviving lane that
         # the bitmap lets through; skip_wrong must be 0)
         keys = ("ring_chunks", "ring_pass", "skip_tested", "skip_rejects", "skip_missed", "skip_wrong")
+    if "--fp-depth" in args:
+        print(f"Scored ring tiles per anchor by depth, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX {NX}:\n")
+        print("| stream | scored ring tiles | depth 1-2 | depth 3-4 | depth > 4 |\n|---|---|---|---|---|")
+        for prof in profiles:
+            off, a = synth.make_stream(prof, reads, m, seed=1, q_span=span)
+            off = off.numpy(); a = a.numpy().view(np.uint64)
+            n_anchors, ring_pass, deep = 0, 0, {2: 0, 4: 0}
+            for k in range(reads):
+                t = a[off[k]:off[k + 1]]
+                for nf in (2, 4):
+                    st = {}
+                    chain_tile_model(P, t, avg_qspan(t), stats=st, NX=NX, NF=nf)
+                    deep[nf] += st["deep_fp"]
+                n_anchors += st["anchors"]; ring_pass += st["ring_pass"]
+            print(f"| {prof} | {ring_pass / n_anchors:.3f} | {(ring_pass - deep[2]) / n_anchors:.3f} | {(deep[2] - deep[4]) / n_anchors:.3f} | {deep[4] / n_anchors:.3f} |")
+        sys.exit(0)
     print(f"Per anchor, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX {NX} / NF 2:\n")
     print("| stream | " + " | ".join(keys) + " |")
     print("|---|" + "---|" * len(keys))
