@@ -95,8 +95,10 @@ __device__ __forceinline__ void write_lane2(int &v0, int &v1, int a0, int a1, in
 // scored tile deeper than the f / p ring loads that one word instead of f[] and p[] and needs none of their fix-ups.  Limits, checked per task by the prepass
 // (chain_window_start_t: bit 3 of the class byte marks the tasks that fit; every other task runs the RING 1 instantiation): p <= 8191, so a piece of at most
 // PK_MAX_N = 8192 anchors (a device-cut piece is never longer than its task, whose length is what is tested); f - FBIAS < 2^17, and f[i] is at most the sum of
-// the spans of the task (a score adds at most the anchor's span to f[j], chain.c:207-220), so tasks whose span sum is at most PK_MAX_F = 2^17 - 1.  f >= 0 always
-// (it starts at the anchor's span), so f - FBIAS >= -14 fits the signed field.
+// the spans of the task WHILE THE GAP COST IS NOT A GAIN (gap_scale >= 0: a score then adds at most the anchor's span to f[j], chain.c:207-220), so tasks whose span
+// sum is at most PK_MAX_F = 2^17 - 1.  With gap_scale < 0, which the table forms admit, a link adds its span AND |gap_scale| times its gap cost and f passes any
+// bound made of spans: such a plan does not take this form at all (mm2c_plan_run_device, packed_ok; chain_dp_coop.h guards gap_scale >= 0 likewise).  f >= 0
+// always (it starts at the anchor's span), so f - FBIAS >= -14 fits the signed field.
 template <int NX, int NF, bool GEN, bool TAB, int RING = 0>
 struct Lds {
 	static constexpr int SN = 64 * NX;           // anchors with a stamp slot = anchors in the x / q ring

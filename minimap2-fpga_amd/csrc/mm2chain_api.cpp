@@ -1091,7 +1091,9 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	// A plan with a task longer than the packed word can hold (PK_MAX_N anchors) runs without the packed ring altogether: its long tasks would run the form with pairs
 	// in a launch of their own beside or after the packed one, and that split costs more than the packed ring returns (ragged mixed stream: 49.0 -> 53.1 ms with the
 	// split, whichever form goes first; profiles/packed_fp.md).  The variant text then says packed_fp=0.
-	const bool packed_ok = G.packed_fp && pl->sizes_desc[0] <= mm2c::PK_MAX_N;
+	// Nor does a plan whose gap cost can be a gain (gap_scale < 0): the packed word holds f up to the task's span sum, and f[i] stays below that sum only while no score
+	// adds more than the anchor's span (chain_dp_tile.h, Lds<> RING 3; chain_dp_coop.h guards gap_scale >= 0 for the same reason).
+	const bool packed_ok = G.packed_fp && pl->sizes_desc[0] <= mm2c::PK_MAX_N && pl->par.gap_scale >= 0.f;
 	if (!pl->d_w && packed_ok && G.compact_ring && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535 && L.P.max_dq >= 1 && L.P.max_dq <= 32768)
 		if (dev_alloc((void **)&pl->d_w, (size_t)std::max<int64_t>(pl->total, 1) * 4) != hipSuccess) { pl->d_w = nullptr; (void)hipGetLastError(); }
 	L.n_tasks = pl->n_tasks; L.d_offsets = pl->d_off_user ? pl->d_off_user : pl->d_off; L.d_order = pl->d_order;
@@ -1099,7 +1101,9 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	L.d_avg_ws = pl->d_avg_ws;
 	L.d_cls = pl->d_cls; L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10;
 	L.d_cls_stat = (unsigned long long *)(pl->d_cls + (((size_t)std::max<int64_t>(pl->n_tasks, 1) + 15) & ~(size_t)15));
-	HIP_TRY(hipMemsetAsync(L.d_cls_stat, 0, 32 * mm2c::CLS_STAT_SLOTS, st));
+	// the class bytes with the counters behind them: the prepass writes no byte for a task without anchors, and chain_cls_settle only adds to what it finds there --
+	// such a task would keep the bits an earlier run of the plan (or an earlier owner of the block) left
+	HIP_TRY(hipMemsetAsync(pl->d_cls, 0, (size_t)((char *)L.d_cls_stat - (char *)pl->d_cls) + 32 * mm2c::CLS_STAT_SLOTS, st));
 	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.wide_pct = G.wide_pct; L.noskip_loop = G.noskip_loop;
 	HIP_TRY(hipMemsetAsync(pl->d_status, 0, (size_t)pl->n_tasks * 4, st));
 	// Few long pieces: several waves per piece (chain_dp_coop.h; launch_chain_dp takes it for the variants of the hand-written loop).  "coop_plans" 2 (default, round 6):

@@ -134,3 +134,16 @@ def fold_driver_tasks(rng, shapes=((3000, 4, 0.05, 0.15), (2600, 3, 0.0, 0.3), (
         o = np.argsort(x, kind="stable")
         tasks.append(np.stack((x[o], y[o]), 1))
     return tasks
+
+
+def steep_colinear_task(rng, n, step_lo, step_hi, jitter_lo, jitter_hi):
+    """one colinear chain whose links are `step` apart in x and differ by `jitter` between x and q: every anchor's best predecessor is its neighbour, the gap cost of a
+    link is (int)(jitter * avg) + log2(jitter) / 2"""
+    step = rng.integers(step_lo, step_hi + 1, n)
+    jit = rng.integers(jitter_lo, jitter_hi + 1, n) * rng.choice([-1, 1], n)
+    pos = (1 << 20) + np.cumsum(step)
+    q = 100 + np.cumsum(np.maximum(step + jit, 1))
+    assert pos[-1] < (1 << 31) and q[-1] < (1 << 31)
+    x = (np.uint64(1) << np.uint64(32)) | pos.astype(np.uint64)
+    y = (np.uint64(15) << np.uint64(32)) | q.astype(np.uint64)
+    return np.stack((x, y), 1)

@@ -6,12 +6,9 @@ import numpy as np
 import pytest
 
 from helpers import assert_same, gpu_batch, oracle_batch
+from reuse_data import PK_MAX_F, PK_MAX_N, batch, chain_with_noise, span_sum, task_of
 
 pytestmark = pytest.mark.gpu
-
-PK_MAX_N = 8192            # csrc/chain_kernel.h
-PK_MAX_F = (1 << 17) - 1   # csrc/chain_dp_tile.h
-RID = np.uint64(1) << np.uint64(32)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -39,41 +36,16 @@ def knobs():
         mm2chain.tune(key, val)
 
 
-def task_of(pos, q, span):
-    """uint64 [n, 2] from reference positions, query positions and spans, sorted by x (stable)"""
-    x = RID | np.asarray(pos, np.int64).astype(np.uint64)
-    y = (np.asarray(span, np.int64).astype(np.uint64) << np.uint64(32)) | (np.asarray(q, np.int64).astype(np.uint64) & np.uint64(0xffffffff))
-    o = np.argsort(x, kind="stable")
-    return np.ascontiguousarray(np.stack((x[o], y[o]), 1))
-
-
-def chain_with_noise(rng, n, every, step=450, span=15, q0=100):
-    """A colinear chain with one anchor every `every` positions of the array, `step` apart in x and q (about 5000 / step of them inside a window of 5000), and noise
-    anchors in between whose q lies 3000-4000 off the diagonal (no pair of a chain anchor and a noise anchor passes bw = 500): the scored predecessors of a chain
-    anchor sit every, 2 * every, ... anchors back, i.e. in tiles 1, 2, 3, ... before its own."""
-    k = np.arange(n)
-    pos = 1000 + (k * step) // every
-    on = k % every == 0
-    q = np.where(on, q0 + pos - 1000, q0 + pos - 1000 + 3000 + rng.integers(0, 1000, n))
-    return task_of(pos, q, np.full(n, span))
-
-
-def batch(tasks):
-    return np.concatenate(tasks), np.concatenate(([0], np.cumsum([t.shape[0] for t in tasks]))).astype(np.int64)
-
-
-def span_sum(t):
-    return int(((t[:, 1] >> np.uint64(32)) & np.uint64(0xff)).sum())
-
-
-def run_both(P, tasks, knobs, what):
+def run_both(P, tasks, knobs, what, ref_tasks=None):
     """oracle == GPU with packed_fp 1 == GPU with packed_fp 0; returns the class bytes of the run with the knob on"""
     import torch
     import mm2chain
     a, off = batch(tasks)
-    f_ref, p_ref = oracle_batch(P, off, a)
+    # (ref_tasks: the anchors the oracle runs on, where P holds something the oracle's scalars do not -- q_span_override -- and other anchors say the same)
+    f_ref, p_ref = oracle_batch(P, off, a if ref_tasks is None else batch(ref_tasks)[0])
     out = {}
-    plan_packed = max(t.shape[0] for t in tasks) <= PK_MAX_N      # a plan with a longer task runs without the packed ring altogether, and says so
+    # a plan with a longer task runs without the packed ring altogether, and says so; so does a plan whose gap cost can be a gain (gap_scale < 0: f may pass the span sum)
+    plan_packed = max(t.shape[0] for t in tasks) <= PK_MAX_N and P.gap_scale >= 0
     for pk in (1, 0):
         knobs("packed_fp", pk)
         v = []
@@ -97,7 +69,8 @@ def run_both(P, tasks, knobs, what):
         assert_same(d_f.cpu().numpy(), d_p.cpu().numpy(), f_ref, p_ref, off, f"{what}, class read-back run, packed_fp={pk}")
     cls = by_knob[1]
     assert not (by_knob[0] & 8).any() and np.array_equal(by_knob[0], cls & ~np.uint8(8)), (by_knob[0], cls)
-    want = np.array([plan_packed and span_sum(t) <= PK_MAX_F for t in tasks])
+    f_bound = [P.q_span_override * t.shape[0] if P.q_span_override >= 0 else span_sum(t) for t in tasks]   # what the scores add: the anchors' spans, or the override for each
+    want = np.array([plan_packed and b <= PK_MAX_F for b in f_bound])
     assert np.array_equal((cls & 8) != 0, want), (cls, want)
     return cls
 
@@ -220,3 +193,68 @@ def test_device_cut_pieces_inherit_the_form(knobs):
     assert [bool(c & 8) for c in cls] == [True, True, False]
     cls = run_both(P, tasks, knobs, "device-cut pieces, with a task too long for the word")
     assert not (cls & 8).any()
+
+
+def _gaining_colinear_task(rng, n, span):
+    """the recipe of helpers.steep_colinear_task (one colinear chain, every anchor's best predecessor its neighbour, x and q of a link apart by a jitter of 200 .. 420,
+    within bw = 500) with the jitter always on the side of x: q advances 5 .. 25 per link, so the q values of 2000 anchors span less than the compact ring allows, while
+    the gap cost of a link is (int)(dd * avg) + log2(dd) / 2 with dd = 200 .. 420"""
+    dq = rng.integers(5, 26, n)
+    dd = rng.integers(200, 421, n)
+    return task_of((1 << 20) + np.cumsum(dq + dd), 100 + np.cumsum(dq), np.full(n, span))
+
+
+@pytest.mark.parametrize("coop_plans", [0, 2])
+@pytest.mark.parametrize("gap_scale,span", [(-15.0, 15), (-0.5, 60)])
+def test_a_gap_cost_that_is_a_gain_takes_f_beyond_the_span_sum(gap_scale, span, coop_plans, knobs):
+    """gap_scale < 0 (the table forms admit -20 < gap_scale < 20): every link of a colinear chain with jitter GAINS |gap_scale| * ((int)(dd * avg) + log2(dd) / 2), so
+    f passes the sum of the spans -- the bound by which the prepass says a task fits the packed word.  Three tasks of 300, 700 and 2000 anchors with compact q and span
+    sums of at most 120 000, so nothing else keeps them from the packed ring.  gap_scale -15, span 15: about 750 a link, every task's f passes 2^17 + 14.  gap_scale
+    -0.5: f of the 300-anchor task stays below 2^17 and that of the 2000-anchor task passes it (with span 60: at span 15 and bw 500 a link gains at most
+    0.5 * (75 + 4) + 15 = 55, and 2000 links stay below 2^17 whatever the anchors).  Equal to the oracle with the knob on and off, one wave per piece and by the
+    library's own route; the plan runs without the packed ring and says so."""
+    from mm2chain import params
+    from reuse_data import expected_class_bits
+    P = params.make_params(gap_scale=gap_scale, bw=500)
+    rng = np.random.default_rng(1517)
+    tasks = [_gaining_colinear_task(rng, n, span) for n in (300, 700, 2000)]
+    assert all(span_sum(t) <= PK_MAX_F for t in tasks) and not (expected_class_bits(tasks) & 2).any()      # tasks of the compact ring, within the stated bound
+    a, off = batch(tasks)
+    f_ref, p_ref = oracle_batch(P, off, a)
+    top = [int(f_ref[off[k]:off[k + 1]].max()) for k in range(3)]
+    if gap_scale == -15.0:
+        assert min(top) > PK_MAX_F + 14, top
+    else:
+        assert top[0] < (1 << 17) < top[2], top
+    knobs("coop_plans", coop_plans)
+    if coop_plans == 0:
+        cls = run_both(P, tasks, knobs, f"gap_scale={gap_scale}")
+        assert not (cls & 8).any()
+        return
+    for pk in (1, 0):                    # the library's own route
+        knobs("packed_fp", pk)
+        v = []
+        f, p = gpu_batch(P, off, a, variant=v)
+        assert_same(f, p, f_ref, p_ref, off, f"gap_scale={gap_scale}, coop_plans=2, packed_fp={pk}: {v[0]}")
+        assert "packed_fp=1" not in v[0], v
+
+
+def test_q_span_override_at_the_limit_of_f(knobs):
+    """with q_span_override every score adds the override, whatever the anchors' own spans: the bound on f is override * n.  255 * 514 = 131 070 fits the word and
+    255 * 515 = 131 325 does not; the anchors' own spans (15) would let both in.  The oracle's scalars have no override: it runs on the same anchors with span 255
+    written into them, which is the same computation here -- every pair of a strictly colinear chain has dd = 0, so its gap cost is 0 whatever avg_qspan is, the one
+    other place a span enters."""
+    from mm2chain import params
+    from reuse_data import with_spans
+    P = params.make_params(q_span_override=255)
+    tasks = []
+    for n in (514, 515):
+        k = np.arange(n)
+        tasks.append(task_of(1000 + 255 * k, 100 + 255 * k, np.full(n, 15)))
+    as_255 = [with_spans(t, 255) for t in tasks]
+    assert 255 * 514 <= PK_MAX_F < 255 * 515 and all(span_sum(t) <= PK_MAX_F for t in tasks)
+    a, off = batch(as_255)
+    f_ref, _ = oracle_batch(P, off, a)
+    assert int(f_ref[:off[1]].max()) == 255 * 514 and int(f_ref[off[1]:].max()) == 255 * 515      # f reaches the bound exactly
+    cls = run_both(P, tasks, knobs, "q_span_override at the f bound", ref_tasks=as_255)
+    assert [bool(c & 8) for c in cls] == [True, False]

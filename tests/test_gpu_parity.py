@@ -9,6 +9,7 @@ import torch
 
 import oracle_binding as ob
 from helpers import mk_anchor, pack, oracle_batch, gpu_batch, assert_same
+from helpers import steep_colinear_task as _steep_colinear_task
 
 pytestmark = pytest.mark.gpu
 
@@ -157,19 +158,6 @@ def test_drive_every_fold_of_the_hand_written_loop(compact, gap_scale, knobs):
         f, p = gpu_batch(P, off, a, variant=v)
         assert_same(f, p, f_ref, p_ref, off, f"fold drivers, max_skip={max_skip} gap_scale={gap_scale} compact={compact}: {v[0]}")
         assert "loop=asm" in v[0] and f"compact={compact}" in v[0] and f"TAB={int(gap_scale != 1.0)}" in v[0], v
-
-
-def _steep_colinear_task(rng, n, step_lo, step_hi, jitter_lo, jitter_hi):
-    """one colinear chain whose links are `step` apart in x and differ by `jitter` between x and q: every anchor's best predecessor is its neighbour, the gap cost of a
-    link is (int)(jitter * avg) + log2(jitter) / 2"""
-    step = rng.integers(step_lo, step_hi + 1, n)
-    jit = rng.integers(jitter_lo, jitter_hi + 1, n) * rng.choice([-1, 1], n)
-    pos = (1 << 20) + np.cumsum(step)
-    q = 100 + np.cumsum(np.maximum(step + jit, 1))
-    assert pos[-1] < (1 << 31) and q[-1] < (1 << 31)
-    x = (np.uint64(1) << np.uint64(32)) | pos.astype(np.uint64)
-    y = (np.uint64(15) << np.uint64(32)) | q.astype(np.uint64)
-    return np.stack((x, y), 1)
 
 
 @pytest.mark.parametrize("case", ["profiles", "fold-drivers", "tile-paths", "compact-corners", "random-scalars", "ava-ont", "tiny-and-ragged", "steep-scores"])
