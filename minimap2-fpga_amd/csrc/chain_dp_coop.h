@@ -250,6 +250,10 @@ chain_dp_coop(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 	const int n = __builtin_amdgcn_readfirstlane((int)((ends ? ends[task] : mt ? MT.off[task + 1] : offsets[task + 1]) - base0));
 	// the one-word keys of the straight-line pushes (score << 7 | origin) need |score| < 2^23: at most 255 gained per link and a gap cost that cannot overflow
 	// the word either (<= gap_scale * (2.55 * bw + 17) before the shift)
+	// The guards are on the safe side by a factor of two, and each is still exact one step past itself: the word is score * 128 + code with code <= 127, so it
+	// holds every |score| < 2^24.  n = 2^15 anchors of span 255 reach 32768 * 255 = 8 355 840, a q_span_override of 256 reaches 32767 * 256 = 8 388 352, both below
+	// 2^23.  A gap_scale other than 1 comes here only with the gap-cost table (bw <= 511, |gap_scale| < 20: a link costs at most 20 * (2.55 * 511 + 5) = 26 161),
+	// and with gap_scale 1 a link of bw = 2^17 costs 2.55 * 2^17 + 9 = 334 243: far below 2^24 either way.  (tests/test_gpu_scalar_limits.py runs both sides.)
 	const bool key32_ok = n < (1 << 15) && P.span_override <= 255 && P.gap_scale >= 0.f && P.gap_scale <= 4.f && P.bw <= (1 << 17);
 	if (n <= 0) { coop_host_done(H); return; }
 	const uint4 *a = a_all + base0;

@@ -24,6 +24,17 @@ def ava_ont():
     return make_params(max_dist_x=10000, max_dist_y=10000, bw=2000)
 
 
+def splice():
+    """-x splice (options.c:141-144): max_gap=2000 on the query, max_gap_ref=bw=200000 on the reference (map.c:308-310), MM_F_SPLICE -> is_cdna (map.c:275,316)."""
+    return make_params(max_dist_x=200000, max_dist_y=2000, bw=200000, is_cdna=1)
+
+
+def sr(qlen_sum=300, n_segs=2):
+    """-x sr (options.c:123-132): max_gap=100, bw=100, max_frag_len=800.  map.c:306-307: the query gap is max(qlen_sum, max_gap); map.c:311-313: the
+    reference gap is max(max_frag_len - qlen_sum, max_gap).  Default: a pair of 150-base reads chained as two segments."""
+    return make_params(max_dist_x=max(800 - qlen_sum, 100), max_dist_y=max(qlen_sum, 100), bw=100, n_segs=n_segs)
+
+
 def fpga_v2(max_dist_x=5000, max_dist_y=5000, bw=500, q_span=15):
     """What the reference's FPGA kernel computes for one run_chaining_on_hw call (device/minimap2_opencl.cl)."""
     return make_params(max_dist_x, max_dist_y, bw, INT32_MAX, 1024, 1.0, 0, 1, q_span, MM2C_F_IGNORE_SEG)
