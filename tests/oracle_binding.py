@@ -177,3 +177,10 @@ def collect_seed_hits(matches, hits, qlen, flag=0, ref_rank=None, ref_len=None, 
     n = fn(m.size, _ptr(m), _ptr(h), int(qlen), int(flag), _ptr(rr) if rr is not None else None,
                                             _ptr(rl) if rl is not None else None, int(q_lo), int(q_eq), _ptr(a))
     return a[:n]
+
+
+def radix_sort_128x(anchors):
+    """radix_sort_128x (ksort.h:101-151 on mm128_t keyed on x; not stable) of a copy of anchors uint64 [n, 2]"""
+    a = np.array(as_anchor_array(anchors), dtype=np.uint64, order="C", copy=True)
+    load().mm2o_radix_sort_128x(_ptr(a), a.shape[0])
+    return a
