@@ -153,6 +153,14 @@ int mm2c_plan_run_device(mm2c_plan_t *plan, const void *d_anchors, const float *
  * NULL goes back to the plan's own.  The buffers handed to the run / chains entries keep the plan's (capacity) extents. */
 int mm2c_plan_set_device_offsets(mm2c_plan_t *plan, const int64_t *d_offsets);
 
+/* Chaining distances per task: from now on task k is chained with max_dist_x = d_dists[2 k] and max_dist_y = d_dists[2 k + 1] (2 * n_tasks int32 in device
+ * memory, read when a run executes) in the place of par's two scalars.  The values should be >= 0: they cannot be checked on the host, so the kernels take a
+ * negative one as 0 (par's own max_dist_x < 0 is refused) -- the window start (chain.c:192), the filters of chain.c:202-206 and
+ * the places where a long task is cut into pieces all go by the task's own pair.  Such a run takes the general variant of the one-wave kernel
+ * (chain_dp_wave<.., GEN=1, ..>, as mm2c_plan_last_variant says), which computes the same f / p as the simple one for single-segment tasks; the tile and the
+ * cooperative kernels stay per call.  NULL goes back to par's scalars and to the kernels the plan ran before. */
+int mm2c_plan_set_task_dists(mm2c_plan_t *plan, const int32_t *d_dists);
+
 /* The same with the extent of every buffer stated (elements, not bytes): MM2C_E_TOOBIG when one is shorter than the plan needs, the way
  * the reference refuses n > BUFFER_N (chain_hardware.cpp:34-37).  The entries without _n trust the caller. */
 int mm2c_plan_run_device_n(mm2c_plan_t *plan, const void *d_anchors, int64_t n_anchors, const float *d_avg_qspan, int64_t n_avg,
@@ -510,11 +518,25 @@ int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_fr
  * had made it.  max_occ <= mid_occ switches the second pass off.  Chunks of "read_chunk_bases" bases are cut between fragments, never inside one.
  * Every fragment must have exactly par->n_segs segments (mm_chain_dp gets the fragment's own n_segs, chain.c:206; MM2C_E_ARG otherwise): a host with fragments of
  * different segment counts makes one call per count.  par->max_dist_x / max_dist_y are the call's: under -x sr they depend on the fragment's total length
- * (max_dist_y = max(qlen_sum, max_gap), max_dist_x = max(max_frag_len - qlen_sum, max_gap), map.c:306-314), so such a host makes one call per total length --
- * fixed-length pairs are one call.  skip: its per-read arrays are per fragment.  mm2c_tune("heap_sort", 1) applies (-x sr sets MM_F_HEAP_SORT). */
+ * (max_dist_y = max(qlen_sum, max_gap), max_dist_x = max(max_frag_len - qlen_sum, max_gap), map.c:306-314): fixed-length pairs are one call of this entry,
+ * fragments of mixed lengths one call of mm2c_frag_chain_batch_gaps below, which makes the two distances per fragment.  skip: its per-read arrays are per fragment.  mm2c_tune("heap_sort", 1) applies (-x sr sets MM_F_HEAP_SORT). */
 int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, int64_t n_frags,
                           const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
                           mm2c_read_result_t *res);
+/* The same with the chaining distances of map.c:305-314 made PER FRAGMENT, on the device, from the fragment's total length qlen_sum and four scalars of the
+ * mapping options:
+ *     max_dist_y = is_sr ? max(qlen_sum, max_gap) : max_gap
+ *     max_dist_x = max_gap_ref > 0 ? max_gap_ref : max_frag_len > 0 ? max(max_frag_len - qlen_sum, max_gap) : max_gap
+ * par->max_dist_x / max_dist_y are not used for chaining, but par is checked as a whole as in every entry (max_dist_x >= 0); everything else -- par->n_segs (one call per segment count), the results, the re-chain (a re-chained fragment keeps
+ * its pair), the chunks -- is mm2c_frag_chain_batch's.  The DP runs through mm2c_plan_set_task_dists.  Refused before any device work: gaps == NULL,
+ * max_gap < 0, and whatever mm2c_frag_chain_batch refuses. */
+typedef struct { int32_t is_sr, max_gap, max_gap_ref, max_frag_len; } mm2c_frag_gaps_t;
+int mm2c_frag_chain_batch_gaps(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, const mm2c_frag_gaps_t *gaps,
+                               int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
+                               const mm2c_seed_skip_host_t *skip, mm2c_read_result_t *res);
+/* the pairs the last mm2c_frag_chain_batch_gaps call on `res` chained with: dists[2 g] = max_dist_x (the reference's frag_gap, map.c:341), dists[2 g + 1] =
+ * max_dist_y of fragment g, as the device made them; library-owned like the arrays of the result.  NULL / 0 after every other entry. */
+int mm2c_read_result_task_dists(const mm2c_read_result_t *res, const int32_t **dists, int64_t *n_frags);
 /* the fragment entries since mm2c_init or the last reset: calls, fragments processed, fragments re-chained, and the time of the second pass on the call's
  * stream.  rechain_ns is the time ELAPSED between two HIP events, one in front of the decision kernel and one behind the second pass's epilogue: it holds the
  * decision, the compaction, the second lookups -> epilogue AND the gaps in which the stream waits for the host (the counts coming down, the second pass's seed
@@ -559,7 +581,7 @@ typedef struct {
 	uint64_t setup_ns;           /* host: checking the offsets, launch orders, plan objects and their small synchronous uploads */
 	uint64_t h2d_ns;             /* device: uploads (matches, hits or anchors, per-read metadata) */
 	uint64_t seed_ns;            /* device: seed hits -> sorted anchors */
-	uint64_t dp_ns;              /* device: window prepass + chaining DP */
+	uint64_t dp_ns;              /* device: window prepass + chaining DP (the reads-in and fragment entries add their chain plans' own timers here) */
 	uint64_t epi_ns;             /* device: v[], backtrack, chain order */
 	uint64_t d2h_ns;             /* device: downloads of offsets and chains (or f / p) */
 	uint64_t wait_ns;            /* host: blocked on a stream or an event */

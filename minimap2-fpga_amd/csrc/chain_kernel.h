@@ -34,6 +34,7 @@ struct CutArgs {
 	int32_t *d_has_cut = nullptr;   // per task (n_tasks entries), zero on entry: set by the prepass where a window is empty
 	float *d_avg = nullptr;
 	uint8_t *d_cls = nullptr;       // per piece: ring-size class of its task (nullptr: no classes)
+	int32_t *d_dists = nullptr;     // per piece, two words: (max_dist_x, max_dist_y) of its task (plans with per-task distances only, LaunchArgs::d_task_dists)
 };
 
 struct LaunchArgs {
@@ -82,6 +83,9 @@ struct LaunchArgs {
 	int force_tab = 0;          // 1: the gap-cost table of the tile kernel also for gap_scale == 1 (mm2c_tune("force_tab"); slower, kept for the parity tests)
 	int ring_class;             // 3: tile kernel (general variant: first-generation kernel); 4: tile kernel for every variant; 0 / 1 / 2: first-generation kernel with 256 / 512 / 1024 anchors of LDS ring
 	CutArgs cut;                // plans: cut the tasks into independent pieces on the device first
+	const int32_t *d_task_dists = nullptr;   // two words per task or nullptr: the task's own (max_dist_x, max_dist_y) in the place of P's (max_dq: their minimum).  Such a pass takes
+	                                         // the general route -- the TD instantiations of the prepass, of the cut and of chain_dp_wave<256, .., GEN = true, ..> -- whatever
+	                                         // ring_class says; the routing conditions of the other kernels stay per call
 };
 
 // which instantiation launch_chain_dp chose for the tasks' first pass (mm2c_plan_last_variant; the parity tests assert it, so that a vector set

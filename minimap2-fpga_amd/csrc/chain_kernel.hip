@@ -254,7 +254,8 @@ constexpr int PREPASS_SEG = 32768;   // anchors of a long task per block of the 
 // class count, stay the same) per block, blockIdx.y the segment: the first tiles of a segment search in memory until the window start of the tile before lies inside the
 // segment (two tiles, typically), the sums and extremes of a task are added up in `seg_ws` (4 words of 64 bits per task, zero between runs) and the block that arrives
 // last writes avg / class and puts the words back to zero.  The answers are the same by construction: same bounds, same condition, integer sums.
-template <bool SEG>
+// TD: the task's own (max_dist_x, max_dist_y) from task_dists (two words per task) in the place of P's: one scalar load per block.
+template <bool SEG, bool TD = false>
 __global__ void __launch_bounds__(256)
 chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, const int32_t *__restrict__ order,
                    const ulonglong2 *__restrict__ a_all, int32_t *__restrict__ st_all, int32_t *__restrict__ has_cut /* per task, or nullptr */,
@@ -263,11 +264,12 @@ chain_window_start_t(KParams P, int64_t n_tasks, const int64_t *__restrict__ off
                    unsigned q_span_max /* compact x / q ring: the widest span of q values a task may have (0: no task takes it) */,
                    int q24 /* the long ring is the q24 ring: a task with a q value of 2^24 or more stays out of class 1 (and carries bit 2) */,
                    int packed_fp /* the packed f / p ring (chain_dp_tile.h, Lds<> RING 3) is in use: a task it can hold carries bit 3 */,
-                   int seg_anchors, unsigned long long *__restrict__ seg_ws)
+                   int seg_anchors, unsigned long long *__restrict__ seg_ws, const int32_t *__restrict__ task_dists /* TD only */)
 {
 	const int lane = threadIdx.x;
 	const int64_t task = order ? (int64_t)order[blockIdx.x] : (int64_t)blockIdx.x;
 	if (task >= n_tasks) return;
+	if constexpr (TD) { P.max_dist_x = max(task_dists[2 * task], 0); P.max_dist_y = max(task_dists[2 * task + 1], 0); }   // (a negative distance counts as 0)
 	const int64_t base = offsets[task];
 	const int n = (int)(offsets[task + 1] - base);
 	const int s0 = SEG ? (int)min((long long)blockIdx.y * seg_anchors, (long long)INT_MAX) : 0;
@@ -549,9 +551,12 @@ chain_predict(int32_t max_dist_x, int64_t n_tasks, const int64_t *__restrict__ o
 // short pieces = many waves instead of one long dependent chain.  Pieces shorter than seg_min are merged with their successor.  One wave
 // per task: count the pieces, reserve a contiguous range of piece slots, write them in order.  avg_qspan_scaled is a whole-task quantity
 // (chain.c:48-49): computed here (or taken from the caller) and copied to every piece.
+// TD: a piece also inherits its task's (max_dist_x, max_dist_y) (C.d_dists, two words per piece); where the cuts fall already follows the task's own
+// max_dist_x through st[].
+template <bool TD>
 __global__ void __launch_bounds__(64)
 chain_cut(int seg_min, int64_t n_tasks, const int64_t *__restrict__ offsets, const int32_t *__restrict__ order, const uint4 *__restrict__ a_all,
-          const float *__restrict__ avg_in, const int32_t *__restrict__ st_all, CutArgs C, const uint8_t *__restrict__ cls)
+          const float *__restrict__ avg_in, const int32_t *__restrict__ st_all, CutArgs C, const uint8_t *__restrict__ cls, const int32_t *__restrict__ task_dists /* TD only */)
 {
 	const int lane = threadIdx.x;
 	const int64_t task = order ? (int64_t)order[blockIdx.x] : (int64_t)blockIdx.x;
@@ -559,12 +564,15 @@ chain_cut(int seg_min, int64_t n_tasks, const int64_t *__restrict__ offsets, con
 	const int64_t base = offsets[task];
 	const int n = (int)(offsets[task + 1] - base);
 	if (n <= 0) return;
+	int dist_x = 0, dist_y = 0;
+	if constexpr (TD) { dist_x = max(task_dists[2 * task], 0); dist_y = max(task_dists[2 * task + 1], 0); }
 	const int32_t *st = st_all + base;
 	if (n < C.min_anchors || C.d_has_cut[task] == 0) {
 		// a short task, or no empty window inside it (the prepass saw none): one piece; its avg is left to the DP kernel (negative = "not computed")
 		if (lane == 0) {
 			const int k = atomicAdd(C.d_count, 1);
 			C.d_start[k] = base; C.d_end[k] = base + n; C.d_pbase[k] = 0; C.d_avg[k] = avg_in ? avg_in[task] : -1.0f; if (C.d_cls) C.d_cls[k] = cls ? cls[task] : 0;
+			if constexpr (TD) { C.d_dists[2 * k] = dist_x; C.d_dists[2 * k + 1] = dist_y; }
 		}
 		return;
 	}
@@ -591,6 +599,7 @@ chain_cut(int seg_min, int64_t n_tasks, const int64_t *__restrict__ offsets, con
 				if (pass == 1 && lane == 0) {
 					const int k = slot0 + cnt;
 					C.d_start[k] = base + s0; C.d_end[k] = base + c; C.d_pbase[k] = s0; C.d_avg[k] = avg; if (C.d_cls) C.d_cls[k] = cls ? cls[task] : 0;
+					if constexpr (TD) { C.d_dists[2 * k] = dist_x; C.d_dists[2 * k + 1] = dist_y; }
 				}
 				++cnt; s0 = c;
 				m &= m - 1;
@@ -599,6 +608,7 @@ chain_cut(int seg_min, int64_t n_tasks, const int64_t *__restrict__ offsets, con
 		if (pass == 1 && lane == 0) {
 			const int k = slot0 + cnt;
 			C.d_start[k] = base + s0; C.d_end[k] = base + n; C.d_pbase[k] = s0; C.d_avg[k] = avg; if (C.d_cls) C.d_cls[k] = cls ? cls[task] : 0;
+			if constexpr (TD) { C.d_dists[2 * k] = dist_x; C.d_dists[2 * k + 1] = dist_y; }
 		}
 		++cnt;                                                    // the last piece
 		if (pass == 0) {
@@ -609,12 +619,15 @@ chain_cut(int seg_min, int64_t n_tasks, const int64_t *__restrict__ offsets, con
 }
 
 // ---------------------------------------------------------------- the kernel: one wave per task
-template <int R, bool SKIP, bool GEN, bool GS1, bool FAR>
+// TD: every task (or piece) chains with its own (max_dist_x, max_dist_y) from task_dists (two words each) in the place of P's -- one scalar load per workgroup,
+// the scan then reads them from P as before.
+template <int R, bool SKIP, bool GEN, bool GS1, bool FAR, bool TD = false>
 __global__ void __launch_bounds__(64)
 chain_dp_wave(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, const int32_t *__restrict__ order,
               const uint4 *__restrict__ a_all, const float *__restrict__ avg_in, const int32_t *__restrict__ pbase_in,
               const int32_t *__restrict__ st_all, int32_t *__restrict__ f_all, int32_t *__restrict__ p_all, int32_t *__restrict__ t_all,
-              int32_t *__restrict__ status, int only_flagged, const int64_t *__restrict__ ends, const int32_t *__restrict__ n_live)
+              int32_t *__restrict__ status, int only_flagged, const int64_t *__restrict__ ends, const int32_t *__restrict__ n_live,
+              const int32_t *__restrict__ task_dists /* TD only */)
 {
 	static_assert(R >= 128 && (R & (R - 1)) == 0, "ring must be a power of two >= 128");
 	__shared__ uint2 s_xq[R];        // x low word, query position
@@ -630,6 +643,10 @@ chain_dp_wave(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 	const int64_t base = offsets[task];
 	const int n = __builtin_amdgcn_readfirstlane((int)((ends ? ends[task] : offsets[task + 1]) - base));   // wave-uniform: loop bounds stay on the scalar unit
 	if (n <= 0) return;
+	if constexpr (TD) {
+		P.max_dist_x = max(__builtin_amdgcn_readfirstlane(task_dists[2 * task]), 0); P.max_dist_y = max(__builtin_amdgcn_readfirstlane(task_dists[2 * task + 1]), 0);
+		P.max_dq = min(P.max_dist_x, P.max_dist_y);
+	}
 	const uint4 *a = a_all + base;         // {x lo, x hi, y lo (= query pos), y hi (span | flags | seg)}
 	const int32_t *st = st_all + base;
 	int32_t *f = f_all + base, *p = p_all + base, *t = FAR ? t_all + base : nullptr;
@@ -732,20 +749,31 @@ chain_dp_wave(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 }
 
 // ---------------------------------------------------------------- host-side launcher
-template <int R, bool SKIP, bool GEN, bool GS1, bool FAR>
+template <int R, bool SKIP, bool GEN, bool GS1, bool FAR, bool TD = false>
 static hipError_t launch_one(const LaunchArgs &L, hipStream_t st, int only_flagged)
 {
 	if (L.cut.max_pieces > 0) {
-		// pieces cut on the device: starts / ends / p base / avg per piece, st[] relative to the task
-		hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR>), dim3((unsigned)L.cut.max_pieces), dim3(64), 0, st,
+		// pieces cut on the device: starts / ends / p base / avg (TD: and distances) per piece, st[] relative to the task
+		hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR, TD>), dim3((unsigned)L.cut.max_pieces), dim3(64), 0, st,
 		                   L.P, L.cut.max_pieces, L.cut.d_start, (const int32_t *)nullptr, (const uint4 *)L.d_anchors, L.cut.d_avg, L.cut.d_pbase, L.d_st, L.d_f, L.d_p,
-		                   L.d_t, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_count);
+		                   L.d_t, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_count, TD ? (const int32_t *)L.cut.d_dists : (const int32_t *)nullptr);
 		return hipGetLastError();
 	}
-	hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR>), dim3((unsigned)L.n_tasks), dim3(64), 0, st,
+	hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR, TD>), dim3((unsigned)L.n_tasks), dim3(64), 0, st,
 	                   L.P, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, L.d_avg, L.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t,
-	                   L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr);
+	                   L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, TD ? L.d_task_dists : (const int32_t *)nullptr);
 	return hipGetLastError();
+}
+
+// per-task distances (LaunchArgs::d_task_dists): the general variant of the first-generation kernel with 256 anchors of LDS ring
+static hipError_t launch_td(const LaunchArgs &L, hipStream_t st, bool skip, bool gs1, bool far_, int only_flagged)
+{
+	if (skip) {
+		if (gs1) return far_ ? launch_one<256, true, true, true, true, true>(L, st, only_flagged) : launch_one<256, true, true, true, false, true>(L, st, only_flagged);
+		return far_ ? launch_one<256, true, true, false, true, true>(L, st, only_flagged) : launch_one<256, true, true, false, false, true>(L, st, only_flagged);
+	}
+	if (gs1) return far_ ? launch_one<256, false, true, true, true, true>(L, st, only_flagged) : launch_one<256, false, true, true, false, true>(L, st, only_flagged);
+	return far_ ? launch_one<256, false, true, false, true, true>(L, st, only_flagged) : launch_one<256, false, true, false, false, true>(L, st, only_flagged);
 }
 
 // ---- second-generation kernel (chain_dp_tile.h): x / q rings of NX tiles, f / p rings of NF tiles
@@ -962,7 +990,11 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 	// nearest one is never stamped, so the counter stays below max_iter.  Such calls (the V2 scalars of run_chaining_on_hw: max_skip = INT_MAX, max_iter = 1024) used to
 	// take the instantiations without the max-skip machinery, which have no hand-written loop; with max_skip = max_iter - 1 the machinery is compiled in and runs, still
 	// cannot fire, and the hand-written loop serves them (same f / p, V2 scalars: mixed 47.3 -> 44.3 ms per 1.6e8 anchors, dense 85.4 -> 67.5).
-	const bool want_gen = L.P.is_cdna || L.P.n_segs > 1 || (L.P.flags & KF_FORCE_GENERAL);
+	// per-task distances: the general variant of the first-generation kernel, the one route that reads them (every condition below that looks at P's distances -- the
+	// compact rings, the hand-written loop, the cooperative kernel -- is per call and is not asked)
+	const bool td = L.d_task_dists != nullptr && (L.cut.max_pieces == 0 || L.cut.d_dists != nullptr);
+	if (L.d_task_dists && !td) return hipErrorInvalidValue;
+	const bool want_gen = L.P.is_cdna || L.P.n_segs > 1 || (L.P.flags & KF_FORCE_GENERAL) || td;
 	const bool loop_ok = L.P.gap_scale == 1.0f || L_in.force_tab || (L.P.bw <= 511 && L.P.gap_scale > -20.f && L.P.gap_scale < 20.f);   // gap cost computed or from the table
 	if (L.noskip_loop && (int64_t)L.P.max_skip >= (int64_t)L.P.max_iter && L.P.max_iter >= 1 && L.ring_class >= 3 && !want_gen && L.P.bw >= 0 && L.P.max_dq - 1 >= L.P.bw && loop_ok)
 		L.P.max_skip = L.P.max_iter - 1;
@@ -973,7 +1005,7 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 	const bool tile = L.ring_class >= 3;                   // second-generation kernel: 448 anchors before the current tile without global memory
 	// the general variant (segment ids / cDNA) has no hand-written loop in the tile kernel and is faster in the first-generation one (headline
 	// stream with --general: 92.0 vs 108.7 ms, dense 151.8 vs 163.8): ring_class 3 sends it there, ring_class 4 keeps it in the tile kernel
-	const bool tile_gen = L.ring_class >= 4;
+	const bool tile_gen = L.ring_class >= 4 && !td;
 	const bool far_ = (int64_t)P.max_iter > (int64_t)R;   // the ring always holds the R anchors before the current tile
 	const bool far_old = (int64_t)P.max_iter > 256;       // ... of the first-generation kernel when it stands in (R = 256)
 	// the gap-cost table of the tile kernel: dd <= bw <= 511 entries of int16 (cost <= 2.55 * 511 + 4, times gap_scale)
@@ -995,8 +1027,8 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 		info->single_ok = info->fused_st && info->host_out && L.d_avg != nullptr;   // such a pass can do without stage_in (LaunchArgs::h_anchors)
 		const bool t0 = tile && (!want_gen || tile_gen);          // pass 0 runs in the tile kernel
 		info->coop = coop ? coop_width(L) : 0;
-		info->tile = t0; info->nx = t0 ? MM2C_NX : 0; info->nf = t0 ? MM2C_NF : 0; info->r = t0 ? 64 * (MM2C_NX - 1) : (tile ? 256 : R);
-		info->skip = skip; info->gen = want_gen; info->gs1 = gs1; info->far_ = t0 ? far_ : (tile ? far_old : far_); info->tab = t0 && tab && !want_gen;
+		info->tile = t0; info->nx = t0 ? MM2C_NX : 0; info->nf = t0 ? MM2C_NF : 0; info->r = t0 ? 64 * (MM2C_NX - 1) : (tile || td ? 256 : R);
+		info->skip = skip; info->gen = want_gen; info->gs1 = gs1; info->far_ = t0 ? far_ : (tile || td ? far_old : far_); info->tab = t0 && tab && !want_gen;
 		info->asm_loop = t0 && skip && !want_gen && (gs1 || tab) && P.bw >= 0 && P.max_dq - 1 >= P.bw;   // = ASM of chain_dp_tile
 		info->classes = t0 && use_classes(L, skip, want_gen);
 		info->c16 = t0 && compact_q_span(L, info->asm_loop != 0) != 0;
@@ -1028,13 +1060,17 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 		// long tasks (the caller knows the longest and lends the words for the sums): a block per segment of PREPASS_SEG anchors instead of a block per task
 		// (few tasks only: 2 048 blocks fill the GPU as they are -- 2 048 tasks of 100 000 anchors 1.12 ms by task, 1.46 by segment; 255 of 10^6: 4.7 -> 1.6 ms)
 		const bool seg = L.d_seg_ws != nullptr && L.n_tasks <= 512 && L.longest_task >= 2 * PREPASS_SEG && (L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG <= 65535;
-#define MM2C_WS(SEG, GRID, SEGN, WS) hipLaunchKernelGGL(chain_window_start_t<SEG>, GRID, dim3(256), 0, st, P, L.n_tasks, L.d_offsets, L.d_order, \
+#define MM2C_WS(KERN, GRID, SEGN, WS) hipLaunchKernelGGL(KERN, GRID, dim3(256), 0, st, P, L.n_tasks, L.d_offsets, L.d_order, \
 	                   (const ulonglong2 *)L.d_anchors, L.d_st, L.cut.max_pieces > 0 ? L.cut.d_has_cut : (int32_t *)nullptr, avg_out, \
 	                   tile && !coop ? L.d_cls : (uint8_t *)nullptr, L.far_ring, L.far_thr10, tile && !coop ? L.d_cls_stat : (unsigned long long *)nullptr, \
 	                   coop ? 0u : c16_bound,                     /* (the cooperative kernel has one ring form: no classes to find) */ \
-	                   (!coop && tile && q24_ring(L, skip, want_gen, gs1, tab)) ? 1 : 0, (!coop && c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr) ? 1 : 0, SEGN, WS)
-		if (seg) MM2C_WS(true, dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
-		else MM2C_WS(false, dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
+	                   (!coop && tile && q24_ring(L, skip, want_gen, gs1, tab)) ? 1 : 0, (!coop && c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr) ? 1 : 0, SEGN, WS, \
+	                   L.d_task_dists)
+		if (td) {
+			if (seg) MM2C_WS((chain_window_start_t<true, true>), dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
+			else MM2C_WS((chain_window_start_t<false, true>), dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
+		} else if (seg) MM2C_WS(chain_window_start_t<true>, dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
+		else MM2C_WS(chain_window_start_t<false>, dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
 #undef MM2C_WS
 	}
 	hipError_t e = hipGetLastError();
@@ -1046,8 +1082,10 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 		if (n_launches) ++*n_launches;
 	}
 	if (e == hipSuccess && L.cut.max_pieces > 0) {
-		hipLaunchKernelGGL(chain_cut, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order,
-		                   (const uint4 *)L.d_anchors, d_avg, L.d_st, L.cut, tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr);   // (far_ring 0: bit 1, the 32-bit ring, still counts)
+		if (td) hipLaunchKernelGGL(chain_cut<true>, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order,
+		                           (const uint4 *)L.d_anchors, d_avg, L.d_st, L.cut, tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, L.d_task_dists);
+		else hipLaunchKernelGGL(chain_cut<false>, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order,
+		                   (const uint4 *)L.d_anchors, d_avg, L.d_st, L.cut, tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, (const int32_t *)nullptr);   // (far_ring 0: bit 1, the 32-bit ring, still counts)
 		e = hipGetLastError();
 		if (n_launches) ++*n_launches;
 	}
@@ -1068,6 +1106,7 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 		if (coop && !gen) { e = launch_coop(L, d_avg, st, tab, flagged, n_launches); continue; }
 		if (coop_auto && !gen) e = launch_coop(L, d_avg, st, tab, flagged, n_launches);   // (and the one-wave kernels below: each goes by its own count)
 		if (tile && (!gen || tile_gen)) { e = launch_tile(L, d_avg, st, skip, gen, gs1, far_, tab, flagged, n_launches); if (n_launches) ++*n_launches; continue; }
+		if (td) { e = launch_td(L1, st, skip, gs1, far_old, flagged); if (n_launches) ++*n_launches; continue; }
 		if (tile) { e = launch_r<256>(L1, st, skip, gen, gs1, far_old, flagged); if (n_launches) ++*n_launches; continue; }
 		switch (R) {
 		case 256: e = launch_r<256>(L1, st, skip, gen, gs1, far_, flagged); break;

@@ -483,6 +483,7 @@ struct mm2c_plan {
 	mm2c_params_t par;
 	int device = 0;                         // the device the plan's workspace lives on
 	const int64_t *d_off_user = nullptr;    // mm2c_plan_set_device_offsets: task sizes that only the device knows
+	const int32_t *d_dists_user = nullptr;  // mm2c_plan_set_task_dists: (max_dist_x, max_dist_y) per task in the place of par's
 	int64_t n_tasks = 0, total = 0;
 	int64_t *d_off = nullptr; int32_t *d_order = nullptr, *d_status = nullptr, *d_t = nullptr, *d_st = nullptr, *d_w = nullptr; float *d_avg_ws = nullptr; uint8_t *d_cls = nullptr;
 	unsigned long long *d_seg_ws = nullptr; // plans with long tasks: the words in which the segments of a task add up the prepass's sums (chain_window_start_t<true>; zero between runs)
@@ -1074,6 +1075,13 @@ int mm2c_plan_set_device_offsets(mm2c_plan_t *pl, const int64_t *d_offsets)
 	return 0;
 }
 
+int mm2c_plan_set_task_dists(mm2c_plan_t *pl, const int32_t *d_dists)
+{
+	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
+	pl->d_dists_user = d_dists;
+	return 0;
+}
+
 int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_avg_qspan, int32_t *d_f, int32_t *d_p, void *stream)
 {
 	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
@@ -1094,7 +1102,7 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	// Nor does a plan whose gap cost can be a gain (gap_scale < 0): the packed word holds f up to the task's span sum, and f[i] stays below that sum only while no score
 	// adds more than the anchor's span (chain_dp_tile.h, Lds<> RING 3; chain_dp_coop.h guards gap_scale >= 0 for the same reason).
 	const bool packed_ok = G.packed_fp && pl->sizes_desc[0] <= mm2c::PK_MAX_N && pl->par.gap_scale >= 0.f;
-	if (!pl->d_w && packed_ok && G.compact_ring && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535 && L.P.max_dq >= 1 && L.P.max_dq <= 32768)
+	if (!pl->d_w && !pl->d_dists_user && packed_ok && G.compact_ring && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535 && L.P.max_dq >= 1 && L.P.max_dq <= 32768)
 		if (dev_alloc((void **)&pl->d_w, (size_t)std::max<int64_t>(pl->total, 1) * 4) != hipSuccess) { pl->d_w = nullptr; (void)hipGetLastError(); }
 	L.n_tasks = pl->n_tasks; L.d_offsets = pl->d_off_user ? pl->d_off_user : pl->d_off; L.d_order = pl->d_order;
 	L.d_anchors = d_anchors; L.d_avg = d_avg_qspan; L.d_pbase = nullptr; L.d_f = d_f; L.d_p = d_p; L.d_t = pl->d_t; L.d_st = pl->d_st; L.d_w = pl->d_w; L.packed_fp = packed_ok ? 1 : 0; L.d_status = pl->d_status;
@@ -1117,6 +1125,7 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	if (coop_mode == 1 && pl->n_tasks <= G.coop_max_tasks) L.coop_waves = G.coop_waves.load();
 	else if (coop_mode == 2 && !will_cut && !pl->d_off_user && mm2c::coop_pays(pl->n_tasks, longest, pl->total, G.coop_w8_above.load())) L.coop_waves = G.coop_waves.load();
 	else if (coop_mode == 2 && will_cut) L.coop_waves = -1;
+	if (pl->d_dists_user) { L.d_task_dists = pl->d_dists_user; if (L.coop_waves > 1) L.coop_waves = 0; }   // per-task distances: one wave per task or piece (launch_chain_dp)
 	if (L.coop_waves > 1) L.max_task_anchors = longest;
 	if (L.coop_waves <= 1 && G.plan_cut && G.seg_min > 0) {
 		// long reads are chains of loci: cut them at empty windows into independent pieces (one wave each) on the device.  Only tasks of
@@ -1128,19 +1137,20 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 		for (size_t k = 0; k < pl->sizes_desc.size() && pl->sizes_desc[k] >= G.plan_cut_min; ++k) extra += pl->sizes_desc[k] / seg_min;
 		const int64_t max_pieces = pl->n_tasks + extra;
 		if (extra > 0 && max_pieces <= (int64_t)INT32_MAX) {
-			if (!pl->d_cut || pl->cut.max_pieces != max_pieces || pl->cut.seg_min != seg_min) {
+			if (!pl->d_cut || pl->cut.max_pieces != max_pieces || pl->cut.seg_min != seg_min || (pl->d_dists_user && !pl->cut.d_dists)) {
 				dev_free(pl->d_cut); pl->d_cut = nullptr;
 				const size_t mp = (size_t)max_pieces;
 				size_t at = 0;
 				auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 255) & ~(size_t)255; return o; };
 				const size_t o_cnt = take(4), o_stat = take(mp * 4), o_hc = take((size_t)pl->n_tasks * 4), o_start = take(mp * 8), o_end = take(mp * 8),
-				             o_pb = take(mp * 4), o_avg = take(mp * 4), o_cls = take(mp);
+				             o_pb = take(mp * 4), o_avg = take(mp * 4), o_cls = take(mp), o_dd = take(pl->d_dists_user ? mp * 8 : 0);
 				HIP_TRY(dev_alloc((void **)&pl->d_cut, at));
 				char *b = pl->d_cut;
 				pl->cut.max_pieces = max_pieces; pl->cut.seg_min = seg_min;
 				pl->cut.d_count = (int32_t *)(b + o_cnt); pl->cut.d_status = (int32_t *)(b + o_stat); pl->cut.d_has_cut = (int32_t *)(b + o_hc);
 				pl->cut.d_start = (int64_t *)(b + o_start); pl->cut.d_end = (int64_t *)(b + o_end);
 				pl->cut.d_pbase = (int32_t *)(b + o_pb); pl->cut.d_avg = (float *)(b + o_avg); pl->cut.d_cls = (uint8_t *)(b + o_cls);
+				pl->cut.d_dists = pl->d_dists_user ? (int32_t *)(b + o_dd) : nullptr;
 			}
 			pl->cut.min_anchors = G.plan_cut_min;
 			HIP_TRY(hipMemsetAsync(pl->d_cut, 0, 256 + (((size_t)max_pieces * 4 + 255) & ~(size_t)255) + (((size_t)pl->n_tasks * 4 + 255) & ~(size_t)255), st));   // count + status + has_cut

@@ -19,6 +19,7 @@ size_t sketch_push_bytes();
 size_t sketch_lsum_bytes();
 int frag_tag(mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_segs, int64_t n_mini, const uint64_t *seg_tag, const int64_t *frag_off, int64_t n_frags,
              int64_t *frag_mini_off, hipStream_t st);
+int frag_gaps(const int32_t *qlen, int64_t n_frags, const mm2c_frag_gaps_t *gaps, int32_t *dists, hipStream_t st);
 size_t rechain_scan_bytes(int64_t n_frags);
 int rechain_decide(const int64_t *u_off, const uint64_t *u, const int64_t *b_off, const mm2c_anchor_t *b, const int32_t *rep_len, const int64_t *mini_off,
                    int64_t n_frags, int n_segs, uint8_t *flag, int64_t *cnt, int64_t *sel, int64_t *mini_off2, void *scan_tmp, size_t scan_bytes, int64_t h_n[2],
@@ -73,6 +74,7 @@ struct ResPriv {
 	Buf<int32_t> rep_len;
 	Buf<uint64_t> mini_pos, u;
 	Buf<uint8_t> rechained;
+	Buf<int32_t> task_dists;                                   // mm2c_frag_chain_batch_gaps: (max_dist_x, max_dist_y) per fragment (mm2c_read_result_task_dists)
 };
 
 void publish(mm2c_read_result_t *res, int64_t n_reads)
@@ -94,7 +96,7 @@ void clear(mm2c_read_result_t *res)
 {
 	ResPriv &P = *(ResPriv *)res->priv;
 	for (auto *v : { &P.sketch_off, &P.match_off, &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->clear();
-	P.sketch.clear(); P.b.clear(); P.matches.clear(); P.rep_len.clear(); P.mini_pos.clear(); P.u.clear(); P.rechained.clear();
+	P.sketch.clear(); P.b.clear(); P.matches.clear(); P.rep_len.clear(); P.mini_pos.clear(); P.u.clear(); P.rechained.clear(); P.task_dists.clear();
 }
 
 int check_reads(int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
@@ -296,6 +298,10 @@ struct ChainPass {
 	const int64_t *uo = nullptr, *bo = nullptr, *ao = nullptr;
 	char *d = nullptr;
 	ChunkLayout o{};
+	// mm2c_frag_chain_batch_gaps: every fragment of the pass chains with its own (max_dist_x, max_dist_y), made on the device from the qlen the pass uploads
+	// (fr_gaps) -- the second pass's from the gathered qlen, so the pairs follow the compacted fragments.  d_dists: 2 nr words in the pass's arena
+	const mm2c_frag_gaps_t *gaps = nullptr;
+	int32_t *d_dists = nullptr;
 
 	// qlen / skip: of exactly these nr reads (skip's per-read arrays start at the first of them).  on_device: u_off / b_off are wanted on the device even when
 	// the chunk has no anchor at all (the re-chain decision reads them)
@@ -314,7 +320,13 @@ struct ChainPass {
 		if (tot == 0 && !on_device) return 0;                  // no anchors at all: no read has a chain
 		Layout L;
 		o = chunk_layout(L, nr, (size_t)tot, skip_per_read(skip), true);   // (room for the packed anchor_off with or without skip_seed)
+		const size_t o_dd = gaps ? L.take(nr * 8) : 0;
 		HIP_TRY(R.take((void **)&d, L.at));
+		if (gaps) {                                               // (also for a pass without anchors: the caller reads the pairs back)
+			d_dists = (int32_t *)(d + o_dd);
+			HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
+			if (int r = frag_gaps((const int32_t *)(d + o.o_q), (int64_t)nr, gaps, d_dists, st)) return r;
+		}
 		if (tot == 0) {
 			HIP_TRY(hipMemsetAsync(d + o.o_uo, 0, (nr + 1) * 8, st));
 			HIP_TRY(hipMemsetAsync(d + o.o_bo, 0, (nr + 1) * 8, st));
@@ -327,7 +339,8 @@ struct ChainPass {
 		if (!pl) { mm2c_seedplan_destroy(sp); return MM2C_E_HIP; }
 		auto body = [&]() -> int {
 			int r;
-			HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
+			if (gaps) { if ((r = mm2c_plan_set_task_dists(pl, d_dists))) return r; }
+			else HIP_TRY(hipMemcpyAsync(d + o.o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
 			mm2c_seed_skip_t sk;
 			if (skip) HIP_TRY(skip_upload_reads(skip, 0, (int64_t)nr, d_ref, d_ref + n_ref, (int32_t *)(d + o.o_lo), (int32_t *)(d + o.o_eq), st, &sk));
 			Evts seed;                                                // [0], [1]: around the seed hits
@@ -337,6 +350,9 @@ struct ChainPass {
 			HIP_TRY(hipStreamSynchronize(st));
 			if ((r = mm2c_seedplan_check(sp, nullptr))) return r;
 			SS.seed_ns += (uint64_t)(seed.ms(0, 1) * 1e6f);
+			float pre = 0.f, dp = 0.f;                                // the plan's own timers: window prepass (and cut), DP kernels
+			if ((r = mm2c_plan_last_prepass_ms(pl, &pre)) || (r = mm2c_plan_last_kernel_ms(pl, &dp))) return r;
+			SS.dp_ns += (uint64_t)((pre + dp) * 1e6f);
 			return 0;
 		};
 		const int rc = body();
@@ -949,9 +965,10 @@ int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_fr
 	return 0;
 }
 
-int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, int64_t n_frags,
-                          const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
-                          mm2c_read_result_t *res)
+// mm2c_frag_chain_batch (gaps == NULL: par's distances for every fragment) and mm2c_frag_chain_batch_gaps (every fragment its own pair, made on the device)
+static int frag_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, const mm2c_frag_gaps_t *gaps, int64_t n_frags,
+                           const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
+                           mm2c_read_result_t *res)
 {
 	int rc;
 	if ((rc = check_params(par))) return rc;
@@ -968,6 +985,7 @@ int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 	ResPriv &P = *(ResPriv *)res->priv;
 	for (auto *v : { &P.anchor_off, &P.mini_off, &P.u_off, &P.b_off }) v->assign((size_t)n_frags + 1, 0);
 	P.rep_len.assign((size_t)n_frags, 0); P.rechained.assign((size_t)n_frags, 0);
+	if (gaps) P.task_dists.assign(2 * (size_t)n_frags, 0);
 	++FR.calls;
 	if (n_frags == 0) { publish(res, 0); return 0; }
 	const int device = cur_device();
@@ -1003,6 +1021,7 @@ int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 		for (size_t g = 0; g < nf; ++g) qlen[g] = (int32_t)bases(g0 + (int64_t)g, g0 + (int64_t)g + 1);   // qlen_sum
 		const mm2c_seed_skip_host_t sk1 = skip_from(skip, g0);
 		ChainPass C1, C2;
+		C1.gaps = gaps; C2.gaps = gaps;
 		if ((rc = C1.run(R, par, min_cnt, min_sc, d_pool, n_hits, qlen.data(), skip ? &sk1 : nullptr, d_ref, n_ref, nullptr, true))) return rc;
 
 		// the second pass: decided and compacted on the device, looked up with max_occ, chained like the first
@@ -1047,6 +1066,7 @@ int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 
 		// down, in fragment order: a re-chained fragment's second-pass results in the place of its first-pass ones
 		PassHost H1, H2;
+		if (gaps) HIP_TRY(hipMemcpyAsync(P.task_dists.data() + 2 * g0, C1.d_dists, nf * 8, hipMemcpyDeviceToHost, st));   // (the fetch below waits for the stream)
 		if ((rc = H1.fetch(R, C1)) || (n2[0] > 0 && (rc = H2.fetch(R2, C2)))) return rc;
 		size_t j = 0;
 		for (size_t g = 0; g < nf; ++g) {
@@ -1073,6 +1093,31 @@ int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 	G.tasks += (uint64_t)n_frags; G.anchors += (uint64_t)A;
 	publish(res, n_frags);
 	res->n_rechained = n_rechained; res->rechained = P.rechained.data();
+	return 0;
+}
+
+int mm2c_frag_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, int64_t n_frags,
+                          const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, const mm2c_seed_skip_host_t *skip,
+                          mm2c_read_result_t *res)
+{
+	return frag_chain_impl(par, min_cnt, min_sc, idx, mid_occ, max_occ, nullptr, n_frags, frag_off, n_reads, seq_off, seq, skip, res);
+}
+
+int mm2c_frag_chain_batch_gaps(const mm2c_params_t *par, int min_cnt, int min_sc, const mm2c_minidx_t *idx, int mid_occ, int max_occ, const mm2c_frag_gaps_t *gaps,
+                               int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
+                               const mm2c_seed_skip_host_t *skip, mm2c_read_result_t *res)
+{
+	if (!gaps) return fail(MM2C_E_ARG, "gaps is NULL (mm2c_frag_chain_batch takes the distances from par)");
+	if (gaps->max_gap < 0) return fail(MM2C_E_ARG, "max_gap must be >= 0 (got %d)", (int)gaps->max_gap);
+	return frag_chain_impl(par, min_cnt, min_sc, idx, mid_occ, max_occ, gaps, n_frags, frag_off, n_reads, seq_off, seq, skip, res);
+}
+
+int mm2c_read_result_task_dists(const mm2c_read_result_t *res, const int32_t **dists, int64_t *n_frags)
+{
+	if (!res || !res->priv || !dists || !n_frags) return fail(MM2C_E_ARG, "NULL argument");
+	ResPriv &P = *(ResPriv *)res->priv;
+	*dists = P.task_dists.empty() ? nullptr : P.task_dists.data();
+	*n_frags = (int64_t)(P.task_dists.n / 2);
 	return 0;
 }
 

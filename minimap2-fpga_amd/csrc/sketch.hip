@@ -321,6 +321,20 @@ __global__ void fr_mini_off(const int64_t *mini_off, const int64_t *frag_off, in
 	if (g <= n_frags) frag_mini_off[g] = mini_off[frag_off[g]];
 }
 
+// The chaining distances of every fragment (map.c:305-314, in the reference's int arithmetic): dists[2 g] = max_chain_gap_ref (mm_chain_dp's max_dist_x),
+// dists[2 g + 1] = max_chain_gap_qry (max_dist_y), from the fragment's total length and the call's four scalars.
+__global__ void fr_gaps(const int32_t *qlen, int64_t n_frags, mm2c_frag_gaps_t G, int32_t *dists)
+{
+	const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= n_frags) return;
+	const int qlen_sum = qlen[g];
+	const int gap_qry = G.is_sr ? (qlen_sum > G.max_gap ? qlen_sum : G.max_gap) : G.max_gap;
+	int gap_ref = G.max_gap;
+	if (G.max_gap_ref > 0) gap_ref = G.max_gap_ref;
+	else if (G.max_frag_len > 0) { gap_ref = G.max_frag_len - qlen_sum; if (gap_ref < G.max_gap) gap_ref = G.max_gap; }
+	dists[2 * g] = gap_ref; dists[2 * g + 1] = gap_qry;
+}
+
 struct RcArgs {
 	const int64_t *u_off, *b_off; const uint64_t *u; const mm2c_anchor_t *b;   // what the epilogue left: chains per fragment, anchors in chain order
 	const int32_t *rep_len; const int64_t *mini_off;
@@ -503,6 +517,15 @@ int frag_tag(mm2c_anchor_t *mini, const int64_t *mini_off, int64_t n_segs, int64
 		HIP_TRY(hipGetLastError());
 	}
 	fr_mini_off<<<blocks(n_frags + 1), TPB, 0, st>>>(mini_off, frag_off, n_frags, frag_mini_off);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// the fragments' (max_dist_x, max_dist_y) from their total lengths (qlen, n_frags entries, device) -> dists (2 n_frags, device)
+int frag_gaps(const int32_t *qlen, int64_t n_frags, const mm2c_frag_gaps_t *gaps, int32_t *dists, hipStream_t st)
+{
+	if (n_frags <= 0) return 0;
+	fr_gaps<<<blocks(n_frags), TPB, 0, st>>>(qlen, n_frags, *gaps, dists);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

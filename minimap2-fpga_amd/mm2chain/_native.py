@@ -55,6 +55,11 @@ class SketchStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "matches", "h2d_ns", "sketch_ns", "lookup_ns")]
 
 
+class FragGaps(C.Structure):
+    """mm2c_frag_gaps_t: the four scalars the per-fragment chaining distances are made from (map.c:305-314)"""
+    _fields_ = [(k, C.c_int32) for k in ("is_sr", "max_gap", "max_gap_ref", "max_frag_len")]
+
+
 class FragStats(C.Structure):
     """mm2c_frag_stats_t"""
     _fields_ = [(k, C.c_uint64) for k in ("calls", "fragments", "rechained", "rechain_ns")]
@@ -88,6 +93,7 @@ C_SYMBOLS = {
     "mm2c_plan_total_anchors": (C.c_int64, [C.c_void_p]),
     "mm2c_plan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_plan_set_device_offsets": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mm2c_plan_set_task_dists": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mm2c_plan_run_device_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "mm2c_plan_predict_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_plan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -161,6 +167,9 @@ C_SYMBOLS = {
     "mm2c_sketch_match_frag_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
     "mm2c_frag_chain_batch": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_frag_chain_batch_gaps": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(FragGaps), C.c_int64, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadResult)]),
+    "mm2c_read_result_task_dists": (C.c_int, [C.POINTER(ReadResult), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "mm2c_get_frag_stats": (None, [C.POINTER(FragStats)]),
     "mm2c_reset_frag_stats": (None, []),
     "mm2c_get_sketch_stats": (None, [C.POINTER(SketchStats)]),

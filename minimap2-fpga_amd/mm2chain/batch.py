@@ -130,6 +130,14 @@ class ChainPlan:
         self._dev_off = offsets
         N.check(self.lib.mm2c_plan_set_device_offsets(self.handle, offsets.data_ptr() if offsets is not None else None), "mm2c_plan_set_device_offsets")
 
+    def set_task_dists(self, dists: torch.Tensor = None):
+        """chaining distances per task: an int32 device tensor [n_tasks, 2] of (max_dist_x, max_dist_y), every value >= 0, in the place of the
+        params' two scalars; None goes back to them.  The tensor is read when a run executes and must stay alive while the plan uses it."""
+        if dists is not None:
+            assert dists.is_cuda and dists.dtype == torch.int32 and dists.numel() == 2 * self.n_tasks and dists.is_contiguous()
+        self._task_dists = dists
+        N.check(self.lib.mm2c_plan_set_task_dists(self.handle, dists.data_ptr() if dists is not None else None), "mm2c_plan_set_task_dists")
+
     def predict(self, anchors: torch.Tensor, stream=None):
         """chain.c:53-78 on the GPU: returns (num_subparts uint8 [total], total_subparts int64 [n_tasks],
         total_trip_count int64 [n_tasks]) as device tensors"""
@@ -769,22 +777,50 @@ def sketch_match_frag_batch(frags, idx: MinimizerIndex, occ):
             "mini_off": _arr(r.mini_off, nf + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
 
 
-def frag_chain_batch(params: Params, min_cnt, min_sc, frags, idx: MinimizerIndex, mid_occ, max_occ, skip: SeedSkip = None):
+def frag_gaps(is_sr=1, max_gap=100, max_gap_ref=-1, max_frag_len=800):
+    """mm2c_frag_gaps_t; the defaults are the option values of -x sr (options.c)"""
+    return N.FragGaps(int(is_sr), int(max_gap), int(max_gap_ref), int(max_frag_len))
+
+
+def _result_task_dists(R, nf):
+    """mm2c_read_result_task_dists: the (max_dist_x, max_dist_y) the call chained every fragment with, int32 [n_frags, 2] (a copy)"""
+    ptr, n = C.c_void_p(), C.c_int64()
+    N.check(R.lib.mm2c_read_result_task_dists(R.p, C.byref(ptr), C.byref(n)), "mm2c_read_result_task_dists")
+    assert n.value == nf
+    return _arr(ptr.value, 2 * nf, np.int32).reshape(-1, 2)
+
+
+def frag_chain_batch(params: Params, min_cnt, min_sc, frags, idx: MinimizerIndex, mid_occ, max_occ, skip: SeedSkip = None, gaps=None):
     """mm2c_frag_chain_batch: fragments of params.n_segs segments in, chains out, with the max_occ re-chain of map.c:318-340.  Returns the dict of
-    read_chain_batch per fragment, plus rechained (uint8 per fragment) and n_rechained"""
+    read_chain_batch per fragment, plus rechained (uint8 per fragment) and n_rechained.
+    gaps (frag_gaps(...)): mm2c_frag_chain_batch_gaps -- params.max_dist_x / max_dist_y are ignored, every fragment is chained with the pair map.c:305-314
+    gives for its total length; the dict then also holds task_dists, int32 [n_frags, 2] of (max_dist_x, max_dist_y) as the device made them"""
     fo, off, seq = _frags_args(frags)
     nf = fo.size - 1
     sk = skip._native(nf) if skip is not None else None
     R = _Result()
-    N.check(R.lib.mm2c_frag_chain_batch(C.byref(params), int(min_cnt), int(min_sc), idx.handle, int(mid_occ), int(max_occ), nf, _np_ptr(fo), off.size - 1,
-                                        _np_ptr(off), _np_ptr(seq), C.byref(sk) if sk is not None else None, R.p), "mm2c_frag_chain_batch")
+    if gaps is not None:
+        N.check(R.lib.mm2c_frag_chain_batch_gaps(C.byref(params), int(min_cnt), int(min_sc), idx.handle, int(mid_occ), int(max_occ), C.byref(gaps), nf, _np_ptr(fo),
+                                                 off.size - 1, _np_ptr(off), _np_ptr(seq), C.byref(sk) if sk is not None else None, R.p), "mm2c_frag_chain_batch_gaps")
+    else:
+        N.check(R.lib.mm2c_frag_chain_batch(C.byref(params), int(min_cnt), int(min_sc), idx.handle, int(mid_occ), int(max_occ), nf, _np_ptr(fo), off.size - 1,
+                                            _np_ptr(off), _np_ptr(seq), C.byref(sk) if sk is not None else None, R.p), "mm2c_frag_chain_batch")
     r = R.p.contents
     out = {"anchor_off": _arr(r.anchor_off, nf + 1, np.int64), "u_off": _arr(r.u_off, nf + 1, np.int64), "u": _arr(r.u, r.n_u, np.uint64),
            "b_off": _arr(r.b_off, nf + 1, np.int64), "b": _arr(r.b, 2 * r.n_b, np.uint64).reshape(-1, 2), "rep_len": _arr(r.rep_len, nf, np.int32),
            "mini_off": _arr(r.mini_off, nf + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64),
            "rechained": _arr(r.rechained, nf, np.uint8), "n_rechained": int(r.n_rechained)}
+    if gaps is not None:
+        out["task_dists"] = _result_task_dists(R, nf)
     out["chains"] = _split_chains(nf, out["u_off"], out["u"], out["b_off"], out["b"])
     return out
+
+
+def frag_chain_batch_gaps(params: Params, min_cnt, min_sc, frags, idx: MinimizerIndex, mid_occ, max_occ, gaps, skip: SeedSkip = None):
+    """mm2c_frag_chain_batch_gaps: frag_chain_batch with per-fragment chaining distances (gaps: frag_gaps(...), required)"""
+    if gaps is None:
+        raise N.Mm2cError("mm2c_frag_chain_batch_gaps: gaps is None (frag_chain_batch takes the distances from params)")
+    return frag_chain_batch(params, min_cnt, min_sc, frags, idx, mid_occ, max_occ, skip, gaps)
 
 
 def frag_stats(reset=False):
