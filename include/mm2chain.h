@@ -408,7 +408,8 @@ int mm2c_seed_chain_batch_pool_skip(const mm2c_params_t *par, int min_cnt, int m
  * legal; the nucleotide table of sketch.c:9-26 applies.  A read of length 0 has no minimizers.  In the three entries mm2c_sketch_batch, mm2c_sketch_match_batch and
  * mm2c_read_chain_batch every read is ONE segment with rid 0, as collect_minimizers (map.c:64-77) with n_segs = 1; paired and multi-segment reads (n_segs > 1,
  * --frag, -x sr) and the max_occ re-chaining of map.c:318-340 (-x sr sets mid_occ = 1000, max_occ = 5000, options.c:138-139) go through the fragment entries
- * further down.  Results are bit for bit those of the reference, in its order (minimizers, matches, mini_pos).
+ * further down.  Results are bit for bit those of the reference, in its order (minimizers, matches, mini_pos).  A read is a fragment of one segment, for
+ * which the tagging step has nothing to do and is skipped: the sketch and the sketch-and-match entries of the two families are one code path each.
  * Out of scope here -- a host that needs one of these keeps its own sketching for those reads:
  *   - SDUST masking (sdust_thres > 0, map.c:73-74; no preset sets it, options.c:22);
  *   - alignment.

@@ -1,5 +1,7 @@
-// Reads in: the minimizer index resident on the devices, the reads-in entries (mm2c_sketch_batch, mm2c_sketch_match_batch, mm2c_read_chain_batch) and their
-// library-owned result object.  The kernels are in sketch.hip; the seed hits, the DP and the epilogue are the seed / chain plans of the matches-in path.
+// Reads in: the minimizer index resident on the devices, the reads-in entries and their library-owned result object.  The sketch entries and the
+// sketch-and-match entries are one path each (sketch_impl, sketch_match_impl) for reads and for fragments: a read is a fragment of one segment which skips the
+// tagging step (struct Batch).  The chain entries (mm2c_read_chain_batch, frag_chain_impl) are still two.  The kernels are in sketch.hip; the seed hits, the DP
+// and the epilogue are the seed / chain plans of the matches-in path.
 #include "api_internal.h"
 
 using namespace mm2c_api;
@@ -711,68 +713,6 @@ void mm2c_read_result_free(mm2c_read_result_t *res)
 	delete res;
 }
 
-int mm2c_sketch_batch(int k, int w, int is_hpc, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
-{
-	int rc;
-	if (!lib_ready()) return fail_not_ready();
-	if ((rc = check_kw(k, w)) || (rc = check_reads(n_reads, seq_off, seq, res))) return rc;
-	clear(res);
-	ResPriv &P = *(ResPriv *)res->priv;
-	P.sketch_off.assign((size_t)n_reads + 1, 0);
-	if (n_reads > 0) {
-		DeviceScope on(cur_device());
-		HIP_TRY(on.err);
-		OwnStream os;
-		if ((rc = os.make())) return rc;
-		Run R; R.st = os.st;
-		if ((rc = R.sketch(k, w, is_hpc ? 1 : 0, seq_off, seq, 0, n_reads))) return rc;
-		P.sketch.resize((size_t)R.n_mini);
-		HIP_TRY(hipMemcpyAsync(P.sketch_off.data(), R.d_mini_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
-		if (R.n_mini) HIP_TRY(hipMemcpyAsync(P.sketch.data(), R.d_mini, (size_t)R.n_mini * 16, hipMemcpyDeviceToHost, os.st));
-		HIP_TRY(hipStreamSynchronize(os.st));
-		R.time_it(false);
-		++SK.calls; ++SK.chunks;
-	}
-	publish(res, n_reads);
-	return 0;
-}
-
-int mm2c_sketch_match_batch(const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
-{
-	int rc;
-	if (!lib_ready()) return fail_not_ready();
-	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
-	if ((rc = check_reads(n_reads, seq_off, seq, res))) return rc;
-	clear(res);
-	ResPriv &P = *(ResPriv *)res->priv;
-	P.match_off.assign((size_t)n_reads + 1, 0); P.anchor_off.assign((size_t)n_reads + 1, 0); P.mini_off.assign((size_t)n_reads + 1, 0);
-	P.rep_len.assign((size_t)n_reads, 0);
-	if (n_reads > 0) {
-		const int device = cur_device();
-		DeviceScope on(device);
-		HIP_TRY(on.err);
-		OwnStream os;
-		if ((rc = os.make())) return rc;
-		Run R; R.st = os.st;
-		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, 0, n_reads)) || (rc = R.lookup(idx, device, mid_occ))) return rc;
-		P.matches.resize((size_t)R.n_matches); P.mini_pos.resize((size_t)R.n_matches);
-		HIP_TRY(hipMemcpyAsync(P.match_off.data(), R.d_match_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
-		HIP_TRY(hipMemcpyAsync(P.anchor_off.data(), R.d_anchor_off, ((size_t)n_reads + 1) * 8, hipMemcpyDeviceToHost, os.st));
-		HIP_TRY(hipMemcpyAsync(P.rep_len.data(), R.d_rep_len, (size_t)n_reads * 4, hipMemcpyDeviceToHost, os.st));
-		if (R.n_matches) {
-			HIP_TRY(hipMemcpyAsync(P.matches.data(), R.d_matches, (size_t)R.n_matches * sizeof(mm2c_match_t), hipMemcpyDeviceToHost, os.st));
-			HIP_TRY(hipMemcpyAsync(P.mini_pos.data(), R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, os.st));
-		}
-		HIP_TRY(hipStreamSynchronize(os.st));
-		P.mini_off.resize(P.match_off.n);           // one mini_pos per kept match
-		std::copy(P.match_off.p, P.match_off.p + P.match_off.n, P.mini_off.p);
-		R.time_it(true);
-		++SK.calls; ++SK.chunks;
-	}
-	publish(res, n_reads);
-	return 0;
-}
-
 int mm2c_minidx_lookup(const mm2c_minidx_t *idx, int64_t n_q, const uint64_t *keys, int64_t *cr_off, uint32_t *n)
 {
 	if (!lib_ready()) return fail_not_ready();
@@ -894,62 +834,92 @@ int check_frag_call(int64_t n_frags, const int64_t *frag_off, int64_t n_reads, c
 	return check_frags(n_frags, frag_off, n_reads, seq_off);
 }
 
-} // namespace
+// The input of a reads-in call: n_items reads, or fragments of the segments frag_off groups.  A read is a fragment of one segment: with frag_off == NULL the
+// segment of item g is g, and the tagging step (Run::to_frags) would add zero to every y and copy mini_off, so it is skipped.
+struct Batch {
+	int64_t n_items;
+	const int64_t *frag_off;
+	int64_t n_reads;                                           // segments
+	const int64_t *seq_off;
+	const uint8_t *seq;
+	bool as_frags;                                             // a fragment entry's call: frag_off is checked (NULL is legal for an empty batch only), FR counts
+	int64_t seg(int64_t g) const { return frag_off ? frag_off[g] : g; }                                  // items [g0, g1) are the segments [seg(g0), seg(g1))
+	int64_t bases(int64_t g0, int64_t g1) const { return seq_off[seg(g1)] - seq_off[seg(g0)]; }
+};
 
-extern "C" {
+Batch reads_of(int64_t n_reads, const int64_t *seq_off, const uint8_t *seq) { return Batch{ n_reads, nullptr, n_reads, seq_off, seq, false }; }
+Batch frags_of(int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq)
+{
+	return Batch{ n_frags, frag_off, n_reads, seq_off, seq, true };
+}
 
-int mm2c_sketch_frag_batch(int k, int w, int is_hpc, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
-                           mm2c_read_result_t *res)
+// the checks the entries share, before any device work
+int check_batch(const Batch &b, mm2c_read_result_t *res)
+{
+	if (int rc = check_reads(b.n_reads, b.seq_off, b.seq, res)) return rc;
+	return b.as_frags ? check_frags(b.n_items, b.frag_off, b.n_reads, b.seq_off) : 0;
+}
+
+// R sketches the items [g0, g1) and, where they are fragments, joins their segments' lists
+int sketch_items(Run &R, int k, int w, int hpc, const Batch &b, int64_t g0, int64_t g1)
+{
+	if (int rc = R.sketch(k, w, hpc, b.seq_off, b.seq, b.seg(g0), b.seg(g1))) return rc;
+	return b.frag_off ? R.to_frags(b.frag_off, g0, g1) : 0;
+}
+
+// mm2c_sketch_batch and mm2c_sketch_frag_batch
+int sketch_impl(int k, int w, int hpc, const Batch &b, mm2c_read_result_t *res)
 {
 	int rc;
-	if ((rc = check_kw(k, w)) || (rc = check_frag_call(n_frags, frag_off, n_reads, seq_off, seq, res))) return rc;   // before any device work
+	if ((rc = check_kw(k, w)) || (rc = check_batch(b, res))) return rc;
 	if (!lib_ready()) return fail_not_ready();
 	clear(res);
 	ResPriv &P = *(ResPriv *)res->priv;
-	P.sketch_off.assign((size_t)n_frags + 1, 0);
-	if (n_frags > 0) {
+	const int64_t n = b.n_items;
+	P.sketch_off.assign((size_t)n + 1, 0);
+	if (n > 0) {
 		DeviceScope on(cur_device());
 		HIP_TRY(on.err);
 		OwnStream os;
 		if ((rc = os.make())) return rc;
 		Run R; R.st = os.st;
-		if ((rc = R.sketch(k, w, is_hpc ? 1 : 0, seq_off, seq, 0, n_reads)) || (rc = R.to_frags(frag_off, 0, n_frags))) return rc;
+		if ((rc = sketch_items(R, k, w, hpc, b, 0, n))) return rc;
 		P.sketch.resize((size_t)R.n_mini);
-		HIP_TRY(hipMemcpyAsync(P.sketch_off.data(), R.d_mini_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.sketch_off.data(), R.d_mini_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, os.st));
 		if (R.n_mini) HIP_TRY(hipMemcpyAsync(P.sketch.data(), R.d_mini, (size_t)R.n_mini * 16, hipMemcpyDeviceToHost, os.st));
 		HIP_TRY(hipStreamSynchronize(os.st));
 		R.time_it(false);
 		++SK.calls; ++SK.chunks;
-		FR.fragments += (uint64_t)n_frags;
 	}
-	++FR.calls;
-	publish(res, n_frags);
+	if (b.as_frags) { ++FR.calls; FR.fragments += (uint64_t)n; }
+	publish(res, n);
 	return 0;
 }
 
-int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off,
-                                 const uint8_t *seq, mm2c_read_result_t *res)
+// mm2c_sketch_match_batch and mm2c_sketch_match_frag_batch
+int sketch_match_impl(const mm2c_minidx_t *idx, int occ, const Batch &b, mm2c_read_result_t *res)
 {
 	int rc;
 	if (!idx) return fail(MM2C_E_ARG, "minimizer index is NULL");
-	if ((rc = check_frag_call(n_frags, frag_off, n_reads, seq_off, seq, res))) return rc;                             // before any device work
+	if ((rc = check_batch(b, res))) return rc;
 	if (!lib_ready()) return fail_not_ready();
 	clear(res);
 	ResPriv &P = *(ResPriv *)res->priv;
-	P.match_off.assign((size_t)n_frags + 1, 0); P.anchor_off.assign((size_t)n_frags + 1, 0); P.mini_off.assign((size_t)n_frags + 1, 0);
-	P.rep_len.assign((size_t)n_frags, 0);
-	if (n_frags > 0) {
+	const int64_t n = b.n_items;
+	P.match_off.assign((size_t)n + 1, 0); P.anchor_off.assign((size_t)n + 1, 0); P.mini_off.assign((size_t)n + 1, 0);
+	P.rep_len.assign((size_t)n, 0);
+	if (n > 0) {
 		const int device = cur_device();
 		DeviceScope on(device);
 		HIP_TRY(on.err);
 		OwnStream os;
 		if ((rc = os.make())) return rc;
 		Run R; R.st = os.st;
-		if ((rc = R.sketch(idx->k, idx->w, idx->hpc, seq_off, seq, 0, n_reads)) || (rc = R.to_frags(frag_off, 0, n_frags)) || (rc = R.lookup(idx, device, occ))) return rc;
+		if ((rc = sketch_items(R, idx->k, idx->w, idx->hpc, b, 0, n)) || (rc = R.lookup(idx, device, occ))) return rc;
 		P.matches.resize((size_t)R.n_matches); P.mini_pos.resize((size_t)R.n_matches);
-		HIP_TRY(hipMemcpyAsync(P.match_off.data(), R.d_match_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
-		HIP_TRY(hipMemcpyAsync(P.anchor_off.data(), R.d_anchor_off, ((size_t)n_frags + 1) * 8, hipMemcpyDeviceToHost, os.st));
-		HIP_TRY(hipMemcpyAsync(P.rep_len.data(), R.d_rep_len, (size_t)n_frags * 4, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.match_off.data(), R.d_match_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.anchor_off.data(), R.d_anchor_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, os.st));
+		HIP_TRY(hipMemcpyAsync(P.rep_len.data(), R.d_rep_len, (size_t)n * 4, hipMemcpyDeviceToHost, os.st));
 		if (R.n_matches) {
 			HIP_TRY(hipMemcpyAsync(P.matches.data(), R.d_matches, (size_t)R.n_matches * sizeof(mm2c_match_t), hipMemcpyDeviceToHost, os.st));
 			HIP_TRY(hipMemcpyAsync(P.mini_pos.data(), R.d_mini_pos, (size_t)R.n_matches * 8, hipMemcpyDeviceToHost, os.st));
@@ -958,11 +928,39 @@ int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_fr
 		std::copy(P.match_off.p, P.match_off.p + P.match_off.n, P.mini_off.p);   // one mini_pos per kept match
 		R.time_it(true);
 		++SK.calls; ++SK.chunks;
-		FR.fragments += (uint64_t)n_frags;
 	}
-	++FR.calls;
-	publish(res, n_frags);
+	if (b.as_frags) { ++FR.calls; FR.fragments += (uint64_t)n; }
+	publish(res, n);
 	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// The read entries answer "not initialised" before any argument check; the fragment entries check every argument first.
+int mm2c_sketch_batch(int k, int w, int is_hpc, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	if (!lib_ready()) return fail_not_ready();
+	return sketch_impl(k, w, is_hpc ? 1 : 0, reads_of(n_reads, seq_off, seq), res);
+}
+
+int mm2c_sketch_frag_batch(int k, int w, int is_hpc, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq,
+                           mm2c_read_result_t *res)
+{
+	return sketch_impl(k, w, is_hpc ? 1 : 0, frags_of(n_frags, frag_off, n_reads, seq_off, seq), res);
+}
+
+int mm2c_sketch_match_batch(const mm2c_minidx_t *idx, int mid_occ, int64_t n_reads, const int64_t *seq_off, const uint8_t *seq, mm2c_read_result_t *res)
+{
+	if (!lib_ready()) return fail_not_ready();
+	return sketch_match_impl(idx, mid_occ, reads_of(n_reads, seq_off, seq), res);
+}
+
+int mm2c_sketch_match_frag_batch(const mm2c_minidx_t *idx, int occ, int64_t n_frags, const int64_t *frag_off, int64_t n_reads, const int64_t *seq_off,
+                                 const uint8_t *seq, mm2c_read_result_t *res)
+{
+	return sketch_match_impl(idx, occ, frags_of(n_frags, frag_off, n_reads, seq_off, seq), res);
 }
 
 // mm2c_frag_chain_batch (gaps == NULL: par's distances for every fragment) and mm2c_frag_chain_batch_gaps (every fragment its own pair, made on the device)

@@ -696,14 +696,23 @@ class MinimizerIndex:
             pass
 
 
+# what the reads-in entries return, from their result r = mm2c_read_result_t over n reads or fragments (a read is a fragment of one segment)
+def _sketch_out(r, n):
+    return _arr(r.sketch_off, n + 1, np.int64), _arr(r.sketch, 2 * r.n_sketch, np.uint64).reshape(-1, 2)
+
+
+def _match_dict(r, n):
+    return {"match_off": _arr(r.match_off, n + 1, np.int64), "matches": _arr(r.matches, r.n_matches, MATCH_DTYPE),
+            "anchor_off": _arr(r.anchor_off, n + 1, np.int64), "rep_len": _arr(r.rep_len, n, np.int32),
+            "mini_off": _arr(r.mini_off, n + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+
+
 def sketch_batch(seqs, k, w, is_hpc=False):
     """mm2c_sketch_batch: mm_sketch per read.  seqs: list of reads (bytes / str) or (seq_off, seq).  Returns (off int64 [n+1], minimizers uint64 [m, 2] = x, y)"""
     off, seq = _reads_args(seqs)
     R = _Result()
     N.check(R.lib.mm2c_sketch_batch(int(k), int(w), int(bool(is_hpc)), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p), "mm2c_sketch_batch")
-    r = R.p.contents
-    so = _arr(r.sketch_off, off.size, np.int64)
-    return so, _arr(r.sketch, 2 * r.n_sketch, np.uint64).reshape(-1, 2)
+    return _sketch_out(R.p.contents, off.size - 1)
 
 
 def sketch_match_batch(seqs, idx: MinimizerIndex, mid_occ):
@@ -711,10 +720,7 @@ def sketch_match_batch(seqs, idx: MinimizerIndex, mid_occ):
     off, seq = _reads_args(seqs)
     R = _Result()
     N.check(R.lib.mm2c_sketch_match_batch(idx.handle, int(mid_occ), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p), "mm2c_sketch_match_batch")
-    r, nr = R.p.contents, off.size - 1
-    return {"match_off": _arr(r.match_off, nr + 1, np.int64), "matches": _arr(r.matches, r.n_matches, MATCH_DTYPE),
-            "anchor_off": _arr(r.anchor_off, nr + 1, np.int64), "rep_len": _arr(r.rep_len, nr, np.int32),
-            "mini_off": _arr(r.mini_off, nr + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+    return _match_dict(R.p.contents, off.size - 1)
 
 
 def read_chain_batch(params: Params, min_cnt, min_sc, seqs, idx: MinimizerIndex, mid_occ, skip: SeedSkip = None):
@@ -761,8 +767,7 @@ def sketch_frag_batch(frags, k, w, is_hpc=False):
     R = _Result()
     N.check(R.lib.mm2c_sketch_frag_batch(int(k), int(w), int(bool(is_hpc)), fo.size - 1, _np_ptr(fo), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p),
             "mm2c_sketch_frag_batch")
-    r = R.p.contents
-    return _arr(r.sketch_off, fo.size, np.int64), _arr(r.sketch, 2 * r.n_sketch, np.uint64).reshape(-1, 2)
+    return _sketch_out(R.p.contents, fo.size - 1)
 
 
 def sketch_match_frag_batch(frags, idx: MinimizerIndex, occ):
@@ -771,10 +776,7 @@ def sketch_match_frag_batch(frags, idx: MinimizerIndex, occ):
     R = _Result()
     N.check(R.lib.mm2c_sketch_match_frag_batch(idx.handle, int(occ), fo.size - 1, _np_ptr(fo), off.size - 1, _np_ptr(off), _np_ptr(seq), R.p),
             "mm2c_sketch_match_frag_batch")
-    r, nf = R.p.contents, fo.size - 1
-    return {"match_off": _arr(r.match_off, nf + 1, np.int64), "matches": _arr(r.matches, r.n_matches, MATCH_DTYPE),
-            "anchor_off": _arr(r.anchor_off, nf + 1, np.int64), "rep_len": _arr(r.rep_len, nf, np.int32),
-            "mini_off": _arr(r.mini_off, nf + 1, np.int64), "mini_pos": _arr(r.mini_pos, r.n_mini_pos, np.uint64)}
+    return _match_dict(R.p.contents, fo.size - 1)
 
 
 def frag_gaps(is_sr=1, max_gap=100, max_gap_ref=-1, max_frag_len=800):

@@ -6,6 +6,7 @@ import subprocess
 
 import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,3 +64,44 @@ def test_fragment_refusals_come_before_any_device_work():
     late = np.array([0, 2**30, 2**30 + 5], np.int64)                                                 # fits 31 bits, but `sum << 1` overflows the reference's int
     assert call([0, 2], late, seq=np.zeros(1, np.uint8)) == -3 and b"2^30" in lib.mm2c_last_error()
     lib.mm2c_read_result_free(res)
+
+
+def _entries_with_seq_off_not_monotone():
+    """every reads-in entry handed seq_off = [0, 5, 3]: (name, code, message) per entry.  The index is never read before the offsets are refused; a zeroed
+    block stands in for it"""
+    from mm2chain import _native as N
+    from mm2chain import params
+    lib = N.load()
+    res = lib.mm2c_read_result_create()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    so, fo, seq = np.array([0, 5, 3], np.int64), np.array([0, 1, 2], np.int64), np.zeros(8, np.uint8)
+    par, idx = params.map_ont(), C.cast(C.create_string_buffer(256), C.c_void_p)
+    gaps = N.FragGaps(1, 100, -1, 800)
+    calls = {
+        "mm2c_sketch_batch": lambda: lib.mm2c_sketch_batch(15, 10, 0, 2, ptr(so), ptr(seq), res),
+        "mm2c_sketch_match_batch": lambda: lib.mm2c_sketch_match_batch(idx, 50, 2, ptr(so), ptr(seq), res),
+        "mm2c_read_chain_batch": lambda: lib.mm2c_read_chain_batch(C.byref(par), 3, 40, idx, 50, 2, ptr(so), ptr(seq), None, res),
+        "mm2c_sketch_frag_batch": lambda: lib.mm2c_sketch_frag_batch(15, 10, 0, 2, ptr(fo), 2, ptr(so), ptr(seq), res),
+        "mm2c_sketch_match_frag_batch": lambda: lib.mm2c_sketch_match_frag_batch(idx, 50, 2, ptr(fo), 2, ptr(so), ptr(seq), res),
+        "mm2c_frag_chain_batch": lambda: lib.mm2c_frag_chain_batch(C.byref(par), 3, 40, idx, 50, 50, 2, ptr(fo), 2, ptr(so), ptr(seq), None, res),
+        "mm2c_frag_chain_batch_gaps": lambda: lib.mm2c_frag_chain_batch_gaps(C.byref(par), 3, 40, idx, 50, 50, C.byref(gaps), 2, ptr(fo), 2, ptr(so), ptr(seq), None, res),
+    }
+    out = [(name, f(), lib.mm2c_last_error() or b"") for name, f in calls.items()]
+    lib.mm2c_read_result_free(res)
+    return out
+
+
+def test_fragment_entries_refuse_malformed_seq_off_before_asking_for_a_device():
+    """the fragment entries check every argument first: MM2C_E_ARG for seq_off that is not monotone, with or without a device"""
+    for name, code, msg in _entries_with_seq_off_not_monotone():
+        if "frag" in name:
+            assert code == -2 and b"not monotone at read 1" in msg, (name, code, msg)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks the order of refusals where the library cannot be initialised")
+def test_read_entries_answer_not_initialised_before_any_argument_check():
+    """the three read entries share the fragment entries' code path but keep their own order of refusals: without mm2c_init they answer MM2C_E_NODEVICE,
+    malformed seq_off or not"""
+    for name, code, msg in _entries_with_seq_off_not_monotone():
+        if "frag" not in name:
+            assert code == -1 and b"not monotone" not in msg, (name, code, msg)

@@ -143,6 +143,32 @@ def test_single_segment_fragments_equal_read_chain_batch(fx):
     idx.close()
 
 
+def _one_segment(fx):
+    """every segment of the fixture, the zero-length ones included, as reads and as fragments of one segment each"""
+    reads = (fx["seq_off"], fx["seq"])
+    nr = fx["seq_off"].size - 1
+    assert (np.diff(fx["seq_off"]) == 0).any()
+    return nr, reads, (np.arange(nr + 1),) + reads
+
+
+@pytest.mark.parametrize("hpc", [0, 1])
+def test_single_segment_fragments_equal_the_sketch_and_match_entries(fx, hpc):
+    """a read is a fragment of one segment: the fragment entries give what the read entries give, array for array"""
+    import mm2chain
+    nr, reads, frags = _one_segment(fx)
+    a = mm2chain.sketch_batch(reads, int(fx["k"]), int(fx["w"]), bool(hpc))
+    b = mm2chain.sketch_frag_batch(frags, int(fx["k"]), int(fx["w"]), bool(hpc))
+    assert a[0].size == nr + 1 and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[1].shape[0] > 0
+    idx = _index(fx, "hpc_" if hpc else "")
+    a = mm2chain.sketch_match_batch(reads, idx, int(fx["mid_occ"]))
+    b = mm2chain.sketch_match_frag_batch(frags, idx, int(fx["mid_occ"]))
+    assert set(a) == set(b) == {"match_off", "matches", "anchor_off", "rep_len", "mini_off", "mini_pos"}
+    for key in a:
+        assert a[key].dtype == b[key].dtype and np.array_equal(a[key], b[key]), key
+    assert (np.diff(a["match_off"]) > 0).any() and a["match_off"].size == nr + 1
+    idx.close()
+
+
 def test_chunks_are_cut_between_fragments(fx):
     import mm2chain
     mm2chain.tune("heap_sort", 1)
