@@ -83,6 +83,14 @@ struct Global {
 	uint64_t epoch = 0;                     // bumped by shutdown so stale thread-local pointers are dropped
 };
 extern Global G;
+// the tuning knobs a DP launch goes by (mm2c::launch_chain_dp).  cls_arrays: the launch has class arrays of its own (LaunchArgs::d_cls, d_cls_stat) -- the knobs of the
+// ring-size classes and of the wide share go with them
+inline void knobs_into(mm2c::LaunchArgs &L, bool cls_arrays = true)
+{
+	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop;
+	L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
+	if (cls_arrays) { L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct; }
+}
 extern std::atomic<int64_t> read_chunk_bases;   // mm2c_read_chain_batch: bases per chunk of whole reads (mm2c_tune("read_chunk_bases"); mm2chain_sketch.cpp)
 extern std::atomic<int64_t> index_chunk_bases;  // mm2c_minidx_build: bases per chunk of whole sequences (mm2c_tune("index_chunk_bases"); mm2chain_sketch.cpp)
 // mm2c_init_async: the initialisation runs on a thread of its own while the host does something else (a minimap2 host loads its index, main.c:371-399, before the

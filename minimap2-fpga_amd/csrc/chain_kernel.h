@@ -118,7 +118,9 @@ __host__ __device__ inline bool coop_pays(long long n_pieces, long long longest,
 	if (n_pieces <= 0 || n_pieces > COOP_ROUTE_MAX_PIECES) return false;
 	return 1450ll * longest > total || (n_pieces > w8_above && longest >= 8192 && 2300ll * longest > total);
 }
-
+// the scalars the compact x / q ring of the tile kernel takes (chain_dp_tile.h, Lds<>): differences of the low halves of x are exact below 2^16, and a task's q values
+// may then span 65535 - max_dq.  The launcher's route and the plans' allocation of the packed words (LaunchArgs::d_w) both go by this.
+inline bool compact_scalars_ok(const KParams &P) { return P.max_dist_x >= 0 && P.max_dist_x <= 65535 && P.max_dq >= 1 && P.max_dq <= 32768; }
 
 int chain_ring_anchors(int ring_class);
 // label counters of the hand-written loop (builds with -DMM2C_LABEL_COUNT only; hipErrorNotSupported otherwise): 8 rows (compact << 2 | table << 1 | far) x 32 labels

@@ -48,6 +48,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "chain_kernel.h"
 #include "chain_wave.h"
 #ifndef MM2C_NX
@@ -749,72 +750,171 @@ chain_dp_wave(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 }
 
 // ---------------------------------------------------------------- host-side launcher
-template <int R, bool SKIP, bool GEN, bool GS1, bool FAR, bool TD = false>
+// Which kernels a call takes is decided once, by decide_route, before anything is launched; the launches below and LaunchInfo (the text the tests assert) both read the
+// Route and nothing else, so what is reported is what runs.  tests/test_cpu_route.py pins the decision over a table of calls (dry runs: no device needed).
+enum { PRE_NONE, PRE_WIDE, PRE_SEG, PRE_TASK };
+struct Route {
+	KParams P;              // the call's scalars, max_skip mapped (below)
+	bool td;                // per-task distances: the TD instantiations of the prepass, of the cut and of the first-generation kernel
+	bool gen, skip, gs1, tab;   // pass 0: the general variant (segment ids / cDNA); the max-skip machinery; gap cost computed with gap_scale 1 / from the table of the tile kernel (!gen only)
+	bool tile, tile_gen, tile0;   // ring_class >= 3: the second-generation kernel ... for the general variant as well (ring_class 4); pass 0 runs in it
+	bool asm_loop;          // ... through the hand-written loop (= ASM of chain_dp_tile); the one condition of the cooperative kernel, the compact rings and the max_skip mapping
+	int wave_r;             // LDS ring of the first-generation kernel where it runs (256 when it stands in for the tile kernel or takes per-task distances)
+	bool far_tile, far_wave, far_coop;   // FAR of each kernel: max_iter reaches beyond its ring
+	bool coop, coop_auto;   // several waves per task: asked for by the caller (no cut) / left to the device after the cut (chain_route, both kernels are launched)
+	bool auto_w8;           // ... where the eight-wave kernel is launched beside the sixteen-wave one
+	int width;              // coop: waves per task (16 or 8), else 0
+	bool makes_st, host_out, single_ok;   // the sixteen-wave kernel makes the window starts itself (no prepass launch) / writes the caller's buffer and raises the flag / could run as one launch
+	bool classes, q24, packed;   // tile kernel: class-1 tasks take the long ring / in its q24 form; the packed f / p ring beside the compact one
+	unsigned c16_bound;     // the compact x / q ring: the span of q values a task may have (the prepass compares), 0: not used
+	int prepass;            // PRE_*: nothing, a block per 256 anchors, per segment, per task
+	bool settle, cut;       // chain_cls_settle, chain_cut<td> run (chain_route: coop_auto)
+	bool second_pass;       // tasks that turn out to carry more than one segment id are redone with the general variant
+};
+
+int chain_ring_anchors(int ring_class) { return ring_class == 0 ? 256 : ring_class == 1 ? 512 : ring_class == 2 ? 1024 : 64 * (MM2C_NX - 1); }   // 3, 4: the tile kernel
+
+// the hand-written loop of the tile kernel and of the cooperative kernel serves the simple variant with the max-skip machinery, a gap cost it can compute
+// (gap_scale 1) or look up (`cost_ok`), and a band that the distance filter does not cut short
+static bool hand_loop(const KParams &P, bool gen, bool skip, bool cost_ok) { return skip && !gen && cost_ok && P.bw >= 0 && P.max_dq - 1 >= P.bw; }
+
+static Route decide_route(const LaunchArgs &L)
+{
+	Route r;
+	r.P = L.P;
+	KParams &P = r.P;
+	r.cut = L.cut.max_pieces > 0;
+	// per-task distances: the general variant of the first-generation kernel, the one route that reads them (every condition below that looks at P's distances -- the
+	// compact rings, the hand-written loop, the cooperative kernel -- is per call and is not asked)
+	r.td = L.d_task_dists != nullptr;
+	r.gen = P.is_cdna || P.n_segs > 1 || (P.flags & KF_FORCE_GENERAL) || r.td;
+	r.gs1 = P.gap_scale == 1.0f;
+	r.tile = L.ring_class >= 3;                            // second-generation kernel: 448 anchors before the current tile without global memory
+	// the general variant (segment ids / cDNA) has no hand-written loop in the tile kernel and is faster in the first-generation one (headline
+	// stream with --general: 92.0 vs 108.7 ms, dense 151.8 vs 163.8): ring_class 3 sends it there, ring_class 4 keeps it in the tile kernel
+	r.tile_gen = L.ring_class >= 4 && !r.td;
+	r.tile0 = r.tile && (!r.gen || r.tile_gen);
+	// the gap-cost table of the tile kernel: dd <= bw <= 511 entries of int16 (cost <= 2.55 * 511 + 4, times gap_scale)
+	// used when gap_scale != 1 (it takes the f64 path of chain.c:219 out of the loop); with gap_scale 1 computing the cost is as fast and the
+	// kernel's LDS stays at 6 KB (measured: 62.8 vs 66.3 ms on the headline batch)
+	static const bool force_tab_env = getenv("MM2C_FORCE_TAB") != nullptr;   // experiment switch: the table also for gap_scale == 1
+	const bool tab_fits = P.bw <= 511 && P.gap_scale > -20.f && P.gap_scale < 20.f;
+	r.tab = r.tile && (!r.gs1 || force_tab_env || L.force_tab != 0) && P.bw >= 0 && tab_fits;
+	// The early exit of chain.c:231 can never fire when the skip counter cannot exceed max_skip inside one window: a window holds at most max_iter candidates and the
+	// nearest one is never stamped, so the counter stays below max_iter.  Such calls (the V2 scalars of run_chaining_on_hw: max_skip = INT_MAX, max_iter = 1024) used to
+	// take the instantiations without the max-skip machinery, which have no hand-written loop; with max_skip = max_iter - 1 the machinery is compiled in and runs, still
+	// cannot fire, and the hand-written loop serves them (same f / p, V2 scalars: mixed 47.3 -> 44.3 ms per 1.6e8 anchors, dense 85.4 -> 67.5).
+	// (force_tab counts as a cost the loop can take even where the table does not fit: such a call then runs the C++ loop with the machinery compiled in)
+	if (L.noskip_loop && (int64_t)P.max_skip >= (int64_t)P.max_iter && P.max_iter >= 1 && r.tile && hand_loop(P, r.gen, true, r.gs1 || L.force_tab || tab_fits))
+		P.max_skip = P.max_iter - 1;
+	r.skip = (int64_t)P.max_skip < (int64_t)P.max_iter;
+	r.asm_loop = r.tile && hand_loop(P, r.gen, r.skip, r.gs1 || r.tab);
+	r.wave_r = r.tile || r.td ? 256 : chain_ring_anchors(L.ring_class);
+	r.far_tile = (int64_t)P.max_iter > 64 * (MM2C_NX - 1);     // the ring always holds the R anchors before the current tile
+	r.far_wave = (int64_t)P.max_iter > (int64_t)r.wave_r;
+	r.far_coop = (int64_t)P.max_iter > 64 * (COOP_NX - 1);
+	// several waves per task: asked for by the caller for a pass of few tasks; the variants with the hand-written loop, tasks not cut on the device
+	r.coop = L.coop_waves > 1 && r.asm_loop && !r.cut;
+	// ... or left to the device: with a cut, how many pieces there are and how long is only known there (chain_route, after chain_cut)
+	r.coop_auto = L.coop_waves < 0 && r.asm_loop && r.cut && L.cut.d_count != nullptr;
+	r.auto_w8 = r.coop_auto && L.cut.max_pieces > (int64_t)L.coop_w8_above;
+	r.width = !r.coop ? 0 : L.n_tasks > (int64_t)L.coop_w8_above ? 8 : 16;   // (pieces = tasks: no cut on the device)
+	const bool have_avg = L.d_avg != nullptr || L.d_avg_ws != nullptr;
+	// a pass of few SHORT tasks whose window starts nobody has made: the sixteen-wave kernel makes them itself (chain_dp_coop.h, st_out) -- no prepass launch
+	r.makes_st = r.width == 16 && L.fuse_st && !L.st_ready && L.max_task_anchors > 0 && L.max_task_anchors <= COOP_ST_MAX && have_avg;
+	r.host_out = r.coop && L.h_flag && L.h_f && L.h_p && L.d_done && (P.flags & KF_IGNORE_SEG);
+	r.single_ok = r.makes_st && r.host_out && L.d_avg != nullptr;
+	// The rings of the tile kernel (the cooperative kernel has one ring form: no classes to find).  The class array of the prepass must reach the kernels: plans
+	// have it; the piece arrays of a device-side cut must carry it too.
+	const bool have_cls = L.d_cls != nullptr && (!r.cut || L.cut.d_cls != nullptr);
+	// ring-size classes: class-1 tasks run the instantiation with the long ring
+	r.classes = !r.coop && r.tile && !r.gen && r.skip && L.far_ring != 0 && have_cls;
+	// the q24 ring (chain_dp_tile.h, Lds<> RING 2) is the form of the LONG ring (ring-size class 1): dr from the low halves of x needs max_dist_x < 2^16, q is exact for
+	// tasks whose q values are below 2^24 -- the prepass keeps every other task out of class 1 (bit 2 of the class byte)
+	r.q24 = r.classes && L.q24 != 0 && (r.gs1 || r.tab) && P.max_dist_x >= 0 && P.max_dist_x <= 65535;
+	// the compact x / q ring (chain_dp_tile.h, Lds<>): differences of the low halves are exact when max_dist_x < 2^16 and, per task, the q values span
+	// at most 65535 - max_dq
+	r.c16_bound = !r.coop && r.asm_loop && L.compact && have_cls && compact_scalars_ok(P) ? 65535u - (unsigned)P.max_dq : 0u;
+	// the packed f / p ring (chain_dp_tile.h, Lds<> RING 3): for the tasks of the compact x / q ring whose p and f fit its word (bit 3 of the class, set by the prepass
+	// when this says so); needs the side array of one word per anchor, which plans have
+	r.packed = r.c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr;
+	// The prepass.  Nothing to launch: st[] came with the pass (mm2chain_host.cpp) and avg was handed in, or the cooperative kernel makes both itself (short tasks).
+	// A pass of few tasks that wants nothing but st[] (the cooperative kernel: no classes; no cut on the device): one block per tile (avg not handed in: the blocks
+	// add up the spans into the avg workspace and a small kernel finishes them -- a plan of few long tasks: 256 reads of 10^6 anchors 3.9 -> about 1 ms, one block per
+	// task walks its tiles one after the other).  Long tasks (the caller knows the longest and lends the words for the sums): a block per segment of PREPASS_SEG anchors
+	// instead of a block per task (few tasks only: 2 048 blocks fill the GPU as they are -- 2 048 tasks of 100 000 anchors 1.12 ms by task, 1.46 by segment; 255 of
+	// 10^6: 4.7 -> 1.6 ms)
+	if (r.coop && ((L.st_ready && L.d_avg != nullptr) || r.makes_st)) r.prepass = PRE_NONE;
+	else if (r.coop && L.max_task_anchors > 0 && L.max_task_anchors <= (1 << 22) && have_avg && (L.max_task_anchors + 255) / 256 <= 65535) r.prepass = PRE_WIDE;
+	else if (L.d_seg_ws != nullptr && L.n_tasks <= 512 && L.longest_task >= 2 * PREPASS_SEG && (L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG <= 65535) r.prepass = PRE_SEG;
+	else r.prepass = PRE_TASK;
+	r.settle = r.tile && !r.coop && L.d_cls && L.d_cls_stat && (L.far_ring == 1 || r.c16_bound != 0);
+	r.second_pass = !r.gen && !(P.flags & KF_IGNORE_SEG);
+	return r;
+}
+
+static void fill_info(const Route &r, LaunchInfo *I)
+{
+	I->tile = r.tile0;
+	I->nx = r.coop ? COOP_NX : r.tile0 ? MM2C_NX : 0; I->nf = r.coop ? COOP_NF : r.tile0 ? MM2C_NF : 0;
+	I->r = r.coop ? 64 * (COOP_NX - 1) : r.tile0 ? 64 * (MM2C_NX - 1) : r.wave_r;
+	I->skip = r.skip; I->gen = r.gen; I->gs1 = r.gs1; I->far_ = r.coop ? r.far_coop : r.tile0 ? r.far_tile : r.far_wave; I->tab = r.tile0 && r.tab && !r.gen;
+	I->asm_loop = r.asm_loop; I->classes = r.classes; I->c16 = r.c16_bound != 0; I->q24 = r.q24; I->packed = r.packed;
+	I->cut = r.cut; I->coop = r.width; I->host_out = r.host_out; I->single_ok = r.single_ok; I->fused_st = r.makes_st; I->route_auto = r.coop_auto;
+}
+
+// Run-time flags to template arguments: fn(std::bool_constant<flag>{} ...).  fn is instantiated for every combination of values, so it keeps the ones that are never
+// asked for from reaching a kernel with `if constexpr`.  The compiler emits the kernels in the order of the combinations (true first, the first flag slowest) and of
+// the launchers in this file: keep both when only the host side changes, and the device code objects stay the same text (profiles/dp_launcher_refactor.md).
+template <class F> static hipError_t with_flags(F fn) { return fn(); }
+template <class F, class... B> static hipError_t with_flags(F fn, bool flag, B... rest)
+{
+	if (flag) return with_flags([&](auto... c) { return fn(std::true_type{}, c...); }, rest...);
+	return with_flags([&](auto... c) { return fn(std::false_type{}, c...); }, rest...);
+}
+
+// what the DP kernels run over: the caller's tasks, or the pieces cut on the device (starts / ends / p base / avg -- TD: and distances -- per piece, st[] relative to the task)
+struct Tasks { bool cut; int64_t n; const int64_t *off, *end; const int32_t *order, *pbase, *dists; const float *avg; int32_t *status; };
+static Tasks tasks_of(const LaunchArgs &L)
+{
+	if (L.cut.max_pieces > 0) return {true, L.cut.max_pieces, L.cut.d_start, L.cut.d_end, nullptr, L.cut.d_pbase, L.cut.d_dists, L.cut.d_avg, L.cut.d_status};
+	return {false, L.n_tasks, L.d_offsets, nullptr, L.d_order, L.d_pbase, L.d_task_dists, L.d_avg, L.d_status};
+}
+
+template <int R, bool SKIP, bool GEN, bool GS1, bool FAR, bool TD>
 static hipError_t launch_one(const LaunchArgs &L, hipStream_t st, int only_flagged)
 {
-	if (L.cut.max_pieces > 0) {
-		// pieces cut on the device: starts / ends / p base / avg (TD: and distances) per piece, st[] relative to the task
-		hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR, TD>), dim3((unsigned)L.cut.max_pieces), dim3(64), 0, st,
-		                   L.P, L.cut.max_pieces, L.cut.d_start, (const int32_t *)nullptr, (const uint4 *)L.d_anchors, L.cut.d_avg, L.cut.d_pbase, L.d_st, L.d_f, L.d_p,
-		                   L.d_t, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_count, TD ? (const int32_t *)L.cut.d_dists : (const int32_t *)nullptr);
-		return hipGetLastError();
-	}
-	hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR, TD>), dim3((unsigned)L.n_tasks), dim3(64), 0, st,
-	                   L.P, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, L.d_avg, L.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t,
-	                   L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, TD ? L.d_task_dists : (const int32_t *)nullptr);
+	const Tasks T = tasks_of(L);
+	hipLaunchKernelGGL((chain_dp_wave<R, SKIP, GEN, GS1, FAR, TD>), dim3((unsigned)T.n), dim3(64), 0, st, L.P, T.n, T.off, T.order, (const uint4 *)L.d_anchors, T.avg, T.pbase, L.d_st,
+	                   L.d_f, L.d_p, L.d_t, T.status, only_flagged, T.end, T.cut ? L.cut.d_count : (int32_t *)nullptr, TD ? T.dists : (const int32_t *)nullptr);
 	return hipGetLastError();
 }
 
 // per-task distances (LaunchArgs::d_task_dists): the general variant of the first-generation kernel with 256 anchors of LDS ring
-static hipError_t launch_td(const LaunchArgs &L, hipStream_t st, bool skip, bool gs1, bool far_, int only_flagged)
+static hipError_t launch_td(const Route &rt, const LaunchArgs &L, hipStream_t st, int only_flagged)
 {
-	if (skip) {
-		if (gs1) return far_ ? launch_one<256, true, true, true, true, true>(L, st, only_flagged) : launch_one<256, true, true, true, false, true>(L, st, only_flagged);
-		return far_ ? launch_one<256, true, true, false, true, true>(L, st, only_flagged) : launch_one<256, true, true, false, false, true>(L, st, only_flagged);
-	}
-	if (gs1) return far_ ? launch_one<256, false, true, true, true, true>(L, st, only_flagged) : launch_one<256, false, true, true, false, true>(L, st, only_flagged);
-	return far_ ? launch_one<256, false, true, false, true, true>(L, st, only_flagged) : launch_one<256, false, true, false, false, true>(L, st, only_flagged);
+	return with_flags([&](auto skip, auto gs1, auto far_) { return launch_one<256, skip(), true, gs1(), far_(), true>(L, st, only_flagged); }, rt.skip, rt.gs1, rt.far_wave);
+}
+
+// the first-generation kernel with R anchors of LDS ring
+template <int R>
+static hipError_t launch_wave(const Route &rt, const LaunchArgs &L, hipStream_t st, bool gen, int only_flagged)
+{
+	return with_flags([&](auto gen_, auto far_, auto skip, auto gs1) { return launch_one<R, skip(), gen_(), gs1(), far_(), false>(L, st, only_flagged); },
+	                  gen, rt.far_wave, rt.skip, rt.gs1);
 }
 
 // ---- second-generation kernel (chain_dp_tile.h): x / q rings of NX tiles, f / p rings of NF tiles
 // with_cls: the kernel takes the tasks whose class (prepass) masked with cls_mask equals my_cls
 template <int NX, int NF, bool SKIP, bool GEN, bool GS1, bool FAR, bool TAB, int C16>
-static hipError_t launch_tile_nx(const LaunchArgs &L, const float *d_avg, hipStream_t st, int only_flagged, bool with_cls, int my_cls, int cls_mask)
+static hipError_t launch_tile_nx(const LaunchArgs &L, hipStream_t st, int only_flagged, bool with_cls, int my_cls, int cls_mask)
 {
-	if (L.cut.max_pieces > 0) {
-		hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)L.cut.max_pieces), dim3(64), 0, st,
-		                   L.P, L.cut.max_pieces, L.cut.d_start, (const int32_t *)nullptr, (const uint4 *)L.d_anchors, L.cut.d_avg, L.cut.d_pbase, L.d_st, L.d_f, L.d_p,
-		                   L.d_t, L.d_w, L.cut.d_status, only_flagged, L.cut.d_end, L.cut.d_live ? L.cut.d_live : L.cut.d_count, with_cls ? (const uint8_t *)L.cut.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
-		return hipGetLastError();
-	}
-	hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)L.n_tasks), dim3(64), 0, st,
-	                   L.P, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, d_avg, L.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t,
-	                   L.d_w, L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, with_cls ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, my_cls, cls_mask);
+	const Tasks T = tasks_of(L);
+	const int32_t *n_live = !T.cut ? nullptr : L.cut.d_live ? L.cut.d_live : L.cut.d_count;
+	const uint8_t *cls = !with_cls ? nullptr : T.cut ? L.cut.d_cls : L.d_cls;
+	hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)T.n), dim3(64), 0, st, L.P, T.n, T.off, T.order, (const uint4 *)L.d_anchors, T.avg, T.pbase, L.d_st,
+	                   L.d_f, L.d_p, L.d_t, L.d_w, T.status, only_flagged, T.end, n_live, cls, my_cls, cls_mask);
 	return hipGetLastError();
-}
-
-// the class array of the prepass reaches the kernels (plans have it; the piece arrays of a device-side cut must carry it too)
-static bool have_cls(const LaunchArgs &L) { return L.d_cls != nullptr && (L.cut.max_pieces == 0 || L.cut.d_cls != nullptr); }
-// ring-size classes: class-1 tasks run the instantiation with the long ring (variants with the hand-written loop only)
-static bool use_classes(const LaunchArgs &L, bool skip, bool gen) { return !gen && skip && L.far_ring != 0 && have_cls(L); }
-// the compact x / q ring (chain_dp_tile.h, Lds<>): differences of the low halves are exact when max_dist_x < 2^16 and, per task, the q values span
-// at most 65535 - max_dq; returns that bound for the prepass (0: not used)
-static unsigned compact_q_span(const LaunchArgs &L, bool asm_loop)
-{
-	const KParams &P = L.P;
-	if (!L.compact || !asm_loop || !have_cls(L) || P.max_dist_x < 0 || P.max_dist_x > 65535 || P.max_dq < 1 || P.max_dq > 32768) return 0;
-	return 65535u - (unsigned)P.max_dq;
-}
-
-// the packed f / p ring (chain_dp_tile.h, Lds<> RING 3): for the tasks of the compact x / q ring whose p and f fit its word (bit 3 of the class, set by the prepass
-// when this says so); needs the side array of one word per anchor, which plans have
-static bool packed_fp_ring(const LaunchArgs &L, bool asm_loop) { return L.packed_fp != 0 && L.d_w != nullptr && compact_q_span(L, asm_loop) != 0; }
-
-// the q24 ring (chain_dp_tile.h, Lds<> RING 2) is the form of the LONG ring (ring-size class 1): dr from the low halves of x needs max_dist_x < 2^16, q is exact for
-// tasks whose q values are below 2^24 -- the prepass keeps every other task out of class 1 (bit 2 of the class byte)
-static bool q24_ring(const LaunchArgs &L, bool skip, bool gen, bool gs1, bool tab)
-{
-	return L.q24 != 0 && use_classes(L, skip, gen) && (gs1 || tab) && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535;
 }
 
 // The 32-bit rings: one ring size for every task, or -- ring-size classes, variants with the hand-written loop only -- the short ring for class 0 and a ring of
@@ -822,11 +922,10 @@ static bool q24_ring(const LaunchArgs &L, bool skip, bool gen, bool gs1, bool ta
 // with it instead (a ring of MM2C_CNX tiles, whatever their ring-size class).  Every instantiation is launched over all tasks and returns at once for the tasks
 // of another one (0.02 ms per launch); the 32-bit ones go first: they hold the longest tasks (a wide span of q values comes with a long read).
 template <bool SKIP, bool GEN, bool GS1, bool FAR, bool TAB>
-static hipError_t launch_tile_one(const LaunchArgs &L, const float *d_avg, hipStream_t st, int only_flagged, int *n_launches)
+static hipError_t launch_tile_one(const Route &rt, const LaunchArgs &L, hipStream_t st, int only_flagged, int *n_launches)
 {
-	const bool classes = use_classes(L, SKIP, GEN);
-	bool c16 = false;
-	if constexpr (SKIP && !GEN && (GS1 || TAB)) c16 = compact_q_span(L, L.P.bw >= 0 && L.P.max_dq - 1 >= L.P.bw) != 0;
+	constexpr bool LOOP = SKIP && !GEN && (GS1 || TAB);    // the instantiations of the hand-written loop: the q24, compact and packed rings exist for them alone
+	const bool classes = !GEN && rt.classes, c16 = LOOP && rt.c16_bound != 0, pk = LOOP && rt.packed;   // (GEN: the second pass of a simple call has no classes)
 	const int wide = c16 ? 2 : 0, mask = (c16 ? 2 : 0) | (classes ? 1 : 0);
 	// the 32-bit instantiations beside the compact one: on the side stream, between a fork and a join event
 	const bool fork = c16 && L.side != nullptr && L.ev_fork != nullptr && L.ev_join != nullptr;
@@ -834,28 +933,26 @@ static hipError_t launch_tile_one(const LaunchArgs &L, const float *d_avg, hipSt
 	hipError_t e = hipSuccess;
 	bool forked = false;                                   // the side stream has been made to wait for `st`: it is joined again whatever fails in between
 	if (fork) { e = hipEventRecord(L.ev_fork, st); if (e == hipSuccess) { e = hipStreamWaitEvent(sw, L.ev_fork, 0); forked = e == hipSuccess; } }
-	if (e == hipSuccess) e = launch_tile_nx<MM2C_NX, MM2C_NF, SKIP, GEN, GS1, FAR, TAB, 0>(L, d_avg, sw, only_flagged, mask != 0, wide, mask);
+	if (e == hipSuccess) e = launch_tile_nx<MM2C_NX, MM2C_NF, SKIP, GEN, GS1, FAR, TAB, 0>(L, sw, only_flagged, mask != 0, wide, mask);
 	if constexpr (!GEN && SKIP)
 		if (e == hipSuccess && classes) {
 			bool done = false;
 			if constexpr (GS1 || TAB)
-				if (q24_ring(L, SKIP, GEN, GS1, TAB)) { e = launch_tile_nx<2 * MM2C_NX, MM2C_NF1, SKIP, GEN, GS1, FAR, TAB, 2>(L, d_avg, sw, only_flagged, true, wide | 1, mask); done = true; }
-			if (!done) e = launch_tile_nx<2 * MM2C_NX, MM2C_NF1, SKIP, GEN, GS1, FAR, TAB, 0>(L, d_avg, sw, only_flagged, true, wide | 1, mask);
+				if (rt.q24) { e = launch_tile_nx<2 * MM2C_NX, MM2C_NF1, SKIP, GEN, GS1, FAR, TAB, 2>(L, sw, only_flagged, true, wide | 1, mask); done = true; }
+			if (!done) e = launch_tile_nx<2 * MM2C_NX, MM2C_NF1, SKIP, GEN, GS1, FAR, TAB, 0>(L, sw, only_flagged, true, wide | 1, mask);
 			if (n_launches) ++*n_launches;
 		}
 	// the compact ring.  Tasks the packed f / p word can hold (bit 3) take the instantiation with it, the others -- the long ones -- the one with pairs, which goes
 	// FIRST and, where there is a side stream, beside the packed one (two launches one after the other on one stream each end with the GPU part empty, and the
 	// longest tasks started last would make the batch wait for their whole length); without the packed ring bit 3 is not looked at
-	bool pk = false;
-	if constexpr (SKIP && !GEN && (GS1 || TAB)) pk = c16 && packed_fp_ring(L, true);
-	if constexpr (SKIP && !GEN && (GS1 || TAB))
-		if (e == hipSuccess && c16 && pk) { e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, d_avg, sw, only_flagged, true, 0, 2 | 8); if (n_launches) ++*n_launches; }
+	if constexpr (LOOP)
+		if (e == hipSuccess && pk) { e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, sw, only_flagged, true, 0, 2 | 8); if (n_launches) ++*n_launches; }
 	bool joined = false;
 	if (forked) joined = hipEventRecord(L.ev_join, sw) == hipSuccess;
-	if constexpr (SKIP && !GEN && (GS1 || TAB))
+	if constexpr (LOOP)
 		if (e == hipSuccess && c16) {
-			if (pk) e = launch_tile_nx<MM2C_CNX, MM2C_PNF, SKIP, GEN, GS1, FAR, TAB, 3>(L, d_avg, st, only_flagged, true, 8, 2 | 8);
-			else e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, d_avg, st, only_flagged, true, 0, 2);
+			if (pk) e = launch_tile_nx<MM2C_CNX, MM2C_PNF, SKIP, GEN, GS1, FAR, TAB, 3>(L, st, only_flagged, true, 8, 2 | 8);
+			else e = launch_tile_nx<MM2C_CNX, MM2C_CNF, SKIP, GEN, GS1, FAR, TAB, 1>(L, st, only_flagged, true, 0, 2);
 			if (n_launches) ++*n_launches;
 		}
 	if (forked) {
@@ -868,91 +965,51 @@ static hipError_t launch_tile_one(const LaunchArgs &L, const float *d_avg, hipSt
 // ---- several waves per task (chain_dp_coop.h): passes too small to fill the GPU with one wave per task; the variants of the hand-written loop only
 // Waves per piece: sixteen (one workgroup per CU: the pieces of a pass of at most one per CU get a CU each) or eight (two workgroups per CU: with more pieces than CUs a CU
 // that holds two fills the waits of one -- its barriers, 52 % of the wave cycles at sixteen -- with the rows of the other: 1 020 reads of 300 000 anchors 129.3 -> 111.3 ms,
-// 2 048 of 100 000 96.1 -> 77.7, while 255 of 10^6 take 153.9 instead of 101.5: profiles/r6_long_reads.md).  `w8_above`: pieces beyond which eight are taken.
+// 2 048 of 100 000 96.1 -> 77.7, while 255 of 10^6 take 153.9 instead of 101.5: profiles/r6_long_reads.md).  LaunchArgs::coop_w8_above: pieces beyond which eight are taken.
 template <int W>
-static hipError_t launch_coop_w(const LaunchArgs &L, const float *d_avg, hipStream_t st, bool tab, int only_flagged, const int32_t *n_live, int32_t *st_out = nullptr, float *avg_out = nullptr, const uint4 *a_src = nullptr)
+static hipError_t launch_coop_w(const Route &rt, const LaunchArgs &L, hipStream_t st, int only_flagged, const float *avg_in, const int32_t *n_live, int32_t *st_out = nullptr, float *avg_out = nullptr,
+                                const uint4 *a_src = nullptr)
 {
-	const bool far_ = (int64_t)L.P.max_iter > 64 * (COOP_NX - 1);
-	const dim3 block(64 * W);
-	if (L.cut.max_pieces > 0) {
-		// the pieces chain_route gave to this kernel (*n_live of them: at most COOP_ROUTE_MAX_PIECES, or none)
-		const dim3 grid((unsigned)std::min<int64_t>(L.cut.max_pieces, COOP_ROUTE_MAX_PIECES));
-#define MM2C_COOP(GS1, FAR, TAB) hipLaunchKernelGGL((chain_dp_coop<W, GS1, FAR, TAB>), grid, block, 0, st, L.P, L.cut.max_pieces, L.cut.d_start, (const int32_t *)nullptr, \
-	                                            (const uint4 *)L.d_anchors, (const float *)L.cut.d_avg, L.cut.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t, L.cut.d_status, only_flagged, \
-	                                            (const int64_t *)L.cut.d_end, n_live, CoopHostOut(), (int32_t *)nullptr, (float *)nullptr, (const uint4 *)nullptr, CoopMeta())
-		if (tab) { if (far_) MM2C_COOP(true, true, true); else MM2C_COOP(true, false, true); }
-		else { if (far_) MM2C_COOP(true, true, false); else MM2C_COOP(true, false, false); }
-#undef MM2C_COOP
-		return hipGetLastError();
-	}
-	const dim3 grid((unsigned)L.n_tasks);
+	const Tasks T = tasks_of(L);                           // cut: the pieces chain_route gave to this kernel (*n_live of them: at most COOP_ROUTE_MAX_PIECES, or none)
+	const dim3 grid((unsigned)(T.cut ? std::min<int64_t>(T.n, COOP_ROUTE_MAX_PIECES) : T.n)), block(64 * W);
 	CoopHostOut H;
-	if (L.h_flag && L.h_f && L.h_p && L.d_done && (L.P.flags & KF_IGNORE_SEG) && !only_flagged) { H.f = L.h_f; H.p = L.h_p; H.d_done = L.d_done; H.h_flag = L.h_flag; H.seq = L.seq; }
+	if (rt.host_out) { H.f = L.h_f; H.p = L.h_p; H.d_done = L.d_done; H.h_flag = L.h_flag; H.seq = L.seq; }   // (KF_IGNORE_SEG: no second pass that could write it again)
 	CoopMeta MT;
 	if (a_src && H.h_flag && L.hm_off && L.hm_avg && L.hm_pbase && L.n_tasks <= COOP_META_MAX && !L.d_order) {
 		MT.n = (int32_t)L.n_tasks;
 		for (int64_t k = 0; k < L.n_tasks; ++k) { MT.off[k] = L.hm_off[k]; MT.avg[k] = L.hm_avg[k]; MT.pbase[k] = L.hm_pbase[k]; }
 		MT.off[L.n_tasks] = L.hm_off[L.n_tasks];
 	}
-#define MM2C_COOP(GS1, FAR, TAB) hipLaunchKernelGGL((chain_dp_coop<W, GS1, FAR, TAB>), grid, block, 0, st, L.P, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, \
-	                                            d_avg, L.d_pbase, L.d_st, L.d_f, L.d_p, L.d_t, L.d_status, only_flagged, (const int64_t *)nullptr, (const int32_t *)nullptr, H, st_out, avg_out, H.h_flag ? a_src : (const uint4 *)nullptr, MT)
-	if (tab) { if (far_) MM2C_COOP(true, true, true); else MM2C_COOP(true, false, true); }
-	else { if (far_) MM2C_COOP(true, true, false); else MM2C_COOP(true, false, false); }
-#undef MM2C_COOP
-	return hipGetLastError();
+	return with_flags([&](auto tab, auto far_) {
+		hipLaunchKernelGGL((chain_dp_coop<W, true, far_(), tab()>), grid, block, 0, st, L.P, T.n, T.off, T.order, (const uint4 *)L.d_anchors, T.cut ? T.avg : avg_in, T.pbase, L.d_st, L.d_f, L.d_p,
+		                   L.d_t, T.status, only_flagged, T.end, n_live, H, st_out, avg_out, H.h_flag ? a_src : (const uint4 *)nullptr, MT);
+		return hipGetLastError();
+	}, rt.tab, rt.far_coop);
 }
 
-static int coop_width(const LaunchArgs &L) { return L.n_tasks > (int64_t)L.coop_w8_above ? 8 : 16; }   // (pieces = tasks: no cut on the device)
-
-// a pass of few SHORT tasks whose window starts nobody has made: the sixteen-wave kernel makes them itself (chain_dp_coop.h, st_out) -- no prepass launch
-static bool coop_makes_st(const LaunchArgs &L)
+// avg_ws: the workspace for avg when the caller handed none in (else nullptr)
+static hipError_t launch_coop(const Route &rt, const LaunchArgs &L, hipStream_t st, int only_flagged, float *avg_ws, int *n_launches)
 {
-	return L.fuse_st && !L.st_ready && L.cut.max_pieces == 0 && coop_width(L) == 16 && L.max_task_anchors > 0 && L.max_task_anchors <= COOP_ST_MAX && (L.d_avg != nullptr || L.d_avg_ws != nullptr);
-}
-
-static hipError_t launch_coop(const LaunchArgs &L, const float *d_avg, hipStream_t st, bool tab, int only_flagged, int *n_launches)
-{
-	if (L.cut.max_pieces > 0) {
+	if (n_launches) ++*n_launches;
+	if (rt.coop_auto) {
 		// cut on the device: chain_route put the count under the width it chose (d_count[2]: sixteen waves, [3]: eight); the launch that was not chosen finds 0
-		hipError_t e = launch_coop_w<16>(L, d_avg, st, tab, only_flagged, L.cut.d_count + 2);
-		if (n_launches) ++*n_launches;
-		if (e == hipSuccess && L.cut.max_pieces > (int64_t)L.coop_w8_above) { e = launch_coop_w<8>(L, d_avg, st, tab, only_flagged, L.cut.d_count + 3); if (n_launches) ++*n_launches; }
+		hipError_t e = launch_coop_w<16>(rt, L, st, only_flagged, nullptr, L.cut.d_count + 2);
+		if (e == hipSuccess && rt.auto_w8) { e = launch_coop_w<8>(rt, L, st, only_flagged, nullptr, L.cut.d_count + 3); if (n_launches) ++*n_launches; }
 		return e;
 	}
-	if (n_launches) ++*n_launches;
-	if (coop_width(L) == 8) return launch_coop_w<8>(L, d_avg, st, tab, only_flagged, nullptr);
-	const bool makes = coop_makes_st(L) && !only_flagged;
-	// (no avg handed in: the kernel sweeps the task itself and leaves the value in the workspace)
-	return launch_coop_w<16>(L, makes && !L.d_avg ? (const float *)nullptr : d_avg, st, tab, only_flagged, nullptr, makes ? L.d_st : (int32_t *)nullptr, makes && !L.d_avg ? L.d_avg_ws : (float *)nullptr,
-	                         makes && L.d_avg ? (const uint4 *)L.h_anchors : (const uint4 *)nullptr);
+	if (rt.width == 8) return launch_coop_w<8>(rt, L, st, only_flagged, L.d_avg, nullptr);
+	if (!rt.makes_st || only_flagged) return launch_coop_w<16>(rt, L, st, only_flagged, L.d_avg, nullptr);
+	// the kernel makes the window starts; no avg handed in: it sweeps the task itself and leaves the value in the workspace; handed in: the pass may come from the pinned arena
+	return launch_coop_w<16>(rt, L, st, only_flagged, avg_ws ? (const float *)nullptr : L.d_avg, nullptr, L.d_st, avg_ws, avg_ws ? (const uint4 *)nullptr : (const uint4 *)L.h_anchors);
 }
 
-template <bool SKIP, bool FAR>
-static hipError_t launch_tile_sf(const LaunchArgs &L, const float *d_avg, hipStream_t st, bool gen, bool gs1, bool tab, int only_flagged, int *nl)
+static hipError_t launch_tile(const Route &rt, const LaunchArgs &L, hipStream_t st, bool gen, int only_flagged, int *nl)
 {
-	if (tab && !gen) return launch_tile_one<SKIP, false, true, FAR, true>(L, d_avg, st, only_flagged, nl);   // the table absorbs gap_scale
-	if (gen) return gs1 ? launch_tile_one<SKIP, true, true, FAR, false>(L, d_avg, st, only_flagged, nl) : launch_tile_one<SKIP, true, false, FAR, false>(L, d_avg, st, only_flagged, nl);
-	return gs1 ? launch_tile_one<SKIP, false, true, FAR, false>(L, d_avg, st, only_flagged, nl) : launch_tile_one<SKIP, false, false, FAR, false>(L, d_avg, st, only_flagged, nl);
-}
-
-static hipError_t launch_tile(const LaunchArgs &L, const float *d_avg, hipStream_t st, bool skip, bool gen, bool gs1, bool far_, bool tab, int only_flagged, int *nl)
-{
-	if (skip) return far_ ? launch_tile_sf<true, true>(L, d_avg, st, gen, gs1, tab, only_flagged, nl) : launch_tile_sf<true, false>(L, d_avg, st, gen, gs1, tab, only_flagged, nl);
-	return far_ ? launch_tile_sf<false, true>(L, d_avg, st, gen, gs1, tab, only_flagged, nl) : launch_tile_sf<false, false>(L, d_avg, st, gen, gs1, tab, only_flagged, nl);
-}
-
-template <int R, bool GEN, bool FAR>
-static hipError_t launch_sg(const LaunchArgs &L, hipStream_t st, bool skip, bool gs1, int only_flagged)
-{
-	if (skip) return gs1 ? launch_one<R, true, GEN, true, FAR>(L, st, only_flagged) : launch_one<R, true, GEN, false, FAR>(L, st, only_flagged);
-	return gs1 ? launch_one<R, false, GEN, true, FAR>(L, st, only_flagged) : launch_one<R, false, GEN, false, FAR>(L, st, only_flagged);
-}
-
-template <int R>
-static hipError_t launch_r(const LaunchArgs &L, hipStream_t st, bool skip, bool gen, bool gs1, bool far_, int only_flagged)
-{
-	if (gen) return far_ ? launch_sg<R, true, true>(L, st, skip, gs1, only_flagged) : launch_sg<R, true, false>(L, st, skip, gs1, only_flagged);
-	return far_ ? launch_sg<R, false, true>(L, st, skip, gs1, only_flagged) : launch_sg<R, false, false>(L, st, skip, gs1, only_flagged);
+	const bool tab = rt.tab && !gen;                       // the table absorbs gap_scale: TAB only with !GEN, and then GS1
+	return with_flags([&](auto skip, auto far_, auto tab_, auto gen_, auto gs1) {
+		if constexpr (tab_() && (gen_() || !gs1())) return hipErrorInvalidValue;
+		else return launch_tile_one<skip(), gen_(), gs1(), far_(), tab_()>(rt, L, st, only_flagged, nl);
+	}, rt.skip, rt.far_tile, tab, gen, rt.gs1 || tab);
 }
 
 hipError_t launch_predict(int32_t max_dist_x, int64_t n_tasks, const int64_t *d_offsets, const int32_t *d_order, const void *d_anchors,
@@ -980,138 +1037,70 @@ hipError_t label_hits_read(unsigned long long *out, bool reset)
 #endif
 }
 
-int chain_ring_anchors(int ring_class) { return ring_class == 0 ? 256 : ring_class == 1 ? 512 : ring_class == 2 ? 1024 : 64 * (MM2C_NX - 1); }   // 3, 4: the tile kernel
-
 hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launches, hipEvent_t ev_dp_begin, LaunchInfo *info)
 {
 	if (L_in.n_tasks <= 0) return hipSuccess;
+	if (L_in.d_task_dists && L_in.cut.max_pieces > 0 && !L_in.cut.d_dists) return hipErrorInvalidValue;   // per-task distances: the pieces of a cut must carry them
+	const Route rt = decide_route(L_in);
+	if (info) fill_info(rt, info);
+	if (L_in.dry_run) return hipSuccess;                               // the caller only wanted to know (info)
 	LaunchArgs L = L_in;
-	// The early exit of chain.c:231 can never fire when the skip counter cannot exceed max_skip inside one window: a window holds at most max_iter candidates and the
-	// nearest one is never stamped, so the counter stays below max_iter.  Such calls (the V2 scalars of run_chaining_on_hw: max_skip = INT_MAX, max_iter = 1024) used to
-	// take the instantiations without the max-skip machinery, which have no hand-written loop; with max_skip = max_iter - 1 the machinery is compiled in and runs, still
-	// cannot fire, and the hand-written loop serves them (same f / p, V2 scalars: mixed 47.3 -> 44.3 ms per 1.6e8 anchors, dense 85.4 -> 67.5).
-	// per-task distances: the general variant of the first-generation kernel, the one route that reads them (every condition below that looks at P's distances -- the
-	// compact rings, the hand-written loop, the cooperative kernel -- is per call and is not asked)
-	const bool td = L.d_task_dists != nullptr && (L.cut.max_pieces == 0 || L.cut.d_dists != nullptr);
-	if (L.d_task_dists && !td) return hipErrorInvalidValue;
-	const bool want_gen = L.P.is_cdna || L.P.n_segs > 1 || (L.P.flags & KF_FORCE_GENERAL) || td;
-	const bool loop_ok = L.P.gap_scale == 1.0f || L_in.force_tab || (L.P.bw <= 511 && L.P.gap_scale > -20.f && L.P.gap_scale < 20.f);   // gap cost computed or from the table
-	if (L.noskip_loop && (int64_t)L.P.max_skip >= (int64_t)L.P.max_iter && L.P.max_iter >= 1 && L.ring_class >= 3 && !want_gen && L.P.bw >= 0 && L.P.max_dq - 1 >= L.P.bw && loop_ok)
-		L.P.max_skip = L.P.max_iter - 1;
-	const KParams &P = L.P;
-	const bool skip = (int64_t)P.max_skip < (int64_t)P.max_iter;
-	const bool gs1 = P.gap_scale == 1.0f;
-	const int R = chain_ring_anchors(L.ring_class);
-	const bool tile = L.ring_class >= 3;                   // second-generation kernel: 448 anchors before the current tile without global memory
-	// the general variant (segment ids / cDNA) has no hand-written loop in the tile kernel and is faster in the first-generation one (headline
-	// stream with --general: 92.0 vs 108.7 ms, dense 151.8 vs 163.8): ring_class 3 sends it there, ring_class 4 keeps it in the tile kernel
-	const bool tile_gen = L.ring_class >= 4 && !td;
-	const bool far_ = (int64_t)P.max_iter > (int64_t)R;   // the ring always holds the R anchors before the current tile
-	const bool far_old = (int64_t)P.max_iter > 256;       // ... of the first-generation kernel when it stands in (R = 256)
-	// the gap-cost table of the tile kernel: dd <= bw <= 511 entries of int16 (cost <= 2.55 * 511 + 4, times gap_scale)
-	// used when gap_scale != 1 (it takes the f64 path of chain.c:219 out of the loop); with gap_scale 1 computing the cost is as fast and the
-	// kernel's LDS stays at 6 KB (measured: 62.8 vs 66.3 ms on the headline batch)
-	static const bool force_tab_env = getenv("MM2C_FORCE_TAB") != nullptr;   // experiment switch: the table also for gap_scale == 1
-	const bool force_tab = force_tab_env || L.force_tab != 0;
-	const bool tab = tile && (!gs1 || force_tab) && P.bw >= 0 && P.bw <= 511 && P.gap_scale > -20.f && P.gap_scale < 20.f;
-	// several waves per task: asked for by the caller for a pass of few tasks; the variants with the hand-written loop, tasks not cut on the device
-	const bool coop_cfg = tile && !want_gen && skip && (gs1 || tab) && P.bw >= 0 && P.max_dq - 1 >= P.bw;
-	const bool coop = L.coop_waves > 1 && coop_cfg && L.cut.max_pieces == 0;
-	// ... or left to the device: with a cut, how many pieces there are and how long is only known there (chain_route, after chain_cut)
-	const bool coop_auto = L.coop_waves < 0 && coop_cfg && L.cut.max_pieces > 0 && L.cut.d_count != nullptr;
-	if (coop_auto) { L.cut.d_live = L.cut.d_count + 1; L.cut.w8_above = L.coop_w8_above; }
-	if (info) {
-		info->route_auto = coop_auto ? 1 : 0;
-		info->fused_st = coop && coop_makes_st(L) ? 1 : 0;
-		info->host_out = (coop && L.h_flag && L.h_f && L.h_p && L.d_done && (L.P.flags & KF_IGNORE_SEG)) ? 1 : 0;
-		info->single_ok = info->fused_st && info->host_out && L.d_avg != nullptr;   // such a pass can do without stage_in (LaunchArgs::h_anchors)
-		const bool t0 = tile && (!want_gen || tile_gen);          // pass 0 runs in the tile kernel
-		info->coop = coop ? coop_width(L) : 0;
-		info->tile = t0; info->nx = t0 ? MM2C_NX : 0; info->nf = t0 ? MM2C_NF : 0; info->r = t0 ? 64 * (MM2C_NX - 1) : (tile || td ? 256 : R);
-		info->skip = skip; info->gen = want_gen; info->gs1 = gs1; info->far_ = t0 ? far_ : (tile || td ? far_old : far_); info->tab = t0 && tab && !want_gen;
-		info->asm_loop = t0 && skip && !want_gen && (gs1 || tab) && P.bw >= 0 && P.max_dq - 1 >= P.bw;   // = ASM of chain_dp_tile
-		info->classes = t0 && use_classes(L, skip, want_gen);
-		info->c16 = t0 && compact_q_span(L, info->asm_loop != 0) != 0;
-		info->q24 = t0 && info->classes && q24_ring(L, skip, want_gen, gs1, tab);
-		info->packed = t0 && info->c16 && packed_fp_ring(L, info->asm_loop != 0);
-		info->cut = L.cut.max_pieces > 0;
-		if (coop) { info->nx = COOP_NX; info->nf = COOP_NF; info->r = 64 * (COOP_NX - 1); info->far_ = (int64_t)P.max_iter > 64 * (COOP_NX - 1); info->classes = 0; info->c16 = 0; info->q24 = 0; info->packed = 0; }
-	}
-	if (L.dry_run) return hipSuccess;                                  // the caller only wanted to know (info)
+	L.P = rt.P;
+	if (rt.coop_auto) { L.cut.d_live = L.cut.d_count + 1; L.cut.w8_above = L.coop_w8_above; }
 	// avg_qspan_scaled per task: the caller's, or computed by the prepass into the workspace (else the DP kernel sweeps the task itself)
-	float *avg_out = L.d_avg ? nullptr : L.d_avg_ws;
-	const float *d_avg = L.d_avg ? L.d_avg : L.d_avg_ws;
-	const unsigned c16_bound = tile && (!want_gen || tile_gen) ? compact_q_span(L, skip && !want_gen && (gs1 || tab) && P.bw >= 0 && P.max_dq - 1 >= P.bw) : 0u;
-	// a pass of few tasks that wants nothing but st[] from the prepass (the cooperative kernel: no classes; avg handed in; no cut on the device): one block per tile
-	// (avg not handed in: the blocks add up the spans into the avg workspace and a small kernel finishes them -- a plan of few long tasks: 256 reads of 10^6 anchors
-	// 3.9 -> about 1 ms, one block per task walks its tiles one after the other)
-	const bool wide_prepass = coop && L.max_task_anchors > 0 && L.max_task_anchors <= (1 << 22) && (L.d_avg != nullptr || L.d_avg_ws != nullptr) && L.cut.max_pieces == 0
-	                          && (L.max_task_anchors + 255) / 256 <= 65535;
-	const bool no_prepass = coop && ((L.st_ready && L.d_avg != nullptr) || coop_makes_st(L));
-	if (no_prepass) {
-		// nothing to launch: st[] came with the pass (mm2chain_host.cpp) and avg was handed in, or the cooperative kernel makes both itself (short tasks); it has no classes
-	} else if (wide_prepass) {
-		unsigned *sums = L.d_avg ? nullptr : (unsigned *)L.d_avg_ws;
-		if (sums && hipMemsetAsync(sums, 0, (size_t)L.n_tasks * 4, st) != hipSuccess) return hipGetLastError();
-		hipLaunchKernelGGL(chain_window_start_wide, dim3((unsigned)L.n_tasks, (unsigned)((L.max_task_anchors + 255) / 256)), dim3(256), 0, st, P, L.n_tasks, L.d_offsets,
-		                   (const ulonglong2 *)L.d_anchors, L.d_st, sums);
-		if (sums) hipLaunchKernelGGL(chain_avg_finish, dim3((unsigned)((L.n_tasks + 255) / 256)), dim3(256), 0, st, L.n_tasks, L.d_offsets, sums);
-	} else {
-		// long tasks (the caller knows the longest and lends the words for the sums): a block per segment of PREPASS_SEG anchors instead of a block per task
-		// (few tasks only: 2 048 blocks fill the GPU as they are -- 2 048 tasks of 100 000 anchors 1.12 ms by task, 1.46 by segment; 255 of 10^6: 4.7 -> 1.6 ms)
-		const bool seg = L.d_seg_ws != nullptr && L.n_tasks <= 512 && L.longest_task >= 2 * PREPASS_SEG && (L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG <= 65535;
-#define MM2C_WS(KERN, GRID, SEGN, WS) hipLaunchKernelGGL(KERN, GRID, dim3(256), 0, st, P, L.n_tasks, L.d_offsets, L.d_order, \
-	                   (const ulonglong2 *)L.d_anchors, L.d_st, L.cut.max_pieces > 0 ? L.cut.d_has_cut : (int32_t *)nullptr, avg_out, \
-	                   tile && !coop ? L.d_cls : (uint8_t *)nullptr, L.far_ring, L.far_thr10, tile && !coop ? L.d_cls_stat : (unsigned long long *)nullptr, \
-	                   coop ? 0u : c16_bound,                     /* (the cooperative kernel has one ring form: no classes to find) */ \
-	                   (!coop && tile && q24_ring(L, skip, want_gen, gs1, tab)) ? 1 : 0, (!coop && c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr) ? 1 : 0, SEGN, WS, \
-	                   L.d_task_dists)
-		if (td) {
-			if (seg) MM2C_WS((chain_window_start_t<true, true>), dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
-			else MM2C_WS((chain_window_start_t<false, true>), dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
-		} else if (seg) MM2C_WS(chain_window_start_t<true>, dim3((unsigned)L.n_tasks, (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG)), PREPASS_SEG, L.d_seg_ws);
-		else MM2C_WS(chain_window_start_t<false>, dim3((unsigned)L.n_tasks), 0, (unsigned long long *)nullptr);
-#undef MM2C_WS
+	float *avg_ws = L.d_avg ? nullptr : L.d_avg_ws;
+	if (rt.prepass == PRE_WIDE) {
+		if (avg_ws && hipMemsetAsync(avg_ws, 0, (size_t)L.n_tasks * 4, st) != hipSuccess) return hipGetLastError();
+		hipLaunchKernelGGL(chain_window_start_wide, dim3((unsigned)L.n_tasks, (unsigned)((L.max_task_anchors + 255) / 256)), dim3(256), 0, st, L.P, L.n_tasks, L.d_offsets,
+		                   (const ulonglong2 *)L.d_anchors, L.d_st, (unsigned *)avg_ws);
+		if (avg_ws) hipLaunchKernelGGL(chain_avg_finish, dim3((unsigned)((L.n_tasks + 255) / 256)), dim3(256), 0, st, L.n_tasks, L.d_offsets, (unsigned *)avg_ws);
+	} else if (rt.prepass != PRE_NONE) {
+		const bool seg = rt.prepass == PRE_SEG, cls = rt.tile && !rt.coop;   // (the classes are the tile kernel's)
+		const dim3 grid((unsigned)L.n_tasks, seg ? (unsigned)((L.longest_task + PREPASS_SEG - 1) / PREPASS_SEG) : 1u);
+		(void)with_flags([&](auto td, auto seg_) {
+			hipLaunchKernelGGL((chain_window_start_t<seg_(), td()>), grid, dim3(256), 0, st, L.P, L.n_tasks, L.d_offsets, L.d_order, (const ulonglong2 *)L.d_anchors, L.d_st,
+			                   rt.cut ? L.cut.d_has_cut : (int32_t *)nullptr, avg_ws, cls ? L.d_cls : (uint8_t *)nullptr, L.far_ring, L.far_thr10,
+			                   cls ? L.d_cls_stat : (unsigned long long *)nullptr, rt.c16_bound, rt.q24 ? 1 : 0, rt.packed ? 1 : 0, seg ? PREPASS_SEG : 0,
+			                   seg ? L.d_seg_ws : (unsigned long long *)nullptr, L.d_task_dists);
+			return hipSuccess;
+		}, rt.td, seg);
 	}
-	hipError_t e = hipGetLastError();
-	if (n_launches && !no_prepass) ++*n_launches;
-	if (e == hipSuccess && tile && !coop && L.d_cls && L.d_cls_stat && (L.far_ring == 1 || c16_bound != 0)) {
+	hipError_t e = hipGetLastError();                                  // (asked whichever form ran, none included)
+	if (n_launches && rt.prepass != PRE_NONE) ++*n_launches;
+	L.d_avg = L.d_avg ? L.d_avg : L.d_avg_ws;
+	if (e == hipSuccess && rt.settle) {
 		hipLaunchKernelGGL(chain_cls_settle, dim3((unsigned)((L.n_tasks + 255) / 256)), dim3(256), 0, st, L.n_tasks, L.d_cls, L.d_cls_stat, L.far_ring == 1 ? 1 : 0,
-		                   c16_bound != 0 ? L.wide_pct : 100);
+		                   rt.c16_bound != 0 ? L.wide_pct : 100);
 		e = hipGetLastError();
 		if (n_launches) ++*n_launches;
 	}
-	if (e == hipSuccess && L.cut.max_pieces > 0) {
-		if (td) hipLaunchKernelGGL(chain_cut<true>, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order,
-		                           (const uint4 *)L.d_anchors, d_avg, L.d_st, L.cut, tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, L.d_task_dists);
-		else hipLaunchKernelGGL(chain_cut<false>, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order,
-		                   (const uint4 *)L.d_anchors, d_avg, L.d_st, L.cut, tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, (const int32_t *)nullptr);   // (far_ring 0: bit 1, the 32-bit ring, still counts)
-		e = hipGetLastError();
+	if (e == hipSuccess && rt.cut) {
+		e = with_flags([&](auto td) {
+			hipLaunchKernelGGL(chain_cut<td()>, dim3((unsigned)L.n_tasks), dim3(64), 0, st, L.cut.seg_min, L.n_tasks, L.d_offsets, L.d_order, (const uint4 *)L.d_anchors, L.d_avg,
+			                   L.d_st, L.cut, rt.tile ? (const uint8_t *)L.d_cls : (const uint8_t *)nullptr, L.d_task_dists);   // (far_ring 0: bit 1, the 32-bit ring, still counts)
+			return hipGetLastError();
+		}, rt.td);
 		if (n_launches) ++*n_launches;
 	}
-	if (e == hipSuccess && coop_auto) {
+	if (e == hipSuccess && rt.coop_auto) {
 		hipLaunchKernelGGL(chain_route, dim3(1), dim3(256), 0, st, L.cut);
 		e = hipGetLastError();
 		if (n_launches) ++*n_launches;
 	}
 	if (e == hipSuccess && ev_dp_begin) e = hipEventRecord(ev_dp_begin, st);
-	LaunchArgs L1 = L; L1.d_avg = d_avg;
-	for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
-		// pass 0: the variant the parameters ask for; pass 1 (simple variant only, segments not ignored): redo the
-		// tasks that turned out to carry more than one segment id with the general variant.
-		const bool gen = want_gen || pass == 1;
-		if (pass == 1 && (want_gen || (P.flags & KF_IGNORE_SEG))) break;
-		const int flagged = pass;
-		if (pass == 1) { L.cut.d_live = nullptr; L1.cut.d_live = nullptr; }   // the pieces flagged for the general variant come from either kernel: every piece is looked at
-		if (coop && !gen) { e = launch_coop(L, d_avg, st, tab, flagged, n_launches); continue; }
-		if (coop_auto && !gen) e = launch_coop(L, d_avg, st, tab, flagged, n_launches);   // (and the one-wave kernels below: each goes by its own count)
-		if (tile && (!gen || tile_gen)) { e = launch_tile(L, d_avg, st, skip, gen, gs1, far_, tab, flagged, n_launches); if (n_launches) ++*n_launches; continue; }
-		if (td) { e = launch_td(L1, st, skip, gs1, far_old, flagged); if (n_launches) ++*n_launches; continue; }
-		if (tile) { e = launch_r<256>(L1, st, skip, gen, gs1, far_old, flagged); if (n_launches) ++*n_launches; continue; }
-		switch (R) {
-		case 256: e = launch_r<256>(L1, st, skip, gen, gs1, far_, flagged); break;
-		case 512: e = launch_r<512>(L1, st, skip, gen, gs1, far_, flagged); break;
-		default:  e = launch_r<1024>(L1, st, skip, gen, gs1, far_, flagged); break;
+	// pass 0: the variant the parameters ask for; pass 1 (simple variant only, segments not ignored): redo the
+	// tasks that turned out to carry more than one segment id with the general variant.
+	for (int pass = 0; pass < (rt.second_pass ? 2 : 1) && e == hipSuccess; ++pass) {
+		const bool gen = rt.gen || pass == 1;
+		if (pass == 1) L.cut.d_live = nullptr;                 // the pieces flagged for the general variant come from either kernel: every piece is looked at
+		if (rt.coop && !gen) { e = launch_coop(rt, L, st, pass, avg_ws, n_launches); continue; }
+		if (rt.coop_auto && !gen) e = launch_coop(rt, L, st, pass, avg_ws, n_launches);   // (and the one-wave kernels below: each goes by its own count)
+		if (rt.tile && (!gen || rt.tile_gen)) e = launch_tile(rt, L, st, gen, pass, n_launches);
+		else if (rt.td) e = launch_td(rt, L, st, pass);
+		else switch (rt.wave_r) {
+		case 256: e = launch_wave<256>(rt, L, st, gen, pass); break;
+		case 512: e = launch_wave<512>(rt, L, st, gen, pass); break;
+		default:  e = launch_wave<1024>(rt, L, st, gen, pass); break;
 		}
 		if (n_launches) ++*n_launches;
 	}

@@ -1092,7 +1092,7 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	HIP_TRY(on.err);
 	hipStream_t st;
 	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
-	mm2c::LaunchArgs L;
+	mm2c::LaunchArgs L; knobs_into(L);
 	L.P = to_kparams(&pl->par);
 	// the packed f / p words of finished tiles (chain_dp_tile.h, Lds<> RING 3), 4 B per anchor: taken by the first run that can use them (the knobs on, scalars the
 	// compact ring takes); a plan that cannot get them runs without the packed ring
@@ -1102,17 +1102,16 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	// Nor does a plan whose gap cost can be a gain (gap_scale < 0): the packed word holds f up to the task's span sum, and f[i] stays below that sum only while no score
 	// adds more than the anchor's span (chain_dp_tile.h, Lds<> RING 3; chain_dp_coop.h guards gap_scale >= 0 for the same reason).
 	const bool packed_ok = G.packed_fp && pl->sizes_desc[0] <= mm2c::PK_MAX_N && pl->par.gap_scale >= 0.f;
-	if (!pl->d_w && !pl->d_dists_user && packed_ok && G.compact_ring && L.P.max_dist_x >= 0 && L.P.max_dist_x <= 65535 && L.P.max_dq >= 1 && L.P.max_dq <= 32768)
+	if (!pl->d_w && !pl->d_dists_user && packed_ok && G.compact_ring && mm2c::compact_scalars_ok(L.P))
 		if (dev_alloc((void **)&pl->d_w, (size_t)std::max<int64_t>(pl->total, 1) * 4) != hipSuccess) { pl->d_w = nullptr; (void)hipGetLastError(); }
 	L.n_tasks = pl->n_tasks; L.d_offsets = pl->d_off_user ? pl->d_off_user : pl->d_off; L.d_order = pl->d_order;
 	L.d_anchors = d_anchors; L.d_avg = d_avg_qspan; L.d_pbase = nullptr; L.d_f = d_f; L.d_p = d_p; L.d_t = pl->d_t; L.d_st = pl->d_st; L.d_w = pl->d_w; L.packed_fp = packed_ok ? 1 : 0; L.d_status = pl->d_status;
 	L.d_avg_ws = pl->d_avg_ws;
-	L.d_cls = pl->d_cls; L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10;
+	L.d_cls = pl->d_cls;
 	L.d_cls_stat = (unsigned long long *)(pl->d_cls + (((size_t)std::max<int64_t>(pl->n_tasks, 1) + 15) & ~(size_t)15));
 	// the class bytes with the counters behind them: the prepass writes no byte for a task without anchors, and chain_cls_settle only adds to what it finds there --
 	// such a task would keep the bits an earlier run of the plan (or an earlier owner of the block) left
 	HIP_TRY(hipMemsetAsync(pl->d_cls, 0, (size_t)((char *)L.d_cls_stat - (char *)pl->d_cls) + 32 * mm2c::CLS_STAT_SLOTS, st));
-	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.wide_pct = G.wide_pct; L.noskip_loop = G.noskip_loop;
 	HIP_TRY(hipMemsetAsync(pl->d_status, 0, (size_t)pl->n_tasks * 4, st));
 	// Few long pieces: several waves per piece (chain_dp_coop.h; launch_chain_dp takes it for the variants of the hand-written loop).  "coop_plans" 2 (default, round 6):
 	// decided per run by coop_pays (chain_kernel.h) -- here when the tasks run as they are, on the device (chain_route) when long tasks are cut into pieces first;
@@ -1121,7 +1120,7 @@ int mm2c_plan_run_device(mm2c_plan_t *pl, const void *d_anchors, const float *d_
 	const int64_t longest = pl->sizes_desc.empty() ? 0 : (int64_t)pl->sizes_desc[0];
 	const bool will_cut = G.plan_cut && G.seg_min > 0 && longest >= G.plan_cut_min;
 	if (pl->d_seg_ws && !pl->d_off_user && G.seg_prepass.load()) { L.d_seg_ws = pl->d_seg_ws; L.longest_task = longest; }
-	L.coop_waves = 0; L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
+	L.coop_waves = 0;
 	if (coop_mode == 1 && pl->n_tasks <= G.coop_max_tasks) L.coop_waves = G.coop_waves.load();
 	else if (coop_mode == 2 && !will_cut && !pl->d_off_user && mm2c::coop_pays(pl->n_tasks, longest, pl->total, G.coop_w8_above.load())) L.coop_waves = G.coop_waves.load();
 	else if (coop_mode == 2 && will_cut) L.coop_waves = -1;

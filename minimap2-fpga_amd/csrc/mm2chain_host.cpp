@@ -216,18 +216,14 @@ int run_requests(ThreadCtx *c, HostReq **reqs, int n_req)
 			HIP_TRY(hipMemcpyAsync(c->d_in + o_a + (size_t)a0 * 16, src + a0, (size_t)(a1 - a0) * 16, hipMemcpyHostToDevice, c->st_up));
 			HIP_TRY(hipEventRecord(ev_up, c->st_up));
 			HIP_TRY(hipStreamWaitEvent(st, ev_up, 0));
-			mm2c::LaunchArgs L; L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
+			mm2c::LaunchArgs L; knobs_into(L, (size_t)k < max_launches);
 			L.P = to_kparams(par);
 			L.n_tasks = s1 - s0; L.d_offsets = (const int64_t *)(c->d_in + o_off) + s0; L.d_order = nullptr;
 			L.d_anchors = c->d_in + o_a; L.d_avg = kernel_avg ? nullptr : (const float *)(c->d_in + o_avg) + s0;
 			L.d_pbase = (const int32_t *)(c->d_in + o_pb) + s0; L.d_status = (int32_t *)(c->d_in + o_stat) + s0;
 			L.d_f = (int32_t *)c->d_out; L.d_p = (int32_t *)(c->d_out + (size_t)total * 4);
 			L.d_t = (int32_t *)c->d_scratch; L.d_st = (int32_t *)(c->d_scratch + (size_t)total * 4);
-			L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop;
-			if ((size_t)k < max_launches) {
-				L.d_cls = (uint8_t *)(c->d_in + o_cls) + s0; L.d_cls_stat = (unsigned long long *)(c->d_in + o_cstat + cstat_bytes * (size_t)k);
-				L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct;
-			}
+			if ((size_t)k < max_launches) { L.d_cls = (uint8_t *)(c->d_in + o_cls) + s0; L.d_cls_stat = (unsigned long long *)(c->d_in + o_cstat + cstat_bytes * (size_t)k); }
 			// the LAST chunks of the pipeline: nothing follows them that could hide the length of their longest task (one wave per task: 3.5 ms for 5 000 anchors on an
 			// otherwise empty GPU, the tail of the whole batch) -- chunks of few enough pieces take several waves per piece instead ("pipe_coop_chunks": how many, 0 = none)
 			// Round 6: ANY chunk of few long pieces does (coop_pays: a chunk of long reads has fewer pieces than the GPU has wave slots).
@@ -267,7 +263,7 @@ int run_requests(ThreadCtx *c, HostReq **reqs, int n_req)
 			at += nb;
 		}
 	}
-	mm2c::LaunchArgs L; L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
+	mm2c::LaunchArgs L; knobs_into(L);
 	L.P = to_kparams(par);
 	L.n_tasks = n_seg; L.d_offsets = (const int64_t *)(c->d_in + o_off); L.d_order = (const int32_t *)(c->d_in + o_ord);
 	L.d_anchors = c->d_in + o_a; L.d_avg = kernel_avg ? nullptr : (const float *)(c->d_in + o_avg); L.d_pbase = (const int32_t *)(c->d_in + o_pb);
@@ -275,9 +271,7 @@ int run_requests(ThreadCtx *c, HostReq **reqs, int n_req)
 	L.d_f = (int32_t *)c->d_out; L.d_p = (int32_t *)(c->d_out + (size_t)total * 4);
 	L.d_t = (int32_t *)c->d_scratch; L.d_st = (int32_t *)(c->d_scratch + (size_t)total * 4);
 	if (staged && host_st) { L.d_st = (int32_t *)(c->d_in + o_hst); L.st_ready = 1; }   // (came up with the arena; a pass that runs one wave per piece after all computes them again, with its classes)
-	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop;
 	L.d_cls = (uint8_t *)(c->d_in + o_cls); L.d_cls_stat = (unsigned long long *)(c->d_in + o_cstat);
-	L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct;
 	// a pass of few pieces (a lone call, a handful of combined calls) cannot fill the GPU with one wave per piece: several waves per piece (chain_dp_coop.h)
 	// (round 6: and a bigger pass of few LONG pieces, coop_pays)
 	{
@@ -724,14 +718,12 @@ int mm2c_mm_chain_dp_batch_host(const mm2c_params_t *par, int min_cnt, int min_s
 		HIP_TRY(hipMemcpyAsync(w.d_in + o_off, w.h_meta, meta_bytes, hipMemcpyHostToDevice, w.st));
 		HIP_TRY(hipMemcpyAsync(w.d_in, a0 + (h_offsets[k0] - h_offsets[0]), tot * 16, hipMemcpyHostToDevice, w.st));
 		int32_t *d_f = (int32_t *)w.d_work, *d_p = d_f + tot;
-		mm2c::LaunchArgs L; L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
+		mm2c::LaunchArgs L; knobs_into(L);
 		L.P = to_kparams(par);
 		L.n_tasks = (int64_t)nt; L.d_offsets = (const int64_t *)(w.d_in + o_off); L.d_order = (const int32_t *)(w.d_in + o_ord);
 		L.d_anchors = w.d_in; L.d_avg = nullptr; L.d_pbase = nullptr; L.d_status = (int32_t *)(w.d_in + o_stat);
 		L.d_f = d_f; L.d_p = d_p; L.d_t = d_p + tot; L.d_st = d_p + 2 * tot;
-		L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop;
 		L.d_cls = (uint8_t *)(w.d_in + o_cls); L.d_cls_stat = (unsigned long long *)(w.d_in + o_clstat);       // the prepass classes, as plans have them
-		L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct;
 		if (mp > 0 && mp <= (size_t)INT32_MAX) {
 			char *b = w.d_work;
 			L.cut.max_pieces = (int64_t)mp; L.cut.seg_min = G.seg_min; L.cut.min_anchors = G.plan_cut_min;
