@@ -136,6 +136,7 @@ def test_bucket_forms_of_the_replay(route, monkeypatch):
     _all(sd.set_d(), route)
 
 
+# (the epilogue's other limits -- key width, 1 024 chain ends, 768 with distinct x, CAP / 2, 4 096 tied chains, chunks of 256: tests/test_gpu_epilogue_limits.py)
 def test_epilogue_orders_64_65_768_and_769_chains_with_equal_first_x():
     import mm2chain
     from mm2chain import params
