@@ -3,7 +3,7 @@
  *
  *   sketch_dump sketch <k> <w> <is_hpc> <reads.bin> <out.bin>
  *       per read: int64 n, then n x {uint64 x, y} -- what mm_sketch appends for that read with rid 0 (collect_minimizers, map.c:64-77, n_segs = 1)
- *   sketch_dump index <k> <w> <ref.fa> <reads.bin> <out.bin>
+ *   sketch_dump index <k> <w> <ref.fa> <reads.bin> <out.bin> [is_hpc]
  *       the first index part of <ref.fa> (mm_idx_reader_read, MM_I_NO_SEQ) and, against it, collect_matches per read (map.c:90-123, restated):
  *       int32 mid_occ (mm_idx_cal_max_occ(mi, 2e-4), options.c:21,62-63), int64 n_pool, n_pool x uint64 pool, int64 n_keys, n_keys x {uint64 key,
  *       int64 cr_off, uint32 n}, then per read: int64 n_mini, n_mini x {x, y}; int32 rep_len; int64 n_m, n_m x {int64 cr_off, uint32 n, q_pos, q_span,
@@ -71,7 +71,7 @@ int main(int argc, char *argv[])
 		fclose(out);
 		return 0;
 	}
-	if (argc == 7 && strcmp(argv[1], "index") == 0) {
+	if ((argc == 7 || argc == 8) && strcmp(argv[1], "index") == 0) {
 		mm_idxopt_t io;
 		mm_idx_reader_t *rd;
 		mm_idx_t *mi;
@@ -83,6 +83,7 @@ int main(int argc, char *argv[])
 		mm_verbose = 1;
 		mm_idxopt_init(&io);
 		io.k = atoi(argv[2]); io.w = atoi(argv[3]); io.flag |= MM_I_NO_SEQ;
+		if (argc == 8 && atoi(argv[7])) io.flag |= MM_I_HPC;
 		rd = mm_idx_reader_open(argv[4], &io, 0);
 		if (!rd || !(mi = mm_idx_reader_read(rd, 1))) { fprintf(stderr, "cannot index %s\n", argv[4]); return 1; }
 		load_reads(argv[5]);
@@ -172,6 +173,6 @@ int main(int argc, char *argv[])
 		fclose(out);
 		return 0;
 	}
-	fprintf(stderr, "usage: %s sketch <k> <w> <is_hpc> <reads.bin> <out.bin> | index <k> <w> <ref.fa> <reads.bin> <out.bin>\n", argv[0]);
+	fprintf(stderr, "usage: %s sketch <k> <w> <is_hpc> <reads.bin> <out.bin> | index <k> <w> <ref.fa> <reads.bin> <out.bin> [is_hpc]\n", argv[0]);
 	return 1;
 }

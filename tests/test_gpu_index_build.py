@@ -17,6 +17,7 @@ import torch
 
 import index_model as im
 import oracle_binding as ob
+from helpers import assert_table as _assert_table
 
 pytestmark = pytest.mark.gpu
 
@@ -136,24 +137,6 @@ def _ava_reads(seed=77):
 
 
 # ---- comparison ----------------------------------------------------------------------------------------------------------------------------------------
-
-def _assert_table(got, ref, what):
-    """(keys, cr_off, n, pool) of an export against a table whose offsets may differ: keys, counts and every key's hit list"""
-    keys, cr, n, pool = got
-    rk, rcr, rn, rpool = ref
-    assert np.array_equal(keys, rk), f"{what}: {keys.size} keys, expected {rk.size}"
-    assert np.array_equal(n, rn), f"{what}: counts differ at rows {np.nonzero(n != rn)[0][:8]}"
-    assert pool.size == int(n.astype(np.int64).sum()), f"{what}: one pool slot per hit"
-    if keys.size:
-        assert np.array_equal(cr, np.concatenate([[0], np.cumsum(n.astype(np.int64))[:-1]])), f"{what}: cr_off is the exclusive scan of n"
-    # every key's hits, gathered in key order from either pool
-    take = lambda c, m, p: p[np.repeat(c.astype(np.int64), m) + (np.arange(int(m.astype(np.int64).sum())) - np.repeat(np.cumsum(m.astype(np.int64)) - m, m))]
-    a, b = take(cr, n, pool), take(rcr, rn, rpool)
-    if not np.array_equal(a, b):
-        i = int(np.nonzero(a != b)[0][0])
-        row = int(np.searchsorted(np.cumsum(n.astype(np.int64)), i, side="right"))
-        raise AssertionError(f"{what}: key {int(keys[row]):#x} ({int(n[row])} hits) differs")
-
 
 def _model_occ(n, frac):
     """index_model.cal_max_occ, and INT32_MAX for an index without keys (the reference is undefined there; include/mm2chain.h says what the library returns)"""
