@@ -300,6 +300,53 @@ int mm2c_mm_chain_dp_batch_host(const mm2c_params_t *par, int min_cnt, int min_s
                                 const mm2c_anchor_t *h_anchors, int epilogue_threads, int64_t *u_off, uint64_t *u, int64_t *b_off,
                                 mm2c_anchor_t *b);
 
+/* ---- chains -> regions on the GPU (mm_gen_regs, hit.c:52-88: the line of mm_map_frag behind mm_chain_dp, map.c:344) ----
+ * mm2c_reg_t has the fields of mm_reg1_t (minimap.h:85-100) in the same order at the same offsets, 80 bytes: the bit-field word is `flags`
+ * (mapq bits 0-7, split bits 8-9, rev bit 10, ... as GCC lays out minimap.h:96) and the pointer p is a uint64_t, always 0 here.  The regions the
+ * entries below write are, byte for byte, the calloc'ed array mm_gen_regs returns: a host may memcpy them into its mm_reg1_t[]. */
+typedef struct {
+	int32_t id, cnt, rid, score;
+	int32_t qs, qe, rs, re;
+	int32_t parent, subsc;
+	int32_t as;
+	int32_t mlen, blen;
+	int32_t n_sub;
+	int32_t score0;
+	uint32_t flags;
+	uint32_t hash;
+	float div;
+	uint64_t p;
+} mm2c_reg_t;
+#define MM2C_REG_REV_BIT 10
+
+/* A plan for batches of up to n_reads reads, n_u_cap chains and n_b_cap chain anchors in all (its scratch, 64 bytes per chain, is sized from the capacities).
+ * The input is the compact output of the device epilogue (mm2c_plan_chains_device): d_u_off / d_b_off (n_reads + 1 entries each), d_u, d_b, plus per
+ * read d_qlen (the qlen argument of mm_gen_regs: the summed length of the fragment's segments) and d_hash (map.c:290-292, mm2c_read_hash).  The regions
+ * of read r are d_regs[u_off[r] .. u_off[r+1]) in the reference's order: regions are indexed like u, and d_regs (8-byte aligned) has room for n_u_cap of
+ * them.  All pointers are device memory; the call is asynchronous on `stream` (NULL / MM2C_STREAM_LIBRARY as everywhere) and may follow
+ * mm2c_plan_chains_device on the same stream with that call's outputs, the host never having seen u_off.
+ * Preconditions (mm_chain_dp guarantees them): every chain has cnt = (int32_t)u[i] >= 1, and the counts of a read add up to b_off[r+1] - b_off[r].
+ * A read that breaks them -- or whose offsets leave the capacities -- gets unspecified regions and mm2c_regplan_check answers MM2C_E_ARG; nothing is read
+ * outside [b_off[r], b_off[r+1]) for read r whatever u holds, and the regions of the other reads are not affected.  mm_mark_alt / mm_hit_sort (indices
+ * with ALT contigs) are not part of this. */
+typedef struct mm2c_regplan mm2c_regplan_t;
+mm2c_regplan_t *mm2c_regplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_b_cap);
+void mm2c_regplan_destroy(mm2c_regplan_t *plan);
+int mm2c_regplan_run_device(mm2c_regplan_t *plan, const int64_t *d_u_off, const uint64_t *d_u, const int64_t *d_b_off, const void *d_b,
+                            const int32_t *d_qlen, const uint32_t *d_hash, mm2c_reg_t *d_regs, void *stream);
+/* waits for the last run; MM2C_E_ARG if a read's counts disagreed.  *n_reads_with_ties: reads in which two chains had the same sort key (hit.c:65) */
+int mm2c_regplan_check(mm2c_regplan_t *plan, int64_t *n_reads_with_ties);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: the same for the sort kernel (keys, order, fields) and the fill kernel (mlen, blen) */
+int mm2c_regplan_last_ms(mm2c_regplan_t *plan, float *ms);
+int mm2c_regplan_last_kernel_ms(mm2c_regplan_t *plan, float *sort_ms, float *fill_ms);
+/* host arrays in, regions out (regs: room for u_off[n_reads] - u_off[0] regions).  Checks the offsets, cnt >= 1 and the count sums first (MM2C_E_ARG,
+ * before any device work), then uploads, runs, downloads and waits. */
+int mm2c_gen_regs_batch_host(int64_t n_reads, const int64_t *u_off, const uint64_t *u, const int64_t *b_off, const mm2c_anchor_t *b,
+                             const int32_t *qlen, const uint32_t *hash, mm2c_reg_t *regs);
+/* the hash mm_map_frag hands to mm_gen_regs (map.c:290-292): X31 string hash of the read name (0 for NULL) ^ (Wang(qlen_sum) + Wang(seed)), then Wang again.
+ * seed = mm_mapopt_t::seed (11 by default).  Host only, needs no device. */
+uint32_t mm2c_read_hash(const char *qname, int32_t qlen_sum, int32_t seed);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

@@ -70,6 +70,12 @@ class IndexStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("calls", "chunks", "bases", "minimizers", "keys", "h2d_ns", "sketch_ns", "sort_ns", "group_ns", "occ_ns", "replicate_ns")]
 
 
+class Reg(C.Structure):
+    """mm2c_reg_t = mm_reg1_t (minimap.h:85-100), 80 bytes; flags: mapq bits 0-7, split bits 8-9, rev bit 10"""
+    _fields_ = [(k, C.c_int32) for k in ("id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "as_", "mlen", "blen", "n_sub", "score0")] + \
+               [("flags", C.c_uint32), ("hash", C.c_uint32), ("div", C.c_float), ("p", C.c_uint64)]
+
+
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
     "mm2c_init_devices": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
@@ -122,6 +128,14 @@ C_SYMBOLS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_mm_chain_dp_batch_host": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_regplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64]),
+    "mm2c_regplan_destroy": (None, [C.c_void_p]),
+    "mm2c_regplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_regplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "mm2c_regplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_regplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mm2c_gen_regs_batch_host": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_read_hash": (C.c_uint32, [C.c_char_p, C.c_int32, C.c_int32]),
     "mm2c_seedplan_create": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_seedplan_destroy": (None, [C.c_void_p]),
     "mm2c_seedplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -337,6 +337,89 @@ def chain_epilogue_host(min_cnt, min_sc, offsets, anchors, f, p, n_threads=4):
     return _split_chains(n_tasks, u_off, u, b_off, b)
 
 
+REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "as", "mlen", "blen", "n_sub", "score0")] +
+                     [("flags", "<u4"), ("hash", "<u4"), ("div", "<f4"), ("p", "<u8")])   # mm2c_reg_t = mm_reg1_t, 80 bytes
+
+
+class RegPlan:
+    """mm2c_regplan_t: chains -> regions on the GPU (mm_gen_regs, hit.c:52-88) for batches of up to n_reads reads, n_u_cap chains, n_b_cap chain anchors"""
+
+    def __init__(self, n_reads, n_u_cap, n_b_cap):
+        self.lib = N.load()
+        self.n_reads, self.n_u_cap, self.n_b_cap = int(n_reads), int(n_u_cap), int(n_b_cap)
+        self.handle = self.lib.mm2c_regplan_create(self.n_reads, self.n_u_cap, self.n_b_cap)
+        if not self.handle:
+            N.check(-1, "mm2c_regplan_create")
+
+    def run(self, u_off: torch.Tensor, u: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, qlen: torch.Tensor, hash: torch.Tensor, regs: torch.Tensor = None,
+            stream=None):
+        """the device epilogue's compact output (u_off / b_off int64 [n_reads + 1], u int64, b int64 [., 2]) plus qlen int32 and hash (32-bit integers) per read, all on
+        the GPU; returns regs: uint8 [n_u_cap, 80], the regions of read r in rows u_off[r] .. u_off[r+1] (view the host copy as REG_DTYPE).  Asynchronous."""
+        for t in (u_off, u, b_off, b, qlen, hash):
+            assert t.is_cuda and t.is_contiguous()
+        assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1 and b_off.numel() == self.n_reads + 1
+        assert u.element_size() == 8 and u.numel() >= self.n_u_cap and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
+        assert qlen.dtype == torch.int32 and qlen.numel() == self.n_reads and hash.element_size() == 4 and hash.numel() == self.n_reads
+        if regs is None:
+            regs = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u.device)
+        assert regs.is_cuda and regs.is_contiguous() and regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_regplan_run_device(self.handle, u_off.data_ptr(), u.data_ptr(), b_off.data_ptr(), b.data_ptr(), qlen.data_ptr(), hash.data_ptr(),
+                                                 regs.data_ptr(), st), "mm2c_regplan_run_device")
+        return regs
+
+    def check(self):
+        """waits for the run; raises if a read's chain counts disagreed with its extent of b; returns the number of reads that held equal sort keys"""
+        n = C.c_int64(0)
+        N.check(self.lib.mm2c_regplan_check(self.handle, C.byref(n)), "mm2c_regplan_check")
+        return n.value
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_regplan_last_ms(self.handle, C.byref(ms)), "mm2c_regplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(sort kernel, fill kernel) of the last run"""
+        a, b = C.c_float(0), C.c_float(0)
+        N.check(self.lib.mm2c_regplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_regplan_last_kernel_ms")
+        return a.value, b.value
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_regplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gen_regs_batch(u_off, u, b_off, b, qlen, hash):
+    """mm2c_gen_regs_batch_host: host arrays in, the regions of every read out (REG_DTYPE [u_off[-1] - u_off[0]], indexed like u)"""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
+    uu = np.ascontiguousarray(u, dtype=np.uint64)
+    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    q = np.ascontiguousarray(qlen, dtype=np.int32); h = np.ascontiguousarray(hash, dtype=np.uint32)
+    n_reads = uo.size - 1
+    if bo.size != uo.size or q.size != n_reads or h.size != n_reads or (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > uu.size or bo.max() > bb.shape[0])):
+        raise ValueError("offsets do not fit the arrays")
+    regs = np.zeros(max(int(uo[-1] - uo[0]), 1) if n_reads > 0 else 1, REG_DTYPE)
+    N.check(lib.mm2c_gen_regs_batch_host(n_reads, _np_ptr(uo), _np_ptr(uu), _np_ptr(bo), _np_ptr(bb), _np_ptr(q), _np_ptr(h), _np_ptr(regs)),
+            "mm2c_gen_regs_batch_host")
+    return regs[:int(uo[-1] - uo[0]) if n_reads > 0 else 0]
+
+
+def read_hash(name, qlen_sum, seed=11):
+    """mm2c_read_hash: the hash mm_map_frag hands to mm_gen_regs (map.c:290-292); name: str, bytes or None.  Needs no device."""
+    if isinstance(name, str):
+        name = name.encode()
+    return int(N.load().mm2c_read_hash(name, int(qlen_sum), int(seed)))
+
+
 MATCH_DTYPE = np.dtype([("cr_off", "<i8"), ("n", "<u4"), ("q_pos", "<u4"), ("q_span", "<u4"), ("seg_tandem", "<u4")])   # mm2c_match_t
 
 
