@@ -347,6 +347,40 @@ int mm2c_gen_regs_batch_host(int64_t n_reads, const int64_t *u_off, const uint64
  * seed = mm_mapopt_t::seed (11 by default).  Host only, needs no device. */
 uint32_t mm2c_read_hash(const char *qname, int32_t qlen_sum, int32_t seed);
 
+/* ---- regions -> hits on the GPU (chain_post for one-segment reads, map.c:249-258: mm_set_parent hit.c:125-186, then mm_select_sub hit.c:255-272 with
+ * mm_sync_regs / mm_set_sam_pri hit.c:220-253) ----
+ * Which regions are primary, which stay as secondary, and the subsc / n_sub the mapping quality is later made of.  The regions of read r are
+ * d_regs_in[u_off[r] .. u_off[r+1]) exactly as mm2c_regplan_run_device wrote them; the same u_off indexes d_regs_out, whose first d_n_out[r] entries from
+ * u_off[r] on are, byte for byte, the array the reference holds after the two calls on that read (d_n_out[r] is *n_ after mm_select_sub); the entries behind
+ * them up to u_off[r+1] are unspecified.  With pri_ratio <= 0 mm_select_sub does nothing: n_out = n and the regions carry mm_set_parent's changes only.
+ * The fields p, is_alt and inv are always 0 in these regions, so the reference's branches on them (hit.c:168, 171-176, 261, 266-267: ALT contigs, alignment
+ * extras, inversions) are dead and are not built; sub_diff and alt_diff_frac therefore have no counterpart in mm2c_hit_opt_t.
+ * The float tests (hit.c:165, :263) are evaluated in IEEE single precision as written.  mm_select_sub compacts in place while it still reads r[p]: a child is
+ * judged against whatever region lies at its parent's position by then, and so it is here.
+ * d_regs_out must not alias d_regs_in; both 8-byte aligned with room for n_u_cap regions, d_n_out for n_reads.  The call is asynchronous on `stream` (NULL /
+ * MM2C_STREAM_LIBRARY as everywhere) and may follow mm2c_regplan_run_device on the same stream, the host never having seen u_off.  A read whose offsets leave
+ * the capacities touches nothing and mm2c_hitplan_check answers MM2C_E_ARG.  Reads of up to MM2C_HIT_LDS_REGIONS regions are worked in on-chip memory, longer
+ * ones in the plan's scratch (60 bytes per region), with the same result.  mm_select_sub_multi (fragments of several segments) is not part of this. */
+typedef struct {
+	float mask_level; int32_t mask_len; int32_t hard_mask_level;   /* mm_set_parent: opt->mask_level, opt->mask_len, opt->flag & MM_F_HARD_MLEVEL */
+	float pri_ratio; int32_t min_diff; int32_t best_n;             /* mm_select_sub: opt->pri_ratio, mi->k * 2, opt->best_n */
+} mm2c_hit_opt_t;
+#define MM2C_REG_SAM_PRI_BIT 12
+#define MM2C_HIT_LDS_REGIONS 128
+typedef struct mm2c_hitplan mm2c_hitplan_t;
+mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap);
+void mm2c_hitplan_destroy(mm2c_hitplan_t *plan);
+int mm2c_hitplan_run_device(mm2c_hitplan_t *plan, const mm2c_hit_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in,
+                            mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream);
+/* waits for the last run; MM2C_E_ARG if a read's offsets left the capacities.  *n_hits_total: the sum of n_out */
+int mm2c_hitplan_check(mm2c_hitplan_t *plan, int64_t *n_hits_total);
+/* milliseconds of the last run between HIP events on its stream */
+int mm2c_hitplan_last_ms(mm2c_hitplan_t *plan, float *ms);
+/* host arrays in, hits out (regs_out: room for u_off[n_reads] - u_off[0] regions, read r from u_off[r] - u_off[0] on).  Checks the offsets first
+ * (MM2C_E_ARG, before any device work), then uploads, runs, downloads and waits. */
+int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out,
+                                int32_t *n_out);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

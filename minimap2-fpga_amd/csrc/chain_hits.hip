@@ -1,0 +1,208 @@
+// chain_hits.hip -- mm_set_parent (hit.c:125-186) and mm_select_sub (hit.c:255-272, with mm_sync_regs / mm_set_sam_pri hit.c:220-253) on the GPU: the
+// regions of the region plan (chain_regs.hip) become the reference's hits, byte for byte.  The fields p, is_alt and inv are always 0 here, so the branches on
+// them (hit.c:168, 171-176, 261, 266-267) are not built.
+//
+// One kernel, hits_select, one wave per read.  The reference is sequential in the regions of a read; what is parallel is the walk over the primaries:
+//
+//   tables    : qs qe score cnt subsc n_sub parent rid rs re per region, and (qs, qe) of the primaries in the order they were made (w, hit.c:132).  In LDS for
+//               reads of up to HITS_LDS_MAX regions, in the plan's scratch beyond -- the same code, instantiated on the two kinds of pointer.
+//   set_parent: for region i the lanes take the primaries 64 at a time.  Pass 1 packs the clipped overlaps (hit.c:138-145) with a ballot; uncov_len is the
+//               measure of [qs_i, qe_i) outside their union.  The reference sorts the intervals and sweeps; the measure does not depend on how it is found, so
+//               here every lane takes one candidate gap start g (qs_i or the end of an interval): it opens a gap if no interval holds g, g < qe_i and no earlier
+//               interval ends at g too, and the gap reaches to the nearest interval start beyond g (or qe_i).  Integers only; O(n_cov^2 / 64).  Pass 2
+//               evaluates hit.c:160-165 per lane -- int -> float, two IEEE divisions, one subtraction, one comparison, as written -- and the first passing
+//               primary in w order is the lowest set bit of the first non-empty ballot.  Lane 0 then updates that primary's subsc / n_sub or appends the region
+//               to the primaries, before the next region looks.
+//   select_sub: hit.c:259-268 compacts in place while it reads r[p]: at step i position p holds the kept region of rank p if k > p, else the original r[p].
+//               Lane 0 walks that chain over the tables and leaves the source index of every kept position; no record moves yet.
+//   move      : the 80-byte records go from the input to the output through that map, lane-parallel as 8-byte words, patched on the way: id, parent, subsc,
+//               n_sub, and -- only when something was dropped (hit.c:269) -- the new ids, the parents through them, and sam_pri (bit 12) on the first hit.
+//
+// A read whose offsets leave the plan's capacities touches nothing and is counted in flags[0].
+
+#include <hip/hip_runtime.h>
+#include <climits>
+#include "chain_hits.h"
+#include "chain_regs.h"
+
+namespace mm2c {
+
+namespace {
+
+constexpr uint32_t SAM_PRI = 1u << 12;                                         // minimap.h:96: mapq:8, split:2, rev:1, inv:1, sam_pri:1
+
+struct HitTab {
+	int32_t *qs, *qe, *score, *cnt, *subsc, *nsub, *parent, *rid, *rs, *re, *w;
+	int2 *pq, *cov;
+};
+
+__device__ __forceinline__ int wave_sum(int v)
+{
+	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+	return v;
+}
+
+__device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, const uint64_t *in, uint64_t *out, int32_t *n_out, const int n, const int lane)
+{
+	for (int i = lane; i < n; i += 64) {
+		const uint64_t *r = in + (int64_t)i * REG_WORDS;
+		const uint64_t w0 = r[0], w1 = r[1], w2 = r[2], w3 = r[3], w4 = r[4], w6 = r[6];
+		T.cnt[i] = (int32_t)(w0 >> 32); T.rid[i] = (int32_t)w1; T.score[i] = (int32_t)(w1 >> 32);
+		T.qs[i] = (int32_t)w2; T.qe[i] = (int32_t)(w2 >> 32); T.rs[i] = (int32_t)w3; T.re[i] = (int32_t)(w3 >> 32);
+		T.parent[i] = (int32_t)w4; T.subsc[i] = (int32_t)(w4 >> 32); T.nsub[i] = (int32_t)(w6 >> 32);
+	}
+	__syncthreads();
+
+	// ---- mm_set_parent (hit.c:133-183) ----
+	if (lane == 0) { T.w[0] = 0; T.parent[0] = 0; T.pq[0] = make_int2(T.qs[0], T.qe[0]); }
+	__syncthreads();
+	int k = 1;
+	const uint64_t lt = (1ull << lane) - 1;
+	for (int i = 1; i < n; ++i) {
+		const int si = __builtin_amdgcn_readfirstlane(T.qs[i]), ei = __builtin_amdgcn_readfirstlane(T.qe[i]);
+		int uncov_len = 0;
+		if (!A.hard_mask_level) {
+			int n_cov = 0, len1 = 0;
+			for (int j0 = 0; j0 < k; j0 += 64) {                                 // hit.c:138-145
+				const int j = j0 + lane;
+				int2 q = make_int2(0, 0);
+				if (j < k) q = T.pq[j];
+				const bool ov = j < k && !(q.y <= si || q.x >= ei);
+				const uint64_t m = __ballot(ov);
+				const int cs = q.x < si ? si : q.x, ce = q.y > ei ? ei : q.y;
+				if (ov) T.cov[n_cov + __popcll(m & lt)] = make_int2(cs, ce);
+				if (m) len1 = __shfl(ce - cs, __ffsll((unsigned long long)m) - 1);
+				n_cov += __popcll(m);
+			}
+			if (n_cov == 1) uncov_len = (ei - si) - len1;                        // one interval, clipped to the region: what it leaves
+			else if (n_cov > 1) {                                                // hit.c:148-156 as a measure
+				__syncthreads();
+				int len = 0;
+				for (int t0 = 0; t0 <= n_cov; t0 += 64) {
+					const int t = t0 + lane;
+					const int g = t < n_cov ? T.cov[t].y : si;
+					bool open = t <= n_cov && g < ei;
+					int end = ei;
+					for (int q = 0; q < n_cov; ++q) {
+						const int2 c = T.cov[q];
+						if (c.x <= g && g < c.y) open = false;
+						if (c.x > g && c.x < end) end = c.x;
+						if (q < t && t < n_cov && c.y == g) open = false;
+					}
+					if (open) len += end - g;
+				}
+				uncov_len = wave_sum(len);
+				__syncthreads();
+			}
+		}
+		int found = -1;
+		for (int j0 = 0; j0 < k && found < 0; j0 += 64) {                        // hit.c:158-165
+			const int j = j0 + lane;
+			int2 q = make_int2(0, 0);
+			if (j < k) q = T.pq[j];
+			const int sj = q.x, ej = q.y;
+			const bool ov = j < k && !(ej <= si || sj >= ei);
+			const int mn = ej - sj < ei - si ? ej - sj : ei - si;
+			const int mx = ej - sj > ei - si ? ej - sj : ei - si;
+			const int ol = si < sj ? (ei < sj ? 0 : ei < ej ? ei - sj : ej - sj) : (ej < si ? 0 : ej < ei ? ej - si : ei - si);
+			const float lhs = (float)ol / (float)mn - (float)uncov_len / (float)mx;
+			const uint64_t m = __ballot(ov && lhs > A.mask_level && uncov_len <= A.mask_len);
+			if (m) found = j0 + __ffsll((unsigned long long)m) - 1;
+		}
+		if (lane == 0) {
+			if (found >= 0) {                                                    // hit.c:166-178
+				const int pi = T.w[found], sci = T.score[i];
+				T.parent[i] = pi;                                                // rp->parent: a primary is its own parent
+				if (T.subsc[pi] < sci) T.subsc[pi] = sci;
+				if (T.cnt[i] >= T.cnt[pi]) ++T.nsub[pi];
+			} else {                                                             // hit.c:182
+				T.w[k] = i; T.pq[k] = make_int2(si, ei); T.parent[i] = i; T.nsub[i] = 0;
+			}
+		}
+		if (found < 0) ++k;
+		__syncthreads();
+	}
+
+	// ---- mm_select_sub (hit.c:257-270): which regions stay, and which region a kept position comes from ----
+	int32_t *src = T.w, *newidx = T.cnt;                                        // (w and cnt have served)
+	int kept = n;
+	if (A.pri_ratio > 0.0f) {
+		if (lane == 0) {
+			int kk = 0, n_2nd = 0;
+			for (int i = 0; i < n; ++i) {
+				const int p = T.parent[i];
+				bool keep = p == i;
+				if (!keep) {
+					const int pp = kk > p ? src[p] : p;                          // what lies at position p by now
+					const int sc = T.score[i], scp = T.score[pp];
+					if (((float)sc >= (float)scp * A.pri_ratio || (int32_t)((uint32_t)sc + (uint32_t)A.min_diff) >= scp) && n_2nd < A.best_n) {
+						if (!(T.qs[i] == T.qs[pp] && T.qe[i] == T.qe[pp] && T.rid[i] == T.rid[pp] && T.rs[i] == T.rs[pp] && T.re[i] == T.re[pp])) keep = true, ++n_2nd;
+					}
+				}
+				if (keep) src[kk++] = i;
+			}
+			src[n] = kk;
+		}
+		__syncthreads();
+		kept = src[n];
+	} else {
+		for (int i = lane; i < n; i += 64) src[i] = i;
+		__syncthreads();
+	}
+	const bool sync = kept != n;                                                // hit.c:269
+	if (sync) {
+		for (int t = lane; t < kept; t += 64) newidx[src[t]] = t;
+		__syncthreads();
+	}
+
+	// ---- the records ----
+	for (int e = lane; e < kept * REG_WORDS; e += 64) {
+		const int t = e / REG_WORDS, wd = e - t * REG_WORDS, s = src[t];
+		uint64_t v = in[(int64_t)s * REG_WORDS + wd];
+		if (wd == 0) v = (v & 0xffffffff00000000ull) | (uint32_t)(sync ? t : s);
+		else if (wd == 4) v = (uint64_t)(uint32_t)(sync ? newidx[T.parent[s]] : T.parent[s]) | (uint64_t)(uint32_t)T.subsc[s] << 32;
+		else if (wd == 6) v = (v & 0xffffffffull) | (uint64_t)(uint32_t)T.nsub[s] << 32;
+		else if (wd == 7 && sync) v = (v & ~((uint64_t)SAM_PRI << 32)) | (uint64_t)(t == 0 ? SAM_PRI : 0u) << 32;   // hit.c:220-229: region 0 is the first primary
+		out[(int64_t)t * REG_WORDS + wd] = v;
+	}
+	if (lane == 0) { *n_out = kept; atomicAdd(A.total, (unsigned long long)kept); }
+}
+
+__global__ __launch_bounds__(64) void hits_select(HitArgs A)
+{
+	__shared__ int32_t s_tab[HITS_TAB_ROWS][HITS_LDS_MAX + 1];
+	__shared__ int2 s_pq[HITS_LDS_MAX], s_cov[HITS_LDS_MAX];
+	const int r = (int)blockIdx.x, lane = (int)threadIdx.x;
+	const int64_t base = A.u_off[r], n64 = A.u_off[r + 1] - base;
+	if (base < 0 || n64 < 0 || n64 > INT_MAX || base + n64 > A.n_u_cap) {
+		if (lane == 0) atomicAdd(&A.flags[0], 1);                                // offsets that leave the plan's capacities: nothing of this read is touched
+		return;
+	}
+	const int n = (int)n64;
+	if (n == 0) { if (lane == 0) A.n_out[r] = 0; return; }
+	const uint64_t *in = A.in + base * REG_WORDS;
+	uint64_t *out = A.out + base * REG_WORDS;
+	HitTab T;
+	if (n <= HITS_LDS_MAX) {
+		T.qs = s_tab[0]; T.qe = s_tab[1]; T.score = s_tab[2]; T.cnt = s_tab[3]; T.subsc = s_tab[4]; T.nsub = s_tab[5]; T.parent = s_tab[6];
+		T.rid = s_tab[7]; T.rs = s_tab[8]; T.re = s_tab[9]; T.w = s_tab[10]; T.pq = s_pq; T.cov = s_cov;
+		hits_read(A, T, in, out, A.n_out + r, n, lane);
+	} else {                                                                     // rows of n_u_cap + n_reads entries: a read's rows hold one entry more than it has regions
+		const int64_t row = A.n_u_cap + A.n_reads;
+		int32_t *g = A.tab + base + r;
+		T.qs = g; T.qe = g + row; T.score = g + 2 * row; T.cnt = g + 3 * row; T.subsc = g + 4 * row; T.nsub = g + 5 * row; T.parent = g + 6 * row;
+		T.rid = g + 7 * row; T.rs = g + 8 * row; T.re = g + 9 * row; T.w = g + 10 * row; T.pq = A.pq + base; T.cov = A.cov + base;
+		hits_read(A, T, in, out, A.n_out + r, n, lane);
+	}
+}
+
+} // namespace
+
+hipError_t launch_chain_hits(const HitArgs &A, hipStream_t st)
+{
+	if (A.n_reads <= 0) return hipSuccess;
+	hipLaunchKernelGGL(hits_select, dim3((unsigned)A.n_reads), dim3(64), 0, st, A);
+	return hipGetLastError();
+}
+
+} // namespace mm2c

@@ -1,0 +1,150 @@
+// mm2chain_hits.cpp -- C-ABI entries of the regions-to-hits step (include/mm2chain.h): hit plans (mm_set_parent + mm_select_sub on the device,
+// chain_hits.hip) and the host-buffer entry built on them.
+#include "api_internal.h"
+#include "chain_hits.h"
+#include "chain_regs.h"
+
+using namespace mm2c_api;
+
+static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_hit_opt_t) == 24, "layout");
+static_assert(MM2C_HIT_LDS_REGIONS == mm2c::HITS_LDS_MAX && MM2C_REG_SAM_PRI_BIT == 12, "constants of mm2chain.h");
+
+struct mm2c_hitplan {
+	int64_t n_reads = 0, n_u_cap = 0;
+	int device = 0;
+	char *d_mem = nullptr;                 // [flags, total | tab | pq | cov]
+	mm2c::HitArgs H;
+	hipEvent_t ev[2] = {};
+	bool ran = false;
+};
+
+extern "C" {
+
+mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap)
+{
+	if (!lib_ready()) { fail_not_ready(); return nullptr; }
+	if (n_reads < 0 || n_reads > INT32_MAX || n_u_cap < 0 || n_u_cap > INT32_MAX) { fail(MM2C_E_ARG, "bad argument"); return nullptr; }
+	mm2c_hitplan *pl = new mm2c_hitplan();
+	pl->n_reads = n_reads; pl->n_u_cap = n_u_cap;
+	const size_t nu = (size_t)std::max<int64_t>(n_u_cap, 1), row = (size_t)(n_u_cap + n_reads) + 1;
+	Layout L;
+	const size_t o_fl = L.take(16), o_tab = L.take(row * 4 * mm2c::HITS_TAB_ROWS), o_pq = L.take(nu * 8), o_cov = L.take(nu * 8);
+	pl->device = cur_device();
+	DeviceScope on(pl->device);
+	hipError_t e = on.err;
+	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
+	for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_hitplan_create: %s", hipGetErrorString(e)); mm2c_hitplan_destroy(pl); return nullptr; }
+	mm2c::HitArgs &H = pl->H;
+	char *b = pl->d_mem;
+	H.n_reads = n_reads; H.n_u_cap = n_u_cap;
+	H.flags = (int32_t *)(b + o_fl); H.total = (unsigned long long *)(b + o_fl + 8);
+	H.tab = (int32_t *)(b + o_tab); H.pq = (int2 *)(b + o_pq); H.cov = (int2 *)(b + o_cov);
+	return pl;
+}
+
+void mm2c_hitplan_destroy(mm2c_hitplan_t *pl)
+{
+	if (!pl) return;
+	{
+		DeviceScope on(pl->device);
+		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
+		dev_free_synced(pl->d_mem);
+		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
+	}
+	delete pl;
+}
+
+int mm2c_hitplan_run_device(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in,
+                            mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream)
+{
+	if (!pl || !opt) return fail(MM2C_E_ARG, "plan or options are NULL");
+	if (!lib_ready()) return fail_not_ready();
+	if (pl->n_reads == 0) return 0;
+	if (!d_u_off || !d_n_out || (pl->n_u_cap > 0 && (!d_regs_in || !d_regs_out))) return fail(MM2C_E_ARG, "device pointer is NULL");
+	if (((uintptr_t)d_regs_in | (uintptr_t)d_regs_out) & 7) return fail(MM2C_E_ARG, "regions are not 8-byte aligned");
+	if (pl->n_u_cap > 0 && (const mm2c_reg_t *)d_regs_out == d_regs_in) return fail(MM2C_E_ARG, "d_regs_out must not alias d_regs_in");
+	DeviceScope on(pl->device);
+	HIP_TRY(on.err);
+	hipStream_t st;
+	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
+	mm2c::HitArgs &H = pl->H;
+	H.mask_level = opt->mask_level; H.mask_len = opt->mask_len; H.hard_mask_level = opt->hard_mask_level;
+	H.pri_ratio = opt->pri_ratio; H.min_diff = opt->min_diff; H.best_n = opt->best_n;
+	H.u_off = d_u_off; H.in = (const uint64_t *)d_regs_in; H.out = (uint64_t *)d_regs_out; H.n_out = d_n_out;
+	HIP_TRY(hipMemsetAsync(H.flags, 0, 16, st));
+	HIP_TRY(hipEventRecord(pl->ev[0], st));
+	HIP_TRY(mm2c::launch_chain_hits(H, st));
+	HIP_TRY(hipEventRecord(pl->ev[1], st));
+	pl->ran = true;
+	G.launches += 1;
+	return 0;
+}
+
+int mm2c_hitplan_check(mm2c_hitplan_t *pl, int64_t *n_hits_total)
+{
+	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
+	if (n_hits_total) *n_hits_total = 0;
+	if (!pl->ran || pl->n_reads == 0) return 0;
+	DeviceScope on(pl->device);
+	HIP_TRY(on.err);
+	HIP_TRY(hipEventSynchronize(pl->ev[1]));
+	int64_t fl[2] = {0, 0};
+	HIP_TRY(hipMemcpy(fl, pl->H.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if ((int32_t)fl[0] != 0) return fail(MM2C_E_ARG, "%d read(s): offsets beyond the plan's capacities", (int32_t)fl[0]);
+	if (n_hits_total) *n_hits_total = fl[1];
+	return 0;
+}
+
+int mm2c_hitplan_last_ms(mm2c_hitplan_t *pl, float *ms)
+{
+	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
+	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
+	DeviceScope on(pl->device);
+	HIP_TRY(on.err);
+	HIP_TRY(hipEventSynchronize(pl->ev[1]));
+	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+	return 0;
+}
+
+int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out)
+{
+	if (n_reads < 0 || n_reads > INT32_MAX || !opt) return fail(MM2C_E_ARG, "bad argument");
+	if (n_reads == 0) return 0;
+	if (!u_off || !n_out) return fail(MM2C_E_ARG, "host pointer is NULL");
+	const int64_t ub = u_off[0];
+	for (int64_t r = 0; r < n_reads; ++r)
+		if (u_off[r + 1] < u_off[r]) return fail(MM2C_E_ARG, "region offsets not monotone at read %lld", (long long)r);
+	const int64_t n_u = u_off[n_reads] - ub;
+	if (n_u > INT32_MAX) return fail(MM2C_E_TOOBIG, "%lld regions in one call", (long long)n_u);
+	if (n_u > 0 && (!regs_in || !regs_out)) return fail(MM2C_E_ARG, "host pointer is NULL");
+	if (!lib_ready()) return fail_not_ready();
+	std::vector<int64_t> off((size_t)n_reads + 1);
+	for (int64_t k = 0; k <= n_reads; ++k) off[(size_t)k] = u_off[k] - ub;
+	mm2c_hitplan_t *pl = mm2c_hitplan_create(n_reads, n_u);
+	if (!pl) return MM2C_E_HIP;
+	const size_t nr = (size_t)n_reads, rb = (size_t)n_u * sizeof(mm2c_reg_t);
+	char *d = nullptr;
+	Layout L;
+	const size_t o_off = L.take((nr + 1) * 8), o_in = L.take(rb + 8), o_out = L.take(rb + 8), o_n = L.take(nr * 4);
+	auto body = [&]() -> int {
+		DeviceScope on(pl->device);
+		HIP_TRY(on.err);
+		HIP_TRY(dev_alloc((void **)&d, L.at));
+		hipStream_t st = G.stream;
+		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
+		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs_in + ub, rb, hipMemcpyHostToDevice, st));
+		if (const int r = mm2c_hitplan_run_device(pl, opt, (const int64_t *)(d + o_off), (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
+		                                          (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY)) return r;
+		if (n_u > 0) HIP_TRY(hipMemcpyAsync(regs_out, d + o_out, rb, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(n_out, d + o_n, nr * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		return mm2c_hitplan_check(pl, nullptr);
+	};
+	const int rc = body();
+	dev_free(d);
+	mm2c_hitplan_destroy(pl);
+	return rc;
+}
+
+} // extern "C"

@@ -76,6 +76,15 @@ class Reg(C.Structure):
                [("flags", C.c_uint32), ("hash", C.c_uint32), ("div", C.c_float), ("p", C.c_uint64)]
 
 
+class HitOpt(C.Structure):
+    """mm2c_hit_opt_t: mm_set_parent's mask_level, mask_len, MM_F_HARD_MLEVEL and mm_select_sub's pri_ratio, min_diff (2k), best_n"""
+    _fields_ = [("mask_level", C.c_float), ("mask_len", C.c_int32), ("hard_mask_level", C.c_int32), ("pri_ratio", C.c_float), ("min_diff", C.c_int32),
+                ("best_n", C.c_int32)]
+
+
+MM2C_REG_SAM_PRI_BIT = 12
+MM2C_HIT_LDS_REGIONS = 128
+
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
     "mm2c_init_devices": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
@@ -136,6 +145,12 @@ C_SYMBOLS = {
     "mm2c_regplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mm2c_gen_regs_batch_host": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_read_hash": (C.c_uint32, [C.c_char_p, C.c_int32, C.c_int32]),
+    "mm2c_hitplan_create": (C.c_void_p, [C.c_int64, C.c_int64]),
+    "mm2c_hitplan_destroy": (None, [C.c_void_p]),
+    "mm2c_hitplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(HitOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_hitplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "mm2c_hitplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_select_hits_batch_host": (C.c_int, [C.c_int64, C.POINTER(HitOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mm2c_seedplan_create": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_seedplan_destroy": (None, [C.c_void_p]),
     "mm2c_seedplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

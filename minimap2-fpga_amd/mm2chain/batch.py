@@ -420,6 +420,72 @@ def read_hash(name, qlen_sum, seed=11):
     return int(N.load().mm2c_read_hash(name, int(qlen_sum), int(seed)))
 
 
+class HitPlan:
+    """mm2c_hitplan_t: regions -> hits on the GPU (mm_set_parent hit.c:125-186, then mm_select_sub hit.c:255-272) for batches of up to n_reads reads and n_u_cap
+    regions; it stands behind a RegPlan on the same stream"""
+
+    def __init__(self, n_reads, n_u_cap):
+        self.lib = N.load()
+        self.n_reads, self.n_u_cap = int(n_reads), int(n_u_cap)
+        self.handle = self.lib.mm2c_hitplan_create(self.n_reads, self.n_u_cap)
+        if not self.handle:
+            N.check(-1, "mm2c_hitplan_create")
+
+    def run(self, opt, u_off: torch.Tensor, regs_in: torch.Tensor, regs_out: torch.Tensor = None, n_out: torch.Tensor = None, stream=None):
+        """opt: params.hit_opts(); u_off int64 [n_reads + 1] and regs_in (what RegPlan.run returned) on the GPU.  Returns (regs_out uint8 [n_u_cap, 80], n_out int32
+        [n_reads]): the hits of read r are rows u_off[r] .. u_off[r] + n_out[r]; the rows behind them are unspecified.  Asynchronous."""
+        assert u_off.is_cuda and u_off.is_contiguous() and u_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1
+        assert regs_in.is_cuda and regs_in.is_contiguous() and regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        if regs_out is None:
+            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
+        if n_out is None:
+            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
+        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_hitplan_run_device(self.handle, C.byref(opt), u_off.data_ptr(), regs_in.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(), st),
+                "mm2c_hitplan_run_device")
+        return regs_out, n_out[:self.n_reads]
+
+    def check(self):
+        """waits for the run; raises if a read's offsets left the capacities; returns the number of hits of all reads"""
+        n = C.c_int64(0)
+        N.check(self.lib.mm2c_hitplan_check(self.handle, C.byref(n)), "mm2c_hitplan_check")
+        return n.value
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_hitplan_last_ms(self.handle, C.byref(ms)), "mm2c_hitplan_last_ms")
+        return ms.value
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_hitplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def select_hits_batch(opt, u_off, regs):
+    """mm2c_select_hits_batch_host: host arrays in -> (regs_out REG_DTYPE [u_off[-1] - u_off[0]], n_out int32 [n_reads]); the hits of read r are
+    regs_out[u_off[r] - u_off[0] :][:n_out[r]]"""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64))
+    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    n_reads = uo.size - 1
+    if n_reads > 0 and (uo[0] < 0 or uo.max() > rr.shape[0]):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
+    out = np.zeros(max(n_u, 1), REG_DTYPE)
+    n_out = np.zeros(max(n_reads, 1), np.int32)
+    N.check(lib.mm2c_select_hits_batch_host(n_reads, C.byref(opt), _np_ptr(uo), _np_ptr(rr), _np_ptr(out), _np_ptr(n_out)), "mm2c_select_hits_batch_host")
+    return out[:n_u], n_out[:n_reads]
+
+
 MATCH_DTYPE = np.dtype([("cr_off", "<i8"), ("n", "<u4"), ("q_pos", "<u4"), ("q_span", "<u4"), ("seg_tandem", "<u4")])   # mm2c_match_t
 
 

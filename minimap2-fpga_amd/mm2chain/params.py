@@ -1,5 +1,5 @@
 """Chaining parameter presets, mirroring options.c of the reference (file:line cited per preset)."""
-from ._native import Params, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
+from ._native import Params, HitOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
 
 INT32_MAX = 2**31 - 1
 
@@ -38,6 +38,20 @@ def sr(qlen_sum=300, n_segs=2):
 def fpga_v2(max_dist_x=5000, max_dist_y=5000, bw=500, q_span=15):
     """What the reference's FPGA kernel computes for one run_chaining_on_hw call (device/minimap2_opencl.cl)."""
     return make_params(max_dist_x, max_dist_y, bw, INT32_MAX, 1024, 1.0, 0, 1, q_span, MM2C_F_IGNORE_SEG)
+
+
+def hit_opts(k=15, **kw):
+    """mm2c_hit_opt_t with the defaults of options.c:33-36: mask_level 0.5, mask_len INT_MAX, pri_ratio 0.8, best_n 5; min_diff = 2k as mm_map_frag passes it
+    (map.c:253); hard_mask_level = opt->flag & MM_F_HARD_MLEVEL, off by default.  What the presets change (options.c:82-151; k is the index's):
+    ava-ont: pri_ratio 0 (k 15) -- mm_select_sub then does nothing, and with MM_F_ALL_CHAINS chain_post skips both calls (map.c:251);  ava-pb: the same
+    with k 19;  map-pb / map10k: k 19;  map-ont: k 15;
+    asm5 / asm10 / asm20: best_n 50, k 19;  sr / short: pri_ratio 0.5, best_n 20, k 21;  splice / cdna: k 15.  Keywords override single fields."""
+    v = dict(mask_level=0.5, mask_len=INT32_MAX, hard_mask_level=0, pri_ratio=0.8, min_diff=2 * k, best_n=5)
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"hit_opts: unknown field(s) {sorted(unknown)}")
+    v.update(kw)
+    return HitOpt(v["mask_level"], v["mask_len"], int(bool(v["hard_mask_level"])), v["pri_ratio"], v["min_diff"], v["best_n"])
 
 
 def as_dict(p):
