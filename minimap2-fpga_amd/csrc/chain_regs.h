@@ -24,7 +24,8 @@ struct RegArgs {
 	uint64_t *zkey, *key0, *key1;      // the sort keys z.x in chain order (never overwritten) / the two buffers of the sorts
 	int64_t *cstart, *cend;            // per chain: its anchors are b[cstart .. cend), clamped to the read's extent
 	int32_t *val0, *val1, *crank, *tiecnt, *stack, *moved;   // crank: chain -> its region
-	int32_t *flags;                    // [0]: reads whose counts or offsets disagree, [1]: reads that hold equal keys; zero on entry
+	int32_t *flags;                    // [0]: reads whose counts or offsets disagree, [1]: reads that hold equal keys, [2]: reads refused for their offsets (regs_fill
+	                                   // then goes read by read); four words, zero on entry
 };
 // ev_mid (optional) is recorded between the two kernels
 hipError_t launch_chain_regs(const RegArgs &A, hipStream_t st, hipEvent_t ev_mid, int *n_launches);

@@ -10,14 +10,15 @@
 //                 replay only for reads of more than 64 chains that hold equal keys, the stable sort of the replayed arrangement, and the reversal
 //                 as rank = n_u - 1 - position -- what epi_tiesort does for chain.c:411.
 //     fields    : every byte of the region except mlen / blen, which are written as 0 (hit.c:75-85; calloc's zeros included)
-//   regs_fill (anchor-parallel, one wave per slice of 1 024 chain anchors of the whole batch)
+//   regs_fill (anchor-parallel, one wave per slice of 1 024 chain anchors of the whole batch; regs_fill_reads: the same slices read by read)
 //     mlen, blen: sums of one term per chain anchor -- the span for the first, the pair term of hit.c:15-19 for every other.  `int` adds wrap, so
 //                 the sums are associative: 16-byte loads a row of 64 anchors at a time, a segmented scan inside the wave, the open segment carried
 //                 from row to row; a chain that lies inside the slice is stored, one that crosses slices is added with integer atomics.
 //
 // Preconditions (the host-buffer entry checks them; here they are clamped and counted in flags[0]): every chain has cnt >= 1 and the counts of a
 // read add up to its extent of b.  Whatever u holds, an anchor is read only inside [b_off[r], b_off[r+1]) of its read and contributes only to
-// a chain of that read.
+// a chain of that read.  A read whose offsets leave the plan's capacities is refused (counted in flags[0] and flags[2]); regs_fill_reads then takes the
+// place of regs_fill and fills the other reads one by one, because the scratch of the refused read's chains was not written by this run.
 
 #include <hip/hip_runtime.h>
 #include <climits>
@@ -41,6 +42,15 @@ __device__ __forceinline__ uint64_t hash64(uint64_t key)                        
 	return key;
 }
 
+// the extents of read r; false when its offsets are not ordered inside the plan's capacities.  Both kernels ask: a read regs_sort refuses writes none of its
+// per-chain scratch, so regs_fill must not look there either
+__device__ __forceinline__ bool read_extents(const RegArgs &A, int64_t r, int64_t &base, int64_t &nu, int64_t &bbase, int64_t &nb)
+{
+	base = A.u_off[r]; bbase = A.b_off[r];
+	nu = A.u_off[r + 1] - base; nb = A.b_off[r + 1] - bbase;
+	return !(base < 0 || bbase < 0 || nu < 0 || nb < 0 || nu > INT_MAX || nb > INT_MAX || base + nu > A.n_u_cap || bbase + nb > A.n_b_cap);
+}
+
 // ---- kernel S: keys, order, every field but the fuzzy lengths --------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void regs_sort(RegArgs A)
 {
@@ -49,10 +59,9 @@ __global__ __launch_bounds__(64) void regs_sort(RegArgs A)
 	__shared__ __attribute__((aligned(8))) int s_cur[576];
 	__shared__ int s_lo[257], s_sp;
 	const int r = (int)blockIdx.x, lane = (int)threadIdx.x;
-	const int64_t base = A.u_off[r], bbase = A.b_off[r];
-	const int64_t nu64 = A.u_off[r + 1] - base, nb = A.b_off[r + 1] - bbase;
-	if (base < 0 || bbase < 0 || nu64 < 0 || nb < 0 || nu64 > INT_MAX || nb > INT_MAX || base + nu64 > A.n_u_cap || bbase + nb > A.n_b_cap) {
-		if (lane == 0) atomicAdd(&A.flags[0], 1);                                // offsets that leave the plan's capacities: nothing of this read is touched
+	int64_t base, nu64, bbase, nb;
+	if (!read_extents(A, r, base, nu64, bbase, nb)) {
+		if (lane == 0) { atomicAdd(&A.flags[0], 1); atomicAdd(&A.flags[2], 1); }  // offsets that leave the plan's capacities: nothing of this read is touched
 		return;
 	}
 	const int nu = (int)nu64;
@@ -198,10 +207,10 @@ struct SliceTab {
 };
 
 template <bool LDS>
-__device__ __forceinline__ void fill_flush(const RegArgs &A, const SliceTab &T, int n_u, int c, int vb, int vm, int64_t len)
+__device__ __forceinline__ void fill_flush(const RegArgs &A, const SliceTab &T, int c, int vb, int vm, int64_t len)
 {
 	const int rk = A.crank[c];
-	if ((uint32_t)rk >= (uint32_t)n_u) return;                                   // (a read regs_sort refused)
+	if ((uint32_t)rk >= (uint32_t)A.n_u_cap) return;                             // (every chain looked up here had its rank written by this run: the bound of the write all the same)
 	int32_t *p = (int32_t *)A.regs + (int64_t)rk * (2 * REG_WORDS) + 11;          // mlen, blen
 	if (T.start<LDS>(c) >= 0 && T.end<LDS>(c) <= len) { p[0] = vm; p[1] = vb; }  // the whole chain lies in this wave's slice
 	else { atomicAdd(p, vm); atomicAdd(p + 1, vb); }
@@ -209,7 +218,7 @@ __device__ __forceinline__ void fill_flush(const RegArgs &A, const SliceTab &T, 
 
 // the rows of one slice [g0, g1); the chains of its anchors are c_lo .. c_hi
 template <bool LDS>
-__device__ __forceinline__ void fill_slice(const RegArgs &A, const SliceTab &T, int n_u, int64_t g0, int64_t g1, int c_lo, int c_hi, int lane)
+__device__ __forceinline__ void fill_slice(const RegArgs &A, const SliceTab &T, int64_t g0, int64_t g1, int c_lo, int c_hi, int lane)
 {
 	const int64_t len = g1 - g0;
 	uint32_t pxl = 0, pyl = 0;                                                   // low words of the anchor before the row
@@ -241,14 +250,14 @@ __device__ __forceinline__ void fill_slice(const RegArgs &A, const SliceTab &T, 
 		}
 		if (ccid >= 0) {                                                         // the segment the row before left open goes on in lane 0, or is done
 			const int k0 = __shfl(key, 0);
-			if (lane == 0) { if (k0 == ccid) { tb += cb; tm += cm; } else fill_flush<LDS>(A, T, n_u, ccid, cb, cm, len); }
+			if (lane == 0) { if (k0 == ccid) { tb += cb; tm += cm; } else fill_flush<LDS>(A, T, ccid, cb, cm, len); }
 		}
 		for (int o = 1; o < 64; o <<= 1) {                                       // segmented inclusive scan: the lanes of a chain are neighbours
 			const int yb = __shfl_up(tb, o), ym = __shfl_up(tm, o), yk = __shfl_up(key, o);
 			if (lane >= o && yk == key) { tb += yb; tm += ym; }
 		}
 		const int nk = __shfl_down(key, 1);
-		if (key >= 0 && lane != 63 && nk != key) fill_flush<LDS>(A, T, n_u, key, tb, tm, len);
+		if (key >= 0 && lane != 63 && nk != key) fill_flush<LDS>(A, T, key, tb, tm, len);
 		ccid = __shfl(key, 63); cb = __shfl(tb, 63); cm = __shfl(tm, 63);
 		row_lo = __shfl(cid, 63);                                                // ascending: no later anchor belongs to an earlier chain
 	};
@@ -264,31 +273,59 @@ __device__ __forceinline__ void fill_slice(const RegArgs &A, const SliceTab &T, 
 		for (int k = 0; k < REGS_FILL_AHEAD; ++k)
 			if (g + 64 * k < g1) row(g + 64 * k, a[k]);
 	}
-	if (ccid >= 0 && lane == 0) fill_flush<LDS>(A, T, n_u, ccid, cb, cm, len);
+	if (ccid >= 0 && lane == 0) fill_flush<LDS>(A, T, ccid, cb, cm, len);
 }
 
+// one slice [g0, g1) of b; its anchors belong to chains among u_lo .. u_hi, whose cstart / cend this run wrote and which ascend
+__device__ __forceinline__ void fill_wave_slice(const RegArgs &A, int16_t (*s_tab)[REGS_FILL_CAP + 1], int u_lo, int u_hi, int64_t g0, int64_t g1, int lane)
+{
+	const int c_lo = wave_find_chain(A.cstart, u_lo, u_hi, g0, lane), c_hi = wave_find_chain(A.cstart, c_lo, u_hi, g1 - 1, lane);
+	SliceTab T;
+	T.cstart = A.cstart; T.cend = A.cend; T.s_cs = s_tab[0]; T.s_ce = s_tab[1]; T.g0 = g0; T.c_lo = c_lo;
+	if (c_hi - c_lo < REGS_FILL_CAP) {
+		for (int k = lane; k <= c_hi - c_lo; k += 64) {
+			const int64_t cs = A.cstart[c_lo + k] - g0, ce = A.cend[c_lo + k] - g0;
+			s_tab[0][k] = (int16_t)(cs < -REL_FAR ? -REL_FAR : cs > REL_FAR ? REL_FAR : cs);
+			s_tab[1][k] = (int16_t)(ce < -REL_FAR ? -REL_FAR : ce > REL_FAR ? REL_FAR : ce);
+		}
+		rp_wave_sync();
+		fill_slice<true>(A, T, g0, g1, c_lo, c_hi, lane);
+	} else fill_slice<false>(A, T, g0, g1, c_lo, c_hi, lane);
+}
+
+// Two routes.  regs_sort accepted every read (flags[2] == 0): the offsets ascend from u_off[0] to u_off[n_reads] inside the capacities, every chain between them has
+// its cstart / cend / crank from this run, and a wave takes one slice of b of the whole batch.  It refused a read: the scratch of that read's chains holds whatever an
+// earlier run left, so nothing may be searched across reads and nothing derived from u_off[n_reads] / b_off[n_reads].  The waves then stride over the reads, skip those
+// that fail regs_sort's test, and take an accepted read's slices one after another, looking only at its own chains and anchors.  Slower, and exact beside a broken read.
+// Two kernels, of which one works: they are launched one after the other and each leaves at once when the route is the other's (a kernel of both routes needs a
+// third more registers than regs_fill alone, on every run).
 __global__ __launch_bounds__(64 * REGS_FILL_WAVES) void regs_fill(RegArgs A)
 {
 	__shared__ int16_t s_tab[REGS_FILL_WAVES][2][REGS_FILL_CAP + 1];                // per wave: starts, ends (private to the wave: wave-local synchronisation only)
 	const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-	const int64_t nb_all = A.b_off[A.n_reads], nu_all = A.u_off[A.n_reads];
-	const int64_t n_b = nb_all < A.n_b_cap ? nb_all : A.n_b_cap;
-	const int n_u = (int)(nu_all < A.n_u_cap ? nu_all : A.n_u_cap);
+	if (A.flags[2] != 0) return;
+	const int64_t u_lo = A.u_off[0], u_hi = A.u_off[A.n_reads], n_b = A.b_off[A.n_reads];
 	const int64_t g0 = ((int64_t)blockIdx.x * REGS_FILL_WAVES + wave) * (64 * REGS_FILL_ROWS);
-	if (g0 >= n_b || n_u <= 0) return;
+	if (g0 >= n_b || u_hi <= u_lo) return;
 	const int64_t g1 = g0 + 64 * REGS_FILL_ROWS < n_b ? g0 + 64 * REGS_FILL_ROWS : n_b;
-	const int c_lo = wave_find_chain(A.cstart, 0, n_u - 1, g0, lane), c_hi = wave_find_chain(A.cstart, c_lo, n_u - 1, g1 - 1, lane);
-	SliceTab T;
-	T.cstart = A.cstart; T.cend = A.cend; T.s_cs = s_tab[wave][0]; T.s_ce = s_tab[wave][1]; T.g0 = g0; T.c_lo = c_lo;
-	if (c_hi - c_lo < REGS_FILL_CAP) {
-		for (int k = lane; k <= c_hi - c_lo; k += 64) {
-			const int64_t cs = A.cstart[c_lo + k] - g0, ce = A.cend[c_lo + k] - g0;
-			s_tab[wave][0][k] = (int16_t)(cs < -REL_FAR ? -REL_FAR : cs > REL_FAR ? REL_FAR : cs);
-			s_tab[wave][1][k] = (int16_t)(ce < -REL_FAR ? -REL_FAR : ce > REL_FAR ? REL_FAR : ce);
+	fill_wave_slice(A, s_tab[wave], (int)u_lo, (int)u_hi - 1, g0, g1, lane);
+}
+
+__global__ __launch_bounds__(64 * REGS_FILL_WAVES) void regs_fill_reads(RegArgs A)
+{
+	__shared__ int16_t s_tab[REGS_FILL_WAVES][2][REGS_FILL_CAP + 1];
+	const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+	if (A.flags[2] == 0) return;
+	const int64_t n_waves = (int64_t)gridDim.x * REGS_FILL_WAVES;
+	for (int64_t r = (int64_t)blockIdx.x * REGS_FILL_WAVES + wave; r < A.n_reads; r += n_waves) {
+		int64_t base, nu, bbase, nb;
+		if (!read_extents(A, r, base, nu, bbase, nb) || nu == 0) continue;
+		for (int64_t g0 = bbase; g0 < bbase + nb; g0 += 64 * REGS_FILL_ROWS) {
+			const int64_t g1 = g0 + 64 * REGS_FILL_ROWS < bbase + nb ? g0 + 64 * REGS_FILL_ROWS : bbase + nb;
+			fill_wave_slice(A, s_tab[wave], (int)base, (int)(base + nu) - 1, g0, g1, lane);
+			rp_wave_sync();                                                      // the table is written again for the next slice
 		}
-		rp_wave_sync();
-		fill_slice<true>(A, T, n_u, g0, g1, c_lo, c_hi, lane);
-	} else fill_slice<false>(A, T, n_u, g0, g1, c_lo, c_hi, lane);
+	}
 }
 
 } // namespace
@@ -304,7 +341,10 @@ hipError_t launch_chain_regs(const RegArgs &A, hipStream_t st, hipEvent_t ev_mid
 	if (A.n_b_cap > 0) {
 		const int64_t per = 64 * REGS_FILL_ROWS * REGS_FILL_WAVES;
 		hipLaunchKernelGGL(regs_fill, dim3((unsigned)((A.n_b_cap + per - 1) / per)), dim3(64 * REGS_FILL_WAVES), 0, st, A);
-		++nl;
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+		const int64_t blocks = (A.n_reads + REGS_FILL_WAVES - 1) / REGS_FILL_WAVES;  // a wave per read, the reads beyond 16 384 in turns
+		hipLaunchKernelGGL(regs_fill_reads, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(64 * REGS_FILL_WAVES), 0, st, A);
+		nl += 2;
 	}
 	if (n_launches) *n_launches += nl;
 	return hipGetLastError();

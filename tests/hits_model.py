@@ -4,7 +4,9 @@ The keyword variants restate the step the "natural" way instead; the tests use t
   pick="best"      the passing primary of highest score instead of the first in w order
   in_place=False   mm_select_sub reads the parent from the untouched array instead of from the array it is compacting
   fp=np.float64    the two float tests in double
-  always_sync=True mm_sync_regs (ids, parents, sam_pri) even when nothing was dropped"""
+  always_sync=True mm_sync_regs (ids, parents, sam_pri) even when nothing was dropped
+  uncov=f          uncov_len by f(si, ei, prim) instead of the sorted sweep: uncov_by_gaps (the kernel's way, equal to the sweep) and its two wrong forms,
+                   uncov_by_gaps_round_lost and uncov_by_gaps_every_end (tests/hits_limit_data.py holds the cases that tell them from the reference)"""
 import numpy as np
 
 from regs_model import REG
@@ -33,19 +35,31 @@ def uncov_len(si, ei, prim):
     return un, len(cov)
 
 
-def uncov_by_gaps(si, ei, prim):
+def uncov_by_gaps(si, ei, prim, round_lost=False, every_end=False):
     """the same measure as the kernel finds it (csrc/chain_hits.hip): every candidate gap start g -- si or the end of a clipped interval -- opens a gap if no interval
-    holds g, g < ei and no earlier interval ends there too; the gap reaches to the nearest interval start beyond g, or ei"""
+    holds g, g < ei and no earlier interval ends there too; the gap reaches to the nearest interval start beyond g, or ei.
+    The candidates are taken 64 at a time and si is candidate number n_cov; round_lost: the rounds stop at t0 < n_cov, so si is lost when n_cov is a multiple of 64;
+    every_end: every interval that ends at g opens the gap, not only the first"""
     cov = [(max(sj, si), min(ej, ei)) for sj, ej in prim if not (ej <= si or sj >= ei)]
     if not cov:
         return 0
     un = 0
     for t in range(len(cov) + 1):
+        if round_lost and t == len(cov) and t % 64 == 0:
+            continue
         g = cov[t][1] if t < len(cov) else si
-        if g >= ei or any(a <= g < b for a, b in cov) or any(cov[q][1] == g for q in range(min(t, len(cov)))):
+        if g >= ei or any(a <= g < b for a, b in cov) or (not every_end and any(cov[q][1] == g for q in range(min(t, len(cov))))):
             continue
         un += min([a for a, _ in cov if a > g] + [ei]) - g
     return un
+
+
+def uncov_by_gaps_round_lost(si, ei, prim):
+    return uncov_by_gaps(si, ei, prim, round_lost=True)
+
+
+def uncov_by_gaps_every_end(si, ei, prim):
+    return uncov_by_gaps(si, ei, prim, every_end=True)
 
 
 def passes(si, ei, sj, ej, un, mask_level, mask_len, fp=np.float32):
@@ -57,7 +71,7 @@ def passes(si, ei, sj, ej, un, mask_level, mask_len, fp=np.float32):
         return bool(v > fp(np.float32(mask_level))) and un <= mask_len
 
 
-def set_parent(regs, mask_level, mask_len, hard_mask_level, fp=np.float32, pick="first"):
+def set_parent(regs, mask_level, mask_len, hard_mask_level, fp=np.float32, pick="first", uncov=None):
     r = regs.copy()
     n = r.size
     if n <= 0:
@@ -67,7 +81,8 @@ def set_parent(regs, mask_level, mask_len, hard_mask_level, fp=np.float32, pick=
     r["parent"][0] = 0
     for i in range(1, n):
         si, ei = int(r["qs"][i]), int(r["qe"][i])
-        un = 0 if hard_mask_level else uncov_len(si, ei, [(int(r["qs"][j]), int(r["qe"][j])) for j in w])[0]
+        prim = [(int(r["qs"][j]), int(r["qe"][j])) for j in w]
+        un = 0 if hard_mask_level else uncov_len(si, ei, prim)[0] if uncov is None else uncov(si, ei, prim)
         hit = []
         for j in w:
             sj, ej = int(r["qs"][j]), int(r["qe"][j])
@@ -142,7 +157,7 @@ def select_sub(regs, pri_ratio, min_diff, best_n, fp=np.float32, in_place=True, 
 
 def select_hits(regs, opt, **variant):
     """opt: dict with the fields of mm2c_hit_opt_t -> the array the reference holds after mm_set_parent + mm_select_sub"""
-    sp = {k: v for k, v in variant.items() if k in ("fp", "pick")}
+    sp = {k: v for k, v in variant.items() if k in ("fp", "pick", "uncov")}
     ss = {k: v for k, v in variant.items() if k in ("fp", "in_place", "always_sync")}
     r = set_parent(np.asarray(regs, REG), opt["mask_level"], opt["mask_len"], opt["hard_mask_level"], **sp)
     return select_sub(r, opt["pri_ratio"], opt["min_diff"], opt["best_n"], **ss)
