@@ -381,6 +381,56 @@ int mm2c_hitplan_last_ms(mm2c_hitplan_t *plan, float *ms);
 int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out,
                                 int32_t *n_out);
 
+/* ---- hits -> mapping quality on the GPU (the rest of chain_post and the mapq of one-segment reads mapped without CIGAR: mm_join_long map.c:255-256,
+ * hit.c:295-371; mm_set_mapq map.c:361, hit.c:463-508) ----
+ * The hits of read r are d_regs_in[u_off[r] .. u_off[r] + d_n_in[r]) exactly as mm2c_hitplan_run_device wrote them (its d_regs_out / d_n_out), its chain anchors
+ * d_b[b_off[r] .. b_off[r+1]) as the region plan got them; d_qlen and d_rep_len (collect_matches' rep_len, map.c:342) are per read.  The first d_n_out[r] entries
+ * of d_regs_out from u_off[r] on are, byte for byte, the array the reference holds after mm_join_long (only with do_join) and
+ * mm_set_mapq(km, n, regs, min_chain_score, match_sc, rep_len[r], is_sr); the entries behind them are unspecified.  p, inv and is_alt are always 0 in these regions,
+ * so hit.c:484-491, 494-496, 504 and mm_set_inv_mapq are dead and not built, and match_sc / is_sr have no counterpart here.  `div` passes through: mm_est_err
+ * (map.c:357), which writes nothing else, stays the host's.  Every other field of the final mm_reg1_t is the reference's.
+ * Anchors: mm_join_long starts with mm_squeeze_a whenever a read has two hits or more -- the anchors of the hits that are left, in ascending as, are packed to the
+ * front of the read's a[] and as is renumbered -- and a join sets MM_SEED_LONG_JOIN (bit 40 of y) on the first anchor of the absorbed chain.  The as in d_regs_out
+ * are always the reference's (squeezed).  With d_b_out, read r's segment from b_off[r] on holds d_n_b_out[r] anchors that are the reference's a[] byte for byte:
+ * the sum of cnt for a squeezed read, the whole segment for a read of fewer than two hits or with do_join == 0.  With d_b_out == NULL (and d_n_b_out NULL with
+ * it) no anchor is copied and the join bit is recorded nowhere; a host that needs neither a[] nor the bit saves the copy.  d_b is never written.
+ * The logarithms: mm_set_mapq calls logf on two integers, and libms differ in the last bit.  The plan holds a table L[i] = logf((float)i), 0 <= i <= max_log_arg
+ * (at most MM2C_MAPQ_MAX_LOG_ARG, where every integer still is a float), which the HOST fills at creation by calling its own logf: what the reference computes on
+ * that host, on whatever libm is installed.  The float arithmetic around the lookup is evaluated in IEEE single precision as written.  A primary hit whose score
+ * or n_sub + 1 exceeds max_log_arg gets mapq 0 and is counted; mm2c_mapqplan_check then answers MM2C_E_TOOBIG with the count.  Nothing wraps, nothing else changes.
+ * Preconditions (the hit plan guarantees them): id == index in every read, cnt >= 1, chains that do not overlap in a[].  The reference sizes mm_sync_regs' table
+ * by the largest id left and reads beyond it when a dropped parent has a larger one; here such a parent gives MM_PARENT_UNSET.
+ * d_regs_out must not alias d_regs_in, nor d_b_out d_b; regions 8-byte, anchors 16-byte aligned.  Asynchronous on `stream`; may follow mm2c_hitplan_run_device
+ * on the same stream, the host never having seen u_off or n_out.  A read whose u_off / b_off / n_in leave the capacities or each other, or a hit of which leaves
+ * the read's anchors, touches nothing and mm2c_mapqplan_check answers MM2C_E_ARG; the reads beside it are not affected. */
+typedef struct {
+	int32_t do_join;                                            /* !(opt->flag & (MM_F_SPLICE|MM_F_SR|MM_F_NO_LJOIN)), map.c:255 */
+	int32_t max_join_long, max_join_short, min_join_flank_sc;   /* options.c:38-40 */
+	float   min_join_flank_ratio;                               /* options.c:41 */
+	int32_t min_cnt;                                            /* mm_filter_regs, hit.c:280 */
+	int32_t min_chain_score;                                    /* mm_set_mapq's min_chain_sc */
+} mm2c_mapq_opt_t;
+#define MM2C_MAPQ_MAX_LOG_ARG 16777215
+#define MM2C_SEED_LONG_JOIN_BIT 40
+typedef struct mm2c_mapqplan mm2c_mapqplan_t;
+mm2c_mapqplan_t *mm2c_mapqplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_b_cap, int32_t max_log_arg);
+void mm2c_mapqplan_destroy(mm2c_mapqplan_t *plan);
+int mm2c_mapqplan_run_device(mm2c_mapqplan_t *plan, const mm2c_mapq_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in, const int32_t *d_n_in,
+                             const int64_t *d_b_off, const void *d_b, const int32_t *d_qlen, const int32_t *d_rep_len, mm2c_reg_t *d_regs_out,
+                             int32_t *d_n_out, void *d_b_out, int64_t *d_n_b_out, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a read was refused for its offsets; else MM2C_E_TOOBIG if a primary lay beyond the table.  *n_joined: joins made;
+ * *n_beyond_table: primaries beyond the table (both filled in either way; either pointer may be NULL) */
+int mm2c_mapqplan_check(mm2c_mapqplan_t *plan, int64_t *n_joined, int64_t *n_beyond_table);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: the same for mapq_join and for mapq_gather (0 when no anchors were asked for) */
+int mm2c_mapqplan_last_ms(mm2c_mapqplan_t *plan, float *ms);
+int mm2c_mapqplan_last_kernel_ms(mm2c_mapqplan_t *plan, float *join_ms, float *gather_ms);
+/* host arrays in and out (regs_out: room for u_off[n_reads] - u_off[0] regions, read r from u_off[r] - u_off[0] on; b_out / n_b_out: NULL, or room for
+ * b_off[n_reads] - b_off[0] anchors and n_reads counts).  Checks the offsets and n_in first (MM2C_E_ARG, before any device work), then uploads, runs,
+ * downloads and waits; with MM2C_E_TOOBIG the outputs are complete all the same. */
+int mm2c_join_mapq_batch_host(int64_t n_reads, const mm2c_mapq_opt_t *opt, int32_t max_log_arg, const int64_t *u_off, const mm2c_reg_t *regs_in,
+                              const int32_t *n_in, const int64_t *b_off, const mm2c_anchor_t *b, const int32_t *qlen, const int32_t *rep_len,
+                              mm2c_reg_t *regs_out, int32_t *n_out, mm2c_anchor_t *b_out, int64_t *n_b_out);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

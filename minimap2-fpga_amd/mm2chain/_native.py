@@ -82,8 +82,16 @@ class HitOpt(C.Structure):
                 ("best_n", C.c_int32)]
 
 
+class MapqOpt(C.Structure):
+    """mm2c_mapq_opt_t: mm_join_long's switch and thresholds (options.c:38-41), mm_filter_regs' min_cnt, mm_set_mapq's min_chain_sc"""
+    _fields_ = [("do_join", C.c_int32), ("max_join_long", C.c_int32), ("max_join_short", C.c_int32), ("min_join_flank_sc", C.c_int32),
+                ("min_join_flank_ratio", C.c_float), ("min_cnt", C.c_int32), ("min_chain_score", C.c_int32)]
+
+
 MM2C_REG_SAM_PRI_BIT = 12
 MM2C_HIT_LDS_REGIONS = 128
+MM2C_MAPQ_MAX_LOG_ARG = (1 << 24) - 1
+MM2C_SEED_LONG_JOIN_BIT = 40
 
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
@@ -151,6 +159,13 @@ C_SYMBOLS = {
     "mm2c_hitplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mm2c_hitplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_select_hits_batch_host": (C.c_int, [C.c_int64, C.POINTER(HitOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "mm2c_mapqplan_destroy": (None, [C.c_void_p]),
+    "mm2c_mapqplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(MapqOpt)] + [C.c_void_p] * 12),
+    "mm2c_mapqplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_mapqplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_mapqplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mm2c_join_mapq_batch_host": (C.c_int, [C.c_int64, C.POINTER(MapqOpt), C.c_int32] + [C.c_void_p] * 11),
     "mm2c_seedplan_create": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_seedplan_destroy": (None, [C.c_void_p]),
     "mm2c_seedplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

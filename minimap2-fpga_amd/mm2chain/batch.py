@@ -486,6 +486,111 @@ def select_hits_batch(opt, u_off, regs):
     return out[:n_u], n_out[:n_reads]
 
 
+class MapqPlan:
+    """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
+    reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the
+    plan's table holds -- the host's own logf, filled at creation; 2^22 (16 MB) by default, at most 2^24 - 1."""
+
+    def __init__(self, n_reads, n_u_cap, n_b_cap, max_log_arg=1 << 22):
+        self.lib = N.load()
+        self.n_reads, self.n_u_cap, self.n_b_cap, self.max_log_arg = int(n_reads), int(n_u_cap), int(n_b_cap), int(max_log_arg)
+        self.handle = self.lib.mm2c_mapqplan_create(self.n_reads, self.n_u_cap, self.n_b_cap, self.max_log_arg)
+        if not self.handle:
+            N.check(-1, "mm2c_mapqplan_create")
+
+    def run(self, opt, u_off: torch.Tensor, regs_in: torch.Tensor, n_in: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, qlen: torch.Tensor,
+            rep_len: torch.Tensor, regs_out: torch.Tensor = None, n_out: torch.Tensor = None, anchors=False, b_out: torch.Tensor = None,
+            n_b_out: torch.Tensor = None, stream=None):
+        """opt: params.mapq_opts(); u_off, regs_in and n_in as HitPlan.run took and returned them, b_off / b the device epilogue's chain anchors, qlen and rep_len
+        int32 per read, all on the GPU.  Returns (regs_out uint8 [n_u_cap, 80], n_out int32 [n_reads], b_out, n_b_out): the final regions of read r are rows
+        u_off[r] .. u_off[r] + n_out[r].  With anchors=True (or b_out given) b_out int64 [n_b_cap, 2] holds, from b_off[r] on, the n_b_out[r] anchors of the
+        reference's a[] behind mm_join_long; otherwise both are None, no anchor is copied and the join bit is not recorded.  Asynchronous."""
+        for t in (u_off, regs_in, n_in, b_off, b, qlen, rep_len):
+            assert t.is_cuda and t.is_contiguous()
+        assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1 and b_off.numel() == self.n_reads + 1
+        assert regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
+        assert n_in.dtype == torch.int32 and n_in.numel() >= self.n_reads and qlen.dtype == torch.int32 and qlen.numel() == self.n_reads
+        assert rep_len.dtype == torch.int32 and rep_len.numel() == self.n_reads
+        if regs_out is None:
+            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
+        if n_out is None:
+            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
+        if (anchors or n_b_out is not None) and b_out is None:
+            b_out = torch.empty((max(self.n_b_cap, 1), 2), dtype=torch.int64, device=u_off.device)
+        if b_out is not None and n_b_out is None:
+            n_b_out = torch.empty(max(self.n_reads, 1), dtype=torch.int64, device=u_off.device)
+        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
+        if b_out is not None:
+            assert b_out.is_cuda and b_out.is_contiguous() and b_out.element_size() == 8 and b_out.numel() >= 2 * self.n_b_cap
+            assert n_b_out.is_cuda and n_b_out.is_contiguous() and n_b_out.dtype == torch.int64 and n_b_out.numel() >= self.n_reads
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_mapqplan_run_device(self.handle, C.byref(opt), u_off.data_ptr(), regs_in.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(),
+                                                  qlen.data_ptr(), rep_len.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(),
+                                                  b_out.data_ptr() if b_out is not None else None, n_b_out.data_ptr() if b_out is not None else None, st),
+                "mm2c_mapqplan_run_device")
+        return regs_out, n_out[:self.n_reads], b_out, (n_b_out[:self.n_reads] if b_out is not None else None)
+
+    def counts(self):
+        """waits for the run -> (return code, joins made, primaries beyond the table) without raising"""
+        nj, nb = C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_mapqplan_check(self.handle, C.byref(nj), C.byref(nb))
+        return rc, nj.value, nb.value
+
+    def check(self):
+        """waits for the run; raises if a read was refused for its offsets (code -2) or a primary lay beyond the table (code -3); returns the number of joins"""
+        rc, nj, _ = self.counts()
+        N.check(rc, "mm2c_mapqplan_check")
+        return nj
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_mapqplan_last_ms(self.handle, C.byref(ms)), "mm2c_mapqplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(mapq_join, mapq_gather) of the last run; the second is 0 when no anchors were asked for"""
+        a, b = C.c_float(0), C.c_float(0)
+        N.check(self.lib.mm2c_mapqplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_mapqplan_last_kernel_ms")
+        return a.value, b.value
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_mapqplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=True, max_log_arg=1 << 22):
+    """mm2c_join_mapq_batch_host: host arrays in -> (regs_out REG_DTYPE [u_off[-1] - u_off[0]], n_out int32 [n_reads], b_out uint64 [b_off[-1] - b_off[0], 2] or
+    None, n_b_out int64 [n_reads] or None); the final regions of read r are regs_out[u_off[r] - u_off[0] :][:n_out[r]], its anchors
+    b_out[b_off[r] - b_off[0] :][:n_b_out[r]].  Raises with code -3 when a primary lay beyond the table of max_log_arg entries."""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
+    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    ni = np.ascontiguousarray(n_in, dtype=np.int32); q = np.ascontiguousarray(qlen, dtype=np.int32); rl = np.ascontiguousarray(rep_len, dtype=np.int32)
+    n_reads = uo.size - 1
+    if bo.size != uo.size or ni.size != n_reads or q.size != n_reads or rl.size != n_reads or \
+            (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0])):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
+    n_b = int(bo[-1] - bo[0]) if n_reads > 0 else 0
+    out = np.zeros(max(n_u, 1), REG_DTYPE)
+    n_out = np.zeros(max(n_reads, 1), np.int32)
+    b_out = np.zeros((max(n_b, 1), 2), np.uint64) if anchors else None
+    n_b_out = np.zeros(max(n_reads, 1), np.int64) if anchors else None
+    N.check(lib.mm2c_join_mapq_batch_host(n_reads, C.byref(opt), int(max_log_arg), _np_ptr(uo), _np_ptr(rr), _np_ptr(ni), _np_ptr(bo), _np_ptr(bb), _np_ptr(q),
+                                          _np_ptr(rl), _np_ptr(out), _np_ptr(n_out), _np_ptr(b_out) if anchors else None, _np_ptr(n_b_out) if anchors else None),
+            "mm2c_join_mapq_batch_host")
+    return out[:n_u], n_out[:n_reads], (b_out[:n_b] if anchors else None), (n_b_out[:n_reads] if anchors else None)
+
+
 MATCH_DTYPE = np.dtype([("cr_off", "<i8"), ("n", "<u4"), ("q_pos", "<u4"), ("q_span", "<u4"), ("seg_tandem", "<u4")])   # mm2c_match_t
 
 

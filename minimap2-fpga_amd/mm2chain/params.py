@@ -1,5 +1,5 @@
 """Chaining parameter presets, mirroring options.c of the reference (file:line cited per preset)."""
-from ._native import Params, HitOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
+from ._native import Params, HitOpt, MapqOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
 
 INT32_MAX = 2**31 - 1
 
@@ -52,6 +52,18 @@ def hit_opts(k=15, **kw):
         raise TypeError(f"hit_opts: unknown field(s) {sorted(unknown)}")
     v.update(kw)
     return HitOpt(v["mask_level"], v["mask_len"], int(bool(v["hard_mask_level"])), v["pri_ratio"], v["min_diff"], v["best_n"])
+
+
+def mapq_opts(**kw):
+    """mm2c_mapq_opt_t with the defaults of options.c: do_join 1 (map.c:255: off with MM_F_SPLICE, MM_F_SR or MM_F_NO_LJOIN, so the presets splice / cdna and
+    sr / short pass do_join=0), max_join_long 20000, max_join_short 2000, min_join_flank_sc 1000, min_join_flank_ratio 0.5 (options.c:38-41), min_cnt 3 and
+    min_chain_score 40 (options.c:24-25; sr: min_cnt 2, min_chain_score 25; ava-ont / ava-pb: min_chain_score 100).  Keywords override single fields."""
+    v = dict(do_join=1, max_join_long=20000, max_join_short=2000, min_join_flank_sc=1000, min_join_flank_ratio=0.5, min_cnt=3, min_chain_score=40)
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"mapq_opts: unknown field(s) {sorted(unknown)}")
+    v.update(kw)
+    return MapqOpt(int(bool(v["do_join"])), v["max_join_long"], v["max_join_short"], v["min_join_flank_sc"], v["min_join_flank_ratio"], v["min_cnt"], v["min_chain_score"])
 
 
 def as_dict(p):

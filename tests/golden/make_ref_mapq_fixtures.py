@@ -1,0 +1,69 @@
+"""Mapping-quality fixtures: the reference's own mm_gen_regs -> mm_set_parent -> mm_select_sub -> (mm_join_long) -> mm_set_mapq (hit.o: hit.c:52-88, 125-186, 220-371,
+463-508, with klib's sorts from misc.o and the host's own logf) on every case of tests/mapq_data.py, each under its own options.  Compiles tests/golden/mapq_dump.c
+against the reference objects build() leaves in oracle/_ref/.
+Output: tests/golden/ref_mapq.npz (data only): reg_size, names, libm (the C library's version string the fixture was made with), n_in / in_off / hits_in (the raw
+mm_reg1_t arrays in front of mm_join_long: the plan's input), n_out / out_off / hits_out (the arrays behind mm_set_mapq), n_b_out / a_off / a_out (the final a[] of
+every case: uint64 [., 2]).  The chains and anchors are not stored: mapq_data.cases() makes them again."""
+import os
+import platform
+import struct
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+REF_OBJ = os.path.join(ROOT, "oracle", "_ref")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mapq_data  # noqa: E402
+
+
+def main(out_name="ref_mapq.npz"):
+    tmp = tempfile.mkdtemp()
+    dump = os.path.join(tmp, "mapq_dump")
+    objs = [os.path.join(REF_OBJ, o + ".o") for o in ("hit", "misc", "kalloc")]
+    subprocess.check_call(["gcc", "-O2", "-w", "-DHAVE_KALLOC", "-I/root/reference", os.path.join(HERE, "mapq_dump.c")] + objs + ["-o", dump, "-lm", "-lpthread"])
+    cs = mapq_data.cases()
+    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+    with open(fin, "wb") as f:
+        f.write(struct.pack("<i", len(cs)))
+        for c in cs:
+            h, m = c["hit"], c["mapq"]
+            f.write(struct.pack("<Iiiq", c["hash"], c["qlen"], c["u"].size, c["a"].shape[0]))
+            f.write(c["u"].tobytes()); f.write(c["a"].tobytes())
+            f.write(struct.pack("<fiifii", h["mask_level"], h["mask_len"], h["hard_mask_level"], h["pri_ratio"], h["min_diff"], h["best_n"]))
+            f.write(struct.pack("<iiiifii", m["do_join"], m["max_join_long"], m["max_join_short"], m["min_join_flank_sc"], m["min_join_flank_ratio"], m["min_cnt"],
+                                m["min_chain_score"]))
+            f.write(struct.pack("<i", c["rep_len"]))
+    subprocess.check_call([dump, fin, fout])
+    raw = open(fout, "rb").read()
+    size, = struct.unpack_from("<i", raw, 0)
+    assert size == 80
+    at, n_in, n_out, n_b, p_in, p_out, p_a = 4, [], [], [], [], [], []
+    for c in cs:
+        for cnt, parts in ((n_in, p_in), (n_out, p_out)):
+            n, = struct.unpack_from("<i", raw, at)
+            at += 4
+            parts.append(np.frombuffer(raw, np.uint8, n * size, at).reshape(-1, size))
+            at += n * size
+            cnt.append(n)
+        nb, = struct.unpack_from("<q", raw, at)
+        at += 8
+        p_a.append(np.frombuffer(raw, np.uint64, nb * 2, at).reshape(-1, 2))
+        at += nb * 16
+        n_b.append(nb)
+    assert at == len(raw)
+    off = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+    path = os.path.join(HERE, out_name)
+    np.savez_compressed(path, reg_size=np.array(size), names=np.array([c["name"] for c in cs]), libm=np.array(" ".join(platform.libc_ver())),
+                        n_in=np.array(n_in, np.int64), in_off=off(n_in), hits_in=np.concatenate(p_in),
+                        n_out=np.array(n_out, np.int64), out_off=off(n_out), hits_out=np.concatenate(p_out),
+                        n_b_out=np.array(n_b, np.int64), a_off=off(n_b), a_out=np.concatenate(p_a))
+    print("wrote", path, os.path.getsize(path), "bytes;", len(cs), "cases,", sum(n_in), "hits in,", sum(n_out), "out,", sum(n_b), "anchors")
+    assert os.path.getsize(path) < (1 << 20)
+
+
+if __name__ == "__main__":
+    main(*sys.argv[1:2])
