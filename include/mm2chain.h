@@ -388,7 +388,8 @@ int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, cons
  * of d_regs_out from u_off[r] on are, byte for byte, the array the reference holds after mm_join_long (only with do_join) and
  * mm_set_mapq(km, n, regs, min_chain_score, match_sc, rep_len[r], is_sr); the entries behind them are unspecified.  p, inv and is_alt are always 0 in these regions,
  * so hit.c:484-491, 494-496, 504 and mm_set_inv_mapq are dead and not built, and match_sc / is_sr have no counterpart here.  `div` passes through: mm_est_err
- * (map.c:357), which writes nothing else, stays the host's.  Every other field of the final mm_reg1_t is the reference's.
+ * (map.c:357), which writes nothing else, is the est-err plan's further down (its counts on the device, its one pow on the host).  Every other field of the
+ * final mm_reg1_t is the reference's.
  * Anchors: mm_join_long starts with mm_squeeze_a whenever a read has two hits or more -- the anchors of the hits that are left, in ascending as, are packed to the
  * front of the read's a[] and as is renumbered -- and a join sets MM_SEED_LONG_JOIN (bit 40 of y) on the first anchor of the absorbed chain.  The as in d_regs_out
  * are always the reference's (squeezed).  With d_b_out, read r's segment from b_off[r] on holds d_n_b_out[r] anchors that are the reference's a[] byte for byte:
@@ -430,6 +431,51 @@ int mm2c_mapqplan_last_kernel_ms(mm2c_mapqplan_t *plan, float *join_ms, float *g
 int mm2c_join_mapq_batch_host(int64_t n_reads, const mm2c_mapq_opt_t *opt, int32_t max_log_arg, const int64_t *u_off, const mm2c_reg_t *regs_in,
                               const int32_t *n_in, const int64_t *b_off, const mm2c_anchor_t *b, const int32_t *qlen, const int32_t *rep_len,
                               mm2c_reg_t *regs_out, int32_t *n_out, mm2c_anchor_t *b_out, int64_t *n_b_out);
+
+/* ---- chain-anchor divergence on the GPU (mm_est_err map.c:357, esterr.c: the `div` of a final region, the dv:f: tag) ----
+ * mm_est_err writes only div; it reads the read's mini_pos (q_span << 32 | q_pos of every kept minimizer, as mm2c_sketch_match_batch and the reads-in entries
+ * lay it out: mini_off / mini_pos) and the chain anchors of every final region.  The plan stands behind the mapq plan on the same stream: its regions are that
+ * plan's d_regs_out / d_n_out, its anchors that plan's d_b_out (with do_join == 0 the device epilogue's d_b does as well), both read-only here.
+ * The split: div = n_match >= n_tot ? 0 : (float)(1 - pow((double)n_match / n_tot, 1.0 / avg_k)) (esterr.c:62) calls pow, libms differ in the last bit, and
+ * 1 - p cancels, so a device pow would need a tolerance nobody can derive.  The device therefore makes what is exact by construction -- per region the integers
+ * d_err[u_off[r] + i] = {n_match, n_tot}, per read the float d_avg_k[r] = (float)sum of spans / n (one integer-to-float conversion, one IEEE division) -- and
+ * mm2c_est_err_div applies the one line with the HOST's own pow: what the reference's esterr.o computes on that host.  There is no device-side div.
+ *   n_match >= 1 : the counts of esterr.c:53-61
+ *   n_match == 0 : div = -1 (cnt == 0, or the first anchor of the walk is not in mini_pos, esterr.c:44-51)
+ *   n_match == -1: the read has no mini_pos; esterr.c:36 returns before it touches anything and div stays as it was
+ * Entries behind d_n_in[r] are unspecified.  Everything is evaluated as esterr.c writes it (wrapping int32_t, the strand bit of the anchor itself in
+ * get_for_qpos, qlen - r->qs in the second flank test, int-against-float compares in float); l_ref = (int32_t)d_ref_len[rid], n_ref entries (mi->seq[].len).
+ * Preconditions: mini_pos of a read increases strictly in (int32_t)mini_pos[j] (mm_sketch emits at most one minimizer per position; the kernels rely on it
+ * to test every anchor on its own), and the regions of a read do not overlap in a[] (the mapq plan guarantees it).  A read's regions are ranked by counting,
+ * n^2 loads of one wave for n regions: meant for the few regions mm_select_sub leaves, not for thousands of unfiltered ones per read.
+ * A read (1) whose u_off / b_off / mini_off / n_in leave the capacities or each other, (2) whose mini_pos does not increase strictly, or (3) with a region
+ * whose [as, as + cnt) leaves the read's anchors or whose rid is outside [0, n_ref) touches nothing and is counted; mm2c_errplan_check then answers MM2C_E_ARG,
+ * and the reads beside it are exact.  Regions 8-byte, anchors 16-byte aligned.  Asynchronous on `stream`; may follow mm2c_mapqplan_run_device on the same
+ * stream, the host never having seen u_off or n_out.  A host then downloads 8 bytes per final region and 4 per read. */
+typedef struct { int32_t n_match, n_tot; } mm2c_err_t;
+typedef struct mm2c_errplan mm2c_errplan_t;
+mm2c_errplan_t *mm2c_errplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_b_cap, int64_t n_mini_cap);
+void mm2c_errplan_destroy(mm2c_errplan_t *plan);
+int mm2c_errplan_run_device(mm2c_errplan_t *plan, const int64_t *d_u_off, const mm2c_reg_t *d_regs, const int32_t *d_n_in, const int64_t *d_b_off, const void *d_b,
+                            const int64_t *d_mini_off, const uint64_t *d_mini_pos, const int32_t *d_qlen, int32_t n_ref, const uint32_t *d_ref_len,
+                            mm2c_err_t *d_err, float *d_avg_k, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a read was refused; *n_refused (may be NULL): how many */
+int mm2c_errplan_check(mm2c_errplan_t *plan, int64_t *n_refused);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: the same for err_reads, err_walk and err_finish */
+int mm2c_errplan_last_ms(mm2c_errplan_t *plan, float *ms);
+int mm2c_errplan_last_kernel_ms(mm2c_errplan_t *plan, float *reads_ms, float *walk_ms, float *finish_ms);
+/* esterr.c:62 with the host's own pow; needs no device.  n_match <= 0 gives -1.0f, n_match >= n_tot gives 0.0f */
+float mm2c_est_err_div(int32_t n_match, int32_t n_tot, float avg_k);
+/* writes div into the host's regions: regs[u_off[r] + i].div for i < n_in[r] from err[u_off[r] + i] and avg_k[r]; a region with n_match == -1 is left alone.
+ * Host only. */
+int mm2c_est_err_apply_host(int64_t n_reads, const int64_t *u_off, const int32_t *n_in, const mm2c_err_t *err, const float *avg_k, mm2c_reg_t *regs);
+/* host arrays in, div written in place: the regions of read r are regs[u_off[r] .. u_off[r] + n_in[r]), its anchors b[b_off[r] .. b_off[r+1]), its minimizers
+ * mini_pos[mini_off[r] .. mini_off[r+1]).  Checks the offsets and n_in first (MM2C_E_ARG, before any device work), then uploads, runs, downloads, waits and
+ * applies; behind it div is byte for byte the reference's.  err / avg_k: NULL, or room for u_off[n_reads] - u_off[0] counts (read r from u_off[r] - u_off[0]
+ * on) and n_reads floats.  When a read is refused on the device the answer is MM2C_E_ARG and no region is written. */
+int mm2c_est_err_batch_host(int64_t n_reads, const int64_t *u_off, mm2c_reg_t *regs, const int32_t *n_in, const int64_t *b_off, const mm2c_anchor_t *b,
+                            const int64_t *mini_off, const uint64_t *mini_pos, const int32_t *qlen, int32_t n_ref, const uint32_t *ref_len, mm2c_err_t *err,
+                            float *avg_k);
 
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits

@@ -7,7 +7,8 @@ from .batch import (device_identity, last_host_variant, init, split_model, init_
                     HitPool, seed_chain_batch_pool, stage_stats, slot_stats, chain_task_pred, SeedSkip, seed_hits_batch_skip, seed_chain_batch_skip,
                     seed_chain_batch_pool_skip, MinimizerIndex, sketch_batch, sketch_match_batch, read_chain_batch, sketch_stats, index_stats,
                     sketch_frag_batch, sketch_match_frag_batch, frag_chain_batch, frag_stats, frag_chain_batch_gaps, frag_gaps,
-                    RegPlan, REG_DTYPE, gen_regs_batch, read_hash, HitPlan, select_hits_batch, MapqPlan, join_mapq_batch)
+                    RegPlan, REG_DTYPE, gen_regs_batch, read_hash, HitPlan, select_hits_batch, MapqPlan, join_mapq_batch,
+                    EstErrPlan, est_err_batch, est_err_div, est_err_apply, ERR_DTYPE)
 
 __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE_GENERAL", "load", "params", "synth",
            "sharding", "stream", "device_identity", "last_host_variant", "init", "split_model", "init_devices", "device_count", "split_tasks", "shutdown", "device_info", "tune", "ChainPlan", "chain_batch_host", "chain_batch_host_into", "PinnedArray", "chain_task", "hardware_init",
@@ -15,4 +16,5 @@ __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE
            "HitPool", "seed_chain_batch_pool", "stage_stats", "slot_stats", "chain_task_pred", "SeedSkip", "seed_hits_batch_skip", "seed_chain_batch_skip",
            "seed_chain_batch_pool_skip", "MinimizerIndex", "sketch_batch", "sketch_match_batch", "read_chain_batch", "sketch_stats", "index_stats",
            "sketch_frag_batch", "sketch_match_frag_batch", "frag_chain_batch", "frag_stats", "frag_chain_batch_gaps", "frag_gaps",
-           "RegPlan", "REG_DTYPE", "gen_regs_batch", "read_hash", "HitPlan", "select_hits_batch", "MapqPlan", "join_mapq_batch"]
+           "RegPlan", "REG_DTYPE", "gen_regs_batch", "read_hash", "HitPlan", "select_hits_batch", "MapqPlan", "join_mapq_batch",
+           "EstErrPlan", "est_err_batch", "est_err_div", "est_err_apply", "ERR_DTYPE"]

@@ -88,6 +88,11 @@ class MapqOpt(C.Structure):
                 ("min_join_flank_ratio", C.c_float), ("min_cnt", C.c_int32), ("min_chain_score", C.c_int32)]
 
 
+class Err(C.Structure):
+    """mm2c_err_t: the counts of mm_est_err per final region (esterr.c:53-61); n_match 0: div = -1, n_match -1: the read has no mini_pos"""
+    _fields_ = [("n_match", C.c_int32), ("n_tot", C.c_int32)]
+
+
 MM2C_REG_SAM_PRI_BIT = 12
 MM2C_HIT_LDS_REGIONS = 128
 MM2C_MAPQ_MAX_LOG_ARG = (1 << 24) - 1
@@ -166,6 +171,15 @@ C_SYMBOLS = {
     "mm2c_mapqplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_mapqplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mm2c_join_mapq_batch_host": (C.c_int, [C.c_int64, C.POINTER(MapqOpt), C.c_int32] + [C.c_void_p] * 11),
+    "mm2c_errplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mm2c_errplan_destroy": (None, [C.c_void_p]),
+    "mm2c_errplan_run_device": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] + [C.c_void_p] * 4),
+    "mm2c_errplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "mm2c_errplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_errplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mm2c_est_err_div": (C.c_float, [C.c_int32, C.c_int32, C.c_float]),
+    "mm2c_est_err_apply_host": (C.c_int, [C.c_int64] + [C.c_void_p] * 5),
+    "mm2c_est_err_batch_host": (C.c_int, [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 3),
     "mm2c_seedplan_create": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_seedplan_destroy": (None, [C.c_void_p]),
     "mm2c_seedplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

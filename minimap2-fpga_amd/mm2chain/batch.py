@@ -591,6 +591,121 @@ def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=Tru
     return out[:n_u], n_out[:n_reads], (b_out[:n_b] if anchors else None), (n_b_out[:n_reads] if anchors else None)
 
 
+ERR_DTYPE = np.dtype([("n_match", "<i4"), ("n_tot", "<i4")])                   # mm2c_err_t
+
+
+class EstErrPlan:
+    """mm2c_errplan_t: the counts of mm_est_err (map.c:357, esterr.c) on the GPU for batches of up to n_reads reads, n_u_cap final regions, n_b_cap chain anchors
+    and n_mini_cap minimizer positions; it stands behind a MapqPlan on the same stream.  The device makes (n_match, n_tot) per region and avg_k per read, which
+    are exact by construction; est_err_apply / est_err_div turn them into div with the host's own pow."""
+
+    def __init__(self, n_reads, n_u_cap, n_b_cap, n_mini_cap):
+        self.lib = N.load()
+        self.n_reads, self.n_u_cap, self.n_b_cap, self.n_mini_cap = int(n_reads), int(n_u_cap), int(n_b_cap), int(n_mini_cap)
+        self.handle = self.lib.mm2c_errplan_create(self.n_reads, self.n_u_cap, self.n_b_cap, self.n_mini_cap)
+        if not self.handle:
+            N.check(-1, "mm2c_errplan_create")
+
+    def run(self, u_off: torch.Tensor, regs: torch.Tensor, n_in: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, mini_off: torch.Tensor,
+            mini_pos: torch.Tensor, qlen: torch.Tensor, ref_len: torch.Tensor, err: torch.Tensor = None, avg_k: torch.Tensor = None, stream=None):
+        """u_off, regs and n_in as MapqPlan.run took and returned them (regs_out / n_out), b_off with that run's b_out (or the epilogue's b when nothing was
+        joined), mini_off int64 [n_reads + 1] / mini_pos int64 or uint64 as the reads-in entries return them, qlen int32 per read, ref_len int32 or uint32 per
+        reference sequence, all on the GPU.  Returns (err int32 [n_u_cap, 2], avg_k float32 [n_reads]): row u_off[r] + i holds (n_match, n_tot) of region i of
+        read r.  Nothing of the input is written.  Asynchronous."""
+        for t in (u_off, regs, n_in, b_off, b, mini_off, mini_pos, qlen, ref_len):
+            assert t.is_cuda and t.is_contiguous()
+        assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and mini_off.dtype == torch.int64
+        assert u_off.numel() == self.n_reads + 1 and b_off.numel() == self.n_reads + 1 and mini_off.numel() == self.n_reads + 1
+        assert regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
+        assert mini_pos.element_size() == 8 and mini_pos.numel() >= self.n_mini_cap and ref_len.element_size() == 4
+        assert n_in.dtype == torch.int32 and n_in.numel() >= self.n_reads and qlen.dtype == torch.int32 and qlen.numel() == self.n_reads
+        if err is None:
+            err = torch.empty((max(self.n_u_cap, 1), 2), dtype=torch.int32, device=u_off.device)
+        if avg_k is None:
+            avg_k = torch.empty(max(self.n_reads, 1), dtype=torch.float32, device=u_off.device)
+        assert err.is_cuda and err.is_contiguous() and err.dtype == torch.int32 and err.numel() >= 2 * self.n_u_cap
+        assert avg_k.is_cuda and avg_k.is_contiguous() and avg_k.dtype == torch.float32 and avg_k.numel() >= self.n_reads
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_errplan_run_device(self.handle, u_off.data_ptr(), regs.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(), mini_off.data_ptr(),
+                                                 mini_pos.data_ptr(), qlen.data_ptr(), int(ref_len.numel()), ref_len.data_ptr(), err.data_ptr(), avg_k.data_ptr(), st),
+                "mm2c_errplan_run_device")
+        return err, avg_k[:self.n_reads]
+
+    def refused(self):
+        """waits for the run -> (return code, reads refused) without raising"""
+        n = C.c_int64(0)
+        rc = self.lib.mm2c_errplan_check(self.handle, C.byref(n))
+        return rc, n.value
+
+    def check(self):
+        """waits for the run; raises (code -2) if a read was refused for its offsets, its mini_pos or a region"""
+        N.check(self.refused()[0], "mm2c_errplan_check")
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_errplan_last_ms(self.handle, C.byref(ms)), "mm2c_errplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(err_reads, err_walk, err_finish) of the last run"""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        N.check(self.lib.mm2c_errplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b), C.byref(c)), "mm2c_errplan_last_kernel_ms")
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_errplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def est_err_div(n_match, n_tot, avg_k):
+    """mm2c_est_err_div: esterr.c:62 with the host's own pow -> float32; needs no device"""
+    return np.float32(N.load().mm2c_est_err_div(int(n_match), int(n_tot), float(np.float32(avg_k))))
+
+
+def est_err_apply(u_off, n_in, err, avg_k, regs):
+    """mm2c_est_err_apply_host: writes div into regs (REG_DTYPE, or uint8 rows of 80, contiguous and writable) in place; rows u_off[r] .. u_off[r] + n_in[r] of
+    err and regs belong to read r; a region with n_match == -1 is left alone.  Needs no device."""
+    lib = N.load()
+    uo = np.ascontiguousarray(u_off, dtype=np.int64); ni = np.ascontiguousarray(n_in, dtype=np.int32)
+    ee = np.ascontiguousarray(err).view(np.int32).reshape(-1, 2); ak = np.ascontiguousarray(avg_k, dtype=np.float32)
+    assert regs.flags["C_CONTIGUOUS"] and regs.flags["WRITEABLE"]
+    rows = regs.size * regs.itemsize // REG_DTYPE.itemsize
+    n_reads = ni.size
+    if uo.size < n_reads or ak.size < n_reads or (n_reads > 0 and (uo[:n_reads].min() < 0 or (uo[:n_reads] + np.maximum(ni, 0)).max() > min(rows, ee.shape[0]))):
+        raise ValueError("offsets do not fit the arrays")
+    N.check(lib.mm2c_est_err_apply_host(n_reads, _np_ptr(uo), _np_ptr(ni), _np_ptr(ee), _np_ptr(ak), _np_ptr(regs)), "mm2c_est_err_apply_host")
+    return regs
+
+
+def est_err_batch(u_off, regs, n_in, b_off, b, mini_off, mini_pos, qlen, ref_len):
+    """mm2c_est_err_batch_host: host arrays in -> (regs REG_DTYPE [u_off[-1] - u_off[0]], a copy with div written, err ERR_DTYPE of the same length,
+    avg_k float32 [n_reads]); the regions of read r are regs[u_off[r] - u_off[0] :][:n_in[r]]"""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
+    mo = np.ascontiguousarray(np.asarray(mini_off, dtype=np.int64))
+    rr = np.array(np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize))
+    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2); mp = np.ascontiguousarray(mini_pos, dtype=np.uint64).reshape(-1)
+    ni = np.ascontiguousarray(n_in, dtype=np.int32); q = np.ascontiguousarray(qlen, dtype=np.int32); rl = np.ascontiguousarray(ref_len, dtype=np.uint32)
+    n_reads = uo.size - 1
+    if bo.size != uo.size or mo.size != uo.size or ni.size != n_reads or q.size != n_reads or \
+            (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or mo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0] or mo.max() > mp.size)):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
+    err = np.zeros(max(n_u, 1), ERR_DTYPE)
+    avg_k = np.zeros(max(n_reads, 1), np.float32)
+    N.check(lib.mm2c_est_err_batch_host(n_reads, _np_ptr(uo), _np_ptr(rr), _np_ptr(ni), _np_ptr(bo), _np_ptr(bb), _np_ptr(mo), _np_ptr(mp), _np_ptr(q),
+                                        int(rl.size), _np_ptr(rl), _np_ptr(err), _np_ptr(avg_k)), "mm2c_est_err_batch_host")
+    lo = int(uo[0]) if n_reads > 0 else 0
+    return rr[lo:lo + n_u].reshape(-1).view(REG_DTYPE), err[:n_u], avg_k[:n_reads]
+
+
 MATCH_DTYPE = np.dtype([("cr_off", "<i8"), ("n", "<u4"), ("q_pos", "<u4"), ("q_span", "<u4"), ("seg_tandem", "<u4")])   # mm2c_match_t
 
 
