@@ -360,7 +360,8 @@ uint32_t mm2c_read_hash(const char *qname, int32_t qlen_sum, int32_t seed);
  * d_regs_out must not alias d_regs_in; both 8-byte aligned with room for n_u_cap regions, d_n_out for n_reads.  The call is asynchronous on `stream` (NULL /
  * MM2C_STREAM_LIBRARY as everywhere) and may follow mm2c_regplan_run_device on the same stream, the host never having seen u_off.  A read whose offsets leave
  * the capacities touches nothing and mm2c_hitplan_check answers MM2C_E_ARG.  Reads of up to MM2C_HIT_LDS_REGIONS regions are worked in on-chip memory, longer
- * ones in the plan's scratch (60 bytes per region), with the same result.  mm_select_sub_multi (fragments of several segments) is not part of this. */
+ * ones in the plan's scratch (64 bytes per region), with the same result.  mm_select_sub_multi (fragments of several segments) is the plan's second mode,
+ * mm2c_hitplan_run_device_multi below. */
 typedef struct {
 	float mask_level; int32_t mask_len; int32_t hard_mask_level;   /* mm_set_parent: opt->mask_level, opt->mask_len, opt->flag & MM_F_HARD_MLEVEL */
 	float pri_ratio; int32_t min_diff; int32_t best_n;             /* mm_select_sub: opt->pri_ratio, mi->k * 2, opt->best_n */
@@ -380,6 +381,23 @@ int mm2c_hitplan_last_ms(mm2c_hitplan_t *plan, float *ms);
  * (MM2C_E_ARG, before any device work), then uploads, runs, downloads and waits. */
 int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out,
                                 int32_t *n_out);
+/* The second mode, for fragments of several segments (map.c:252-254): mm_set_parent as above, then mm_select_sub_multi (pe.c:6-43) in the place of mm_select_sub.
+ * A "read" of the plan is a fragment; d_seg_len holds the qlens, fragment-major (n_segs per fragment; read only when n_segs == 2), d_gap_ref the max_chain_gap_ref
+ * of every fragment (map.c:309-314: under -x sr it is max(max_frag_len - qlen_sum, max_gap) and differs from fragment to fragment; the first of each pair of
+ * mm2c_read_result_task_dists), or NULL for mopt->max_gap_ref everywhere.  Everything is as pe.c writes it: max_dist = n_segs == 2 ? qlens[0] + qlens[1] +
+ * max_gap_ref : 0 in wrapping int; score + min_diff >= parent's score first, an integer test; then q->re - p->rs < max_dist && p->re - q->rs < max_dist (strict,
+ * integer) with equal rev and rid choose pri1, otherwise pri_ratio, or pri2 when the parent spans both segments (qs < qlens[0] < qe) and the child does not; the
+ * score test is (float)score >= (float)pscore * ratio in IEEE single precision; the parent is read from the array being compacted in place; every secondary that
+ * passed counts against best_n, kept or not; there is no identical-hit test; mm_sync_regs and sam_pri only when something was dropped; with pri_ratio <= 0 nothing
+ * happens beyond mm_set_parent.  mm2c_hitplan_check and _last_ms serve both modes. */
+#define MM2C_MAX_SEG 255                                           /* MM_MAX_SEG */
+typedef struct { float pri1, pri2; int32_t n_segs; int32_t max_gap_ref; } mm2c_hit_multi_opt_t;   /* map.c:254: 0.2f, 0.7f */
+int mm2c_hitplan_run_device_multi(mm2c_hitplan_t *plan, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *d_u_off,
+                                  const int32_t *d_seg_len, const int32_t *d_gap_ref, const mm2c_reg_t *d_regs_in, mm2c_reg_t *d_regs_out, int32_t *d_n_out,
+                                  void *stream);
+/* host arrays, as mm2c_select_hits_batch_host: seg_len n_frags * n_segs, gap_ref n_frags or NULL */
+int mm2c_select_hits_multi_batch_host(int64_t n_frags, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *u_off, const int32_t *seg_len,
+                                      const int32_t *gap_ref, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out);
 
 /* ---- hits -> mapping quality on the GPU (the rest of chain_post and the mapq of one-segment reads mapped without CIGAR: mm_join_long map.c:255-256,
  * hit.c:295-371; mm_set_mapq map.c:361, hit.c:463-508) ----
@@ -476,6 +494,45 @@ int mm2c_est_err_apply_host(int64_t n_reads, const int64_t *u_off, const int32_t
 int mm2c_est_err_batch_host(int64_t n_reads, const int64_t *u_off, mm2c_reg_t *regs, const int32_t *n_in, const int64_t *b_off, const mm2c_anchor_t *b,
                             const int64_t *mini_off, const uint64_t *mini_pos, const int32_t *qlen, int32_t n_ref, const uint32_t *ref_len, mm2c_err_t *err,
                             float *avg_k);
+
+/* ---- the hits of a fragment -> regions per segment on the GPU (mm_seg_gen map.c:365, hit.c:373-427: fragments of several segments mapped without CIGAR) ----
+ * Behind mm_select_sub_multi the reference splits every hit of a fragment by the segment of its anchors (bits 48-55 of y): segment s gets the chains u (the hit's
+ * score << 32 | its anchors in s, hits without one squeezed out, hit order kept) and the anchors a (in (hit, j) order, y turned into the segment's own coordinates
+ * by the 64-bit subtraction of hit.c:414 with the anchor's own strand bit), and mm_gen_regs(hash, qlens[s], ...) makes regs[s] of them, seg_split set and
+ * seg_id = s.  The plan does the same for a batch.  Input per fragment f: its hits d_regs[u_off[f] .. u_off[f] + d_n_in[f]) as mm2c_hitplan_run_device_multi
+ * wrote them (its d_regs_out / d_n_out), its chain anchors d_b[b_off[f] .. b_off[f+1]) as the region plan got them (`as` counts from b_off[f]), d_seg_len
+ * (n_frags * n_segs qlens, fragment-major), d_hash and optionally d_rep_len per fragment.  Output per "segment read" f * n_segs + s, in the CSR shape every plan
+ * above consumes, so that they run behind it unchanged with n_reads = n_frags * n_segs: d_su_off / d_su (seg[s].u), d_sb_off / d_sb (seg[s].a), d_seg_regs
+ * (indexed like d_su: byte for byte regs[s] of hit.c:419-424, klib's order among equal sort keys included), d_seg_hash and, with d_rep_len, d_seg_rep_len (the
+ * fragment's values once per segment; d_seg_len itself is the qlen of the segment reads).  Then: the hit plan with pri_ratio <= 0 is map.c:368, the mapq plan
+ * with do_join = 0 is map.c:370.
+ * Room: d_su_off / d_sb_off n_frags * n_segs + 1 entries, d_seg_hash / d_seg_rep_len n_frags * n_segs, d_sb n_b_cap anchors, d_su and d_seg_regs
+ * mm2c_segplan_seg_chain_cap() = min(n_segs * n_u_cap, n_b_cap) entries (a segment chain holds at least one anchor).  Regions and chains 8-byte, anchors
+ * 16-byte aligned; d_sb must not alias d_b.  Asynchronous on `stream`; may follow mm2c_hitplan_run_device_multi on the same stream, the host never having seen
+ * u_off or n_out.  A fragment (1) whose u_off / b_off / n_in leave the capacities or each other, (2) with a hit whose [as, as + cnt) leaves the fragment's
+ * anchors, or whose hits count more anchors than the fragment has, or (3) with an anchor whose segment is >= n_segs (the reference would write out of bounds)
+ * touches nothing and is counted: its segment reads are empty, so the CSR stays sound, mm2c_segplan_check answers MM2C_E_ARG and the fragments beside it are
+ * exact.  A fragment without hits, and a segment without anchors, give empty segment reads. */
+#define MM2C_REG_SEG_SPLIT_BIT 15
+#define MM2C_REG_SEG_ID_SHIFT 16
+typedef struct mm2c_segplan mm2c_segplan_t;
+mm2c_segplan_t *mm2c_segplan_create(int64_t n_frags, int32_t n_segs, int64_t n_u_cap, int64_t n_b_cap);
+void mm2c_segplan_destroy(mm2c_segplan_t *plan);
+int64_t mm2c_segplan_seg_chain_cap(const mm2c_segplan_t *plan);
+int mm2c_segplan_run_device(mm2c_segplan_t *plan, const int64_t *d_u_off, const mm2c_reg_t *d_regs, const int32_t *d_n_in, const int64_t *d_b_off, const void *d_b,
+                            const int32_t *d_seg_len, const uint32_t *d_hash, const int32_t *d_rep_len, int64_t *d_su_off, uint64_t *d_su, int64_t *d_sb_off,
+                            void *d_sb, mm2c_reg_t *d_seg_regs, uint32_t *d_seg_hash, int32_t *d_seg_rep_len, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a fragment was refused; *n_refused: how many; *n_seg_chains / *n_seg_anchors: su_off / sb_off of the last segment
+ * read's end (all three filled in either way; any may be NULL) */
+int mm2c_segplan_check(mm2c_segplan_t *plan, int64_t *n_refused, int64_t *n_seg_chains, int64_t *n_seg_anchors);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: the same for seg_count, the two scans, seg_scatter, the region kernels and seg_mark */
+int mm2c_segplan_last_ms(mm2c_segplan_t *plan, float *ms);
+int mm2c_segplan_last_kernel_ms(mm2c_segplan_t *plan, float *count_ms, float *offsets_ms, float *scatter_ms, float *regs_ms, float *mark_ms);
+/* host arrays in and out, room as above with the capacities u_off[n_frags] - u_off[0] and b_off[n_frags] - b_off[0].  Checks the offsets, n_in, every hit's
+ * anchors and their segments first (MM2C_E_ARG, before any device work), then uploads, runs, downloads and waits. */
+int mm2c_seg_gen_batch_host(int64_t n_frags, int32_t n_segs, const int64_t *u_off, const mm2c_reg_t *regs, const int32_t *n_in, const int64_t *b_off,
+                            const mm2c_anchor_t *b, const int32_t *seg_len, const uint32_t *hash, const int32_t *rep_len, int64_t *su_off, uint64_t *su,
+                            int64_t *sb_off, mm2c_anchor_t *sb, mm2c_reg_t *seg_regs, uint32_t *seg_hash, int32_t *seg_rep_len);
 
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits

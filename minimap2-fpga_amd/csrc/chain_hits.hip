@@ -19,6 +19,12 @@
 //               n_sub, and -- only when something was dropped (hit.c:269) -- the new ids, the parents through them, and sam_pri (bit 12) on the first hit.
 //
 // A read whose offsets leave the plan's capacities touches nothing and is counted in flags[0].
+//
+// hits_select_multi is the same kernel with mm_select_sub_multi (pe.c:6-43) in the place of mm_select_sub, for fragments of several segments (map.c:254): the
+// tables gain one row, rev (bit 10 of the bit-field word), and only lane 0's decision walk differs -- the child is judged by min_diff first (integer), then by one
+// of three ratios: pri1 when child and parent lie close on the same strand of the same reference sequence (two strict integer compares against
+// max_dist = qlens[0] + qlens[1] + max_gap_ref, wrapping, 0 unless n_segs == 2), else pri_ratio or pri2 by which of the two spans both segments.  No identical-hit
+// test; n_2nd counts every secondary that passed, kept or not.  hits_select itself is the instantiation without any of it.
 
 #include <hip/hip_runtime.h>
 #include <climits>
@@ -32,7 +38,7 @@ namespace {
 constexpr uint32_t SAM_PRI = 1u << 12;                                         // minimap.h:96: mapq:8, split:2, rev:1, inv:1, sam_pri:1
 
 struct HitTab {
-	int32_t *qs, *qe, *score, *cnt, *subsc, *nsub, *parent, *rid, *rs, *re, *w;
+	int32_t *qs, *qe, *score, *cnt, *subsc, *nsub, *parent, *rid, *rs, *re, *w, *rev;   // rev: hits_select_multi only
 	int2 *pq, *cov;
 };
 
@@ -42,7 +48,12 @@ __device__ __forceinline__ int wave_sum(int v)
 	return v;
 }
 
-__device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, const uint64_t *in, uint64_t *out, int32_t *n_out, const int n, const int lane)
+// what mm_select_sub_multi knows of the fragment: qlens[0] and max_dist (pe.c:10)
+struct MultiFrag { int32_t q0, max_dist; bool two; };
+
+template <bool MULTI>
+__device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, const uint64_t *in, uint64_t *out, int32_t *n_out, const int n, const int lane,
+                                          const MultiFrag F)
 {
 	for (int i = lane; i < n; i += 64) {
 		const uint64_t *r = in + (int64_t)i * REG_WORDS;
@@ -50,6 +61,7 @@ __device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, cons
 		T.cnt[i] = (int32_t)(w0 >> 32); T.rid[i] = (int32_t)w1; T.score[i] = (int32_t)(w1 >> 32);
 		T.qs[i] = (int32_t)w2; T.qe[i] = (int32_t)(w2 >> 32); T.rs[i] = (int32_t)w3; T.re[i] = (int32_t)(w3 >> 32);
 		T.parent[i] = (int32_t)w4; T.subsc[i] = (int32_t)(w4 >> 32); T.nsub[i] = (int32_t)(w6 >> 32);
+		if constexpr (MULTI) T.rev[i] = (int32_t)(r[7] >> (32 + 10)) & 1;
 	}
 	__syncthreads();
 
@@ -132,6 +144,24 @@ __device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, cons
 			for (int i = 0; i < n; ++i) {
 				const int p = T.parent[i];
 				bool keep = p == i;
+				if constexpr (MULTI) {                                           // pe.c:13-36
+					if (!keep) {
+						const int pp = kk > p ? src[p] : p;                      // what lies at position p by now
+						const int sc = T.score[i], scp = T.score[pp];
+						if ((int32_t)((uint32_t)sc + (uint32_t)A.min_diff) >= scp) keep = true;
+						else {
+							float ratio;
+							if (T.rev[pp] == T.rev[i] && T.rid[pp] == T.rid[i] && (int32_t)((uint32_t)T.re[i] - (uint32_t)T.rs[pp]) < F.max_dist &&
+							    (int32_t)((uint32_t)T.re[pp] - (uint32_t)T.rs[i]) < F.max_dist) ratio = A.pri1;
+							else {
+								const bool par_both = F.two && T.qs[pp] < F.q0 && T.qe[pp] > F.q0, chi_both = F.two && T.qs[i] < F.q0 && T.qe[i] > F.q0;
+								ratio = chi_both || chi_both == par_both ? A.pri_ratio : A.pri2;
+							}
+							keep = (float)sc >= (float)scp * ratio;
+						}
+						if (keep && n_2nd++ >= A.best_n) keep = false;           // pe.c:35: every secondary that passed counts
+					}
+				} else
 				if (!keep) {
 					const int pp = kk > p ? src[p] : p;                          // what lies at position p by now
 					const int sc = T.score[i], scp = T.score[pp];
@@ -168,9 +198,10 @@ __device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, cons
 	if (lane == 0) { *n_out = kept; atomicAdd(A.total, (unsigned long long)kept); }
 }
 
-__global__ __launch_bounds__(64) void hits_select(HitArgs A)
+template <bool MULTI>
+__device__ __forceinline__ void hits_block(const HitArgs &A)
 {
-	__shared__ int32_t s_tab[HITS_TAB_ROWS][HITS_LDS_MAX + 1];
+	__shared__ int32_t s_tab[HITS_TAB_ROWS + (MULTI ? 1 : 0)][HITS_LDS_MAX + 1];
 	__shared__ int2 s_pq[HITS_LDS_MAX], s_cov[HITS_LDS_MAX];
 	const int r = (int)blockIdx.x, lane = (int)threadIdx.x;
 	const int64_t base = A.u_off[r], n64 = A.u_off[r + 1] - base;
@@ -180,21 +211,35 @@ __global__ __launch_bounds__(64) void hits_select(HitArgs A)
 	}
 	const int n = (int)n64;
 	if (n == 0) { if (lane == 0) A.n_out[r] = 0; return; }
+	MultiFrag F;
+	F.q0 = 0; F.max_dist = 0; F.two = false;
+	if constexpr (MULTI) {
+		if (A.n_segs == 2) {                                                     // pe.c:10, in wrapping int
+			const int32_t *ql = A.seg_len + (int64_t)r * 2;
+			F.two = true; F.q0 = ql[0];
+			F.max_dist = (int32_t)((uint32_t)ql[0] + (uint32_t)ql[1] + (uint32_t)(A.gap_ref ? A.gap_ref[r] : A.max_gap_ref));
+		}
+	}
 	const uint64_t *in = A.in + base * REG_WORDS;
 	uint64_t *out = A.out + base * REG_WORDS;
 	HitTab T;
 	if (n <= HITS_LDS_MAX) {
 		T.qs = s_tab[0]; T.qe = s_tab[1]; T.score = s_tab[2]; T.cnt = s_tab[3]; T.subsc = s_tab[4]; T.nsub = s_tab[5]; T.parent = s_tab[6];
-		T.rid = s_tab[7]; T.rs = s_tab[8]; T.re = s_tab[9]; T.w = s_tab[10]; T.pq = s_pq; T.cov = s_cov;
-		hits_read(A, T, in, out, A.n_out + r, n, lane);
+		T.rid = s_tab[7]; T.rs = s_tab[8]; T.re = s_tab[9]; T.w = s_tab[10]; T.rev = MULTI ? s_tab[HITS_TAB_ROWS + (MULTI ? 1 : 0) - 1] : nullptr;
+		T.pq = s_pq; T.cov = s_cov;
+		hits_read<MULTI>(A, T, in, out, A.n_out + r, n, lane, F);
 	} else {                                                                     // rows of n_u_cap + n_reads entries: a read's rows hold one entry more than it has regions
 		const int64_t row = A.n_u_cap + A.n_reads;
 		int32_t *g = A.tab + base + r;
 		T.qs = g; T.qe = g + row; T.score = g + 2 * row; T.cnt = g + 3 * row; T.subsc = g + 4 * row; T.nsub = g + 5 * row; T.parent = g + 6 * row;
-		T.rid = g + 7 * row; T.rs = g + 8 * row; T.re = g + 9 * row; T.w = g + 10 * row; T.pq = A.pq + base; T.cov = A.cov + base;
-		hits_read(A, T, in, out, A.n_out + r, n, lane);
+		T.rid = g + 7 * row; T.rs = g + 8 * row; T.re = g + 9 * row; T.w = g + 10 * row; T.rev = MULTI ? g + 11 * row : nullptr;
+		T.pq = A.pq + base; T.cov = A.cov + base;
+		hits_read<MULTI>(A, T, in, out, A.n_out + r, n, lane, F);
 	}
 }
+
+__global__ __launch_bounds__(64) void hits_select(HitArgs A) { hits_block<false>(A); }
+__global__ __launch_bounds__(64) void hits_select_multi(HitArgs A) { hits_block<true>(A); }
 
 } // namespace
 
@@ -202,6 +247,13 @@ hipError_t launch_chain_hits(const HitArgs &A, hipStream_t st)
 {
 	if (A.n_reads <= 0) return hipSuccess;
 	hipLaunchKernelGGL(hits_select, dim3((unsigned)A.n_reads), dim3(64), 0, st, A);
+	return hipGetLastError();
+}
+
+hipError_t launch_chain_hits_multi(const HitArgs &A, hipStream_t st)
+{
+	if (A.n_reads <= 0) return hipSuccess;
+	hipLaunchKernelGGL(hits_select_multi, dim3((unsigned)A.n_reads), dim3(64), 0, st, A);
 	return hipGetLastError();
 }
 

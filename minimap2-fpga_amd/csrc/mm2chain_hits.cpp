@@ -1,12 +1,12 @@
-// mm2chain_hits.cpp -- C-ABI entries of the regions-to-hits step (include/mm2chain.h): hit plans (mm_set_parent + mm_select_sub on the device,
-// chain_hits.hip) and the host-buffer entry built on them.
+// mm2chain_hits.cpp -- C-ABI entries of the regions-to-hits step (include/mm2chain.h): hit plans (mm_set_parent + mm_select_sub, or mm_select_sub_multi for
+// fragments of several segments, on the device, chain_hits.hip) and the host-buffer entries built on them.
 #include "api_internal.h"
 #include "chain_hits.h"
 #include "chain_regs.h"
 
 using namespace mm2c_api;
 
-static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_hit_opt_t) == 24, "layout");
+static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_hit_opt_t) == 24 && sizeof(mm2c_hit_multi_opt_t) == 16, "layout");
 static_assert(MM2C_HIT_LDS_REGIONS == mm2c::HITS_LDS_MAX && MM2C_REG_SAM_PRI_BIT == 12, "constants of mm2chain.h");
 
 struct mm2c_hitplan {
@@ -28,7 +28,7 @@ mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap)
 	pl->n_reads = n_reads; pl->n_u_cap = n_u_cap;
 	const size_t nu = (size_t)std::max<int64_t>(n_u_cap, 1), row = (size_t)(n_u_cap + n_reads) + 1;
 	Layout L;
-	const size_t o_fl = L.take(16), o_tab = L.take(row * 4 * mm2c::HITS_TAB_ROWS), o_pq = L.take(nu * 8), o_cov = L.take(nu * 8);
+	const size_t o_fl = L.take(16), o_tab = L.take(row * 4 * (mm2c::HITS_TAB_ROWS + 1)), o_pq = L.take(nu * 8), o_cov = L.take(nu * 8);
 	pl->device = cur_device();
 	DeviceScope on(pl->device);
 	hipError_t e = on.err;
@@ -55,8 +55,9 @@ void mm2c_hitplan_destroy(mm2c_hitplan_t *pl)
 	delete pl;
 }
 
-int mm2c_hitplan_run_device(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in,
-                            mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream)
+// both modes: mopt == NULL is mm_select_sub
+static int hitplan_run(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *d_u_off, const int32_t *d_seg_len,
+                       const int32_t *d_gap_ref, const mm2c_reg_t *d_regs_in, mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream)
 {
 	if (!pl || !opt) return fail(MM2C_E_ARG, "plan or options are NULL");
 	if (!lib_ready()) return fail_not_ready();
@@ -71,14 +72,31 @@ int mm2c_hitplan_run_device(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const
 	mm2c::HitArgs &H = pl->H;
 	H.mask_level = opt->mask_level; H.mask_len = opt->mask_len; H.hard_mask_level = opt->hard_mask_level;
 	H.pri_ratio = opt->pri_ratio; H.min_diff = opt->min_diff; H.best_n = opt->best_n;
+	H.pri1 = mopt ? mopt->pri1 : 0.0f; H.pri2 = mopt ? mopt->pri2 : 0.0f; H.n_segs = mopt ? mopt->n_segs : 1; H.max_gap_ref = mopt ? mopt->max_gap_ref : 0;
+	H.seg_len = d_seg_len; H.gap_ref = d_gap_ref;
 	H.u_off = d_u_off; H.in = (const uint64_t *)d_regs_in; H.out = (uint64_t *)d_regs_out; H.n_out = d_n_out;
 	HIP_TRY(hipMemsetAsync(H.flags, 0, 16, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
-	HIP_TRY(mm2c::launch_chain_hits(H, st));
+	HIP_TRY(mopt ? mm2c::launch_chain_hits_multi(H, st) : mm2c::launch_chain_hits(H, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
 	pl->ran = true;
 	G.launches += 1;
 	return 0;
+}
+
+int mm2c_hitplan_run_device(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in,
+                            mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream)
+{
+	return hitplan_run(pl, opt, nullptr, d_u_off, nullptr, nullptr, d_regs_in, d_regs_out, d_n_out, stream);
+}
+
+int mm2c_hitplan_run_device_multi(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *d_u_off, const int32_t *d_seg_len,
+                                  const int32_t *d_gap_ref, const mm2c_reg_t *d_regs_in, mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream)
+{
+	if (!mopt) return fail(MM2C_E_ARG, "multi options are NULL");
+	if (mopt->n_segs < 1 || mopt->n_segs > MM2C_MAX_SEG) return fail(MM2C_E_ARG, "n_segs %d outside [1, %d]", mopt->n_segs, MM2C_MAX_SEG);
+	if (pl && pl->n_reads > 0 && mopt->n_segs == 2 && !d_seg_len) return fail(MM2C_E_ARG, "device pointer is NULL");
+	return hitplan_run(pl, opt, mopt, d_u_off, d_seg_len, d_gap_ref, d_regs_in, d_regs_out, d_n_out, stream);
 }
 
 int mm2c_hitplan_check(mm2c_hitplan_t *pl, int64_t *n_hits_total)
@@ -107,11 +125,14 @@ int mm2c_hitplan_last_ms(mm2c_hitplan_t *pl, float *ms)
 	return 0;
 }
 
-int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out)
+// both host entries: mopt == NULL is mm_select_sub
+static int select_hits_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *u_off, const int32_t *seg_len,
+                            const int32_t *gap_ref, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out)
 {
 	if (n_reads < 0 || n_reads > INT32_MAX || !opt) return fail(MM2C_E_ARG, "bad argument");
+	if (mopt && (mopt->n_segs < 1 || mopt->n_segs > MM2C_MAX_SEG)) return fail(MM2C_E_ARG, "n_segs %d outside [1, %d]", mopt->n_segs, MM2C_MAX_SEG);
 	if (n_reads == 0) return 0;
-	if (!u_off || !n_out) return fail(MM2C_E_ARG, "host pointer is NULL");
+	if (!u_off || !n_out || (mopt && mopt->n_segs == 2 && !seg_len)) return fail(MM2C_E_ARG, "host pointer is NULL");
 	const int64_t ub = u_off[0];
 	for (int64_t r = 0; r < n_reads; ++r)
 		if (u_off[r + 1] < u_off[r]) return fail(MM2C_E_ARG, "region offsets not monotone at read %lld", (long long)r);
@@ -123,10 +144,10 @@ int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, cons
 	for (int64_t k = 0; k <= n_reads; ++k) off[(size_t)k] = u_off[k] - ub;
 	mm2c_hitplan_t *pl = mm2c_hitplan_create(n_reads, n_u);
 	if (!pl) return MM2C_E_HIP;
-	const size_t nr = (size_t)n_reads, rb = (size_t)n_u * sizeof(mm2c_reg_t);
+	const size_t nr = (size_t)n_reads, rb = (size_t)n_u * sizeof(mm2c_reg_t), sb = mopt && seg_len ? nr * (size_t)mopt->n_segs * 4 : 0, gb = mopt && gap_ref ? nr * 4 : 0;
 	char *d = nullptr;
 	Layout L;
-	const size_t o_off = L.take((nr + 1) * 8), o_in = L.take(rb + 8), o_out = L.take(rb + 8), o_n = L.take(nr * 4);
+	const size_t o_off = L.take((nr + 1) * 8), o_in = L.take(rb + 8), o_out = L.take(rb + 8), o_n = L.take(nr * 4), o_sl = L.take(sb + 4), o_gr = L.take(gb + 4);
 	auto body = [&]() -> int {
 		DeviceScope on(pl->device);
 		HIP_TRY(on.err);
@@ -134,8 +155,14 @@ int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, cons
 		hipStream_t st = G.stream;
 		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
 		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs_in + ub, rb, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_hitplan_run_device(pl, opt, (const int64_t *)(d + o_off), (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
-		                                          (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY)) return r;
+		if (sb) HIP_TRY(hipMemcpyAsync(d + o_sl, seg_len, sb, hipMemcpyHostToDevice, st));
+		if (gb) HIP_TRY(hipMemcpyAsync(d + o_gr, gap_ref, gb, hipMemcpyHostToDevice, st));
+		const int r = mopt ? mm2c_hitplan_run_device_multi(pl, opt, mopt, (const int64_t *)(d + o_off), sb ? (const int32_t *)(d + o_sl) : nullptr,
+		                                                   gb ? (const int32_t *)(d + o_gr) : nullptr, (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
+		                                                   (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY)
+		                   : mm2c_hitplan_run_device(pl, opt, (const int64_t *)(d + o_off), (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
+		                                             (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY);
+		if (r) return r;
 		if (n_u > 0) HIP_TRY(hipMemcpyAsync(regs_out, d + o_out, rb, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(n_out, d + o_n, nr * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
@@ -145,6 +172,18 @@ int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, cons
 	dev_free(d);
 	mm2c_hitplan_destroy(pl);
 	return rc;
+}
+
+int mm2c_select_hits_batch_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const int64_t *u_off, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out)
+{
+	return select_hits_host(n_reads, opt, nullptr, u_off, nullptr, nullptr, regs_in, regs_out, n_out);
+}
+
+int mm2c_select_hits_multi_batch_host(int64_t n_frags, const mm2c_hit_opt_t *opt, const mm2c_hit_multi_opt_t *mopt, const int64_t *u_off, const int32_t *seg_len,
+                                      const int32_t *gap_ref, const mm2c_reg_t *regs_in, mm2c_reg_t *regs_out, int32_t *n_out)
+{
+	if (!mopt) return fail(MM2C_E_ARG, "bad argument");
+	return select_hits_host(n_frags, opt, mopt, u_off, seg_len, gap_ref, regs_in, regs_out, n_out);
 }
 
 } // extern "C"

@@ -82,6 +82,11 @@ class HitOpt(C.Structure):
                 ("best_n", C.c_int32)]
 
 
+class HitMultiOpt(C.Structure):
+    """mm2c_hit_multi_opt_t: what mm_select_sub_multi takes beyond mm2c_hit_opt_t (pe.c:6; map.c:254 passes 0.2f, 0.7f)"""
+    _fields_ = [("pri1", C.c_float), ("pri2", C.c_float), ("n_segs", C.c_int32), ("max_gap_ref", C.c_int32)]
+
+
 class MapqOpt(C.Structure):
     """mm2c_mapq_opt_t: mm_join_long's switch and thresholds (options.c:38-41), mm_filter_regs' min_cnt, mm_set_mapq's min_chain_sc"""
     _fields_ = [("do_join", C.c_int32), ("max_join_long", C.c_int32), ("max_join_short", C.c_int32), ("min_join_flank_sc", C.c_int32),
@@ -96,6 +101,9 @@ class Err(C.Structure):
 MM2C_REG_SAM_PRI_BIT = 12
 MM2C_HIT_LDS_REGIONS = 128
 MM2C_MAPQ_MAX_LOG_ARG = (1 << 24) - 1
+MM2C_MAX_SEG = 255
+MM2C_REG_SEG_SPLIT_BIT = 15
+MM2C_REG_SEG_ID_SHIFT = 16
 MM2C_SEED_LONG_JOIN_BIT = 40
 
 C_SYMBOLS = {
@@ -164,6 +172,16 @@ C_SYMBOLS = {
     "mm2c_hitplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mm2c_hitplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_select_hits_batch_host": (C.c_int, [C.c_int64, C.POINTER(HitOpt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_hitplan_run_device_multi": (C.c_int, [C.c_void_p, C.POINTER(HitOpt), C.POINTER(HitMultiOpt)] + [C.c_void_p] * 7),
+    "mm2c_select_hits_multi_batch_host": (C.c_int, [C.c_int64, C.POINTER(HitOpt), C.POINTER(HitMultiOpt)] + [C.c_void_p] * 6),
+    "mm2c_segplan_create": (C.c_void_p, [C.c_int64, C.c_int32, C.c_int64, C.c_int64]),
+    "mm2c_segplan_destroy": (None, [C.c_void_p]),
+    "mm2c_segplan_seg_chain_cap": (C.c_int64, [C.c_void_p]),
+    "mm2c_segplan_run_device": (C.c_int, [C.c_void_p] * 17),
+    "mm2c_segplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_segplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_segplan_last_kernel_ms": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_float)] * 5),
+    "mm2c_seg_gen_batch_host": (C.c_int, [C.c_int64, C.c_int32] + [C.c_void_p] * 15),
     "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "mm2c_mapqplan_destroy": (None, [C.c_void_p]),
     "mm2c_mapqplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(MapqOpt)] + [C.c_void_p] * 12),

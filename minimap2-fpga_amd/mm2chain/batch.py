@@ -447,6 +447,27 @@ class HitPlan:
                 "mm2c_hitplan_run_device")
         return regs_out, n_out[:self.n_reads]
 
+    def run_multi(self, opt, mopt, u_off: torch.Tensor, seg_len: torch.Tensor, regs_in: torch.Tensor, gap_ref: torch.Tensor = None, regs_out: torch.Tensor = None,
+                  n_out: torch.Tensor = None, stream=None):
+        """mm2c_hitplan_run_device_multi: mm_set_parent, then mm_select_sub_multi (pe.c:6-43) for fragments of mopt.n_segs segments.  mopt: params.hit_multi_opts();
+        seg_len int32 [n_frags * n_segs] (qlens, fragment-major); gap_ref int32 [n_frags] (max_chain_gap_ref per fragment) or None for mopt.max_gap_ref everywhere.
+        Everything else as run()."""
+        assert u_off.is_cuda and u_off.is_contiguous() and u_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1
+        assert regs_in.is_cuda and regs_in.is_contiguous() and regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        assert seg_len.is_cuda and seg_len.is_contiguous() and seg_len.dtype == torch.int32 and seg_len.numel() >= self.n_reads * mopt.n_segs
+        assert gap_ref is None or (gap_ref.is_cuda and gap_ref.is_contiguous() and gap_ref.dtype == torch.int32 and gap_ref.numel() >= self.n_reads)
+        if regs_out is None:
+            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
+        if n_out is None:
+            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
+        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
+        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_hitplan_run_device_multi(self.handle, C.byref(opt), C.byref(mopt), u_off.data_ptr(), seg_len.data_ptr(),
+                                                       gap_ref.data_ptr() if gap_ref is not None else None, regs_in.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(), st),
+                "mm2c_hitplan_run_device_multi")
+        return regs_out, n_out[:self.n_reads]
+
     def check(self):
         """waits for the run; raises if a read's offsets left the capacities; returns the number of hits of all reads"""
         n = C.c_int64(0)
@@ -484,6 +505,130 @@ def select_hits_batch(opt, u_off, regs):
     n_out = np.zeros(max(n_reads, 1), np.int32)
     N.check(lib.mm2c_select_hits_batch_host(n_reads, C.byref(opt), _np_ptr(uo), _np_ptr(rr), _np_ptr(out), _np_ptr(n_out)), "mm2c_select_hits_batch_host")
     return out[:n_u], n_out[:n_reads]
+
+
+def select_hits_multi_batch(opt, mopt, u_off, seg_len, regs, gap_ref=None):
+    """mm2c_select_hits_multi_batch_host: host arrays in -> (regs_out, n_out) as select_hits_batch, with mm_select_sub_multi in the place of mm_select_sub"""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64))
+    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    sl = np.ascontiguousarray(seg_len, dtype=np.int32).reshape(-1)
+    gr = None if gap_ref is None else np.ascontiguousarray(gap_ref, dtype=np.int32)
+    n_reads = uo.size - 1
+    if (n_reads > 0 and (uo[0] < 0 or uo.max() > rr.shape[0])) or sl.size != n_reads * mopt.n_segs or (gr is not None and gr.size != n_reads):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
+    out = np.zeros(max(n_u, 1), REG_DTYPE)
+    n_out = np.zeros(max(n_reads, 1), np.int32)
+    N.check(lib.mm2c_select_hits_multi_batch_host(n_reads, C.byref(opt), C.byref(mopt), _np_ptr(uo), _np_ptr(sl), _np_ptr(gr) if gr is not None else None,
+                                                  _np_ptr(rr), _np_ptr(out), _np_ptr(n_out)), "mm2c_select_hits_multi_batch_host")
+    return out[:n_u], n_out[:n_reads]
+
+
+class SegPlan:
+    """mm2c_segplan_t: the hits of fragments of n_segs segments -> chains, anchors and regions per segment on the GPU (mm_seg_gen hit.c:373-427) for batches of up
+    to n_frags fragments, n_u_cap hits and n_b_cap chain anchors; it stands behind HitPlan.run_multi on the same stream, and a HitPlan (pri_ratio 0) and a MapqPlan
+    (do_join 0) over n_frags * n_segs "segment reads" stand behind it."""
+
+    def __init__(self, n_frags, n_segs, n_u_cap, n_b_cap):
+        self.lib = N.load()
+        self.n_frags, self.n_segs, self.n_u_cap, self.n_b_cap = int(n_frags), int(n_segs), int(n_u_cap), int(n_b_cap)
+        self.handle = self.lib.mm2c_segplan_create(self.n_frags, self.n_segs, self.n_u_cap, self.n_b_cap)
+        if not self.handle:
+            N.check(-1, "mm2c_segplan_create")
+        self.n_seg_reads = self.n_frags * self.n_segs
+        self.n_su_cap = int(self.lib.mm2c_segplan_seg_chain_cap(self.handle))
+
+    def run(self, u_off: torch.Tensor, regs: torch.Tensor, n_in: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, seg_len: torch.Tensor, hash: torch.Tensor,
+            rep_len: torch.Tensor = None, out: dict = None, stream=None):
+        """u_off, regs and n_in as HitPlan.run_multi took and returned them, b_off / b the fragments' chain anchors, seg_len int32 [n_frags * n_segs], hash (32-bit)
+        and optionally rep_len int32 per fragment, all on the GPU.  Returns a dict of GPU tensors (out: one from an earlier run, to write into again): su_off /
+        sb_off int64 [n_seg_reads + 1], su int64 [n_su_cap], sb int64 [n_b_cap, 2], seg_regs uint8 [n_su_cap, 80], seg_hash int32 [n_seg_reads], seg_rep_len int32
+        [n_seg_reads] or None.  Asynchronous."""
+        for t in (u_off, regs, n_in, b_off, b, seg_len, hash) + ((rep_len,) if rep_len is not None else ()):
+            assert t.is_cuda and t.is_contiguous()
+        assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and u_off.numel() == self.n_frags + 1 and b_off.numel() == self.n_frags + 1
+        assert regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
+        assert n_in.dtype == torch.int32 and n_in.numel() >= self.n_frags and seg_len.dtype == torch.int32 and seg_len.numel() >= self.n_seg_reads
+        assert hash.element_size() == 4 and hash.numel() >= self.n_frags and (rep_len is None or (rep_len.dtype == torch.int32 and rep_len.numel() >= self.n_frags))
+        dev, ns = u_off.device, max(self.n_seg_reads, 1)
+        if out is None:
+            out = dict(su_off=torch.empty(ns + 1, dtype=torch.int64, device=dev), sb_off=torch.empty(ns + 1, dtype=torch.int64, device=dev),
+                       su=torch.empty(max(self.n_su_cap, 1), dtype=torch.int64, device=dev), sb=torch.empty((max(self.n_b_cap, 1), 2), dtype=torch.int64, device=dev),
+                       seg_regs=torch.empty((max(self.n_su_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=dev),
+                       seg_hash=torch.empty(ns, dtype=torch.int32, device=dev), seg_rep_len=None)
+        if rep_len is not None and out.get("seg_rep_len") is None:
+            out["seg_rep_len"] = torch.empty(ns, dtype=torch.int32, device=dev)
+        assert out["su_off"].numel() >= self.n_seg_reads + 1 and out["sb_off"].numel() >= self.n_seg_reads + 1 and out["su"].numel() >= self.n_su_cap
+        assert out["sb"].numel() >= 2 * self.n_b_cap and out["seg_regs"].numel() >= self.n_su_cap * REG_DTYPE.itemsize and out["seg_hash"].numel() >= self.n_seg_reads
+        for t in out.values():
+            assert t is None or (t.is_cuda and t.is_contiguous())
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_segplan_run_device(self.handle, u_off.data_ptr(), regs.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(), seg_len.data_ptr(),
+                                                 hash.data_ptr(), rep_len.data_ptr() if rep_len is not None else None, out["su_off"].data_ptr(), out["su"].data_ptr(),
+                                                 out["sb_off"].data_ptr(), out["sb"].data_ptr(), out["seg_regs"].data_ptr(), out["seg_hash"].data_ptr(),
+                                                 out["seg_rep_len"].data_ptr() if rep_len is not None else None, st), "mm2c_segplan_run_device")
+        return out
+
+    def counts(self):
+        """waits for the run -> (return code, fragments refused, segment chains, segment anchors) without raising"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_segplan_check(self.handle, C.byref(a), C.byref(b), C.byref(c))
+        return rc, a.value, b.value, c.value
+
+    def check(self):
+        """waits for the run; raises (code -2) if a fragment was refused; returns (segment chains, segment anchors) of the batch"""
+        rc, _, nu, na = self.counts()
+        N.check(rc, "mm2c_segplan_check")
+        return nu, na
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_segplan_last_ms(self.handle, C.byref(ms)), "mm2c_segplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(seg_count, the two scans, seg_scatter, the region kernels, seg_mark) of the last run"""
+        v = [C.c_float(0) for _ in range(5)]
+        N.check(self.lib.mm2c_segplan_last_kernel_ms(self.handle, *[C.byref(x) for x in v]), "mm2c_segplan_last_kernel_ms")
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_segplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def seg_gen_batch(n_segs, u_off, regs, n_in, b_off, b, seg_len, hash, rep_len=None):
+    """mm2c_seg_gen_batch_host: host arrays in -> dict(su_off, su uint64, sb_off, sb uint64 [., 2], seg_regs REG_DTYPE, seg_hash uint32, seg_rep_len int32 or None);
+    segment read f * n_segs + s owns su[su_off[k] : su_off[k+1]] (and seg_regs likewise) and sb[sb_off[k] : sb_off[k+1]]"""
+    lib = N.load()
+    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
+    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    ni = np.ascontiguousarray(n_in, dtype=np.int32); sl = np.ascontiguousarray(seg_len, dtype=np.int32).reshape(-1); h = np.ascontiguousarray(hash, dtype=np.uint32)
+    rl = None if rep_len is None else np.ascontiguousarray(rep_len, dtype=np.int32)
+    n_frags, n_segs = uo.size - 1, int(n_segs)
+    if bo.size != uo.size or ni.size != n_frags or h.size != n_frags or sl.size != n_frags * n_segs or (rl is not None and rl.size != n_frags) or \
+            (n_frags > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0])):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(uo[-1] - uo[0]) if n_frags > 0 else 0
+    n_b = int(bo[-1] - bo[0]) if n_frags > 0 else 0
+    ns, n_su = max(n_frags * n_segs, 0), min(n_segs * n_u, n_b)
+    su_off = np.zeros(ns + 1, np.int64); sb_off = np.zeros(ns + 1, np.int64)
+    su = np.zeros(max(n_su, 1), np.uint64); sb = np.zeros((max(n_b, 1), 2), np.uint64); seg_regs = np.zeros(max(n_su, 1), REG_DTYPE)
+    seg_hash = np.zeros(max(ns, 1), np.uint32); seg_rl = np.zeros(max(ns, 1), np.int32) if rl is not None else None
+    N.check(lib.mm2c_seg_gen_batch_host(n_frags, n_segs, _np_ptr(uo), _np_ptr(rr), _np_ptr(ni), _np_ptr(bo), _np_ptr(bb), _np_ptr(sl), _np_ptr(h),
+                                        _np_ptr(rl) if rl is not None else None, _np_ptr(su_off), _np_ptr(su), _np_ptr(sb_off), _np_ptr(sb), _np_ptr(seg_regs),
+                                        _np_ptr(seg_hash), _np_ptr(seg_rl) if rl is not None else None), "mm2c_seg_gen_batch_host")
+    tu, ta = int(su_off[-1]), int(sb_off[-1])
+    return dict(su_off=su_off, su=su[:tu], sb_off=sb_off, sb=sb[:ta], seg_regs=seg_regs[:tu], seg_hash=seg_hash[:ns], seg_rep_len=(seg_rl[:ns] if rl is not None else None))
 
 
 class MapqPlan:

@@ -1,5 +1,5 @@
 """Chaining parameter presets, mirroring options.c of the reference (file:line cited per preset)."""
-from ._native import Params, HitOpt, MapqOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
+from ._native import Params, HitOpt, HitMultiOpt, MapqOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
 
 INT32_MAX = 2**31 - 1
 
@@ -52,6 +52,12 @@ def hit_opts(k=15, **kw):
         raise TypeError(f"hit_opts: unknown field(s) {sorted(unknown)}")
     v.update(kw)
     return HitOpt(v["mask_level"], v["mask_len"], int(bool(v["hard_mask_level"])), v["pri_ratio"], v["min_diff"], v["best_n"])
+
+
+def hit_multi_opts(n_segs=2, max_gap_ref=500, pri1=0.2, pri2=0.7):
+    """mm2c_hit_multi_opt_t: pri1 and pri2 as mm_map_frag passes them to mm_select_sub_multi (map.c:254: 0.2f, 0.7f), the fragment's n_segs, and max_gap_ref for a
+    run without per-fragment values (map.c:309-314; -x sr with 2 x 150 bases: max(800 - 300, 100) = 500)"""
+    return HitMultiOpt(pri1, pri2, int(n_segs), int(max_gap_ref))
 
 
 def mapq_opts(**kw):
