@@ -110,7 +110,9 @@ int  mm2c_device_identity(int *ordinal, char *pci_bus_id, size_t bus_len, char *
  * entries may have in flight at once on each device (default 4; env MM2C_COMBINER_LANES), "combine_max_anchors" = a call of more anchors than this runs alone (env MM2C_COMBINE_MAX);
  * "packed_fp" 1 = plan tasks of the compact ring with at most 8192 anchors and a span sum of at most 131071 run an instantiation that keeps f and p of a ring anchor in one word
  * (four tiles of f / p in the LDS of two, deeper ones from a side array with one load; default; a plan that holds a task of more than 8192 anchors, or whose gap_scale is negative -- the gap cost is then a gain and f is not bounded by the span sum --,
- * runs without it, and mm2c_plan_last_variant says so), 0 = never. */
+ * runs without it, and mm2c_plan_last_variant says so), 0 = never;
+ * "score_bound_exit" 1 = the hand-written loop of the tile kernel ends an anchor's scan once the largest f before its tile plus its span cannot beat its best (the rest of such a scan only
+ * decides where the scan ends, chain.c:231: same f / p; default; a call with gap_scale < 0 runs without it, and the variant text says score_exit=0), 0 = never. */
 int  mm2c_tune(const char *key, int value);
 
 /* HW/SW split model of the reference for this hardware (chain.c:80-81,101; constants in the form of chain_hardware.h:19-30 live in

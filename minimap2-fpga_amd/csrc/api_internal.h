@@ -44,6 +44,7 @@ struct Global {
 	std::atomic<int> split_streams{1};                  // plans: the instantiations a batch is split over (32-bit / compact ring) run side by side on two streams
 	std::atomic<int> compact_ring{1};                   // tile kernel: the compact x / q ring for the tasks whose q values allow it (0: never; the parity tests run both)
 	std::atomic<int> packed_fp{1};                      // tile kernel: the packed f / p ring for the plan tasks it can hold (0: the routing without it; the tests run both)
+	std::atomic<int> score_bound_exit{1};               // tile kernel: the hand-written loop ends an anchor's scan once no older score can beat its best (0: never; the tests run both)
 	std::atomic<int> q24_ring{1};                       // tile kernel: the long ring of class-1 tasks in the q24 form (0: 32-bit slots; the parity tests run both)
 	std::atomic<int> force_tab{0};                      // tile kernel: gap cost from the LDS table also when gap_scale == 1 (tests; slower)
 	std::atomic<int> far_ring{1};                       // plans: tasks whose scans are expected to leave the short LDS ring run with a ring twice as long (0: never, 2: all)
@@ -87,7 +88,7 @@ extern Global G;
 // ring-size classes and of the wide share go with them
 inline void knobs_into(mm2c::LaunchArgs &L, bool cls_arrays = true)
 {
-	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop;
+	L.ring_class = G.ring_class; L.force_tab = G.force_tab; L.compact = G.compact_ring; L.q24 = G.q24_ring; L.noskip_loop = G.noskip_loop; L.score_exit = G.score_bound_exit;
 	L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
 	if (cls_arrays) { L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct; }
 }
@@ -179,14 +180,16 @@ struct ThreadCtx {
 	}
 };
 
-// "chain_dp_tile<...> loop=asm ... compact=1": the text of mm2c_plan_last_variant / mm2c_last_host_variant
-inline void format_variant(const mm2c::LaunchInfo &I, char *buf, size_t len)
+// "chain_dp_tile<...> loop=asm ... compact=1": the text of mm2c_plan_last_variant / mm2c_last_host_variant (score_exit: they add " score_exit=0|1" for the tile
+// kernel; the route table of tests/route_dump.cpp is printed without it)
+inline void format_variant(const mm2c::LaunchInfo &I, char *buf, size_t len, bool score_exit = false)
 {
 	if (I.tile && I.coop) snprintf(buf, len, "chain_dp_coop<W=%d,NX=%d,NF=%d,GS1=%d,FAR=%d,TAB=%d> loop=%s classes=0 cut=0 compact=0 coop=%d st=%s", I.coop, I.nx, I.nf, I.gs1,
 	                               I.far_, I.tab, I.asm_loop ? "asm" : "c++", I.coop, I.fused_st ? "kernel" : "prepass");
 	else if (I.tile) snprintf(buf, len, "chain_dp_tile<NX=%d,NF=%d,SKIP=%d,GEN=%d,GS1=%d,FAR=%d,TAB=%d> loop=%s classes=%d cut=%d compact=%d q24=%d packed_fp=%d", I.nx, I.nf, I.skip, I.gen, I.gs1,
 	                     I.far_, I.tab, I.asm_loop ? "asm" : "c++", I.classes, I.cut, I.c16, I.q24, I.packed);
 	else snprintf(buf, len, "chain_dp_wave<R=%d,SKIP=%d,GEN=%d,GS1=%d,FAR=%d> loop=c++ classes=0 cut=%d", I.r, I.skip, I.gen, I.gs1, I.far_, I.cut);
+	if (score_exit && I.tile && !I.coop) { const size_t k = strlen(buf); snprintf(buf + k, len - k, " score_exit=%d", I.score_exit); }
 }
 void note_host_variant(const mm2c::LaunchInfo &I);   // mm2chain_host.cpp
 

@@ -748,11 +748,18 @@ __device__ unsigned long long g_label_hits[8 * 32];   // row = compact << 2 | ta
 #define MM2C_LB_FOLD "0x10000000"
 #define MM2C_LB_DONE "0x20000000"
 #define MM2C_LB_SPEC "0x40000000"
+#define MM2C_LB_EXIT "0x80000000"   /* the score-bound exit (MM2C_EXIT_TEST); tests/test_gpu_labels.py does not look at this bit */
+// The score-bound exit.  A pair scores at most f[j] + span_i (chain.c:207-220: min(dq, dr, span) minus a gap cost that is >= 0 while gap_scale >= 0), and pfx is the
+// maximum of f over every anchor of the piece before the tile in progress, so once the own-tile chunk is behind the scan and pfx + span_i <= best no anchor still to
+// come can raise the best: what is left of the scan would only count skip events until the `break` of chain.c:231, which decides where the scan ends and never the
+// value.  Tested wherever a fold has just raised the best (fold A leaves it alone); the way out is the `break`'s.  pfx = INT_MAX (the first tile of a piece, gap_scale
+// < 0, mm2c_tune("score_bound_exit", 0)) never passes.  T: a free scalar.
+#define MM2C_EXIT_TEST(T) "s_sub_i32 " T ", %[best], %[span1]\n\t" "s_cmp_gt_i32 " T ", %[pfx]\n\t" MM2C_LC_BR_SCC1("Ldone_%=", MM2C_LB_EXIT)
 #define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, UNPACK, FGFIX, STSH, SCORE, ADDF, SEG_RD, SEG_LK, SEG_HF, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
 template <int NX, int NF> \
 __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, float avg, const int32_t *f, const int32_t *p, const int32_t *wq, int pbase, const uint4 *a, \
                                     int32_t *tg, int tx, int tx1, int tq, int tq1, int tspan, int tlo, int tlo0, int tw, int &own_f, int &own_p, \
-                                    int addr1, int addr2, int lomc, int ownst, int rl, int mdqbw_v, int bw_v, int sent_v, int addr1q, int selq_v MM2C_LC_PARAM) \
+                                    int addr1, int addr2, int lomc, int ownst, int rl, int mdqbw_v, int bw_v, int sent_v, int addr1q, int selq_v MM2C_LC_PARAM, int pfx = INT_MAX) \
 { \
 	typedef Lds<NX, NF, false, TABV, C16V> LY; \
 	typedef Lds<NX, NF, false, true, C16V> LYT; \
@@ -869,6 +876,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_lshl_b32 %[t1], %[d], 6\n\t" \
 		"s_sub_i32 %[bestj], %[i063], %[t1]\n\t"   /* i0 + 63 - 64 d - lane */ \
 		"s_sub_i32 %[bestj], %[bestj], %[t0]\n\t" \
+		MM2C_EXIT_TEST("%[t1]") \
 		"s_sub_i32 %[nskip], %[nskip], 1\n\t" \
 		"s_max_i32 %[nskip], %[nskip], 0\n\t" \
 		"s_bitset0_b64 %[marked], %[t0]\n\t" \
@@ -898,8 +906,10 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_ff1_i32_b64 %[t0], vcc\n\t" \
 		"v_readlane_b32 %[best], %[sc], %[t0]\n\t" \
 		"s_add_i32 %[t1], %[base], 63\n\t" \
-		"s_sub_i32 %[bestj], %[t1], %[t0]\n\t" \
-		"s_branch Lret_%=\n" \
+		"s_sub_i32 %[bestj], %[t1], %[t0]\n" \
+		"Lretx_%=:\n\t"                               /* where the general folds come back with a new best: the score-bound exit, else on with the scan */ \
+		MM2C_EXIT_TEST("%[t0]") \
+		"s_branch " LNEXT "\n" \
 		"Lb1m_%=:\n\t" \
 		MM2C_LC(MM2C_LB_B1M) \
 		"v_mov_b32 %[va], %[sc]\n\t" \
@@ -911,7 +921,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_ff1_i32_b64 %[t0], vcc\n\t" \
 		"s_add_i32 %[t1], %[base], 63\n\t" \
 		"s_sub_i32 %[bestj], %[t1], %[t0]\n\t" \
-		"s_branch Lret_%=\n" \
+		"s_branch Lretx_%=\n" \
 		"Lb2_%=:\n\t" \
 		MM2C_LC(MM2C_LB_B2) \
 		"v_mov_b32 %[va], %[sc]\n\t" \
@@ -1002,7 +1012,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"Laf_%=:\n\t" \
 		MM2C_LC(MM2C_LB_AF) \
 		"s_cmp_eq_u32 %[last], 63\n\t" \
-		"s_cbranch_scc1 Lret_%=\n\t" \
+		"s_cbranch_scc1 Lretx_%=\n\t" \
 		"s_branch Ldone_%=\n" \
 		SEG_END(SCORE, FARFILTER) \
 		"Ldone_%=:\n\t" \
@@ -1030,7 +1040,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		  [dr] "=&v"(dr), [dq] "=&v"(dq), [dd] "=&v"(dd), [u1] "=&v"(u1), [u2] "=&v"(u2), \
 		  [sc] "=&v"(sc), [va] "=&v"(va), [vb] "=&v"(vb), [vc] "=&v"(vc), [addr] "=&v"(addr), [s16v] "=&v"(s16v), [lom1v] "=&v"(lom1v), [fx] "=&v"(fx), [fq] "=&v"(fq), \
 		  [own_f] "+v"(own_f), [own_p] "+v"(own_p) MM2C_PROBE_OPERAND MM2C_LC_OPERAND \
-		: [i0] "s"(i0), [kstart] "s"(k_start), [cnt] "s"(cnt), [icnt1] "s"(i0 + cnt + 1), [i063] "s"(i0 + 63), [c200] "s"(0x200), [maxskip] "s"(max_skip), [avg] "s"(avg), [fptr] "s"(f), [pptr] "s"(p), [wptr] "s"(wq), [pbase] "s"(pbase), [aptr] "s"(a), [tptr] "s"(tg), \
+		: [i0] "s"(i0), [kstart] "s"(k_start), [cnt] "s"(cnt), [icnt1] "s"(i0 + cnt + 1), [i063] "s"(i0 + 63), [c200] "s"(0x200), [maxskip] "s"(max_skip), [avg] "s"(avg), [fptr] "s"(f), [pptr] "s"(p), [wptr] "s"(wq), [pbase] "s"(pbase), [aptr] "s"(a), [tptr] "s"(tg), [pfx] "s"(pfx), \
 		  [tx] "v"(tx), [tx1] "v"(tx1), [tq] "v"(tq), [tq1] "v"(tq1), [tspan] "v"(tspan), [tlo] "v"(tlo), [tlo0] "v"(tlo0), [tw] "v"(tw), \
 		  [addr1] "v"(addr1), [addr2] "v"(addr2), [lomc] "v"(lomc), [ownst] "v"(ownst), [rl] "v"(rl), [mdqbw] "v"(mdqbw_v), [bw] "v"(bw_v), [sent] "v"(sent_v), \
 		  [addr1q] "v"(addr1q), [selq] "v"(selq_v), [QHOFF] "n"(LY::QH), \
@@ -1083,7 +1093,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
               const uint4 *__restrict__ a_all, const float *__restrict__ avg_in, const int32_t *__restrict__ pbase_in,
               const int32_t *__restrict__ st_all, int32_t *__restrict__ f_all, int32_t *__restrict__ p_all, int32_t *__restrict__ t_all,
               int32_t *__restrict__ w_all /* packed f / p words, one per anchor (RING 3 only) */, int32_t *__restrict__ status, int only_flagged, const int64_t *__restrict__ ends, const int32_t *__restrict__ n_live,
-              const uint8_t *__restrict__ cls, int my_cls, int cls_mask)
+              const uint8_t *__restrict__ cls, int my_cls, int cls_mask, int score_exit /* 1: the score-bound exit of the hand-written loop (MM2C_EXIT_TEST; the host: gap_scale >= 0) */)
 {
 	static_assert(!C16 || (SKIP && !GEN && (GS1 || TAB)), "the compact and the q24 ring belong to the variants of the hand-written loop");
 	static_assert(NF >= 1 && NF < NX && (NF & (NF - 1)) == 0 && (NX & (NX - 1)) == 0, "rings of a power of two of tiles, addressed with masks");
@@ -1152,10 +1162,12 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 #ifdef MM2C_LABEL_COUNT
 	int lc_v = 0;                                             // lane b: how often the hand-written loop passed label b since the last flush
 #endif
+	int f_done = INT_MIN;                                     // maximum of f over the finished tiles of this task (a piece cut on the device is a task: it starts its own)
 	uint4 cur = (rl < n) ? a[rl] : make_uint4(0, 0, 0, 0);
 	int cur_st = (rl < n) ? st[rl] - st_sub : 0;
 	for (int i0 = 0; i0 < n; i0 += 64) {
 		const int idx = i0 + rl;
+		const int pfx = __builtin_amdgcn_readfirstlane(score_exit && i0 > 0 ? f_done : INT_MAX);   // what the score-bound exit compares with (MM2C_EXIT_TEST); INT_MAX: off
 		const int cnt = __builtin_amdgcn_readfirstlane(min(64, n - i0));
 		uint4 nxt = make_uint4(0, 0, 0, 0); int nxt_st = 0;
 		if (idx + 64 < n) { nxt = a[idx + 64]; nxt_st = st[idx + 64] - st_sub; }   // prefetch the next tile
@@ -1231,7 +1243,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 		for (int k = 0; k < cnt; ++k) {
 			if (ASM) {
 #define MM2C_CALL(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, w, pbase, a, t, own_x, tx1_l, own_q, tq1_l, span_l, lo_c, \
-                                 LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, addr0 >> 2, selq_v MM2C_LC_ARG)
+                                 LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, addr0 >> 2, selq_v MM2C_LC_ARG, pfx)
 				if (C16 == 2) {
 					// the q24 forms take what the 32-bit ones take (x, q, x - 1, q - 1 in full) + the byte ring's address of the tile before and the byte selector
 					if (FAR && tile_far) k = TAB ? MM2C_CALL(scan_tile_asm_tab_far_q, lo_l) : MM2C_CALL(scan_tile_asm_cmp_far_q, lo_l);
@@ -1239,7 +1251,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 				} else if (C16) {
 					// the compact forms take packed words where the 32-bit ones take x and q: the tile's own {x, q} halves and the anchors' {x - 1, q - 1} halves
 #define MM2C_CALLC(FN, LO0) FN<NX, NF>(i0, __builtin_amdgcn_readfirstlane(k), cnt, P.max_skip, avg, f, p, w, pbase, a, t, own_xq, own_xq1, own_xq, own_xq1, span_l, lo_c, \
-                                 LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, 0, 0 MM2C_LC_ARG)
+                                 LO0, tw_l, own_f, own_p, addr0, addr0b, lomc_v, ownst, rl, mdqbw_v, X.bw_v, sent_v, 0, 0 MM2C_LC_ARG, pfx)
 					if (C16 == 3) {
 						if (FAR && tile_far) k = TAB ? MM2C_CALLC(scan_tile_asm_tab_far_p, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_far_p, lo_l);
 						else k = TAB ? MM2C_CALLC(scan_tile_asm_tab_p, lo_l) : MM2C_CALLC(scan_tile_asm_cmp_p, lo_l);
@@ -1285,6 +1297,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 		}
 		// ---- the finished tile: results leave in coalesced stores ...
 		if (rl < cnt) { f[idx] = own_f; p[idx] = own_p < 0 ? own_p : own_p + pbase; }
+		if (ASMV) f_done = max(f_done, rdlane(prefix_max_incl(rl < cnt ? own_f : INT_MIN), 63));   // one wave reduction per tile
 		if (LY::FS == 4) {
 			const int v = pack_fp(own_f - FBIAS, own_p);   // ... and enters the f / p ring and the side array as one word (lanes beyond the task hold f = 0, p = -1)
 			*(int *)(lds + LY::FP + ((idx << 2) & LY::FMASK)) = v;

@@ -55,6 +55,8 @@ struct LaunchArgs {
 	int compact = 1;            // 0: never the compact x / q ring (mm2c_tune("compact_ring", 0); the parity tests run both)
 	int q24 = 1;                // 0: the long ring of class-1 tasks keeps its 32-bit slots (mm2c_tune("q24_ring", 0); the parity tests run both); 1: the q24 ring (16 + 24 bits, 7 KB)
 	int packed_fp = 1;          // 0: never the packed f / p ring (mm2c_tune("packed_fp", 0): the routing without it); 1: tasks of the compact ring whose p and f fit one word take it (needs d_w)
+	int score_exit = 1;         // 0: the hand-written loop of the tile kernel never leaves a scan by the score bound (mm2c_tune("score_bound_exit", 0); the tests run both); 1: it does where
+	                            // the bound holds, gap_scale >= 0 (decide_route; chain_dp_tile.h, MM2C_EXIT_TEST)
 	int32_t *d_w = nullptr;     // one word per anchor of workspace, or nullptr: the packed f / p words of finished tiles (chain_dp_tile.h, Lds<> RING 3), read back by scans deeper than the f / p ring
 	unsigned long long *d_cls_stat = nullptr;   // CLS_STAT_SLOTS sets of four counters, zero on entry (chain_cls_settle), or nullptr
 	int wide_pct = 40;          // when the tasks that need the 32-bit x / q ring hold more than this share of the batch's anchors, every task takes it
@@ -98,6 +100,7 @@ struct LaunchInfo {
 	int classes;     // ring-size classes: class-1 tasks run the instantiation with 2 * nx tiles
 	int c16;         // tasks whose q values allow it run the instantiations with the compact x / q ring (per task: bit 1 of its class clear)
 	int q24;         // class-1 tasks (long ring) run the instantiation with the q24 ring (chain_dp_tile.h, Lds<> RING 2) instead of 32-bit slots
+	int score_exit;  // the hand-written loop of the tile kernel ends an anchor's scan once no older score can beat its best (chain_dp_tile.h, MM2C_EXIT_TEST)
 	int packed;      // tasks of the compact ring whose p and f fit one word (bit 3 of the class) run the instantiation with the packed f / p ring of four tiles and the one-load deep fetch
 	int cut;         // tasks are cut into pieces on the device first
 	int coop;        // waves per task of the cooperative kernel (chain_dp_coop), 0: one wave per task

@@ -766,6 +766,7 @@ struct Route {
 	int width;              // coop: waves per task (16 or 8), else 0
 	bool makes_st, host_out, single_ok;   // the sixteen-wave kernel makes the window starts itself (no prepass launch) / writes the caller's buffer and raises the flag / could run as one launch
 	bool classes, q24, packed;   // tile kernel: class-1 tasks take the long ring / in its q24 form; the packed f / p ring beside the compact one
+	bool score_exit;        // tile kernel, hand-written loop: the score-bound exit is on
 	unsigned c16_bound;     // the compact x / q ring: the span of q values a task may have (the prepass compares), 0: not used
 	int prepass;            // PRE_*: nothing, a block per 256 anchors, per segment, per task
 	bool settle, cut;       // chain_cls_settle, chain_cut<td> run (chain_route: coop_auto)
@@ -838,6 +839,9 @@ static Route decide_route(const LaunchArgs &L)
 	// the packed f / p ring (chain_dp_tile.h, Lds<> RING 3): for the tasks of the compact x / q ring whose p and f fit its word (bit 3 of the class, set by the prepass
 	// when this says so); needs the side array of one word per anchor, which plans have
 	r.packed = r.c16_bound != 0 && L.packed_fp != 0 && L.d_w != nullptr;
+	// the score-bound exit of the hand-written loop (chain_dp_tile.h, MM2C_EXIT_TEST): a pair adds at most the anchor's span to f[j] only while the gap cost is not a
+	// gain -- gap_scale < 0, which the table forms admit, runs without it (as it runs without the packed ring)
+	r.score_exit = !r.coop && r.asm_loop && L.score_exit != 0 && P.gap_scale >= 0.f;
 	// The prepass.  Nothing to launch: st[] came with the pass (mm2chain_host.cpp) and avg was handed in, or the cooperative kernel makes both itself (short tasks).
 	// A pass of few tasks that wants nothing but st[] (the cooperative kernel: no classes; no cut on the device): one block per tile (avg not handed in: the blocks
 	// add up the spans into the avg workspace and a small kernel finishes them -- a plan of few long tasks: 256 reads of 10^6 anchors 3.9 -> about 1 ms, one block per
@@ -859,7 +863,7 @@ static void fill_info(const Route &r, LaunchInfo *I)
 	I->nx = r.coop ? COOP_NX : r.tile0 ? MM2C_NX : 0; I->nf = r.coop ? COOP_NF : r.tile0 ? MM2C_NF : 0;
 	I->r = r.coop ? 64 * (COOP_NX - 1) : r.tile0 ? 64 * (MM2C_NX - 1) : r.wave_r;
 	I->skip = r.skip; I->gen = r.gen; I->gs1 = r.gs1; I->far_ = r.coop ? r.far_coop : r.tile0 ? r.far_tile : r.far_wave; I->tab = r.tile0 && r.tab && !r.gen;
-	I->asm_loop = r.asm_loop; I->classes = r.classes; I->c16 = r.c16_bound != 0; I->q24 = r.q24; I->packed = r.packed;
+	I->asm_loop = r.asm_loop; I->classes = r.classes; I->c16 = r.c16_bound != 0; I->q24 = r.q24; I->packed = r.packed; I->score_exit = r.score_exit;
 	I->cut = r.cut; I->coop = r.width; I->host_out = r.host_out; I->single_ok = r.single_ok; I->fused_st = r.makes_st; I->route_auto = r.coop_auto;
 }
 
@@ -913,7 +917,7 @@ static hipError_t launch_tile_nx(const LaunchArgs &L, hipStream_t st, int only_f
 	const int32_t *n_live = !T.cut ? nullptr : L.cut.d_live ? L.cut.d_live : L.cut.d_count;
 	const uint8_t *cls = !with_cls ? nullptr : T.cut ? L.cut.d_cls : L.d_cls;
 	hipLaunchKernelGGL((chain_dp_tile<NX, NF, SKIP, GEN, GS1, FAR, TAB, C16>), dim3((unsigned)T.n), dim3(64), 0, st, L.P, T.n, T.off, T.order, (const uint4 *)L.d_anchors, T.avg, T.pbase, L.d_st,
-	                   L.d_f, L.d_p, L.d_t, L.d_w, T.status, only_flagged, T.end, n_live, cls, my_cls, cls_mask);
+	                   L.d_f, L.d_p, L.d_t, L.d_w, T.status, only_flagged, T.end, n_live, cls, my_cls, cls_mask, L.score_exit);
 	return hipGetLastError();
 }
 
@@ -1046,6 +1050,7 @@ hipError_t launch_chain_dp(const LaunchArgs &L_in, hipStream_t st, int *n_launch
 	if (L_in.dry_run) return hipSuccess;                               // the caller only wanted to know (info)
 	LaunchArgs L = L_in;
 	L.P = rt.P;
+	L.score_exit = rt.score_exit ? 1 : 0;
 	if (rt.coop_auto) { L.cut.d_live = L.cut.d_count + 1; L.cut.w8_above = L.coop_w8_above; }
 	// avg_qspan_scaled per task: the caller's, or computed by the prepass into the workspace (else the DP kernel sweeps the task itself)
 	float *avg_ws = L.d_avg ? nullptr : L.d_avg_ws;

@@ -888,6 +888,11 @@ int mm2c_tune(const char *key, int value)
 		G.packed_fp = value;
 		return 0;
 	}
+	if (strcmp(key, "score_bound_exit") == 0) {
+		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "score_bound_exit must be 0 or 1");
+		G.score_bound_exit = value;
+		return 0;
+	}
 	if (strcmp(key, "pin_workers") == 0) {
 		G.pin_workers = value != 0;
 		return 0;
@@ -1215,7 +1220,7 @@ int mm2c_plan_last_variant(mm2c_plan_t *pl, char *buf, size_t len)
 {
 	if (!pl || !buf || len == 0) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	format_variant(pl->info, buf, len);
+	format_variant(pl->info, buf, len, true);
 	return 0;
 }
 

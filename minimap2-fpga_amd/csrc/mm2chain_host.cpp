@@ -788,7 +788,7 @@ int mm2c_last_host_variant(char *buf, size_t len)
 	if (!buf || len == 0) return fail(MM2C_E_ARG, "NULL argument");
 	std::lock_guard<std::mutex> lk(g_variant_mu);
 	if (!g_have_host_info) return fail(MM2C_E_ARG, "no host-buffer entry has launched the DP yet");
-	format_variant(g_last_host_info, buf, len);
+	format_variant(g_last_host_info, buf, len, true);
 	return 0;
 }
 

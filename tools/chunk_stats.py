@@ -4,7 +4,10 @@ ring, deep f / p, beyond the ring; fold A / B1 / B2; the `break` of chain.c:231)
 (tests/tile_model.py, checked against the CPU oracle in tests/test_cpu_oracle.py).  Together with tools/isa_budget.py this decomposes the
 per-anchor instruction counts of the PMC profiles.   python tools/chunk_stats.py [profile ...] [--reads N] [--anchors M]
 --fp-depth: how deep the SCORED ring tiles lie (tiles before the own one): 1-2 = the f / p ring of pairs, 3-4 = what the packed f / p ring adds, > 4 = the deep fetch
-either way (profiles/packed_fp.md).  The model counts a scored ring tile beyond NF tiles as deep_fp, so two runs (NF 2 and NF 4) give the three bins."""
+either way (profiles/packed_fp.md).  The model counts a scored ring tile beyond NF tiles as deep_fp, so two runs (NF 2 and NF 4) give the three bins.
+--score-exit: what the score-bound exit of the loop (chain_dp_tile.h, MM2C_EXIT_TEST) takes away, from the model that has it (tests/tile_model_exit.py) run with the
+exit on and off, NX 16 / NF 4: anchors that leave early, ring tiles no longer visited, how many of those were scored and deep-fetched, and anchors whose f / p differ
+between the two runs (must be 0); last, the scored chunks none of whose candidates could beat the best (what a chunk-level score skip would look at), off -> on."""
 import os
 import sys
 
@@ -34,6 +37,28 @@ if __name__ == "__main__":
         # round 6: what a per-tile bitmap of diagonal buckets would reject (skip_rejects of skip_tested ring-tile visits; skip_missed: visits without a surviving lane that
         # the bitmap lets through; skip_wrong must be 0)
         keys = ("ring_chunks", "ring_pass", "skip_tested", "skip_rejects", "skip_missed", "skip_wrong")
+    if "--score-exit" in args:
+        from tile_model_exit import chain_tile_model_exit
+        print(f"Per anchor, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX 16 / NF 4, exit off -> on:\n")
+        print("| stream | anchors that exit early | ring tiles no longer visited | ... of them scored | ... of them deep-fetched | wrong exits | futile scored chunks |\n|---|---|---|---|---|---|---|")
+        for prof in profiles:
+            off, a = synth.make_stream(prof, reads, m, seed=1, q_span=span)
+            off = off.numpy(); a = a.numpy().view(np.uint64)
+            tot = {mode: dict.fromkeys(("anchors", "exits", "ring_chunks", "ring_pass", "deep_fp", "futile_scores"), 0) for mode in ("off", "auto")}
+            wrong = 0
+            for k in range(reads):
+                t = a[off[k]:off[k + 1]]
+                res = {}
+                for mode in ("off", "auto"):
+                    st = {}
+                    res[mode] = chain_tile_model_exit(P, t, avg_qspan(t), stats=st, NX=16, NF=4, compact=True, score_exit=mode)
+                    for kk in tot[mode]:
+                        tot[mode][kk] += st[kk]
+                wrong += int(((res["off"][0] != res["auto"][0]) | (res["off"][1] != res["auto"][1])).sum())
+            n, o, x = tot["off"]["anchors"], tot["off"], tot["auto"]
+            print(f"| {prof} | {x['exits'] / n:.3f} | {(o['ring_chunks'] - x['ring_chunks']) / n:.3f} of {o['ring_chunks'] / n:.3f} | {(o['ring_pass'] - x['ring_pass']) / n:.3f} of {o['ring_pass'] / n:.3f} | "
+                  f"{(o['deep_fp'] - x['deep_fp']) / n:.3f} of {o['deep_fp'] / n:.3f} | {wrong} | {o['futile_scores'] / n:.3f} -> {x['futile_scores'] / n:.3f} |")
+        sys.exit(0)
     if "--fp-depth" in args:
         print(f"Scored ring tiles per anchor by depth, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX {NX}:\n")
         print("| stream | scored ring tiles | depth 1-2 | depth 3-4 | depth > 4 |\n|---|---|---|---|---|")
