@@ -363,7 +363,8 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 // earlier stores, stamps in the 32-bit global scratch t[] (value i + 1) -- also for the far predecessors of ring lanes.
 // Per anchor: the own tile (lanes L+1 .. L+w), then `nfull` whole older tiles in a count-down loop that branches on VCC (7 VALU + 2 LDS
 // + 1 SALU + 2 branches per tile; x / q of the next tile are requested while this one is filtered), then the partly covered tile.
-// A chunk with a surviving lane goes through Lhf: f / p of its tile (registers, LDS, or L2 beyond NF tiles), stamps, score, fold.
+// A chunk with a surviving lane goes through Lhf: f / p of its tile (registers, LDS, or L2 beyond NF tiles), score, fold -- and its stamps and marks only where the
+// fold goes on with the scan (MM2C_ST_LEAN / MM2C_ST_FAR below): a chunk whose fold B0 takes the score-bound exit leaves without them.
 // The fold: A no lane beats the running best; B0 the first surviving lane does and no other lane beats IT (the usual case on a real chain: the
 // nearest predecessor is the best) -- it is the only new maximum, every marked lane behind it is a skip event, so counter and `break` have a
 // closed form (the `break` needs a skip event: without one the counter is not even compared, max_skip may be negative); B1 some lane does and neither marks nor skips exist (one candidate: no reduction at all);
@@ -445,6 +446,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 #define MM2C_SCORE_TAB "v_min_u32 %[va], 0x1ff, %[dd]\n\t" "v_lshlrev_b32 %[va], 1, %[va]\n\t" "ds_read_i16 %[va], %[va] offset:%[GAPOFF]\n\t" \
 	"v_min3_i32 %[sc], %[dq], %[dr], %[span1]\n\t"
 #define MM2C_ADDF_TAB "v_add3_u32 %[sc], %[sc], %[va], " MM2C_R_F "\n\t" "v_add_u32 %[sc], 14, %[sc]\n\t"   /* vf = f[j] - 14; the table holds 1 - cost */
+#define MM2C_SWAIT_TAB "s_waitcnt lgkmcnt(0)\n\t"   /* the table's value, where no other wait stands between SCORE and ADDF (own tile, deep fetch, tiles from memory) */
 
 // ---- the segments in which the two instantiations of the loop differ.  `far`: the tile holds an anchor whose window reaches beyond the LDS ring
 // (bit 30 of its tw word): stamps with a target before the ring go to the global scratch, and a scan that runs through the whole ring without
@@ -469,32 +471,54 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	MM2C_FAR_REQ \
 	"Lnf_%=:\n\t"
 #define MM2C_LK_LEAN ""
-#define MM2C_HF_FAR \
+// The stamps of a scored own-tile or ring chunk and its marks (chain.c:229,233), entered with exec = the lanes that passed the filters, left with `marked` set and
+// SCC = some lane is marked.  The block stands at the three places of the fold that go on with the scan -- fold A (site "a"), fold B0 behind its exit test ("b"),
+// the general folds at Lslow ("s") -- and not before the fold: a chunk whose fold B0 takes the score-bound exit leaves without them (nothing on that way looks at a
+// mark, and a stamp only means something to the anchor that wrote it).  Far form: the stamps of an anchor with a clamped window (bit 30 of pk), whose targets may
+// lie before the ring and then go to the global scratch, stand out of line in MM2C_END_FAR (MM2C_ST_FAR_OOL) and come back for the marks; every path issues what it
+// issued when the block stood before the fold.  A chunk from memory never gets here: it stamps in memory and makes its marks before its fold, which has its own
+// way in (Lfold .. LslowM in MM2C_END_FAR) and joins the common fold behind the stamps.  T: a free scalar (fold B0 keeps its lane in t0).
+#define MM2C_ST_LDS_FAR \
+	MM2C_LC(MM2C_LB_HF) \
 	"v_cmp_le_i32 vcc, %[lo], " MM2C_R_P "\n\t" \
 	"s_and_b64 %[mk], vcc, %[valid]\n\t" \
 	"v_and_b32 %[u2], %[SNM1], " MM2C_R_P "\n\t" \
 	"s_mov_b64 exec, %[mk]\n\t" \
 	"ds_write_b8 %[u2], %[s16v] offset:%[STOFF]\n\t" \
 	"s_mov_b64 exec, %[valid]\n\t" \
-	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n\t" \
+	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n\t"
+#define MM2C_ST_FAR(SITE) \
 	"s_bitcmp1_b32 %[pk], 30\n\t" \
-	"s_cbranch_scc0 Lmk_%=\n\t" \
+	"s_cbranch_scc1 Lstc" SITE "_%=\n\t" \
+	MM2C_ST_LDS_FAR \
+	"\n" \
+	"Lstm" SITE "_%=:\n\t" \
+	"s_waitcnt lgkmcnt(0)\n\t" \
+	"v_cmp_eq_u32 vcc, %[c], %[vb]\n\t" \
+	"s_and_b64 %[marked], vcc, exec\n\t"
+#define MM2C_ST_FAR_OOL(SITE, T) \
+	"Lstc" SITE "_%=:\n\t" \
+	MM2C_ST_LDS_FAR \
 	"v_cmp_le_i32 vcc, %[lo0], " MM2C_R_P "\n\t" \
 	"s_andn2_b64 %[mask], vcc, %[mk]\n\t"      /* (exec = valid: vcc is already confined to the lanes that passed) */ \
-	"s_cbranch_scc0 Lmk_%=\n\t" \
+	"s_cbranch_scc0 Lstm" SITE "_%=\n\t" \
 	MM2C_LC(MM2C_LB_FARSTAMP) \
-	"s_add_i32 %[t0], %[icnt1], %[c]\n\t" \
-	"v_mov_b32 %[u1], %[t0]\n\t" \
+	"s_add_i32 " T ", %[icnt1], %[c]\n\t" \
+	"v_mov_b32 %[u1], " T "\n\t" \
 	"v_lshlrev_b32 %[u2], 2, " MM2C_R_P "\n\t" \
 	"s_mov_b64 exec, %[mask]\n\t" \
 	"global_store_dword %[u2], %[u1], %[tptr] sc0\n\t" \
-	"s_mov_b64 exec, %[valid]\n"
-#define MM2C_HF_LEAN \
 	"s_mov_b64 exec, %[valid]\n\t" \
+	"s_branch Lstm" SITE "_%=\n"
+#define MM2C_ST_LEAN(SITE) \
+	MM2C_LC(MM2C_LB_HF) \
 	"v_max_i32 %[u2], " MM2C_R_P ", %[lomc]\n\t" \
 	"v_and_b32 %[u2], %[SNM1], %[u2]\n\t" \
 	"ds_write_b8 %[u2], %[s16v] offset:%[STOFF]\n\t" \
-	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n"
+	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n\t" \
+	"s_waitcnt lgkmcnt(0)\n\t" \
+	"v_cmp_eq_u32 vcc, %[c], %[vb]\n\t" \
+	"s_and_b64 %[marked], vcc, exec\n\t"
 #define MM2C_TAIL_FAR \
 	"s_cbranch_scc0 Lret_%=\n\t" \
 	"s_bcnt1_i32_b64 %[t0], %[marked]\n\t" \
@@ -515,7 +539,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"\n" \
 	"Lret_%=:\n\t" \
 	"s_branch Lloop_%=\n"
-#define MM2C_END_FAR(SCORE, FARFILTER) \
+#define MM2C_END_FAR(SCORE, FARFILTER, ADDF) \
 	"Lend_%=:\n\t" \
 	MM2C_LC(MM2C_LB_END) \
 	"s_bitcmp1_b32 %[pk], 30\n\t" \
@@ -575,8 +599,34 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"global_load_dword %[vb], %[u2], %[tptr] sc0\n\t" \
 	"s_waitcnt vmcnt(0)\n\t" \
 	"v_cmp_eq_u32 vcc, %[s16], %[vb]\n\t" \
-	"s_branch Lmk2_%=\n"
-#define MM2C_END_LEAN(SCORE, FARFILTER) \
+	"s_and_b64 %[marked], vcc, exec\n\t"          /* the chunk has stamped and made its marks: its own way into the fold, which joins the common one behind the stamps */ \
+	ADDF \
+	"v_cmp_lt_i32 vcc, %[best], %[sc]\n\t" \
+	"s_cbranch_vccnz Limpm_%=\n\t" \
+	"s_branch Lfat_%=\n"                         /* fold A (SCC: some lane is marked, as SEG_TAIL wants it) */ \
+	"Limpm_%=:\n\t" \
+	MM2C_LC(MM2C_LB_IMP) \
+	"s_ff1_i32_b64 %[t0], %[valid]\n\t" \
+	"v_readfirstlane_b32 %[t1], %[sc]\n\t" \
+	"s_cmp_gt_i32 %[t1], %[best]\n\t" \
+	"s_cbranch_scc0 Lslowm_%=\n\t" \
+	"v_cmp_lt_i32 vcc, %[t1], %[sc]\n\t" \
+	"s_cbranch_vccnz Lslow2m_%=\n\t" \
+	MM2C_LC(MM2C_LB_B0) \
+	"s_mov_b32 %[best], %[t1]\n\t" \
+	"s_lshl_b32 %[t1], %[d], 6\n\t" \
+	"s_sub_i32 %[bestj], %[i063], %[t1]\n\t" \
+	"s_sub_i32 %[bestj], %[bestj], %[t0]\n\t" \
+	MM2C_EXIT_TEST("%[t1]") \
+	"s_branch Lb0s_%=\n" \
+	"Lslow2m_%=:\n\t" \
+	MM2C_LC(MM2C_LB_SLOW2) \
+	"\n" \
+	"Lslowm_%=:\n\t" \
+	MM2C_LC(MM2C_LB_SLOW) \
+	"s_branch Lsls_%=\n" \
+	MM2C_ST_FAR_OOL("a", "%[t0]") MM2C_ST_FAR_OOL("b", "%[t1]") MM2C_ST_FAR_OOL("s", "%[t0]")
+#define MM2C_END_LEAN(SCORE, FARFILTER, ADDF) \
 	"Lend_%=:\n\t" \
 	MM2C_LC(MM2C_LB_END)
 
@@ -721,7 +771,7 @@ __device__ unsigned long long g_label_hits[8 * 32];   // row = compact << 2 | ta
 #define MM2C_LB_OWN "0x2"
 #define MM2C_LB_LOOP "0x4"
 #define MM2C_LB_OLD "0x8"
-#define MM2C_LB_HF "0x10"
+#define MM2C_LB_HF "0x10"            /* a scored own-tile or ring chunk writes its stamps: scored chunks (OWN + OLD) less this = chunks left before stamping (tests/test_gpu_late_stamps.py) */
 #define MM2C_LB_FARSTAMP "0x20"
 #define MM2C_LB_BRKA "0x40"
 #define MM2C_LB_FG "0x80"
@@ -755,7 +805,7 @@ __device__ unsigned long long g_label_hits[8 * 32];   // row = compact << 2 | ta
 // value.  Tested wherever a fold has just raised the best (fold A leaves it alone); the way out is the `break`'s.  pfx = INT_MAX (the first tile of a piece, gap_scale
 // < 0, mm2c_tune("score_bound_exit", 0)) never passes.  T: a free scalar.
 #define MM2C_EXIT_TEST(T) "s_sub_i32 " T ", %[best], %[span1]\n\t" "s_cmp_gt_i32 " T ", %[pfx]\n\t" MM2C_LC_BR_SCC1("Ldone_%=", MM2C_LB_EXIT)
-#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, UNPACK, FGFIX, STSH, SCORE, ADDF, SEG_RD, SEG_LK, SEG_HF, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
+#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, UNPACK, FGFIX, STSH, SCORE, ADDF, SWAIT, SEG_RD, SEG_LK, SEG_ST, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
 template <int NX, int NF> \
 __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, float avg, const int32_t *f, const int32_t *p, const int32_t *wq, int pbase, const uint4 *a, \
                                     int32_t *tg, int tx, int tx1, int tq, int tq1, int tspan, int tlo, int tlo0, int tw, int &own_f, int &own_p, \
@@ -805,6 +855,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"v_mov_b32 " MM2C_R_P ", %[own_p]\n\t" \
 		"v_mov_b32 %[vb], %[ownst]\n\t" \
 		SCORE \
+		SWAIT \
 		"s_branch Lhf_%=\n" \
 		"Lloop_%=:\n\t" \
 		MM2C_LC(MM2C_LB_LOOP) \
@@ -829,22 +880,19 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		UNPACK \
 		"\n" \
 		"Lhf_%=:\n\t" \
-		MM2C_LC(MM2C_LB_HF) \
-		SEG_HF \
-		"Lmk_%=:\n\t"                                  /* exec = the lanes that passed the filters, until the fold has looked at the scores */ \
-		"s_waitcnt lgkmcnt(0)\n\t" \
-		"v_cmp_eq_u32 vcc, %[c], %[vb]\n" \
-		"Lmk2_%=:\n\t" \
+		"s_mov_b64 exec, %[valid]\n\t"                /* exec = the lanes that passed the filters, until the fold has looked at the scores and the marks */ \
 		ADDF \
-		"s_and_b64 %[marked], vcc, exec\n\t" \
 		"v_cmp_lt_i32 vcc, %[best], %[sc]\n\t" \
 		"s_cbranch_vccnz Limp_%=\n\t" \
+		SEG_ST("a")                                    /* fold A: no lane beats the best, the scan goes on (or ends by the marks) */ \
+		"Lfat_%=:\n\t" \
 		"s_mov_b64 exec, %[ex]\n\t" \
 		SEG_TAIL \
 		"Lfg_%=:\n\t" \
 		MM2C_LC(MM2C_LB_FG) \
 		SEG_FG(SCORE) \
 		FGFIX \
+		SWAIT \
 		"s_branch Lhf_%=\n" \
 		"Lpart_%=:\n\t" \
 		MM2C_LC(MM2C_LB_PART) \
@@ -870,13 +918,15 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_cbranch_scc0 Lslow_%=\n\t" \
 		"v_cmp_lt_i32 vcc, %[t1], %[sc]\n\t" \
 		"s_cbranch_vccnz Lslow2_%=\n\t" \
-		"s_mov_b64 exec, %[ex]\n\t" \
 		MM2C_LC(MM2C_LB_B0) \
 		"s_mov_b32 %[best], %[t1]\n\t" \
 		"s_lshl_b32 %[t1], %[d], 6\n\t" \
 		"s_sub_i32 %[bestj], %[i063], %[t1]\n\t"   /* i0 + 63 - 64 d - lane */ \
 		"s_sub_i32 %[bestj], %[bestj], %[t0]\n\t" \
-		MM2C_EXIT_TEST("%[t1]") \
+		MM2C_EXIT_TEST("%[t1]")                        /* the way out that owes no stamp: nothing so far has looked at a mark, Ldone sets exec itself */ \
+		SEG_ST("b") \
+		"Lb0s_%=:\n\t" \
+		"s_mov_b64 exec, %[ex]\n\t" \
 		"s_sub_i32 %[nskip], %[nskip], 1\n\t" \
 		"s_max_i32 %[nskip], %[nskip], 0\n\t" \
 		"s_bitset0_b64 %[marked], %[t0]\n\t" \
@@ -888,9 +938,12 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_branch " LNEXT "\n" \
 		"Lslow2_%=:\n\t" \
 		MM2C_LC(MM2C_LB_SLOW2) \
-		"v_cmp_lt_i32 vcc, %[best], %[sc]\n" \
+		"\n" \
 		"Lslow_%=:\n\t" \
 		MM2C_LC(MM2C_LB_SLOW) \
+		SEG_ST("s") \
+		"Lsls_%=:\n\t" \
+		"v_cmp_lt_i32 vcc, %[best], %[sc]\n\t"        /* (again: the stamps went through VCC) */ \
 		"s_mov_b64 exec, %[ex]\n\t"                     /* the general folds work on all lanes: the lanes that did not pass get the sentinel score */ \
 		"v_cndmask_b32_e64 %[sc], %[sent], %[sc], %[valid]\n\t" \
 		"s_lshl_b32 %[t0], %[d], 6\n\t" \
@@ -1014,7 +1067,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_cmp_eq_u32 %[last], 63\n\t" \
 		"s_cbranch_scc1 Lretx_%=\n\t" \
 		"s_branch Ldone_%=\n" \
-		SEG_END(SCORE, FARFILTER) \
+		SEG_END(SCORE SWAIT, FARFILTER, ADDF) \
 		"Ldone_%=:\n\t" \
 		MM2C_LC(MM2C_LB_DONE) \
 		SEG_DONE \
@@ -1056,28 +1109,28 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 #define MM2C_RING_C MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
 #define MM2C_RING_P MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_P, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PACKED, PF0, MM2C_RDFP_4, MM2C_UNPACK_4, MM2C_FGFIX_4, "2"
 #define MM2C_SCAN_TILE_ASM_(...) MM2C_SCAN_TILE_ASM(__VA_ARGS__)
-#define MM2C_LEAN MM2C_RD_LEAN, MM2C_LK_LEAN, MM2C_HF_LEAN, MM2C_TAIL_LEAN, MM2C_END_LEAN, "", "Lloop_%="
-#define MM2C_FARS MM2C_RD_FAR, MM2C_LK_FAR, MM2C_HF_FAR, MM2C_TAIL_FAR, MM2C_END_FAR, MM2C_DONE_FAR, "Lret_%="
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab, true, false, MM2C_RING_W, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far, true, false, MM2C_RING_W, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
+#define MM2C_LEAN MM2C_RD_LEAN, MM2C_LK_LEAN, MM2C_ST_LEAN, MM2C_TAIL_LEAN, MM2C_END_LEAN, "", "Lloop_%="
+#define MM2C_FARS MM2C_RD_FAR, MM2C_LK_FAR, MM2C_ST_FAR, MM2C_TAIL_FAR, MM2C_END_FAR, MM2C_DONE_FAR, "Lret_%="
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab, true, false, MM2C_RING_W, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far, true, false, MM2C_RING_W, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_FARS)
 // the same four over the compact x / q ring
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_c, false, true, MM2C_RING_C, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_c, false, true, MM2C_RING_C, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_c, false, true, MM2C_RING_C, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_c, false, true, MM2C_RING_C, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_c, true, true, MM2C_RING_C, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_FARS)
 // ... the compact x / q ring with the packed f / p ring and the one-load deep fetch (Lds<> RING 3)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_FARS)
 // ... and over the q24 ring (the long ring of class-1 tasks): everything but a ring tile's request and filter is the 32-bit form's or the compact form's
 #define MM2C_RING_Q MM2C_XQ1_Q, MM2C_NEXT_XQ_Q, MM2C_RFILTER_Q, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_LEAN)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, MM2C_FARS)
-MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
+MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_FARS)
 
 // ---------------------------------------------------------------- the kernel: one wave per task
 // LDS rings before the own tile: x / q of NX tiles, f / p of the NF nearest (NF a power of two dividing NX).

@@ -7,7 +7,11 @@ per-anchor instruction counts of the PMC profiles.   python tools/chunk_stats.py
 either way (profiles/packed_fp.md).  The model counts a scored ring tile beyond NF tiles as deep_fp, so two runs (NF 2 and NF 4) give the three bins.
 --score-exit: what the score-bound exit of the loop (chain_dp_tile.h, MM2C_EXIT_TEST) takes away, from the model that has it (tests/tile_model_exit.py) run with the
 exit on and off, NX 16 / NF 4: anchors that leave early, ring tiles no longer visited, how many of those were scored and deep-fetched, and anchors whose f / p differ
-between the two runs (must be 0); last, the scored chunks none of whose candidates could beat the best (what a chunk-level score skip would look at), off -> on."""
+between the two runs (must be 0); last, the scored chunks none of whose candidates could beat the best (what a chunk-level score skip would look at), off -> on.
+--late-stamps: the fold order in which a chunk stamps only once its fold knows that the scan goes on (chain_dp_tile.h, MM2C_ST_LEAN / MM2C_ST_FAR), from the model
+that has it (tests/tile_model_late_stamps.py), NX 16 / NF 4: exits of the score-bound test and how many of them leave before any stamp of their chunk (fold B0's),
+scored chunks that stamp, scored ring tiles by phase (within the f / p ring, beyond it), anchors that visit a tile beyond the f / p ring, anchors whose ring window
+runs out (Lend), folds B0, and anchors whose f / p differ from the model with the stamps before the fold (must be 0)."""
 import os
 import sys
 
@@ -58,6 +62,29 @@ if __name__ == "__main__":
             n, o, x = tot["off"]["anchors"], tot["off"], tot["auto"]
             print(f"| {prof} | {x['exits'] / n:.3f} | {(o['ring_chunks'] - x['ring_chunks']) / n:.3f} of {o['ring_chunks'] / n:.3f} | {(o['ring_pass'] - x['ring_pass']) / n:.3f} of {o['ring_pass'] / n:.3f} | "
                   f"{(o['deep_fp'] - x['deep_fp']) / n:.3f} of {o['deep_fp'] / n:.3f} | {wrong} | {o['futile_scores'] / n:.3f} -> {x['futile_scores'] / n:.3f} |")
+        sys.exit(0)
+    if "--late-stamps" in args:
+        from tile_model_exit import chain_tile_model_exit
+        from tile_model_late_stamps import chain_tile_model_late_stamps
+        print(f"Per anchor, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX 16 / NF 4:\n")
+        print("| stream | exits | ... before any stamp of the chunk | scored chunks (own + ring) | ... that stamp | scored ring tiles within the f / p ring | ... beyond it | "
+              "anchors that go beyond it | ring windows that run out | folds B0 | wrong |\n|---|---|---|---|---|---|---|---|---|---|---|")
+        for prof in profiles:
+            off, a = synth.make_stream(prof, reads, m, seed=1, q_span=span)
+            off = off.numpy(); a = a.numpy().view(np.uint64)
+            tot = dict.fromkeys(("anchors", "exits", "exits_unstamped", "own_pass", "ring_pass", "stamped_chunks", "cpp_chunks", "near_pass", "deep_pass", "phase_changes", "lend", "fold_b0"), 0)
+            wrong = 0
+            for k in range(reads):
+                t = a[off[k]:off[k + 1]]
+                st = {}
+                f1, p1 = chain_tile_model_late_stamps(P, t, avg_qspan(t), stats=st, NX=16, NF=4, compact=True)
+                f0, p0 = chain_tile_model_exit(P, t, avg_qspan(t), NX=16, NF=4, compact=True)
+                wrong += int(((f0 != f1) | (p0 != p1)).sum())
+                for kk in tot:
+                    tot[kk] += st[kk]
+            n = tot["anchors"]
+            print(f"| {prof} | {tot['exits'] / n:.3f} | {tot['exits_unstamped'] / n:.3f} | {(tot['own_pass'] + tot['ring_pass']) / n:.3f} | {(tot['stamped_chunks'] + tot['cpp_chunks']) / n:.3f} | "
+                  f"{tot['near_pass'] / n:.3f} | {tot['deep_pass'] / n:.3f} | {tot['phase_changes'] / n:.3f} | {tot['lend'] / n:.3f} | {tot['fold_b0'] / n:.3f} | {wrong} |")
         sys.exit(0)
     if "--fp-depth" in args:
         print(f"Scored ring tiles per anchor by depth, map-ont parameters, {reads} reads x {m} anchors of each bench.py stream (seed 1, span {span}), NX {NX}:\n")
