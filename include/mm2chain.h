@@ -536,6 +536,60 @@ int mm2c_seg_gen_batch_host(int64_t n_frags, int32_t n_segs, const int64_t *u_of
                             const mm2c_anchor_t *b, const int32_t *seg_len, const uint32_t *hash, const int32_t *rep_len, int64_t *su_off, uint64_t *su,
                             int64_t *sb_off, mm2c_anchor_t *sb, mm2c_reg_t *seg_regs, uint32_t *seg_hash, int32_t *seg_rep_len);
 
+/* ---- base alignment on the GPU: ksw_extd2_sse (ksw2_extd2_sse.c), the dual-affine banded DP mm_align_pair calls when q != q2 || e != e2 (align.c:313-339) ----
+ * A stand-alone plan: a batch of independent tasks in, ksw_extz_t and CIGAR out, byte for byte what the reference's SSE4.1 build gives (DESIGN.md 3.17 says what
+ * that takes).  Wired into nothing; max_sw_mat (align.c:323) and everything of mm_align1 around the call stay with the caller.
+ * One score set per call (m = 5: mat as ksw_gen_simple_mat makes it, align.c:9-22).  Sequences are codes 0..4 in one byte pool of seq_cap bytes; task i reads
+ * seq[q_off .. q_off + qlen) and seq[t_off .. t_off + tlen).  PRECONDITION: no code above 4 (nothing indexes with a code, so the device does not look; the host
+ * entry does).  flag: the KSW_EZ_* bits of MM2C_KSW_FLAGS -- everything align.c:697,733,737,771,828 passes.  Task i's CIGAR goes to
+ * cigar[cig_off[i] .. cig_off[i + 1]) (BAM words, forward, or reversed with REV_CIGAR, as the reference leaves them).
+ * status of a task: 0; MM2C_KSW_REFUSED -- a flag bit outside MM2C_KSW_FLAGS, a length above MM2C_KSW_MAX_LEN, offsets or lengths that leave seq_cap, or a
+ * CIGAR slot that is negative or leaves cigar_cap: counted, nothing but the status word is written, mm2c_kswplan_check answers MM2C_E_ARG;
+ * MM2C_KSW_TOO_BIG -- the task's p matrix (and, beyond MM2C_KSW_LDS_LEN bases, its array image) does not fit a task slot of the scratch
+ * (mm2c_kswplan_slot_bytes; mm2c_ksw_task_scratch says what a task takes): not run, nothing but the status word is written, MM2C_E_TOOBIG;
+ * MM2C_KSW_CIGAR_CUT -- the CIGAR is longer than its slot: the first words that fit are written, every scalar (n_cigar too) is exact, MM2C_E_TOOBIG.
+ * The tasks beside any of these are exact.  qlen <= 0 || tlen <= 0 leaves the reset ez of ksw_reset_extz and status 0.
+ * Scratch: the plan owns n_slots equal slots of slot_bytes; one wave per slot works the tasks slot, slot + n_slots, ... in turn, so the scratch bounds how many tasks
+ * are resident, not how many a call may hold.  A task runs only in a slot of at least mm2c_ksw_task_scratch(qlen, tlen, w, flag) bytes: about
+ * (qlen + tlen) * (min(qlen, tlen, w + 1) + 32) bytes for its p matrix (nothing with SCORE_ONLY), e.g. 2.2 MB for 2 000 x 2 100 at w = 500, 8.1 MiB for 2 000 x 2 000
+ * at w = 2 000.  That is the only ceiling on a task's size below MM2C_KSW_MAX_LEN.  mm2c_kswplan_create_slots takes the cut from the caller (1 <= n_slots <=
+ * MM2C_KSW_MAX_SLOTS, any slot_bytes the device can hold n_slots times; rounded up to 256); mm2c_kswplan_create(scratch_bytes) is the default cut for tasks of up
+ * to MM2C_KSW_SLOT_BYTES = 4 MiB: n_slots = clamp(scratch_bytes / 4 MiB, 1, MM2C_KSW_MAX_SLOTS) slots of scratch_bytes / n_slots.  A host with larger tasks (-x ava-*:
+ * bw = 2 000) sizes the slots itself. */
+#define MM2C_KSW_FLAGS 0xdb            /* KSW_EZ_SCORE_ONLY 0x01, RIGHT 0x02, APPROX_MAX 0x08, APPROX_DROP 0x10, EXTZ_ONLY 0x40, REV_CIGAR 0x80 */
+#define MM2C_KSW_MAX_LEN (1 << 20)
+#define MM2C_KSW_LDS_LEN 2304          /* tasks up to this target (padded to 16) and query length keep their arrays on chip */
+#define MM2C_KSW_SLOT_BYTES (4ll << 20)
+#define MM2C_KSW_MAX_SLOTS 2048
+#define MM2C_KSW_REFUSED 1
+#define MM2C_KSW_TOO_BIG 2
+#define MM2C_KSW_CIGAR_CUT 3
+typedef struct { int8_t mat[25]; int8_t q, e, q2, e2; } mm2c_ksw_score_t;            /* m = 5 */
+typedef struct { int64_t q_off, t_off; int32_t qlen, tlen, w, zdrop, end_bonus, flag; } mm2c_ksw_task_t;
+typedef struct { uint32_t max; int32_t zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, n_cigar, reach_end, status; } mm2c_ksw_res_t;
+typedef struct mm2c_kswplan mm2c_kswplan_t;
+mm2c_kswplan_t *mm2c_kswplan_create(int64_t n_tasks_cap, int64_t seq_cap, int64_t cigar_cap, int64_t scratch_bytes);
+mm2c_kswplan_t *mm2c_kswplan_create_slots(int64_t n_tasks_cap, int64_t seq_cap, int64_t cigar_cap, int64_t n_slots, int64_t slot_bytes);
+void mm2c_kswplan_destroy(mm2c_kswplan_t *plan);
+int64_t mm2c_kswplan_slot_bytes(const mm2c_kswplan_t *plan);
+int64_t mm2c_kswplan_n_slots(const mm2c_kswplan_t *plan);
+int64_t mm2c_ksw_task_scratch(int32_t qlen, int32_t tlen, int32_t w, int32_t flag);   /* bytes of a slot the task takes */
+/* All pointers are device memory (d_tasks, d_cig_off 8-byte aligned, d_res, d_cigar 4-byte); asynchronous on `stream` (NULL / MM2C_STREAM_LIBRARY as everywhere). */
+int mm2c_kswplan_run_device(mm2c_kswplan_t *plan, const mm2c_ksw_score_t *sc, int64_t n_tasks, const mm2c_ksw_task_t *d_tasks, const uint8_t *d_seq,
+                            const int64_t *d_cig_off, mm2c_ksw_res_t *d_res, uint32_t *d_cigar, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a task was refused, else MM2C_E_TOOBIG if one did not fit a slot or a CIGAR was cut.  *n_too_big counts both kinds. */
+int mm2c_kswplan_check(mm2c_kswplan_t *plan, int64_t *n_refused, int64_t *n_too_big);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: the same for ksw_rows (rows and backtrack are one kernel) */
+int mm2c_kswplan_last_ms(mm2c_kswplan_t *plan, float *ms);
+int mm2c_kswplan_last_kernel_ms(mm2c_kswplan_t *plan, float *rows_ms);
+/* host arrays in and out: res has n_tasks entries, cigar cig_off[n_tasks] words.  Checks the score set, every task's flag, lengths, offsets and slot, and every
+ * base it reads (a code above 4) first (MM2C_E_ARG, before any device work), then uploads, runs, downloads and waits.  Its slots have the size of the call's
+ * largest task, so no task of the call is too big for them: with scratch_bytes <= 0 as many slots as there are tasks, up to 1 280 slots and 4 GiB (one slot if the
+ * largest task alone is beyond that); with scratch_bytes > 0 as many as scratch_bytes holds, and if it does not hold one, a single slot of scratch_bytes: the tasks
+ * beyond it come back MM2C_KSW_TOO_BIG.  With MM2C_E_TOOBIG the outputs are complete all the same. */
+int mm2c_ksw_extd2_batch_host(const mm2c_ksw_score_t *sc, int64_t n_tasks, const mm2c_ksw_task_t *tasks, int64_t seq_len, const uint8_t *seq,
+                              const int64_t *cig_off, mm2c_ksw_res_t *res, uint32_t *cigar, int64_t scratch_bytes);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

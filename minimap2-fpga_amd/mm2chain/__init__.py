@@ -8,7 +8,8 @@ from .batch import (device_identity, last_host_variant, init, split_model, init_
                     seed_chain_batch_pool_skip, MinimizerIndex, sketch_batch, sketch_match_batch, read_chain_batch, sketch_stats, index_stats,
                     sketch_frag_batch, sketch_match_frag_batch, frag_chain_batch, frag_stats, frag_chain_batch_gaps, frag_gaps,
                     RegPlan, REG_DTYPE, gen_regs_batch, read_hash, HitPlan, select_hits_batch, MapqPlan, join_mapq_batch,
-                    EstErrPlan, est_err_batch, est_err_div, est_err_apply, ERR_DTYPE, select_hits_multi_batch, SegPlan, seg_gen_batch)
+                    EstErrPlan, est_err_batch, est_err_div, est_err_apply, ERR_DTYPE, select_hits_multi_batch, SegPlan, seg_gen_batch,
+                    KswPlan, ksw_extd2_batch, ksw_task_scratch, KSW_TASK_DTYPE, KSW_RES_DTYPE, KSW_REFUSED, KSW_TOO_BIG, KSW_CIGAR_CUT)
 
 __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE_GENERAL", "load", "params", "synth",
            "sharding", "stream", "device_identity", "last_host_variant", "init", "split_model", "init_devices", "device_count", "split_tasks", "shutdown", "device_info", "tune", "ChainPlan", "chain_batch_host", "chain_batch_host_into", "PinnedArray", "chain_task", "hardware_init",
@@ -18,4 +19,5 @@ __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE
            "sketch_frag_batch", "sketch_match_frag_batch", "frag_chain_batch", "frag_stats", "frag_chain_batch_gaps", "frag_gaps",
            "RegPlan", "REG_DTYPE", "gen_regs_batch", "read_hash", "HitPlan", "select_hits_batch", "MapqPlan", "join_mapq_batch",
            "EstErrPlan", "est_err_batch", "est_err_div", "est_err_apply", "ERR_DTYPE",
-           "select_hits_multi_batch", "SegPlan", "seg_gen_batch"]
+           "select_hits_multi_batch", "SegPlan", "seg_gen_batch",
+           "KswPlan", "ksw_extd2_batch", "ksw_task_scratch", "KSW_TASK_DTYPE", "KSW_RES_DTYPE", "KSW_REFUSED", "KSW_TOO_BIG", "KSW_CIGAR_CUT"]

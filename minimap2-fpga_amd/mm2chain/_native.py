@@ -182,6 +182,17 @@ C_SYMBOLS = {
     "mm2c_segplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_segplan_last_kernel_ms": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_float)] * 5),
     "mm2c_seg_gen_batch_host": (C.c_int, [C.c_int64, C.c_int32] + [C.c_void_p] * 15),
+    "mm2c_kswplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mm2c_kswplan_create_slots": (C.c_void_p, [C.c_int64] * 5),
+    "mm2c_kswplan_destroy": (None, [C.c_void_p]),
+    "mm2c_kswplan_slot_bytes": (C.c_int64, [C.c_void_p]),
+    "mm2c_kswplan_n_slots": (C.c_int64, [C.c_void_p]),
+    "mm2c_ksw_task_scratch": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "mm2c_kswplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "mm2c_kswplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_kswplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_kswplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_ksw_extd2_batch_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]),
     "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "mm2c_mapqplan_destroy": (None, [C.c_void_p]),
     "mm2c_mapqplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(MapqOpt)] + [C.c_void_p] * 12),

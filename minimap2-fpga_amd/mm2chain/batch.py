@@ -631,6 +631,118 @@ def seg_gen_batch(n_segs, u_off, regs, n_in, b_off, b, seg_len, hash, rep_len=No
     return dict(su_off=su_off, su=su[:tu], sb_off=sb_off, sb=sb[:ta], seg_regs=seg_regs[:tu], seg_hash=seg_hash[:ns], seg_rep_len=(seg_rl[:ns] if rl is not None else None))
 
 
+KSW_TASK_DTYPE = np.dtype([("q_off", "<i8"), ("t_off", "<i8"), ("qlen", "<i4"), ("tlen", "<i4"), ("w", "<i4"), ("zdrop", "<i4"), ("end_bonus", "<i4"), ("flag", "<i4")])
+KSW_RES_DTYPE = np.dtype([("max", "<u4"), ("zdropped", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), ("mqe", "<i4"), ("mqe_t", "<i4"), ("mte", "<i4"), ("mte_q", "<i4"),
+                          ("score", "<i4"), ("n_cigar", "<i4"), ("reach_end", "<i4"), ("status", "<i4")])
+KSW_REFUSED, KSW_TOO_BIG, KSW_CIGAR_CUT = 1, 2, 3
+
+
+def _ksw_score_bytes(score):
+    """(mat int8 [25], q, e, q2, e2) or the dict params.ksw_scores() makes -> the 29 bytes of mm2c_ksw_score_t"""
+    if isinstance(score, dict):
+        score = (score["mat"], score["q"], score["e"], score["q2"], score["e2"])
+    mat, q, e, q2, e2 = score
+    mat = np.asarray(mat, dtype=np.int8).reshape(-1)
+    if mat.size != 25:
+        raise ValueError("mat must hold 5 x 5 scores")
+    return np.ascontiguousarray(np.concatenate([mat, np.array([q, e, q2, e2], np.int8)]))
+
+
+def ksw_task_scratch(qlen, tlen, w, flag):
+    """bytes of a scratch slot a task takes (mm2c_ksw_task_scratch)"""
+    return int(N.load().mm2c_ksw_task_scratch(int(qlen), int(tlen), int(w), int(flag)))
+
+
+class KswPlan:
+    """mm2c_kswplan_t: ksw_extd2_sse (ksw2_extd2_sse.c) on the GPU for batches of up to n_tasks_cap independent tasks over a pool of seq_cap bases and cigar_cap
+    CIGAR words, one wave per scratch slot.  Either scratch_bytes (the default cut into slots of 4 MiB, for tasks up to that size) or n_slots and slot_bytes (the
+    caller's cut: a task runs in a slot of at least ksw_task_scratch(...) bytes).  Byte for byte the reference's ksw_extz_t and CIGAR."""
+
+    def __init__(self, n_tasks_cap, seq_cap, cigar_cap, scratch_bytes=None, n_slots=None, slot_bytes=None):
+        self.lib = N.load()
+        self.n_tasks_cap, self.seq_cap, self.cigar_cap = int(n_tasks_cap), int(seq_cap), int(cigar_cap)
+        if (scratch_bytes is None) == (n_slots is None or slot_bytes is None):
+            raise ValueError("give scratch_bytes, or n_slots and slot_bytes")
+        if scratch_bytes is not None:
+            self.handle = self.lib.mm2c_kswplan_create(self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(scratch_bytes))
+        else:
+            self.handle = self.lib.mm2c_kswplan_create_slots(self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(n_slots), int(slot_bytes))
+        if not self.handle:
+            N.check(-1, "mm2c_kswplan_create")
+        self.slot_bytes, self.n_slots = int(self.lib.mm2c_kswplan_slot_bytes(self.handle)), int(self.lib.mm2c_kswplan_n_slots(self.handle))
+
+    def run(self, score, n_tasks, tasks: torch.Tensor, seq: torch.Tensor, cig_off: torch.Tensor, res: torch.Tensor = None, cigar: torch.Tensor = None, stream=None):
+        """tasks: the bytes of KSW_TASK_DTYPE [n_tasks], seq uint8 [>= seq_cap], cig_off int64 [n_tasks + 1], all on the GPU.  Returns (res, cigar): uint8
+        [n_tasks, 48] (KSW_RES_DTYPE) and int32 [cigar_cap] GPU tensors (given ones are written into).  Asynchronous."""
+        n_tasks = int(n_tasks)
+        for t in (tasks, seq, cig_off):
+            assert t.is_cuda and t.is_contiguous()
+        assert tasks.numel() * tasks.element_size() >= n_tasks * KSW_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap
+        assert cig_off.dtype == torch.int64 and cig_off.numel() >= n_tasks + 1 and 0 <= n_tasks <= self.n_tasks_cap
+        dev = tasks.device
+        if res is None:
+            res = torch.empty((max(n_tasks, 1), KSW_RES_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if cigar is None:
+            cigar = torch.empty(max(self.cigar_cap, 1), dtype=torch.int32, device=dev)
+        assert res.is_cuda and res.is_contiguous() and res.numel() * res.element_size() >= n_tasks * KSW_RES_DTYPE.itemsize
+        assert cigar.is_cuda and cigar.is_contiguous() and cigar.element_size() == 4 and cigar.numel() >= self.cigar_cap
+        sc = _ksw_score_bytes(score)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_kswplan_run_device(self.handle, _np_ptr(sc), n_tasks, tasks.data_ptr(), seq.data_ptr(), cig_off.data_ptr(), res.data_ptr(),
+                                                 cigar.data_ptr(), st), "mm2c_kswplan_run_device")
+        return res, cigar
+
+    def counts(self):
+        """waits for the run -> (return code, tasks refused, tasks too big or CIGARs cut) without raising"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_kswplan_check(self.handle, C.byref(a), C.byref(b))
+        return rc, a.value, b.value
+
+    def check(self):
+        """waits for the run; raises (code -2) if a task was refused, (code -3) if one did not fit a slot or a CIGAR was cut"""
+        N.check(self.counts()[0], "mm2c_kswplan_check")
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_kswplan_last_ms(self.handle, C.byref(ms)), "mm2c_kswplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(ksw_rows,) of the last run: rows and backtrack are one kernel"""
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_kswplan_last_kernel_ms(self.handle, C.byref(ms)), "mm2c_kswplan_last_kernel_ms")
+        return (ms.value,)
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_kswplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ksw_extd2_batch(score, tasks, seq, cig_off, scratch_bytes=0, res=None, cigar=None):
+    """mm2c_ksw_extd2_batch_host: host arrays in (tasks KSW_TASK_DTYPE, seq uint8 codes 0..4, cig_off int64 [n + 1] from 0) -> (res KSW_RES_DTYPE [n], cigar uint32
+    [cig_off[n]]); task i's CIGAR is cigar[cig_off[i] : cig_off[i] + min(n_cigar, its slot)].  Raises before any device work for a bad task; with code -3 (a task
+    beyond the scratch, a CIGAR cut) the arrays given as res / cigar are complete all the same."""
+    lib = N.load()
+    tk = np.ascontiguousarray(tasks, dtype=KSW_TASK_DTYPE); sq = np.ascontiguousarray(seq, dtype=np.uint8); co = np.ascontiguousarray(cig_off, dtype=np.int64)
+    n = tk.size
+    if co.size != n + 1:
+        raise ValueError("cig_off must hold n_tasks + 1 offsets")
+    res = np.zeros(max(n, 1), KSW_RES_DTYPE) if res is None else res
+    cigar = np.zeros(max(int(co[-1]), 1), np.uint32) if cigar is None else cigar
+    assert res.dtype == KSW_RES_DTYPE and res.size >= n and cigar.dtype == np.uint32 and cigar.size >= int(co[-1]) and res.flags.c_contiguous and cigar.flags.c_contiguous
+    sc = _ksw_score_bytes(score)
+    N.check(lib.mm2c_ksw_extd2_batch_host(_np_ptr(sc), n, _np_ptr(tk), sq.size, _np_ptr(sq), _np_ptr(co), _np_ptr(res), _np_ptr(cigar), int(scratch_bytes)),
+            "mm2c_ksw_extd2_batch_host")
+    return res[:n], cigar[:int(co[-1])]
+
+
 class MapqPlan:
     """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
     reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the

@@ -72,5 +72,28 @@ def mapq_opts(**kw):
     return MapqOpt(int(bool(v["do_join"])), v["max_join_long"], v["max_join_short"], v["min_join_flank_sc"], v["min_join_flank_ratio"], v["min_cnt"], v["min_chain_score"])
 
 
+KSW_PRESETS = {   # a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus, bw (options.c:26,45-48 and the presets of :82-151)
+    "map-ont": (2, 4, 4, 2, 24, 1, 1, 400, 200, -1, 500), "map-pb": (2, 4, 4, 2, 24, 1, 1, 400, 200, -1, 500),
+    "ava-ont": (2, 4, 4, 2, 24, 1, 1, 400, 200, -1, 2000), "ava-pb": (2, 4, 4, 2, 24, 1, 1, 400, 200, -1, 2000),
+    "asm5": (1, 19, 39, 3, 81, 1, 1, 200, 200, -1, 500), "asm10": (1, 9, 16, 2, 41, 1, 1, 200, 200, -1, 500), "asm20": (1, 4, 6, 2, 26, 1, 1, 200, 200, -1, 500),
+    "sr": (2, 8, 12, 2, 24, 1, 1, 100, 100, 10, 100),
+}
+
+
+def ksw_scores(preset="map-ont", **kw):
+    """The score set of a base-alignment call as mm_align_skeleton makes it: mat by ksw_gen_simple_mat (align.c:9-22, m = 5: a on the diagonal, -b off it, -sc_ambi in
+    the last row and column) and the preset's scalars (options.c).  Returns dict(mat int8 list of 25, q, e, q2, e2, zdrop, zdrop_inv, end_bonus, bw); keywords
+    (a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus, bw) override single values.  sr has q != q2, so it runs ksw_extd2 as well."""
+    names = ("a", "b", "q", "e", "q2", "e2", "sc_ambi", "zdrop", "zdrop_inv", "end_bonus", "bw")
+    v = dict(zip(names, KSW_PRESETS[preset]))
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"ksw_scores: unknown field(s) {sorted(unknown)}")
+    v.update(kw)
+    a, b, amb = abs(v["a"]), -abs(v["b"]), -abs(v["sc_ambi"])
+    mat = [amb if (i == 4 or j == 4) else (a if i == j else b) for i in range(5) for j in range(5)]
+    return dict(mat=mat, q=v["q"], e=v["e"], q2=v["q2"], e2=v["e2"], zdrop=v["zdrop"], zdrop_inv=v["zdrop_inv"], end_bonus=v["end_bonus"], bw=v["bw"])
+
+
 def as_dict(p):
     return {k: getattr(p, k) for k, _ in p._fields_}
