@@ -590,6 +590,62 @@ int mm2c_kswplan_last_kernel_ms(mm2c_kswplan_t *plan, float *rows_ms);
 int mm2c_ksw_extd2_batch_host(const mm2c_ksw_score_t *sc, int64_t n_tasks, const mm2c_ksw_task_t *tasks, int64_t seq_len, const uint8_t *seq,
                               const int64_t *cig_off, mm2c_ksw_res_t *res, uint32_t *cigar, int64_t scratch_bytes);
 
+/* ---- an aligned region finished on the GPU: mm_update_extra (align.c:240-286, with mm_fix_cigar :91-167 and mm_update_cigar_eqx :169-238) and mm_test_zdrop
+ * (align.c:47-89) ----
+ * A stand-alone plan with two entries, byte for byte what the reference's functions give.  One score set per call: mat, q and e of a
+ * mm2c_ksw_score_t are read (q2, e2 are not).  Behind a gap word the reference clamps the running score but does not update the maximum (:268-269); the plan does the
+ * same.  q < 0 or e < 0 is refused at the entry all the same (MM2C_E_ARG): there `s -= q + e * len` is evaluated in unsigned arithmetic and wraps, which no preset
+ * asks for and the plan does not follow; with 0 <= q, e <= 127 and lengths up to MM2C_KSW_MAX_LEN nothing wraps.  Sequences are codes 0..4 in one pool of seq_cap bytes.
+ *
+ * mm2c_extraplan_run_device: mm_update_extra for n_regs regions.  Region i: qlen = r->qe - r->qs and tlen = r->re - r->rs at entry, the sequences of :787-788 at
+ * q_off / t_off, its CIGAR in cig_in[in_off[i] .. in_off[i] + n_cigar), its output slot cig_out[out_off[i] .. out_off[i + 1]).  The two CIGAR buffers may not
+ * overlap (MM2C_E_ARG).  rev is carried for the caller; the results do not depend on it.  Result: the final n_cigar and CIGAR words, blen, mlen, n_ambi (what the
+ * call adds to p->n_ambi), dp_max, and the leading I / D the function stripped (:157-166): the caller does rs += tshift, and qe -= qshift if rev, else qs += qshift.
+ * Without is_eqx the result never has more words than the input; with is_eqx it may: a result longer than its slot is cut to the words that fit, every scalar
+ * (n_cigar too) is exact, nothing is written behind the slot, status MM2C_EXTRA_CIGAR_CUT, MM2C_E_TOOBIG from mm2c_extraplan_check.
+ * MM2C_EXTRA_REFUSED (counted, MM2C_E_ARG, nothing but the status word written): inputs the reference is not defined on -- an op code above 3, a zero-length word
+ * with op 3, two or more words whose lengths are all zero, op lengths that do not add up to qlen and tlen -- and offsets or lengths that leave a pool or run
+ * backwards, or a length above MM2C_KSW_MAX_LEN.  Base codes above 4 are not looked for on the device (the host entries refuse them).
+ * A CIGAR of up to MM2C_EXTRA_LDS_WORDS words is worked on in LDS; a longer one in one of the plan's n_slots scratch slots of slot_words words (16 bytes a word):
+ * beyond both, MM2C_EXTRA_TOO_BIG (counted, not run, MM2C_E_TOOBIG).  n_slots is also the number of waves resident (<= 0: 2 048; at most MM2C_EXTRA_MAX_SLOTS).
+ * The sequences stay in global memory.  The items beside a refused, too big or cut one are exact.
+ *
+ * mm2c_extraplan_zdrop_run_device: mm_test_zdrop on the arrays of a ksw plan, unchanged and without a download in between (cig_in_cap of the plan is the ksw plan's
+ * cigar_cap).  zdrop_opt.no_inv stands for opt->flag & (MM_F_SPLICE | MM_F_SR | MM_F_FOR_ONLY | MM_F_REV_ONLY) of :72.  Per task: max_zdrop; t0, t1, q0, q1 =
+ * pos[0][0], pos[0][1], pos[1][0], pos[1][1] (-1 when nothing dropped); code = max_zdrop > zdrop (:88); inv_cand = 1 exactly when the condition of :72 holds.  The
+ * ksw_ll_i16 call behind it stays with the host: for a task with inv_cand, run ksw_ll_i16 on the reverse complement of query [q0, q1) against target [t0, t1) as
+ * :76-82 do; the function's return is 2 if that score passes :85, else code.  A task whose ksw status is not 0 gets MM2C_EXTRA_REFUSED and nothing else (counted);
+ * so does one whose CIGAR leaves its slot or its sequences.  n_cigar == 0 gives max_zdrop 0 and positions -1. */
+#define MM2C_EXTRA_LDS_WORDS 2048
+#define MM2C_EXTRA_RUN_LANE 16         /* an indel's match run is walked by one lane up to this many bases, by the whole wave beyond */
+#define MM2C_EXTRA_MAX_SLOTS 4096
+#define MM2C_EXTRA_REFUSED 1
+#define MM2C_EXTRA_TOO_BIG 2
+#define MM2C_EXTRA_CIGAR_CUT 3
+typedef struct { int64_t q_off, t_off; int32_t qlen, tlen; int32_t n_cigar; int32_t rev; } mm2c_extra_task_t;
+typedef struct { int32_t n_cigar, qshift, tshift, blen, mlen, n_ambi, dp_max, status; } mm2c_extra_res_t;
+typedef struct { int32_t zdrop, zdrop_inv, max_gap, no_inv; } mm2c_zdrop_opt_t;
+typedef struct { int32_t max_zdrop, t0, t1, q0, q1, code, inv_cand, status; } mm2c_zdrop_res_t;
+typedef struct mm2c_extraplan mm2c_extraplan_t;
+mm2c_extraplan_t *mm2c_extraplan_create(int64_t n_cap, int64_t seq_cap, int64_t cig_in_cap, int64_t cig_out_cap, int64_t n_slots, int64_t slot_words);
+void mm2c_extraplan_destroy(mm2c_extraplan_t *plan);
+/* asynchronous on `stream`; all pointers are device memory except sc and opt */
+int mm2c_extraplan_run_device(mm2c_extraplan_t *plan, const mm2c_ksw_score_t *sc, int is_eqx, int64_t n_regs, const mm2c_extra_task_t *d_tasks, const uint8_t *d_seq,
+                              const int64_t *d_in_off, const uint32_t *d_cig_in, const int64_t *d_out_off, mm2c_extra_res_t *d_res, uint32_t *d_cig_out, void *stream);
+int mm2c_extraplan_zdrop_run_device(mm2c_extraplan_t *plan, const mm2c_ksw_score_t *sc, const mm2c_zdrop_opt_t *opt, int64_t n_tasks, const mm2c_ksw_task_t *d_tasks,
+                                    const uint8_t *d_seq, const int64_t *d_cig_off, const mm2c_ksw_res_t *d_res, const uint32_t *d_cigar, mm2c_zdrop_res_t *d_zres, void *stream);
+/* waits for the plan's last run (of either entry); n_too_big: CIGARs beyond LDS and slot plus output CIGARs cut */
+int mm2c_extraplan_check(mm2c_extraplan_t *plan, int64_t *n_refused, int64_t *n_too_big);
+/* milliseconds of the last run between HIP events on its stream; _kernel_ms: of the last extra_update and the last extra_zdrop run (0 for one that has not run) */
+int mm2c_extraplan_last_ms(mm2c_extraplan_t *plan, float *ms);
+int mm2c_extraplan_last_kernel_ms(mm2c_extraplan_t *plan, float *update_ms, float *zdrop_ms);
+/* host arrays in and out: check the score set, the offsets and every base code first (MM2C_E_ARG before any device work), then upload, run, download and wait.
+ * Scratch slots take the call's longest CIGAR, so nothing is too big.  With MM2C_E_TOOBIG (a CIGAR cut) the outputs are complete all the same. */
+int mm2c_update_extra_batch_host(const mm2c_ksw_score_t *sc, int is_eqx, int64_t n_regs, const mm2c_extra_task_t *tasks, int64_t seq_len, const uint8_t *seq,
+                                 const int64_t *in_off, int64_t n_cig_in, const uint32_t *cig_in, const int64_t *out_off, mm2c_extra_res_t *res, uint32_t *cig_out);
+int mm2c_test_zdrop_batch_host(const mm2c_ksw_score_t *sc, const mm2c_zdrop_opt_t *opt, int64_t n_tasks, const mm2c_ksw_task_t *tasks, int64_t seq_len, const uint8_t *seq,
+                               const int64_t *cig_off, const mm2c_ksw_res_t *res, const uint32_t *cigar, mm2c_zdrop_res_t *zres);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

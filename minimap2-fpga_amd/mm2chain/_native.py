@@ -193,6 +193,15 @@ C_SYMBOLS = {
     "mm2c_kswplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_kswplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_ksw_extd2_batch_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64]),
+    "mm2c_extraplan_create": (C.c_void_p, [C.c_int64] * 6),
+    "mm2c_extraplan_destroy": (None, [C.c_void_p]),
+    "mm2c_extraplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 8),
+    "mm2c_extraplan_zdrop_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 7),
+    "mm2c_extraplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_extraplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_extraplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mm2c_update_extra_batch_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "mm2c_test_zdrop_batch_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
     "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "mm2c_mapqplan_destroy": (None, [C.c_void_p]),
     "mm2c_mapqplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(MapqOpt)] + [C.c_void_p] * 12),

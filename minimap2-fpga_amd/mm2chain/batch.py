@@ -743,6 +743,145 @@ def ksw_extd2_batch(score, tasks, seq, cig_off, scratch_bytes=0, res=None, cigar
     return res[:n], cigar[:int(co[-1])]
 
 
+EXTRA_TASK_DTYPE = np.dtype([("q_off", "<i8"), ("t_off", "<i8"), ("qlen", "<i4"), ("tlen", "<i4"), ("n_cigar", "<i4"), ("rev", "<i4")])
+EXTRA_RES_DTYPE = np.dtype([("n_cigar", "<i4"), ("qshift", "<i4"), ("tshift", "<i4"), ("blen", "<i4"), ("mlen", "<i4"), ("n_ambi", "<i4"), ("dp_max", "<i4"), ("status", "<i4")])
+ZDROP_OPT_DTYPE = np.dtype([("zdrop", "<i4"), ("zdrop_inv", "<i4"), ("max_gap", "<i4"), ("no_inv", "<i4")])
+ZDROP_RES_DTYPE = np.dtype([("max_zdrop", "<i4"), ("t0", "<i4"), ("t1", "<i4"), ("q0", "<i4"), ("q1", "<i4"), ("code", "<i4"), ("inv_cand", "<i4"), ("status", "<i4")])
+EXTRA_REFUSED, EXTRA_TOO_BIG, EXTRA_CIGAR_CUT = 1, 2, 3
+EXTRA_LDS_WORDS = 2048
+
+
+def _zdrop_opt_bytes(opt):
+    """(zdrop, zdrop_inv, max_gap, no_inv) or the dict params.zdrop_opts() makes -> the 16 bytes of mm2c_zdrop_opt_t"""
+    if isinstance(opt, dict):
+        opt = (opt["zdrop"], opt["zdrop_inv"], opt["max_gap"], opt["no_inv"])
+    return np.ascontiguousarray(np.array([int(x) for x in opt], np.int32))
+
+
+class ExtraPlan:
+    """mm2c_extraplan_t: mm_update_extra (align.c:240-286) for batches of regions and mm_test_zdrop (align.c:47-89) on a KswPlan's device outputs, one wave per item,
+    byte for byte the reference.  n_cap items, a pool of seq_cap bases, cig_in_cap input CIGAR words (for z-drop runs: the ksw plan's cigar_cap), cig_out_cap output
+    words; CIGARs beyond EXTRA_LDS_WORDS words need one of n_slots scratch slots of slot_words words."""
+
+    def __init__(self, n_cap, seq_cap, cig_in_cap, cig_out_cap=0, n_slots=0, slot_words=0):
+        self.lib = N.load()
+        self.n_cap, self.seq_cap, self.cig_in_cap, self.cig_out_cap = int(n_cap), int(seq_cap), int(cig_in_cap), int(cig_out_cap)
+        self.handle = self.lib.mm2c_extraplan_create(self.n_cap, self.seq_cap, self.cig_in_cap, self.cig_out_cap, int(n_slots), int(slot_words))
+        if not self.handle:
+            N.check(-1, "mm2c_extraplan_create")
+
+    def update(self, score, is_eqx, n_regs, tasks: torch.Tensor, seq: torch.Tensor, in_off: torch.Tensor, cig_in: torch.Tensor, out_off: torch.Tensor,
+               res: torch.Tensor = None, cig_out: torch.Tensor = None, stream=None):
+        """tasks: the bytes of EXTRA_TASK_DTYPE [n_regs], seq uint8 [>= seq_cap], in_off int64 [n_regs], cig_in int32 [>= cig_in_cap], out_off int64 [n_regs + 1], all on
+        the GPU.  Returns (res, cig_out): uint8 [n_regs, 32] (EXTRA_RES_DTYPE) and int32 [cig_out_cap] GPU tensors (given ones are written into).  Asynchronous."""
+        n = int(n_regs)
+        for t in (tasks, seq, in_off, cig_in, out_off):
+            assert t.is_cuda and t.is_contiguous()
+        assert tasks.numel() * tasks.element_size() >= n * EXTRA_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap and 0 <= n <= self.n_cap
+        assert in_off.dtype == torch.int64 and in_off.numel() >= n and out_off.dtype == torch.int64 and out_off.numel() >= n + 1
+        assert cig_in.element_size() == 4 and cig_in.numel() >= self.cig_in_cap
+        dev = tasks.device
+        if res is None:
+            res = torch.empty((max(n, 1), EXTRA_RES_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if cig_out is None:
+            cig_out = torch.empty(max(self.cig_out_cap, 1), dtype=torch.int32, device=dev)
+        assert res.is_cuda and res.is_contiguous() and res.numel() * res.element_size() >= n * EXTRA_RES_DTYPE.itemsize
+        assert cig_out.is_cuda and cig_out.is_contiguous() and cig_out.element_size() == 4 and cig_out.numel() >= self.cig_out_cap
+        sc = _ksw_score_bytes(score)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_extraplan_run_device(self.handle, _np_ptr(sc), int(bool(is_eqx)), n, tasks.data_ptr(), seq.data_ptr(), in_off.data_ptr(), cig_in.data_ptr(),
+                                                   out_off.data_ptr(), res.data_ptr(), cig_out.data_ptr(), st), "mm2c_extraplan_run_device")
+        return res, cig_out
+
+    def zdrop(self, score, opt, n_tasks, tasks: torch.Tensor, seq: torch.Tensor, cig_off: torch.Tensor, kres: torch.Tensor, cigar: torch.Tensor, zres: torch.Tensor = None,
+              stream=None):
+        """the arrays of KswPlan.run as they lie on the GPU (tasks, seq, cig_off in; res, cigar out) -> zres uint8 [n_tasks, 32] (ZDROP_RES_DTYPE).  Asynchronous."""
+        n = int(n_tasks)
+        for t in (tasks, seq, cig_off, kres, cigar):
+            assert t.is_cuda and t.is_contiguous()
+        assert tasks.numel() * tasks.element_size() >= n * KSW_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap and 0 <= n <= self.n_cap
+        assert cig_off.dtype == torch.int64 and cig_off.numel() >= n + 1 and kres.numel() * kres.element_size() >= n * KSW_RES_DTYPE.itemsize
+        assert cigar.element_size() == 4 and cigar.numel() >= self.cig_in_cap
+        if zres is None:
+            zres = torch.empty((max(n, 1), ZDROP_RES_DTYPE.itemsize), dtype=torch.uint8, device=tasks.device)
+        assert zres.is_cuda and zres.is_contiguous() and zres.numel() * zres.element_size() >= n * ZDROP_RES_DTYPE.itemsize
+        sc, zo = _ksw_score_bytes(score), _zdrop_opt_bytes(opt)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_extraplan_zdrop_run_device(self.handle, _np_ptr(sc), _np_ptr(zo), n, tasks.data_ptr(), seq.data_ptr(), cig_off.data_ptr(), kres.data_ptr(),
+                                                         cigar.data_ptr(), zres.data_ptr(), st), "mm2c_extraplan_zdrop_run_device")
+        return zres
+
+    def counts(self):
+        """waits for the last run -> (return code, items refused, CIGARs too big or cut) without raising"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_extraplan_check(self.handle, C.byref(a), C.byref(b))
+        return rc, a.value, b.value
+
+    def check(self):
+        """waits for the last run; raises (code -2) if an item was refused, (code -3) if a CIGAR fits neither LDS nor a slot or an output was cut"""
+        N.check(self.counts()[0], "mm2c_extraplan_check")
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        N.check(self.lib.mm2c_extraplan_last_ms(self.handle, C.byref(ms)), "mm2c_extraplan_last_ms")
+        return ms.value
+
+    def last_kernel_ms(self):
+        """(extra_update, extra_zdrop) of their last runs; 0 for one that has not run"""
+        a, b = C.c_float(0), C.c_float(0)
+        N.check(self.lib.mm2c_extraplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_extraplan_last_kernel_ms")
+        return a.value, b.value
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_extraplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def update_extra_batch(score, is_eqx, tasks, seq, in_off, cig_in, out_off, res=None, cig_out=None):
+    """mm2c_update_extra_batch_host: host arrays in (tasks EXTRA_TASK_DTYPE, seq uint8 codes 0..4, in_off int64 [n], cig_in uint32, out_off int64 [n + 1] from 0) ->
+    (res EXTRA_RES_DTYPE [n], cig_out uint32 [out_off[n]]); region i's CIGAR is cig_out[out_off[i] : out_off[i] + min(n_cigar, its slot)].  With code -3 (a CIGAR cut)
+    the arrays given as res / cig_out are complete all the same."""
+    lib = N.load()
+    tk = np.ascontiguousarray(tasks, dtype=EXTRA_TASK_DTYPE); sq = np.ascontiguousarray(seq, dtype=np.uint8)
+    io = np.ascontiguousarray(in_off, dtype=np.int64); ci = np.ascontiguousarray(cig_in, dtype=np.uint32); oo = np.ascontiguousarray(out_off, dtype=np.int64)
+    n = tk.size
+    if oo.size != n + 1 or io.size != n:
+        raise ValueError("in_off must hold n_regs and out_off n_regs + 1 offsets")
+    res = np.zeros(max(n, 1), EXTRA_RES_DTYPE) if res is None else res
+    cig_out = np.zeros(max(int(oo[-1]), 1), np.uint32) if cig_out is None else cig_out
+    assert res.dtype == EXTRA_RES_DTYPE and res.size >= n and cig_out.dtype == np.uint32 and cig_out.size >= int(oo[-1]) and res.flags.c_contiguous and cig_out.flags.c_contiguous
+    sc = _ksw_score_bytes(score)
+    N.check(lib.mm2c_update_extra_batch_host(_np_ptr(sc), int(bool(is_eqx)), n, _np_ptr(tk), sq.size, _np_ptr(sq), _np_ptr(io), ci.size, _np_ptr(ci), _np_ptr(oo), _np_ptr(res),
+                                             _np_ptr(cig_out)), "mm2c_update_extra_batch_host")
+    return res[:n], cig_out[:int(oo[-1])]
+
+
+def test_zdrop_batch(score, opt, tasks, seq, cig_off, kres, cigar, zres=None):
+    """mm2c_test_zdrop_batch_host: the host arrays of ksw_extd2_batch (tasks, seq, cig_off in; res, cigar out) -> zres ZDROP_RES_DTYPE [n]"""
+    lib = N.load()
+    tk = np.ascontiguousarray(tasks, dtype=KSW_TASK_DTYPE); sq = np.ascontiguousarray(seq, dtype=np.uint8); co = np.ascontiguousarray(cig_off, dtype=np.int64)
+    kr = np.ascontiguousarray(kres, dtype=KSW_RES_DTYPE); cg = np.ascontiguousarray(cigar, dtype=np.uint32)
+    n = tk.size
+    if co.size != n + 1 or kr.size < n:
+        raise ValueError("cig_off must hold n_tasks + 1 offsets and kres n_tasks results")
+    zres = np.zeros(max(n, 1), ZDROP_RES_DTYPE) if zres is None else zres
+    assert zres.dtype == ZDROP_RES_DTYPE and zres.size >= n and zres.flags.c_contiguous and cg.size >= int(co[-1])
+    sc, zo = _ksw_score_bytes(score), _zdrop_opt_bytes(opt)
+    N.check(lib.mm2c_test_zdrop_batch_host(_np_ptr(sc), _np_ptr(zo), n, _np_ptr(tk), sq.size, _np_ptr(sq), _np_ptr(co), _np_ptr(kr), _np_ptr(cg), _np_ptr(zres)),
+            "mm2c_test_zdrop_batch_host")
+    return zres[:n]
+
+
+test_zdrop_batch.__test__ = False      # a library function, not a test
+
+
 class MapqPlan:
     """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
     reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the

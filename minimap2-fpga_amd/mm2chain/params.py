@@ -95,5 +95,14 @@ def ksw_scores(preset="map-ont", **kw):
     return dict(mat=mat, q=v["q"], e=v["e"], q2=v["q2"], e2=v["e2"], zdrop=v["zdrop"], zdrop_inv=v["zdrop_inv"], end_bonus=v["end_bonus"], bw=v["bw"])
 
 
+def zdrop_opts(preset="map-ont", max_gap=5000, no_inv=None, **kw):
+    """mm2c_zdrop_opt_t as mm_align1 hands it to mm_test_zdrop (align.c:47-89): the preset's zdrop and zdrop_inv (options.c), max_gap (5 000; sr: 100), and no_inv, which
+    stands for opt->flag & (MM_F_SPLICE | MM_F_SR | MM_F_FOR_ONLY | MM_F_REV_ONLY) of :72 (set for sr).  Returns dict(zdrop, zdrop_inv, max_gap, no_inv)."""
+    s = ksw_scores(preset, **kw)
+    if preset == "sr" and max_gap == 5000:
+        max_gap = 100
+    return dict(zdrop=s["zdrop"], zdrop_inv=s["zdrop_inv"], max_gap=int(max_gap), no_inv=int(preset == "sr" if no_inv is None else bool(no_inv)))
+
+
 def as_dict(p):
     return {k: getattr(p, k) for k, _ in p._fields_}
