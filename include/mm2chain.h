@@ -320,6 +320,7 @@ typedef struct {
 	uint64_t p;
 } mm2c_reg_t;
 #define MM2C_REG_REV_BIT 10
+#define MM2C_REG_SPLIT_INV_BIT 24
 
 /* A plan for batches of up to n_reads reads, n_u_cap chains and n_b_cap chain anchors in all (its scratch, 64 bytes per chain, is sized from the capacities).
  * The input is the compact output of the device epilogue (mm2c_plan_chains_device): d_u_off / d_b_off (n_reads + 1 entries each), d_u, d_b, plus per
@@ -645,6 +646,76 @@ int mm2c_update_extra_batch_host(const mm2c_ksw_score_t *sc, int is_eqx, int64_t
                                  const int64_t *in_off, int64_t n_cig_in, const uint32_t *cig_in, const int64_t *out_off, mm2c_extra_res_t *res, uint32_t *cig_out);
 int mm2c_test_zdrop_batch_host(const mm2c_ksw_score_t *sc, const mm2c_zdrop_opt_t *opt, int64_t n_tasks, const mm2c_ksw_task_t *tasks, int64_t seq_len, const uint8_t *seq,
                                const int64_t *cig_off, const mm2c_ksw_res_t *res, const uint32_t *cigar, mm2c_zdrop_res_t *zres);
+
+/* ---- final regions -> ksw tasks and their sequence pool on the GPU (mm_align1, align.c:565-733, 767-771, up to each mm_align_pair call) ----
+ * mm2c_refseq_t: the packed reference mi->S as the host has it (mm_seq4_set, 8 bases a word) with offset and len of every mi->seq[], resident on the device.
+ *
+ * mm2c_alnplan_t, a stand-alone plan wired into nothing.  Under MM2C_ALN_F_SR it runs mm_max_stretch, the sr form of rs0 .. qe0 (:613-620) and emits
+ * one ungapped item between the extensions instead of what follows.  Otherwise per region it runs mm_fix_bad_ends (unless MM2C_ALN_F_NO_END_FLT), mm_filter_bad_seeds and
+ * mm_filter_bad_seeds_alt with the arguments of :595-596 -- MM_SEED_IGNORE / MM_SEED_LONG_JOIN are written into the caller's anchors, and a LONG_JOIN that is set
+ * already is honoured --, mm_adjust_minier (both forms: k >> 1, and the homopolymer walks under MM2C_ALN_I_HPC), rs0 .. qe0 (:621-684) and then emits the list of calls mm_align1 issues WHEN NO TASK DROPS, in call
+ * order: left extension, gap fills, right extension.  A consumer cuts the list behind the first task the z-drop entry reports as dropped (an item over
+ * max_sw_mat counts as dropped, :323-325).  Outputs: one mm2c_aln_reg_t per region; the items; mm2c_ksw_task_t[] with cig_off[] as mm2c_kswplan_run_device takes
+ * them (a task's CIGAR slot: min(qlen + tlen, ((qlen + tlen) >> cig_shift) + 16) words); and ONE sequence pool that is directly the d_seq of the ksw plan and of
+ * the extra plan.  Per region the pool holds, each from a multiple of 16 on and padded with code 4: the query span [qs0, qe0) on the region's strand at q_off, the
+ * target span [rs0, re0) at t_off, and -- if there is a left extension -- the reversed query [qs0, qs) at left_off and the reversed target [rs0, rs) at left_off +
+ * round16(qs - qs0).  Gap and right-extension tasks point into the spans; [qs1, qe1) x [rs1, re1) of mm_update_extra is q_off + (qs1 - qs0), t_off + (rs1 - rs0).
+ * status: MM2C_ALN_REFUSED (counted, MM2C_E_ARG from _check; only the status is written, the anchors are untouched): MM2C_ALN_F_SPLICE, MM2C_ALN_F_SR
+ * together with MM2C_ALN_I_HPC (:575), an sr stretch whose two lengths differ (:725), as / cnt leaving the read's anchors, anchors not on one x >> 32, rid >= n_seq, an anchor beyond its contig or read or running
+ * backwards, an input on which an assert of :600, 626, 686, 707 would fire or a length would be negative, offsets leaving a capacity.  MM2C_ALN_TOO_BIG: more
+ * long gaps (:367) than MM2C_ALN_LDS_GAPS and than slot_words (counted, not run, MM2C_E_TOOBIG).  MM2C_ALN_OVER_CAP: the region's items, tasks or pool bytes leave
+ * a capacity: counted, MM2C_E_TOOBIG, no item, task or pool byte of it is written and nothing behind a capacity; totals[] of _check still say what the batch needs.  Its
+ * anchors DO carry the flags of its filters already (they are written before the offsets are known); running it again with more room gives the same as1 / cnt1 and
+ * flags, since the filters only add bits and mm_fix_bad_ends sees a LONG_JOIN only behind the ends it has chosen.  With n_regs == 0 only cig_off[0] = 0 is written. */
+#define MM2C_ALN_LDS_GAPS 2048
+#define MM2C_ALN_MAX_SLOTS 4096
+#define MM2C_ALN_REFUSED 1
+#define MM2C_ALN_TOO_BIG 2
+#define MM2C_ALN_OVER_CAP 3
+#define MM2C_ALN_F_SR 1
+#define MM2C_ALN_F_NO_END_FLT 2
+#define MM2C_ALN_F_SPLICE 4
+#define MM2C_ALN_I_HPC 1
+#define MM2C_ALN_LEFT 0
+#define MM2C_ALN_GAP 1
+#define MM2C_ALN_RIGHT 2
+#define MM2C_ALN_UNGAPPED 3            /* the sr gap fill (:724-731): no ksw task, `score` is its ungapped score, qe - qs its one CIGAR word */
+#define MM2C_ALN_OVER 16               /* or-ed into kind: beyond max_sw_mat, no ksw task (task == -1) */
+typedef struct {
+	int32_t a, b, q, e, e2, bw, bw_ext;            /* bw_ext = (int)(opt->bw * 1.5 + 1.), computed by the host (:580) */
+	int32_t min_chain_score, max_gap, min_cnt, min_ksw_len, end_bonus, zdrop, zdrop_inv;
+	int64_t max_sw_mat;
+	int32_t flag, idx_flag, k, reserved;           /* MM2C_ALN_F_*, MM2C_ALN_I_*, mi->k */
+} mm2c_aln_opt_t;
+typedef struct {
+	int32_t as1, cnt1, rs, qs, re, qe, rs0, qs0, re0, qe0, n_items, n_tasks, status, rev;
+	int64_t item0, task0, cig0, q_off, t_off, left_off;
+} mm2c_aln_reg_t;
+typedef struct { int32_t reg, kind, anchor, rs, re, qs, qe, task, score, reserved; } mm2c_aln_item_t;   /* anchor: index into the read's anchors; task: index into the task list */
+typedef struct mm2c_refseq mm2c_refseq_t;
+typedef struct mm2c_alnplan mm2c_alnplan_t;
+/* host arrays; NULL on failure: a contig whose [offset, offset + len) leaves the n_words words, a len of 2^31 or more (MM2C_E_ARG) */
+mm2c_refseq_t *mm2c_refseq_create(int64_t n_seq, const uint64_t *offset, const uint32_t *len, const uint32_t *S, int64_t n_words);
+void mm2c_refseq_destroy(mm2c_refseq_t *ref);
+/* capacities: regions, items, tasks, pool bytes, anchors and read bases of a batch.  n_slots (<= 0: 2 048) waves are resident, each with a slot of slot_words words */
+mm2c_alnplan_t *mm2c_alnplan_create(int64_t n_regs_cap, int64_t n_items_cap, int64_t n_tasks_cap, int64_t pool_cap, int64_t n_b_cap, int64_t reads_cap, int32_t cig_shift,
+                                    int64_t n_slots, int64_t slot_words);
+void mm2c_alnplan_destroy(mm2c_alnplan_t *plan);
+/* asynchronous on `stream`; all pointers are device memory except opt.  d_u_off, d_b_off, d_read_off: n_reads + 1 entries; d_n_b (may be NULL): anchors per read,
+ * as the mapq plan's d_n_b_out.  d_b is in/out.  d_cig_off: n_tasks_cap + 1 entries; d_pool: pool_cap bytes, 16-byte aligned.  Regions 8-byte, anchors 16-byte aligned. */
+int mm2c_alnplan_run_device(mm2c_alnplan_t *plan, const mm2c_aln_opt_t *opt, const mm2c_refseq_t *ref, int64_t n_reads, int64_t n_regs, const int64_t *d_u_off,
+                            const mm2c_reg_t *d_regs, const int64_t *d_b_off, const int64_t *d_n_b, void *d_b, const int64_t *d_read_off, const uint8_t *d_reads,
+                            mm2c_aln_reg_t *d_aln_regs, mm2c_aln_item_t *d_items, mm2c_ksw_task_t *d_tasks, int64_t *d_cig_off, uint8_t *d_pool, void *stream);
+/* waits for the last run; totals (may be NULL): items, tasks, CIGAR words and pool bytes the batch takes; n_too_big counts MM2C_ALN_TOO_BIG and MM2C_ALN_OVER_CAP */
+int mm2c_alnplan_check(mm2c_alnplan_t *plan, int64_t *n_refused, int64_t *n_too_big, int64_t totals[4]);
+/* milliseconds between HIP events of the last run: aln_plan with aln_scan, aln_emit, aln_gather */
+int mm2c_alnplan_last_kernel_ms(mm2c_alnplan_t *plan, float ms[3]);
+/* host arrays in and out.  Checks the offsets and every base code (reads: 0..4; S: nibbles 0..4 inside the contigs) first (MM2C_E_ARG before any device work), then
+ * uploads, runs, downloads and waits.  b comes back with its flags; the capacities are those of the arrays given; totals as _check. */
+int mm2c_align_tasks_batch_host(const mm2c_aln_opt_t *opt, int64_t n_seq, const uint64_t *offset, const uint32_t *len, const uint32_t *S, int64_t n_words,
+                                int64_t n_reads, const int64_t *u_off, const mm2c_reg_t *regs, const int64_t *b_off, mm2c_anchor_t *b, const int64_t *read_off,
+                                const uint8_t *reads, int32_t cig_shift, mm2c_aln_reg_t *aln_regs, int64_t n_items_cap, mm2c_aln_item_t *items, int64_t n_tasks_cap,
+                                mm2c_ksw_task_t *tasks, int64_t *cig_off, int64_t pool_cap, uint8_t *pool, int64_t totals[4]);
 
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits

@@ -202,6 +202,15 @@ C_SYMBOLS = {
     "mm2c_extraplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mm2c_update_extra_batch_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "mm2c_test_zdrop_batch_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "mm2c_refseq_create": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "mm2c_refseq_destroy": (None, [C.c_void_p]),
+    "mm2c_alnplan_create": (C.c_void_p, [C.c_int64] * 6 + [C.c_int32, C.c_int64, C.c_int64]),
+    "mm2c_alnplan_destroy": (None, [C.c_void_p]),
+    "mm2c_alnplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 13),
+    "mm2c_alnplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_alnplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_align_tasks_batch_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "mm2c_mapqplan_destroy": (None, [C.c_void_p]),
     "mm2c_mapqplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(MapqOpt)] + [C.c_void_p] * 12),

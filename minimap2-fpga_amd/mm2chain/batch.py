@@ -882,6 +882,163 @@ def test_zdrop_batch(score, opt, tasks, seq, cig_off, kres, cigar, zres=None):
 test_zdrop_batch.__test__ = False      # a library function, not a test
 
 
+ALN_OPT_DTYPE = np.dtype([(n, "<i4") for n in ("a", "b", "q", "e", "e2", "bw", "bw_ext", "min_chain_score", "max_gap", "min_cnt", "min_ksw_len", "end_bonus", "zdrop", "zdrop_inv")] +
+                         [("max_sw_mat", "<i8"), ("flag", "<i4"), ("idx_flag", "<i4"), ("k", "<i4"), ("reserved", "<i4")])
+ALN_REG_DTYPE = np.dtype([(n, "<i4") for n in ("as1", "cnt1", "rs", "qs", "re", "qe", "rs0", "qs0", "re0", "qe0", "n_items", "n_tasks", "status", "rev")] +
+                         [(n, "<i8") for n in ("item0", "task0", "cig0", "q_off", "t_off", "left_off")])
+ALN_ITEM_DTYPE = np.dtype([(n, "<i4") for n in ("reg", "kind", "anchor", "rs", "re", "qs", "qe", "task", "score", "reserved")])
+ALN_REFUSED, ALN_TOO_BIG, ALN_OVER_CAP = 1, 2, 3
+ALN_LDS_GAPS = 2048
+ALN_LEFT, ALN_GAP, ALN_RIGHT, ALN_UNGAPPED, ALN_OVER = 0, 1, 2, 3, 16
+
+
+def _aln_opt_bytes(opt):
+    """the dict params.aln_opts() makes (or an ALN_OPT_DTYPE record) -> the 80 bytes of mm2c_aln_opt_t"""
+    if isinstance(opt, dict):
+        o = np.zeros(1, ALN_OPT_DTYPE)
+        for k, v in opt.items():
+            o[k] = int(v)
+        return o
+    return np.ascontiguousarray(np.asarray(opt, dtype=ALN_OPT_DTYPE).reshape(1))
+
+
+class RefSeq:
+    """mm2c_refseq_t: the packed reference mi->S (uint32 words, 8 bases each) with offset (uint64) and len (uint32) of every mi->seq[], resident on the GPU"""
+
+    def __init__(self, offset, length, S):
+        self.lib = N.load()
+        off = np.ascontiguousarray(offset, dtype=np.uint64); ln = np.ascontiguousarray(length, dtype=np.uint32); S = np.ascontiguousarray(S, dtype=np.uint32)
+        if off.size != ln.size:
+            raise ValueError("offset and len must have one entry per sequence")
+        self.n_seq, self.n_words = int(off.size), int(S.size)
+        self.handle = self.lib.mm2c_refseq_create(self.n_seq, _np_ptr(off), _np_ptr(ln), _np_ptr(S), self.n_words)
+        if not self.handle:
+            N.check(-2, "mm2c_refseq_create")
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_refseq_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AlnPlan:
+    """mm2c_alnplan_t: final regions -> the ksw tasks mm_align1 (align.c:565-771) issues when no task drops, with their items and ONE sequence pool that is the d_seq
+    of a KswPlan and of an ExtraPlan, byte for byte the reference.  Capacities: regions, items, tasks, pool bytes, anchors, read bases."""
+
+    def __init__(self, n_regs_cap, n_items_cap, n_tasks_cap, pool_cap, n_b_cap, reads_cap, cig_shift=0, n_slots=0, slot_words=0):
+        self.lib = N.load()
+        self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.pool_cap = int(n_regs_cap), int(n_items_cap), int(n_tasks_cap), int(pool_cap)
+        self.n_b_cap, self.reads_cap, self.cig_shift = int(n_b_cap), int(reads_cap), int(cig_shift)
+        self.handle = self.lib.mm2c_alnplan_create(self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.pool_cap, self.n_b_cap, self.reads_cap, self.cig_shift,
+                                                   int(n_slots), int(slot_words))
+        if not self.handle:
+            N.check(-2, "mm2c_alnplan_create")
+
+    def run(self, opt, ref: RefSeq, n_reads, n_regs, u_off: torch.Tensor, regs: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, read_off: torch.Tensor, reads: torch.Tensor,
+            n_b: torch.Tensor = None, aln_regs: torch.Tensor = None, items: torch.Tensor = None, tasks: torch.Tensor = None, cig_off: torch.Tensor = None,
+            pool: torch.Tensor = None, stream=None):
+        """u_off, b_off, read_off int64 [n_reads + 1], regs the bytes of REG_DTYPE [n_regs], b the anchors (16 bytes each, in/out: the seed flags), reads uint8 forward
+        codes, n_b int64 [n_reads] or None, all on the GPU.  Returns (aln_regs uint8 [n_regs, 104], items uint8 [n_items_cap, 40], tasks uint8 [n_tasks_cap, 40],
+        cig_off int64 [n_tasks_cap + 1], pool uint8 [pool_cap]) GPU tensors (given ones are written into).  Asynchronous."""
+        n_reads, n = int(n_reads), int(n_regs)
+        for t in (u_off, regs, b_off, b, read_off, reads):
+            assert t.is_cuda and t.is_contiguous()
+        assert all(t.dtype == torch.int64 and t.numel() >= n_reads + 1 for t in (u_off, b_off, read_off)) and 0 <= n <= self.n_regs_cap
+        assert regs.numel() * regs.element_size() >= n * REG_DTYPE.itemsize and b.numel() * b.element_size() >= 16 * self.n_b_cap and reads.element_size() == 1 and reads.numel() >= self.reads_cap
+        dev = regs.device
+        if aln_regs is None:
+            aln_regs = torch.empty((max(n, 1), ALN_REG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if items is None:
+            items = torch.empty((max(self.n_items_cap, 1), ALN_ITEM_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if tasks is None:
+            tasks = torch.empty((max(self.n_tasks_cap, 1), KSW_TASK_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if cig_off is None:
+            cig_off = torch.empty(self.n_tasks_cap + 1, dtype=torch.int64, device=dev)
+        if pool is None:
+            pool = torch.empty(max(self.pool_cap, 16), dtype=torch.uint8, device=dev)
+        for t in (aln_regs, items, tasks, cig_off, pool):
+            assert t.is_cuda and t.is_contiguous()
+        assert aln_regs.numel() * aln_regs.element_size() >= n * ALN_REG_DTYPE.itemsize and items.numel() * items.element_size() >= self.n_items_cap * ALN_ITEM_DTYPE.itemsize
+        assert tasks.numel() * tasks.element_size() >= self.n_tasks_cap * KSW_TASK_DTYPE.itemsize and cig_off.dtype == torch.int64 and cig_off.numel() >= self.n_tasks_cap + 1
+        assert pool.element_size() == 1 and pool.numel() >= self.pool_cap and (n_b is None or (n_b.is_cuda and n_b.dtype == torch.int64 and n_b.numel() >= n_reads))
+        o = _aln_opt_bytes(opt)
+        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        N.check(self.lib.mm2c_alnplan_run_device(self.handle, _np_ptr(o), ref.handle, n_reads, n, u_off.data_ptr(), regs.data_ptr(), b_off.data_ptr(),
+                                                 n_b.data_ptr() if n_b is not None else None, b.data_ptr(), read_off.data_ptr(), reads.data_ptr(), aln_regs.data_ptr(),
+                                                 items.data_ptr(), tasks.data_ptr(), cig_off.data_ptr(), pool.data_ptr(), st), "mm2c_alnplan_run_device")
+        return aln_regs, items, tasks, cig_off, pool
+
+    def counts(self):
+        """waits for the last run -> (return code, regions refused, regions too big or beyond a capacity, (items, tasks, CIGAR words, pool bytes) the batch takes)"""
+        a, b, t = C.c_int64(0), C.c_int64(0), (C.c_int64 * 4)()
+        rc = self.lib.mm2c_alnplan_check(self.handle, C.byref(a), C.byref(b), t)
+        return rc, a.value, b.value, tuple(int(x) for x in t)
+
+    def check(self):
+        """waits for the last run; raises (code -2) if a region was refused, (code -3) if one was too big or left a capacity; returns the totals"""
+        rc, _, _, tot = self.counts()
+        N.check(rc, "mm2c_alnplan_check")
+        return tot
+
+    def last_kernel_ms(self):
+        """(aln_plan with aln_scan, aln_emit, aln_gather) of the last run"""
+        ms = (C.c_float * 3)()
+        N.check(self.lib.mm2c_alnplan_last_kernel_ms(self.handle, ms), "mm2c_alnplan_last_kernel_ms")
+        return tuple(float(x) for x in ms)
+
+    def last_ms(self):
+        return sum(self.last_kernel_ms())
+
+    def close(self):
+        if self.handle:
+            self.lib.mm2c_alnplan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def align_tasks_batch(opt, ref_offset, ref_len, S, u_off, regs, b_off, b, read_off, reads, n_items_cap, n_tasks_cap, pool_cap, cig_shift=0, fill=None):
+    """mm2c_align_tasks_batch_host: host arrays in (ref_offset uint64, ref_len uint32, S uint32; u_off, b_off, read_off int64 [n_reads + 1] from 0; regs REG_DTYPE; b uint64
+    [n, 2] anchors; reads uint8 forward codes 0..4) -> dict(aln_regs, items, tasks, cig_off, pool, b, totals, rc): b is a copy with the seed flags, totals what the batch
+    takes, rc the return code (0, or -3 when something was too big: the arrays are complete up to the capacities all the same).  Raises for any other failure.
+    fill: a byte the output arrays are filled with beforehand (tests)."""
+    lib = N.load()
+    off = np.ascontiguousarray(ref_offset, dtype=np.uint64); ln = np.ascontiguousarray(ref_len, dtype=np.uint32); S = np.ascontiguousarray(S, dtype=np.uint32)
+    uo = np.ascontiguousarray(u_off, dtype=np.int64); bo = np.ascontiguousarray(b_off, dtype=np.int64); ro = np.ascontiguousarray(read_off, dtype=np.int64)
+    rg = np.ascontiguousarray(regs, dtype=REG_DTYPE); bb = np.array(b, dtype=np.uint64, order="C", copy=True).reshape(-1, 2); rd = np.ascontiguousarray(reads, dtype=np.uint8)
+    n_reads = uo.size - 1
+    if bo.size != n_reads + 1 or ro.size != n_reads + 1 or off.size != ln.size:
+        raise ValueError("u_off, b_off and read_off must hold n_reads + 1 offsets")
+    n_regs = int(uo[-1]) if n_reads > 0 else 0
+    if rg.size < n_regs or bb.shape[0] < int(bo[-1]) or rd.size < int(ro[-1]):
+        raise ValueError("an array is shorter than its offsets say")
+    f = 0 if fill is None else int(fill)
+    aln_regs = np.full(max(n_regs, 1) * ALN_REG_DTYPE.itemsize, f, np.uint8).view(ALN_REG_DTYPE)
+    items = np.full(max(int(n_items_cap), 1) * ALN_ITEM_DTYPE.itemsize, f, np.uint8).view(ALN_ITEM_DTYPE)
+    tasks = np.full(max(int(n_tasks_cap), 1) * KSW_TASK_DTYPE.itemsize, f, np.uint8).view(KSW_TASK_DTYPE)
+    cig_off = np.full((int(n_tasks_cap) + 1) * 8, f, np.uint8).view(np.int64)
+    pool = np.full(max(int(pool_cap), 1), f, np.uint8)
+    tot = (C.c_int64 * 4)()
+    o = _aln_opt_bytes(opt)
+    rc = lib.mm2c_align_tasks_batch_host(_np_ptr(o), off.size, _np_ptr(off), _np_ptr(ln), _np_ptr(S), S.size, n_reads, _np_ptr(uo), _np_ptr(rg), _np_ptr(bo), _np_ptr(bb), _np_ptr(ro),
+                                         _np_ptr(rd), int(cig_shift), _np_ptr(aln_regs), int(n_items_cap), _np_ptr(items), int(n_tasks_cap), _np_ptr(tasks), _np_ptr(cig_off),
+                                         int(pool_cap), _np_ptr(pool), tot)
+    if rc not in (0, -3):
+        N.check(rc, "mm2c_align_tasks_batch_host")
+    return dict(aln_regs=aln_regs[:n_regs], items=items[:int(n_items_cap)], tasks=tasks[:int(n_tasks_cap)], cig_off=cig_off, pool=pool[:int(pool_cap)], b=bb,
+                totals=tuple(int(x) for x in tot), rc=rc)
+
+
 class MapqPlan:
     """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
     reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the

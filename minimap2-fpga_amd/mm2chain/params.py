@@ -104,5 +104,27 @@ def zdrop_opts(preset="map-ont", max_gap=5000, no_inv=None, **kw):
     return dict(zdrop=s["zdrop"], zdrop_inv=s["zdrop_inv"], max_gap=int(max_gap), no_inv=int(preset == "sr" if no_inv is None else bool(no_inv)))
 
 
+ALN_PRESETS = {   # min_chain_score, max_gap, min_cnt, min_ksw_len, flag (MM2C_ALN_F_SR = 1), idx_flag (MM2C_ALN_I_HPC = 1), k (options.c:24-27, 50 and the presets)
+    "map-ont": (40, 5000, 3, 200, 0, 0, 15), "map-pb": (40, 5000, 3, 200, 0, 1, 19), "asm20": (40, 5000, 3, 200, 0, 0, 19), "sr": (25, 100, 2, 200, 1, 0, 21),
+}
+
+
+def aln_opts(preset="map-ont", **kw):
+    """mm2c_aln_opt_t as mm_align1 reads its options (align.c:565-771): the preset's scores, band and z-drops (ksw_scores), the chaining scalars of options.c, bw_ext =
+    (int)(bw * 1.5 + 1.) of :580 computed here, max_sw_mat 0 (off), the preset's k and index flag.  Keywords override single fields.  Returns a dict of the struct's fields."""
+    s = ksw_scores(preset)
+    a, b = KSW_PRESETS[preset][:2]
+    mcs, max_gap, min_cnt, mkl, flag, idx_flag, k = ALN_PRESETS[preset]
+    v = dict(a=a, b=b, q=s["q"], e=s["e"], e2=s["e2"], bw=s["bw"], bw_ext=0, min_chain_score=mcs, max_gap=max_gap, min_cnt=min_cnt, min_ksw_len=mkl, end_bonus=s["end_bonus"],
+             zdrop=s["zdrop"], zdrop_inv=s["zdrop_inv"], max_sw_mat=0, flag=flag, idx_flag=idx_flag, k=k, reserved=0)
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"aln_opts: unknown field(s) {sorted(unknown)}")
+    v.update(kw)
+    if "bw_ext" not in kw:
+        v["bw_ext"] = int(v["bw"] * 1.5 + 1.)
+    return v
+
+
 def as_dict(p):
     return {k: getattr(p, k) for k, _ in p._fields_}
