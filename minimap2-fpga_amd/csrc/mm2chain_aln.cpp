@@ -1,6 +1,6 @@
 // mm2chain_aln.cpp -- C-ABI entries of the step between final regions and base alignment (include/mm2chain.h): the resident packed reference, the alignment-task
 // plan (mm_align1 up to its mm_align_pair calls on the device, align_tasks.hip) and the host-buffer entry built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "align_tasks.h"
 #include <cstddef>
 
@@ -22,16 +22,12 @@ struct mm2c_refseq {
 	uint32_t *d_len = nullptr, *d_S = nullptr;
 };
 
-struct mm2c_alnplan {
+struct mm2c_alnplan : PlanBase {           // d_mem: [flags, totals | scratch]; events: begin, behind aln_scan, behind aln_emit, behind aln_gather
 	int64_t n_regs_cap = 0, items_cap = 0, tasks_cap = 0, pool_cap = 0, b_cap = 0, reads_cap = 0, slot_words = 0;
 	int32_t n_slots = 0, cig_shift = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags, totals | scratch]
 	int32_t *d_flags = nullptr;
 	int64_t *d_totals = nullptr;
 	int32_t *d_scratch = nullptr;
-	hipEvent_t ev[4] = {};                 // begin, behind aln_scan, behind aln_emit, behind aln_gather
-	bool ran = false;
 };
 
 static int check_refseq(int64_t n_seq, const uint64_t *offset, const uint32_t *len, const uint32_t *S, int64_t n_words)
@@ -108,11 +104,7 @@ mm2c_alnplan_t *mm2c_alnplan_create(int64_t n_regs_cap, int64_t n_items_cap, int
 	pl->cig_shift = cig_shift; pl->n_slots = (int32_t)n_slots; pl->slot_words = slot_words;
 	Layout L;
 	const size_t o_fl = L.take(64), o_sc = L.take((size_t)slot_words * 4 * (size_t)n_slots + 256);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	const hipError_t e = pl->open(L.at, 4);
 	if (e != hipSuccess) {
 		(void)fail(MM2C_E_HIP, "mm2c_alnplan_create: %s (%lld slots of %lld words)", hipGetErrorString(e), (long long)n_slots, (long long)slot_words);
 		mm2c_alnplan_destroy(pl);
@@ -125,12 +117,7 @@ mm2c_alnplan_t *mm2c_alnplan_create(int64_t n_regs_cap, int64_t n_items_cap, int
 void mm2c_alnplan_destroy(mm2c_alnplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -151,9 +138,8 @@ int mm2c_alnplan_run_device(mm2c_alnplan_t *pl, const mm2c_aln_opt_t *opt, const
 	if (((uintptr_t)d_b | (uintptr_t)d_pool) & 15) return fail(MM2C_E_ARG, "anchors or pool are not 16-byte aligned");
 	if ((uintptr_t)d_items & 3) return fail(MM2C_E_ARG, "items are not 4-byte aligned");
 	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
 	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
+	if (const int rc = pl->begin(on, stream, &st, pl->d_flags, 64)) return rc;
 	mm2c::AlnArgs X = {};
 	X.n_reads = n_reads; X.n_regs = n_regs; X.items_cap = pl->items_cap; X.tasks_cap = pl->tasks_cap; X.pool_cap = pl->pool_cap; X.b_cap = pl->b_cap; X.reads_cap = pl->reads_cap;
 	memcpy(&X.opt, opt, sizeof X.opt);
@@ -161,7 +147,6 @@ int mm2c_alnplan_run_device(mm2c_alnplan_t *pl, const mm2c_aln_opt_t *opt, const
 	X.reads = d_reads; X.n_seq = ref->n_seq; X.n_words = ref->n_words; X.ref_off = ref->d_off; X.ref_len = ref->d_len; X.S = ref->d_S;
 	X.aregs = (mm2c::AlnReg *)d_aln_regs; X.items = (mm2c::AlnItem *)d_items; X.tasks = (mm2c::KswTask *)d_tasks; X.cig_off = d_cig_off; X.pool = d_pool;
 	X.scratch = pl->d_scratch; X.slot_words = pl->slot_words; X.n_slots = pl->n_slots; X.flags = pl->d_flags; X.totals = pl->d_totals;
-	HIP_TRY(hipMemsetAsync(pl->d_flags, 0, 64, st));
 	if (n_regs == 0 && d_cig_off) HIP_TRY(hipMemsetAsync(d_cig_off, 0, 8, st));            // no kernel runs: the list of 0 tasks still ends at cig_off[0] = 0
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mm2c::launch_aln_plan(X, st));
@@ -170,9 +155,7 @@ int mm2c_alnplan_run_device(mm2c_alnplan_t *pl, const mm2c_aln_opt_t *opt, const
 	HIP_TRY(hipEventRecord(pl->ev[2], st));
 	HIP_TRY(mm2c::launch_aln_gather(X, st));
 	HIP_TRY(hipEventRecord(pl->ev[3], st));
-	pl->ran = true;
-	G.launches += n_regs > 0 ? 4 : 0;
-	return 0;
+	return pl->end(n_regs > 0 ? 4 : 0);
 }
 
 int mm2c_alnplan_check(mm2c_alnplan_t *pl, int64_t *n_refused, int64_t *n_too_big, int64_t totals[4])
@@ -182,11 +165,8 @@ int mm2c_alnplan_check(mm2c_alnplan_t *pl, int64_t *n_refused, int64_t *n_too_bi
 	if (n_too_big) *n_too_big = 0;
 	if (totals) totals[0] = totals[1] = totals[2] = totals[3] = 0;
 	if (!pl->ran) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[3]));
 	int64_t w[6] = {};
-	HIP_TRY(hipMemcpy(w, pl->d_flags, sizeof w, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(3, pl->d_flags, w, sizeof w)) return rc;
 	int32_t fl[4];
 	memcpy(fl, w, sizeof fl);
 	if (n_refused) *n_refused = fl[0];
@@ -204,11 +184,7 @@ int mm2c_alnplan_last_kernel_ms(mm2c_alnplan_t *pl, float ms[3])
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[3]));
-	for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(ms + k, pl->ev[k], pl->ev[k + 1]));
-	return 0;
+	return pl->elapsed(3, {{0, 1, ms}, {1, 2, ms + 1}, {2, 3, ms + 2}});
 }
 
 int mm2c_align_tasks_batch_host(const mm2c_aln_opt_t *opt, int64_t n_seq, const uint64_t *offset, const uint32_t *len, const uint32_t *S, int64_t n_words,
@@ -245,44 +221,19 @@ int mm2c_align_tasks_batch_host(const mm2c_aln_opt_t *opt, int64_t n_seq, const 
 	const int64_t slots = slot_words ? std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_regs, 2048), (1ll << 30) / (slot_words * 4))) : 0;
 	mm2c_alnplan_t *pl = mm2c_alnplan_create(n_regs, n_items_cap, n_tasks_cap, pool_cap, n_b, n_bases, cig_shift, slots, slot_words);
 	if (!pl) { mm2c_refseq_destroy(rf); return MM2C_E_HIP; }
-	char *d = nullptr;
-	Layout L;
-	const size_t nr = (size_t)n_reads, ng = (size_t)n_regs;
-	const size_t o_u = L.take((nr + 1) * 8), o_g = L.take(ng * sizeof(mm2c_reg_t)), o_bo = L.take((nr + 1) * 8), o_b = L.take((size_t)n_b * 16 + 16), o_ro = L.take((nr + 1) * 8),
-	             o_rd = L.take((size_t)n_bases + 16), o_ar = L.take(ng * sizeof(mm2c_aln_reg_t)), o_it = L.take((size_t)n_items_cap * sizeof(mm2c_aln_item_t) + 16),
-	             o_tk = L.take((size_t)n_tasks_cap * sizeof(mm2c_ksw_task_t) + 16), o_co = L.take(((size_t)n_tasks_cap + 1) * 8), o_p = L.take((size_t)pool_cap + 16);
-	int rc_check = 0;
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_u, u_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_g, regs, ng * sizeof(mm2c_reg_t), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_bo, b_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(d + o_b, b, (size_t)n_b * 16, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_ro, read_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
-		if (n_bases > 0) HIP_TRY(hipMemcpyAsync(d + o_rd, reads, (size_t)n_bases, hipMemcpyHostToDevice, st));
-		// what is not written stays the caller's
-		if (n_items_cap > 0) HIP_TRY(hipMemcpyAsync(d + o_it, items, (size_t)n_items_cap * sizeof(mm2c_aln_item_t), hipMemcpyHostToDevice, st));
-		if (n_tasks_cap > 0) HIP_TRY(hipMemcpyAsync(d + o_tk, tasks, (size_t)n_tasks_cap * sizeof(mm2c_ksw_task_t), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_co, cig_off, ((size_t)n_tasks_cap + 1) * 8, hipMemcpyHostToDevice, st));
-		if (pool_cap > 0) HIP_TRY(hipMemcpyAsync(d + o_p, pool, (size_t)pool_cap, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_alnplan_run_device(pl, opt, rf, n_reads, n_regs, (const int64_t *)(d + o_u), (const mm2c_reg_t *)(d + o_g), (const int64_t *)(d + o_bo), nullptr, d + o_b,
-		                                          (const int64_t *)(d + o_ro), (const uint8_t *)(d + o_rd), (mm2c_aln_reg_t *)(d + o_ar), (mm2c_aln_item_t *)(d + o_it),
-		                                          (mm2c_ksw_task_t *)(d + o_tk), (int64_t *)(d + o_co), (uint8_t *)(d + o_p), MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(aln_regs, d + o_ar, ng * sizeof(mm2c_aln_reg_t), hipMemcpyDeviceToHost, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(b, d + o_b, (size_t)n_b * 16, hipMemcpyDeviceToHost, st));
-		if (n_items_cap > 0) HIP_TRY(hipMemcpyAsync(items, d + o_it, (size_t)n_items_cap * sizeof(mm2c_aln_item_t), hipMemcpyDeviceToHost, st));
-		if (n_tasks_cap > 0) HIP_TRY(hipMemcpyAsync(tasks, d + o_tk, (size_t)n_tasks_cap * sizeof(mm2c_ksw_task_t), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(cig_off, d + o_co, ((size_t)n_tasks_cap + 1) * 8, hipMemcpyDeviceToHost, st));
-		if (pool_cap > 0) HIP_TRY(hipMemcpyAsync(pool, d + o_p, (size_t)pool_cap, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		rc_check = mm2c_alnplan_check(pl, nullptr, nullptr, totals);
-		return rc_check;
-	};
-	const int rc = body();
-	dev_free(d);
+	Staging stage;
+	const size_t nr = (size_t)n_reads, ng = (size_t)n_regs, nt = (size_t)n_tasks_cap;
+	// items, tasks, cig_off and pool go up as well: what is not written stays the caller's
+	const int i_u = stage.add(u_off, nullptr, (nr + 1) * 8), i_g = stage.add(regs, nullptr, ng * sizeof(mm2c_reg_t)), i_bo = stage.add(b_off, nullptr, (nr + 1) * 8),
+	          i_b = stage.add(b, b, (size_t)n_b * 16, 16), i_ro = stage.add(read_off, nullptr, (nr + 1) * 8), i_rd = stage.add(reads, nullptr, (size_t)n_bases, 16),
+	          i_ar = stage.add(nullptr, aln_regs, ng * sizeof(mm2c_aln_reg_t)), i_it = stage.add(items, items, (size_t)n_items_cap * sizeof(mm2c_aln_item_t), 16),
+	          i_tk = stage.add(tasks, tasks, nt * sizeof(mm2c_ksw_task_t), 16), i_co = stage.add(cig_off, cig_off, (nt + 1) * 8), i_p = stage.add(pool, pool, (size_t)pool_cap, 16);
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_alnplan_run_device(pl, opt, rf, n_reads, n_regs, stage.at<int64_t>(i_u), stage.at<mm2c_reg_t>(i_g), stage.at<int64_t>(i_bo), nullptr, stage.at<char>(i_b), stage.at<int64_t>(i_ro),
+		                               stage.at<uint8_t>(i_rd), stage.at<mm2c_aln_reg_t>(i_ar), stage.at<mm2c_aln_item_t>(i_it), stage.at<mm2c_ksw_task_t>(i_tk), stage.at<int64_t>(i_co), stage.at<uint8_t>(i_p),
+		                               MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_alnplan_check(pl, nullptr, nullptr, totals); });
+	stage.release();
 	mm2c_alnplan_destroy(pl);
 	mm2c_refseq_destroy(rf);
 	return rc;

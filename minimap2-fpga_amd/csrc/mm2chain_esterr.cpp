@@ -1,6 +1,6 @@
 // mm2chain_esterr.cpp -- C-ABI entries of the chain-anchor divergence step (include/mm2chain.h): est-err plans (the counts of mm_est_err on the device,
 // chain_esterr.hip), the one line of esterr.c:62 with the host's own pow, and the host-buffer entry built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "chain_esterr.h"
 #include "chain_regs.h"
 #include <cmath>
@@ -11,13 +11,9 @@ using namespace mm2c_api;
 static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_err_t) == 8 && offsetof(mm2c_err_t, n_tot) == 4 && sizeof(mm2c_anchor_t) == 16, "layout");
 static_assert(offsetof(mm2c_reg_t, div) == 68, "layout");
 
-struct mm2c_errplan {
+struct mm2c_errplan : PlanBase {           // d_mem: [flags | tab | first_fail | state]; events: in front of err_reads, behind it, behind err_walk, behind err_finish
 	int64_t n_reads = 0, n_u_cap = 0, n_b_cap = 0, n_mini_cap = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags | tab | first_fail | state]
 	mm2c::ErrArgs E;
-	hipEvent_t ev[4] = {};                 // in front of err_reads, behind it, behind err_walk, behind err_finish
-	bool ran = false;
 };
 
 extern "C" {
@@ -57,11 +53,7 @@ mm2c_errplan_t *mm2c_errplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_
 	const size_t nu = (size_t)std::max<int64_t>(n_u_cap, 1), nr = (size_t)std::max<int64_t>(n_reads, 1);
 	Layout L;
 	const size_t o_fl = L.take(16), o_tab = L.take(nu * 16), o_ff = L.take(nu * 4), o_st = L.take(nr * 4);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	const hipError_t e = pl->open(L.at, 4);
 	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_errplan_create: %s", hipGetErrorString(e)); mm2c_errplan_destroy(pl); return nullptr; }
 	mm2c::ErrArgs &E = pl->E;
 	char *b = pl->d_mem;
@@ -73,12 +65,7 @@ mm2c_errplan_t *mm2c_errplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_
 void mm2c_errplan_destroy(mm2c_errplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -95,14 +82,12 @@ int mm2c_errplan_run_device(mm2c_errplan_t *pl, const int64_t *d_u_off, const mm
 		return fail(MM2C_E_ARG, "device pointer is NULL");
 	if (((uintptr_t)d_regs | (uintptr_t)d_err | (uintptr_t)d_mini_pos) & 7) return fail(MM2C_E_ARG, "regions, counts or mini_pos are not 8-byte aligned");
 	if ((uintptr_t)d_b & 15) return fail(MM2C_E_ARG, "anchors are not 16-byte aligned");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::ErrArgs &E = pl->E;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, E.flags, 16)) return rc;
 	E.n_ref = n_ref; E.u_off = d_u_off; E.regs = (const uint64_t *)d_regs; E.n_in = d_n_in; E.b_off = d_b_off; E.b = (const uint4 *)d_b;
 	E.mini_off = d_mini_off; E.mini_pos = d_mini_pos; E.qlen = d_qlen; E.ref_len = d_ref_len; E.err = (int2 *)d_err; E.avg_k = d_avg_k;
-	HIP_TRY(hipMemsetAsync(E.flags, 0, 16, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mm2c::launch_err_reads(E, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
@@ -110,9 +95,7 @@ int mm2c_errplan_run_device(mm2c_errplan_t *pl, const int64_t *d_u_off, const mm
 	HIP_TRY(hipEventRecord(pl->ev[2], st));
 	HIP_TRY(mm2c::launch_err_finish(E, st));
 	HIP_TRY(hipEventRecord(pl->ev[3], st));
-	pl->ran = true;
-	G.launches += 3;
-	return 0;
+	return pl->end(3);
 }
 
 int mm2c_errplan_check(mm2c_errplan_t *pl, int64_t *n_refused)
@@ -120,11 +103,8 @@ int mm2c_errplan_check(mm2c_errplan_t *pl, int64_t *n_refused)
 	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
 	if (n_refused) *n_refused = 0;
 	if (!pl->ran || pl->n_reads == 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[3]));
 	int32_t fl[4] = {0, 0, 0, 0};
-	HIP_TRY(hipMemcpy(fl, pl->E.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(3, pl->E.flags, fl, sizeof fl)) return rc;
 	if (n_refused) *n_refused = fl[0];
 	if (fl[0] != 0) return fail(MM2C_E_ARG, "%d read(s): offsets beyond the plan's capacities or each other, mini_pos not strictly increasing, or a region "
 	                                        "beyond the read's anchors or the reference sequences", fl[0]);
@@ -135,24 +115,14 @@ int mm2c_errplan_last_ms(mm2c_errplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[3]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[3]));
-	return 0;
+	return pl->elapsed(3, {{0, 3, ms}});
 }
 
 int mm2c_errplan_last_kernel_ms(mm2c_errplan_t *pl, float *reads_ms, float *walk_ms, float *finish_ms)
 {
 	if (!pl || !reads_ms || !walk_ms || !finish_ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[3]));
-	HIP_TRY(hipEventElapsedTime(reads_ms, pl->ev[0], pl->ev[1]));
-	HIP_TRY(hipEventElapsedTime(walk_ms, pl->ev[1], pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(finish_ms, pl->ev[2], pl->ev[3]));
-	return 0;
+	return pl->elapsed(3, {{0, 1, reads_ms}, {1, 2, walk_ms}, {2, 3, finish_ms}});
 }
 
 int mm2c_est_err_batch_host(int64_t n_reads, const int64_t *u_off, mm2c_reg_t *regs, const int32_t *n_in, const int64_t *b_off, const mm2c_anchor_t *b,
@@ -181,33 +151,16 @@ int mm2c_est_err_batch_host(int64_t n_reads, const int64_t *u_off, mm2c_reg_t *r
 	mm2c_errplan_t *pl = mm2c_errplan_create(n_reads, n_u, n_b, n_m);
 	if (!pl) return MM2C_E_HIP;
 	const size_t rb = (size_t)n_u * sizeof(mm2c_reg_t), ab = (size_t)n_b * 16, mbytes = (size_t)n_m * 8, fb = (size_t)n_ref * 4;
-	char *d = nullptr;
-	Layout L;
-	const size_t o_off = L.take(off.size() * 8), o_in = L.take(rb + 8), o_ni = L.take(nr * 4), o_q = L.take(nr * 4), o_b = L.take(ab + 16), o_m = L.take(mbytes + 8),
-	             o_ref = L.take(fb + 4), o_err = L.take((size_t)n_u * 8 + 8), o_avg = L.take(nr * 4);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs + ub, rb, hipMemcpyHostToDevice, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(d + o_b, b + bb, ab, hipMemcpyHostToDevice, st));
-		if (n_m > 0) HIP_TRY(hipMemcpyAsync(d + o_m, mini_pos + mb, mbytes, hipMemcpyHostToDevice, st));
-		if (n_ref > 0) HIP_TRY(hipMemcpyAsync(d + o_ref, ref_len, fb, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_ni, n_in, nr * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
-		const int64_t *d_off = (const int64_t *)(d + o_off);
-		if (const int r = mm2c_errplan_run_device(pl, d_off, (const mm2c_reg_t *)(d + o_in), (const int32_t *)(d + o_ni), d_off + nr + 1, d + o_b, d_off + 2 * (nr + 1),
-		                                          (const uint64_t *)(d + o_m), (const int32_t *)(d + o_q), n_ref, (const uint32_t *)(d + o_ref),
-		                                          (mm2c_err_t *)(d + o_err), (float *)(d + o_avg), MM2C_STREAM_LIBRARY)) return r;
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(h_err.data(), d + o_err, (size_t)n_u * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(h_avg.data(), d + o_avg, nr * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_errplan_check(pl, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	Staging stage;
+	const int i_off = stage.add(off.data(), nullptr, off.size() * 8), i_in = stage.add(n_u > 0 ? regs + ub : nullptr, nullptr, rb, 8), i_ni = stage.add(n_in, nullptr, nr * 4),
+	          i_q = stage.add(qlen, nullptr, nr * 4), i_b = stage.add(n_b > 0 ? b + bb : nullptr, nullptr, ab, 16), i_m = stage.add(n_m > 0 ? mini_pos + mb : nullptr, nullptr, mbytes, 8),
+	          i_ref = stage.add(ref_len, nullptr, fb, 4), i_err = stage.add(nullptr, h_err.data(), (size_t)n_u * 8, 8), i_avg = stage.add(nullptr, h_avg.data(), nr * 4);
+	const int rc = stage.through(pl->device, [&] {
+		const int64_t *d_off = stage.at<int64_t>(i_off);
+		return mm2c_errplan_run_device(pl, d_off, stage.at<mm2c_reg_t>(i_in), stage.at<int32_t>(i_ni), d_off + nr + 1, stage.at<char>(i_b), d_off + 2 * (nr + 1), stage.at<uint64_t>(i_m),
+		                               stage.at<int32_t>(i_q), n_ref, stage.at<uint32_t>(i_ref), stage.at<mm2c_err_t>(i_err), stage.at<float>(i_avg), MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_errplan_check(pl, nullptr); });
+	stage.release();
 	mm2c_errplan_destroy(pl);
 	if (rc) return rc;
 	if (err && n_u > 0) memcpy(err, h_err.data(), (size_t)n_u * 8);

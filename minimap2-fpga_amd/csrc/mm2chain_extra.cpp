@@ -1,6 +1,6 @@
 // mm2chain_extra.cpp -- C-ABI entries of the two CIGAR walks around the base alignment (include/mm2chain.h): extra plans (mm_update_extra and mm_test_zdrop on the
 // device, align_extra.hip) and the host-buffer entries built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "align_extra.h"
 #include <cstddef>
 
@@ -13,15 +13,12 @@ static_assert(sizeof(mm2c_zdrop_res_t) == sizeof(mm2c::ZdropRes) && sizeof(mm2c_
 static_assert(MM2C_EXTRA_LDS_WORDS == mm2c::EXTRA_LDS_WORDS && MM2C_EXTRA_RUN_LANE == mm2c::EXTRA_RUN_LANE && MM2C_EXTRA_MAX_SLOTS == mm2c::EXTRA_MAX_SLOTS &&
               MM2C_EXTRA_REFUSED == mm2c::EXTRA_REFUSED && MM2C_EXTRA_TOO_BIG == mm2c::EXTRA_TOO_BIG && MM2C_EXTRA_CIGAR_CUT == mm2c::EXTRA_CIGAR_CUT, "constants of mm2chain.h");
 
-struct mm2c_extraplan {
+struct mm2c_extraplan : PlanBase {         // d_mem: [flags | scratch]; events: begin and end of the last update run (0, 1), of the last z-drop run (2, 3)
 	int64_t n_cap = 0, seq_cap = 0, cig_in_cap = 0, cig_out_cap = 0, slot_words = 0;
 	int32_t n_slots = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags | scratch]
 	int32_t *d_flags = nullptr;
 	uint32_t *d_scratch = nullptr;
-	hipEvent_t ev[2][2] = {};              // begin and end of the last update run, of the last z-drop run
-	bool ran[2] = {false, false};
+	bool did[2] = {false, false};          // update, z-drop: which of the two has run; `ran` is either
 	int last = -1;                         // 0: update, 1: z-drop
 };
 
@@ -52,11 +49,7 @@ static int extraplan_make(int64_t n_cap, int64_t seq_cap, int64_t cig_in_cap, in
 	pl->n_slots = (int32_t)n_slots; pl->slot_words = slot_words;
 	Layout L;
 	const size_t o_fl = L.take(16), o_sc = L.take((size_t)slot_words * 16 * (size_t)n_slots + 256);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i >> 1][i & 1]);
+	const hipError_t e = pl->open(L.at, 4);
 	if (e != hipSuccess) {
 		const int rc = fail(MM2C_E_HIP, "mm2c_extraplan_create: %s (%lld slots of %lld words)", hipGetErrorString(e), (long long)n_slots, (long long)slot_words);
 		mm2c_extraplan_destroy(pl);
@@ -70,17 +63,14 @@ static int extraplan_make(int64_t n_cap, int64_t seq_cap, int64_t cig_in_cap, in
 static int extra_launch(mm2c_extraplan *pl, mm2c::ExtraArgs &X, int which, void *stream)
 {
 	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
 	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
+	if (const int rc = pl->begin(on, stream, &st, pl->d_flags, 16)) return rc;
 	X.seq_cap = pl->seq_cap; X.scratch = pl->d_scratch; X.slot_words = pl->slot_words; X.n_slots = pl->n_slots; X.flags = pl->d_flags;
-	HIP_TRY(hipMemsetAsync(pl->d_flags, 0, 16, st));
-	HIP_TRY(hipEventRecord(pl->ev[which][0], st));
+	HIP_TRY(hipEventRecord(pl->ev[2 * which], st));
 	HIP_TRY(which == 0 ? mm2c::launch_extra_update(X, st) : mm2c::launch_extra_zdrop(X, st));
-	HIP_TRY(hipEventRecord(pl->ev[which][1], st));
-	pl->ran[which] = true; pl->last = which;
-	G.launches += X.n > 0;
-	return 0;
+	HIP_TRY(hipEventRecord(pl->ev[2 * which + 1], st));
+	pl->did[which] = true; pl->last = which;
+	return pl->end(X.n > 0);
 }
 
 extern "C" {
@@ -95,12 +85,7 @@ mm2c_extraplan_t *mm2c_extraplan_create(int64_t n_cap, int64_t seq_cap, int64_t 
 void mm2c_extraplan_destroy(mm2c_extraplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->last >= 0) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &p : pl->ev) for (auto &e : p) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -146,11 +131,8 @@ int mm2c_extraplan_check(mm2c_extraplan_t *pl, int64_t *n_refused, int64_t *n_to
 	if (n_refused) *n_refused = 0;
 	if (n_too_big) *n_too_big = 0;
 	if (pl->last < 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[pl->last][1]));
 	int32_t fl[4] = {};
-	HIP_TRY(hipMemcpy(fl, pl->d_flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(2 * pl->last + 1, pl->d_flags, fl, sizeof fl)) return rc;
 	if (n_refused) *n_refused = fl[0];
 	if (n_too_big) *n_too_big = (int64_t)fl[1] + fl[2];
 	if (fl[0] != 0) return fail(MM2C_E_ARG, "%d item(s) refused: a CIGAR the reference is not defined on (an op above 3, an empty N, only empty words, lengths that do not add up to the "
@@ -164,15 +146,12 @@ int mm2c_extraplan_last_kernel_ms(mm2c_extraplan_t *pl, float *update_ms, float 
 {
 	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
 	if (pl->last < 0) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
 	float *const out[2] = {update_ms, zdrop_ms};
 	for (int w = 0; w < 2; ++w) {
 		if (!out[w]) continue;
 		*out[w] = 0.f;
-		if (!pl->ran[w]) continue;
-		HIP_TRY(hipEventSynchronize(pl->ev[w][1]));
-		HIP_TRY(hipEventElapsedTime(out[w], pl->ev[w][0], pl->ev[w][1]));
+		if (!pl->did[w]) continue;
+		if (const int rc = pl->elapsed(2 * w + 1, {{2 * w, 2 * w + 1, out[w]}})) return rc;
 	}
 	return 0;
 }
@@ -214,32 +193,17 @@ int mm2c_update_extra_batch_host(const mm2c_ksw_score_t *sc, int is_eqx, int64_t
 	const int64_t slots = slot_words ? std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_regs, 2048), (1ll << 30) / (slot_words * 16))) : 0;
 	mm2c_extraplan_t *pl = nullptr;
 	if (const int rc = extraplan_make(n_regs, seq_len, n_cig_in, n_out, slots, slot_words, &pl)) return rc;
-	char *d = nullptr;
-	Layout L;
+	Staging stage;
 	const size_t nr = (size_t)n_regs;
-	const size_t o_t = L.take(nr * sizeof(mm2c_extra_task_t)), o_s = L.take((size_t)seq_len + 16), o_io = L.take(nr * 8), o_oo = L.take((nr + 1) * 8), o_r = L.take(nr * sizeof(mm2c_extra_res_t)),
-	             o_ci = L.take((size_t)n_cig_in * 4 + 16), o_co = L.take((size_t)n_out * 4 + 16);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_t, tasks, nr * sizeof(mm2c_extra_task_t), hipMemcpyHostToDevice, st));
-		if (seq_len > 0) HIP_TRY(hipMemcpyAsync(d + o_s, seq, (size_t)seq_len, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_io, in_off, nr * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_oo, out_off, (nr + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_r, res, nr * sizeof(mm2c_extra_res_t), hipMemcpyHostToDevice, st));   // what a region that is not run leaves is the caller's
-		if (n_cig_in > 0) HIP_TRY(hipMemcpyAsync(d + o_ci, cig_in, (size_t)n_cig_in * 4, hipMemcpyHostToDevice, st));
-		if (n_out > 0) HIP_TRY(hipMemcpyAsync(d + o_co, cig_out, (size_t)n_out * 4, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_extraplan_run_device(pl, sc, is_eqx, n_regs, (const mm2c_extra_task_t *)(d + o_t), (const uint8_t *)(d + o_s), (const int64_t *)(d + o_io),
-		                                            (const uint32_t *)(d + o_ci), (const int64_t *)(d + o_oo), (mm2c_extra_res_t *)(d + o_r), (uint32_t *)(d + o_co), MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(res, d + o_r, nr * sizeof(mm2c_extra_res_t), hipMemcpyDeviceToHost, st));
-		if (n_out > 0) HIP_TRY(hipMemcpyAsync(cig_out, d + o_co, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_extraplan_check(pl, nullptr, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	// res and cig_out go up as well: what a region that is not run leaves is the caller's
+	const int i_t = stage.add(tasks, nullptr, nr * sizeof(mm2c_extra_task_t)), i_s = stage.add(seq, nullptr, (size_t)seq_len, 16), i_io = stage.add(in_off, nullptr, nr * 8),
+	          i_oo = stage.add(out_off, nullptr, (nr + 1) * 8), i_r = stage.add(res, res, nr * sizeof(mm2c_extra_res_t)), i_ci = stage.add(cig_in, nullptr, (size_t)n_cig_in * 4, 16),
+	          i_co = stage.add(cig_out, cig_out, (size_t)n_out * 4, 16);
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_extraplan_run_device(pl, sc, is_eqx, n_regs, stage.at<mm2c_extra_task_t>(i_t), stage.at<uint8_t>(i_s), stage.at<int64_t>(i_io), stage.at<uint32_t>(i_ci), stage.at<int64_t>(i_oo),
+		                                 stage.at<mm2c_extra_res_t>(i_r), stage.at<uint32_t>(i_co), MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_extraplan_check(pl, nullptr, nullptr); });
+	stage.release();
 	mm2c_extraplan_destroy(pl);
 	return rc;
 }
@@ -267,30 +231,15 @@ int mm2c_test_zdrop_batch_host(const mm2c_ksw_score_t *sc, const mm2c_zdrop_opt_
 	const int64_t slots = slot_words ? std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_tasks, 2048), (1ll << 30) / (slot_words * 16))) : 0;
 	mm2c_extraplan_t *pl = nullptr;
 	if (const int rc = extraplan_make(n_tasks, seq_len, n_cig, 0, slots, slot_words, &pl)) return rc;
-	char *d = nullptr;
-	Layout L;
+	Staging stage;
 	const size_t nt = (size_t)n_tasks;
-	const size_t o_t = L.take(nt * sizeof(mm2c_ksw_task_t)), o_s = L.take((size_t)seq_len + 16), o_co = L.take((nt + 1) * 8), o_r = L.take(nt * sizeof(mm2c_ksw_res_t)),
-	             o_c = L.take((size_t)n_cig * 4 + 16), o_z = L.take(nt * sizeof(mm2c_zdrop_res_t));
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_t, tasks, nt * sizeof(mm2c_ksw_task_t), hipMemcpyHostToDevice, st));
-		if (seq_len > 0) HIP_TRY(hipMemcpyAsync(d + o_s, seq, (size_t)seq_len, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_co, cig_off, (nt + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_r, kres, nt * sizeof(mm2c_ksw_res_t), hipMemcpyHostToDevice, st));
-		if (n_cig > 0) HIP_TRY(hipMemcpyAsync(d + o_c, cigar, (size_t)n_cig * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_z, zres, nt * sizeof(mm2c_zdrop_res_t), hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_extraplan_zdrop_run_device(pl, sc, opt, n_tasks, (const mm2c_ksw_task_t *)(d + o_t), (const uint8_t *)(d + o_s), (const int64_t *)(d + o_co),
-		                                                  (const mm2c_ksw_res_t *)(d + o_r), (const uint32_t *)(d + o_c), (mm2c_zdrop_res_t *)(d + o_z), MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(zres, d + o_z, nt * sizeof(mm2c_zdrop_res_t), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_extraplan_check(pl, nullptr, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	const int i_t = stage.add(tasks, nullptr, nt * sizeof(mm2c_ksw_task_t)), i_s = stage.add(seq, nullptr, (size_t)seq_len, 16), i_co = stage.add(cig_off, nullptr, (nt + 1) * 8),
+	          i_r = stage.add(kres, nullptr, nt * sizeof(mm2c_ksw_res_t)), i_c = stage.add(cigar, nullptr, (size_t)n_cig * 4, 16), i_z = stage.add(zres, zres, nt * sizeof(mm2c_zdrop_res_t));
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_extraplan_zdrop_run_device(pl, sc, opt, n_tasks, stage.at<mm2c_ksw_task_t>(i_t), stage.at<uint8_t>(i_s), stage.at<int64_t>(i_co), stage.at<mm2c_ksw_res_t>(i_r), stage.at<uint32_t>(i_c),
+		                                       stage.at<mm2c_zdrop_res_t>(i_z), MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_extraplan_check(pl, nullptr, nullptr); });
+	stage.release();
 	mm2c_extraplan_destroy(pl);
 	return rc;
 }

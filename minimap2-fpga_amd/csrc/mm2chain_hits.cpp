@@ -1,6 +1,6 @@
 // mm2chain_hits.cpp -- C-ABI entries of the regions-to-hits step (include/mm2chain.h): hit plans (mm_set_parent + mm_select_sub, or mm_select_sub_multi for
 // fragments of several segments, on the device, chain_hits.hip) and the host-buffer entries built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "chain_hits.h"
 #include "chain_regs.h"
 
@@ -9,13 +9,9 @@ using namespace mm2c_api;
 static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_hit_opt_t) == 24 && sizeof(mm2c_hit_multi_opt_t) == 16, "layout");
 static_assert(MM2C_HIT_LDS_REGIONS == mm2c::HITS_LDS_MAX && MM2C_REG_SAM_PRI_BIT == 12, "constants of mm2chain.h");
 
-struct mm2c_hitplan {
+struct mm2c_hitplan : PlanBase {           // d_mem: [flags, total | tab | pq | cov]; events: begin, end
 	int64_t n_reads = 0, n_u_cap = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags, total | tab | pq | cov]
 	mm2c::HitArgs H;
-	hipEvent_t ev[2] = {};
-	bool ran = false;
 };
 
 extern "C" {
@@ -29,11 +25,7 @@ mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap)
 	const size_t nu = (size_t)std::max<int64_t>(n_u_cap, 1), row = (size_t)(n_u_cap + n_reads) + 1;
 	Layout L;
 	const size_t o_fl = L.take(16), o_tab = L.take(row * 4 * (mm2c::HITS_TAB_ROWS + 1)), o_pq = L.take(nu * 8), o_cov = L.take(nu * 8);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	const hipError_t e = pl->open(L.at, 2);
 	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_hitplan_create: %s", hipGetErrorString(e)); mm2c_hitplan_destroy(pl); return nullptr; }
 	mm2c::HitArgs &H = pl->H;
 	char *b = pl->d_mem;
@@ -46,12 +38,7 @@ mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap)
 void mm2c_hitplan_destroy(mm2c_hitplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -65,23 +52,19 @@ static int hitplan_run(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const mm2c
 	if (!d_u_off || !d_n_out || (pl->n_u_cap > 0 && (!d_regs_in || !d_regs_out))) return fail(MM2C_E_ARG, "device pointer is NULL");
 	if (((uintptr_t)d_regs_in | (uintptr_t)d_regs_out) & 7) return fail(MM2C_E_ARG, "regions are not 8-byte aligned");
 	if (pl->n_u_cap > 0 && (const mm2c_reg_t *)d_regs_out == d_regs_in) return fail(MM2C_E_ARG, "d_regs_out must not alias d_regs_in");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::HitArgs &H = pl->H;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, H.flags, 16)) return rc;
 	H.mask_level = opt->mask_level; H.mask_len = opt->mask_len; H.hard_mask_level = opt->hard_mask_level;
 	H.pri_ratio = opt->pri_ratio; H.min_diff = opt->min_diff; H.best_n = opt->best_n;
 	H.pri1 = mopt ? mopt->pri1 : 0.0f; H.pri2 = mopt ? mopt->pri2 : 0.0f; H.n_segs = mopt ? mopt->n_segs : 1; H.max_gap_ref = mopt ? mopt->max_gap_ref : 0;
 	H.seg_len = d_seg_len; H.gap_ref = d_gap_ref;
 	H.u_off = d_u_off; H.in = (const uint64_t *)d_regs_in; H.out = (uint64_t *)d_regs_out; H.n_out = d_n_out;
-	HIP_TRY(hipMemsetAsync(H.flags, 0, 16, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mopt ? mm2c::launch_chain_hits_multi(H, st) : mm2c::launch_chain_hits(H, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
-	pl->ran = true;
-	G.launches += 1;
-	return 0;
+	return pl->end(1);
 }
 
 int mm2c_hitplan_run_device(mm2c_hitplan_t *pl, const mm2c_hit_opt_t *opt, const int64_t *d_u_off, const mm2c_reg_t *d_regs_in,
@@ -104,11 +87,8 @@ int mm2c_hitplan_check(mm2c_hitplan_t *pl, int64_t *n_hits_total)
 	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
 	if (n_hits_total) *n_hits_total = 0;
 	if (!pl->ran || pl->n_reads == 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[1]));
 	int64_t fl[2] = {0, 0};
-	HIP_TRY(hipMemcpy(fl, pl->H.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(1, pl->H.flags, fl, sizeof fl)) return rc;
 	if ((int32_t)fl[0] != 0) return fail(MM2C_E_ARG, "%d read(s): offsets beyond the plan's capacities", (int32_t)fl[0]);
 	if (n_hits_total) *n_hits_total = fl[1];
 	return 0;
@@ -118,11 +98,7 @@ int mm2c_hitplan_last_ms(mm2c_hitplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[1]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-	return 0;
+	return pl->elapsed(1, {{0, 1, ms}});
 }
 
 // both host entries: mopt == NULL is mm_select_sub
@@ -145,31 +121,15 @@ static int select_hits_host(int64_t n_reads, const mm2c_hit_opt_t *opt, const mm
 	mm2c_hitplan_t *pl = mm2c_hitplan_create(n_reads, n_u);
 	if (!pl) return MM2C_E_HIP;
 	const size_t nr = (size_t)n_reads, rb = (size_t)n_u * sizeof(mm2c_reg_t), sb = mopt && seg_len ? nr * (size_t)mopt->n_segs * 4 : 0, gb = mopt && gap_ref ? nr * 4 : 0;
-	char *d = nullptr;
-	Layout L;
-	const size_t o_off = L.take((nr + 1) * 8), o_in = L.take(rb + 8), o_out = L.take(rb + 8), o_n = L.take(nr * 4), o_sl = L.take(sb + 4), o_gr = L.take(gb + 4);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs_in + ub, rb, hipMemcpyHostToDevice, st));
-		if (sb) HIP_TRY(hipMemcpyAsync(d + o_sl, seg_len, sb, hipMemcpyHostToDevice, st));
-		if (gb) HIP_TRY(hipMemcpyAsync(d + o_gr, gap_ref, gb, hipMemcpyHostToDevice, st));
-		const int r = mopt ? mm2c_hitplan_run_device_multi(pl, opt, mopt, (const int64_t *)(d + o_off), sb ? (const int32_t *)(d + o_sl) : nullptr,
-		                                                   gb ? (const int32_t *)(d + o_gr) : nullptr, (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
-		                                                   (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY)
-		                   : mm2c_hitplan_run_device(pl, opt, (const int64_t *)(d + o_off), (const mm2c_reg_t *)(d + o_in), (mm2c_reg_t *)(d + o_out),
-		                                             (int32_t *)(d + o_n), MM2C_STREAM_LIBRARY);
-		if (r) return r;
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(regs_out, d + o_out, rb, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(n_out, d + o_n, nr * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_hitplan_check(pl, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	Staging stage;
+	const int i_off = stage.add(off.data(), nullptr, off.size() * 8), i_in = stage.add(n_u > 0 ? regs_in + ub : nullptr, nullptr, rb, 8), i_out = stage.add(nullptr, regs_out, rb, 8),
+	          i_n = stage.add(nullptr, n_out, nr * 4), i_sl = stage.add(seg_len, nullptr, sb, 4), i_gr = stage.add(gap_ref, nullptr, gb, 4);
+	const int rc = stage.through(pl->device, [&] {
+		return mopt ? mm2c_hitplan_run_device_multi(pl, opt, mopt, stage.at<int64_t>(i_off), sb ? stage.at<int32_t>(i_sl) : nullptr, gb ? stage.at<int32_t>(i_gr) : nullptr,
+		                                            stage.at<mm2c_reg_t>(i_in), stage.at<mm2c_reg_t>(i_out), stage.at<int32_t>(i_n), MM2C_STREAM_LIBRARY)
+		            : mm2c_hitplan_run_device(pl, opt, stage.at<int64_t>(i_off), stage.at<mm2c_reg_t>(i_in), stage.at<mm2c_reg_t>(i_out), stage.at<int32_t>(i_n), MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_hitplan_check(pl, nullptr); });
+	stage.release();
 	mm2c_hitplan_destroy(pl);
 	return rc;
 }

@@ -1,6 +1,6 @@
 // mm2chain_ksw.cpp -- C-ABI entries of the base-alignment step (include/mm2chain.h): ksw plans (ksw_extd2_sse on the device, ksw_extd2.hip) and the
 // host-buffer entry built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "ksw_extd2.h"
 #include <cstddef>
 
@@ -12,14 +12,10 @@ static_assert(sizeof(mm2c_ksw_score_t) == 29, "layout");
 static_assert(MM2C_KSW_FLAGS == mm2c::KSW_FLAGS && MM2C_KSW_MAX_LEN == mm2c::KSW_MAX_LEN && MM2C_KSW_LDS_LEN == mm2c::KSW_LDS_T16 && MM2C_KSW_LDS_LEN == mm2c::KSW_LDS_Q &&
               MM2C_KSW_REFUSED == mm2c::KSW_REFUSED && MM2C_KSW_TOO_BIG == mm2c::KSW_TOO_BIG && MM2C_KSW_CIGAR_CUT == mm2c::KSW_CIGAR_CUT, "constants of mm2chain.h");
 
-struct mm2c_kswplan {
+struct mm2c_kswplan : PlanBase {           // d_mem: [flags | scratch]; events: begin, behind ksw_rows
 	int64_t n_tasks_cap = 0, seq_cap = 0, cigar_cap = 0, slot_bytes = 0;
 	int32_t n_slots = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags | scratch]
 	mm2c::KswArgs K;
-	hipEvent_t ev[2] = {};                 // begin, behind ksw_rows
-	bool ran = false;
 };
 
 // what ksw2_extd2_sse.c:78-105 makes of the score set
@@ -55,11 +51,7 @@ static int kswplan_make(int64_t n_tasks_cap, int64_t seq_cap, int64_t cigar_cap,
 	pl->slot_bytes = (slot_bytes + 255) & ~(int64_t)255;
 	Layout L;
 	const size_t o_fl = L.take(16), o_sc = L.take((size_t)pl->slot_bytes * pl->n_slots + 256);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	const hipError_t e = pl->open(L.at, 2);
 	if (e != hipSuccess) {
 		const int rc = fail(MM2C_E_HIP, "mm2c_kswplan_create: %s (%lld slots of %lld bytes)", hipGetErrorString(e), (long long)n_slots, (long long)pl->slot_bytes);
 		mm2c_kswplan_destroy(pl);
@@ -90,12 +82,7 @@ mm2c_kswplan_t *mm2c_kswplan_create(int64_t n_tasks_cap, int64_t seq_cap, int64_
 void mm2c_kswplan_destroy(mm2c_kswplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -114,19 +101,15 @@ int mm2c_kswplan_run_device(mm2c_kswplan_t *pl, const mm2c_ksw_score_t *sc, int6
 	if (n_tasks > 0 && (!d_tasks || !d_cig_off || !d_res || (pl->seq_cap > 0 && !d_seq) || (pl->cigar_cap > 0 && !d_cigar))) return fail(MM2C_E_ARG, "device pointer is NULL");
 	if (((uintptr_t)d_tasks | (uintptr_t)d_cig_off) & 7) return fail(MM2C_E_ARG, "tasks or CIGAR offsets are not 8-byte aligned");
 	if (((uintptr_t)d_res | (uintptr_t)d_cigar) & 3) return fail(MM2C_E_ARG, "results or CIGAR words are not 4-byte aligned");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::KswArgs &K = pl->K;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, K.flags, 16)) return rc;
 	K.n_tasks = n_tasks; K.tasks = (const mm2c::KswTask *)d_tasks; K.seq = d_seq; K.cig_off = d_cig_off; K.res = (mm2c::KswRes *)d_res; K.cigar = d_cigar; K.sc = S;
-	HIP_TRY(hipMemsetAsync(K.flags, 0, 16, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mm2c::launch_ksw_rows(K, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
-	pl->ran = true;
-	G.launches += n_tasks > 0;
-	return 0;
+	return pl->end(n_tasks > 0);
 }
 
 int mm2c_kswplan_check(mm2c_kswplan_t *pl, int64_t *n_refused, int64_t *n_too_big)
@@ -135,11 +118,8 @@ int mm2c_kswplan_check(mm2c_kswplan_t *pl, int64_t *n_refused, int64_t *n_too_bi
 	if (n_refused) *n_refused = 0;
 	if (n_too_big) *n_too_big = 0;
 	if (!pl->ran) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[1]));
 	int32_t fl[4] = {};
-	HIP_TRY(hipMemcpy(fl, pl->K.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(1, pl->K.flags, fl, sizeof fl)) return rc;
 	if (n_refused) *n_refused = fl[0];
 	if (n_too_big) *n_too_big = (int64_t)fl[1] + fl[2];
 	if (fl[0] != 0) return fail(MM2C_E_ARG, "%d task(s) refused: a flag outside MM2C_KSW_FLAGS, a length above MM2C_KSW_MAX_LEN, offsets or lengths that leave seq_cap, or a CIGAR slot that runs "
@@ -153,11 +133,7 @@ int mm2c_kswplan_last_ms(mm2c_kswplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[1]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-	return 0;
+	return pl->elapsed(1, {{0, 1, ms}});
 }
 
 int mm2c_kswplan_last_kernel_ms(mm2c_kswplan_t *pl, float *rows_ms)
@@ -199,30 +175,16 @@ int mm2c_ksw_extd2_batch_host(const mm2c_ksw_score_t *sc, int64_t n_tasks, const
 	slots = std::max<int64_t>(slots, 1);
 	mm2c_kswplan_t *pl = nullptr;
 	if (const int rc = kswplan_make(n_tasks, seq_len, n_cig, slots, slot, &pl)) return rc;
-	char *d = nullptr;
-	Layout L;
+	Staging stage;
 	const size_t nt = (size_t)n_tasks;
-	const size_t o_t = L.take(nt * sizeof(mm2c_ksw_task_t)), o_s = L.take((size_t)seq_len + 16), o_co = L.take((nt + 1) * 8), o_r = L.take(nt * sizeof(mm2c_ksw_res_t)),
-	             o_c = L.take((size_t)n_cig * 4 + 16);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_t, tasks, nt * sizeof(mm2c_ksw_task_t), hipMemcpyHostToDevice, st));
-		if (seq_len > 0) HIP_TRY(hipMemcpyAsync(d + o_s, seq, (size_t)seq_len, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_co, cig_off, (nt + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_r, res, nt * sizeof(mm2c_ksw_res_t), hipMemcpyHostToDevice, st));   // what a task that is not run leaves is the caller's
-		if (n_cig > 0) HIP_TRY(hipMemcpyAsync(d + o_c, cigar, (size_t)n_cig * 4, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_kswplan_run_device(pl, sc, n_tasks, (const mm2c_ksw_task_t *)(d + o_t), (const uint8_t *)(d + o_s), (const int64_t *)(d + o_co),
-		                                          (mm2c_ksw_res_t *)(d + o_r), (uint32_t *)(d + o_c), MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(res, d + o_r, nt * sizeof(mm2c_ksw_res_t), hipMemcpyDeviceToHost, st));
-		if (n_cig > 0) HIP_TRY(hipMemcpyAsync(cigar, d + o_c, (size_t)n_cig * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_kswplan_check(pl, nullptr, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	// res and cigar go up as well: what a task that is not run leaves is the caller's
+	const int i_t = stage.add(tasks, nullptr, nt * sizeof(mm2c_ksw_task_t)), i_s = stage.add(seq, nullptr, (size_t)seq_len, 16), i_co = stage.add(cig_off, nullptr, (nt + 1) * 8),
+	          i_r = stage.add(res, res, nt * sizeof(mm2c_ksw_res_t)), i_c = stage.add(cigar, cigar, (size_t)n_cig * 4, 16);
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_kswplan_run_device(pl, sc, n_tasks, stage.at<mm2c_ksw_task_t>(i_t), stage.at<uint8_t>(i_s), stage.at<int64_t>(i_co), stage.at<mm2c_ksw_res_t>(i_r), stage.at<uint32_t>(i_c),
+		                               MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_kswplan_check(pl, nullptr, nullptr); });
+	stage.release();
 	mm2c_kswplan_destroy(pl);
 	return rc;
 }

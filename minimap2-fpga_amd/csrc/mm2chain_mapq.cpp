@@ -1,6 +1,6 @@
 // mm2chain_mapq.cpp -- C-ABI entries of the hits-to-mapping-quality step (include/mm2chain.h): mapq plans (mm_join_long + mm_set_mapq on the device,
 // chain_mapq.hip), the table of the host's own logf they look up, and the host-buffer entry built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "chain_mapq.h"
 #include "chain_regs.h"
 #include <cmath>
@@ -11,13 +11,10 @@ using namespace mm2c_api;
 static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_mapq_opt_t) == 28 && sizeof(mm2c_anchor_t) == 16, "layout");
 static_assert(MM2C_HIT_LDS_REGIONS == mm2c::MAPQ_LDS_MAX && MM2C_MAPQ_MAX_LOG_ARG == (1 << 24) - 1, "constants of mm2chain.h");
 
-struct mm2c_mapqplan {
+struct mm2c_mapqplan : PlanBase {          // d_mem: [flags, counts | log table | moves | state | tab | junc]; events: in front of mapq_join, behind it, behind mapq_gather
 	int64_t n_reads = 0, n_u_cap = 0, n_b_cap = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags, counts | log table | moves | state | tab | junc]
 	mm2c::MapqArgs M;
-	hipEvent_t ev[3] = {};                 // in front of mapq_join, behind it, behind mapq_gather
-	bool ran = false, gathered = false;
+	bool gathered = false;
 };
 
 // L[i] = logf((float)i) by the host's own libm, the function the reference's hit.o calls on this host (hit.c:498, :501): made once, grown on demand.
@@ -52,12 +49,8 @@ mm2c_mapqplan_t *mm2c_mapqplan_create(int64_t n_reads, int64_t n_u_cap, int64_t 
 	Layout L;
 	const size_t o_fl = L.take(32), o_log = L.take(nl * 4), o_mv = L.take(nu * 16), o_st = L.take(nr * 4), o_tab = L.take(row * 4 * mm2c::MAPQ_TAB_ROWS),
 	             o_j = L.take(nu * 8 * mm2c::MAPQ_JUNC_ROWS);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
-	if (e == hipSuccess) e = hipMemcpy(pl->d_mem + o_log, host_log_table(max_log_arg), nl * 4, hipMemcpyHostToDevice);
+	hipError_t e = pl->open(L.at, 3);
+	if (e == hipSuccess) e = pl->on_device([&] { return hipMemcpy(pl->d_mem + o_log, host_log_table(max_log_arg), nl * 4, hipMemcpyHostToDevice); });
 	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_mapqplan_create: %s", hipGetErrorString(e)); mm2c_mapqplan_destroy(pl); return nullptr; }
 	mm2c::MapqArgs &M = pl->M;
 	char *b = pl->d_mem;
@@ -71,12 +64,7 @@ mm2c_mapqplan_t *mm2c_mapqplan_create(int64_t n_reads, int64_t n_u_cap, int64_t 
 void mm2c_mapqplan_destroy(mm2c_mapqplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -94,24 +82,21 @@ int mm2c_mapqplan_run_device(mm2c_mapqplan_t *pl, const mm2c_mapq_opt_t *opt, co
 	if (((uintptr_t)d_b | (uintptr_t)d_b_out) & 15) return fail(MM2C_E_ARG, "anchors are not 16-byte aligned");
 	if (pl->n_u_cap > 0 && (const mm2c_reg_t *)d_regs_out == d_regs_in) return fail(MM2C_E_ARG, "d_regs_out must not alias d_regs_in");
 	if (d_b_out && d_b_out == d_b) return fail(MM2C_E_ARG, "d_b_out must not alias d_b");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::MapqArgs &M = pl->M;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, M.flags, 32)) return rc;
 	M.do_join = opt->do_join != 0; M.max_join_long = opt->max_join_long; M.max_join_short = opt->max_join_short; M.min_join_flank_sc = opt->min_join_flank_sc;
 	M.min_join_flank_ratio = opt->min_join_flank_ratio; M.min_cnt = opt->min_cnt; M.min_chain_score = opt->min_chain_score;
 	M.u_off = d_u_off; M.in = (const uint64_t *)d_regs_in; M.n_in = d_n_in; M.b_off = d_b_off; M.b = (const uint4 *)d_b; M.qlen = d_qlen; M.rep_len = d_rep_len;
 	M.out = (uint64_t *)d_regs_out; M.n_out = d_n_out; M.b_out = (uint4 *)d_b_out; M.n_b_out = d_n_b_out;
-	HIP_TRY(hipMemsetAsync(M.flags, 0, 32, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mm2c::launch_mapq_join(M, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
 	if (d_b_out) HIP_TRY(mm2c::launch_mapq_gather(M, st));
 	HIP_TRY(hipEventRecord(pl->ev[2], st));
-	pl->ran = true; pl->gathered = d_b_out != nullptr;
-	G.launches += d_b_out ? 2 : 1;
-	return 0;
+	pl->gathered = d_b_out != nullptr;
+	return pl->end(d_b_out ? 2 : 1);
 }
 
 int mm2c_mapqplan_check(mm2c_mapqplan_t *pl, int64_t *n_joined, int64_t *n_beyond_table)
@@ -120,11 +105,8 @@ int mm2c_mapqplan_check(mm2c_mapqplan_t *pl, int64_t *n_joined, int64_t *n_beyon
 	if (n_joined) *n_joined = 0;
 	if (n_beyond_table) *n_beyond_table = 0;
 	if (!pl->ran || pl->n_reads == 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
 	int64_t fl[4] = {0, 0, 0, 0};
-	HIP_TRY(hipMemcpy(fl, pl->M.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(2, pl->M.flags, fl, sizeof fl)) return rc;
 	if (n_joined) *n_joined = fl[1];
 	if (n_beyond_table) *n_beyond_table = fl[2];
 	if ((int32_t)fl[0] != 0) return fail(MM2C_E_ARG, "%d read(s): offsets beyond the plan's capacities or each other", (int32_t)fl[0]);
@@ -137,24 +119,16 @@ int mm2c_mapqplan_last_ms(mm2c_mapqplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[2]));
-	return 0;
+	return pl->elapsed(2, {{0, 2, ms}});
 }
 
 int mm2c_mapqplan_last_kernel_ms(mm2c_mapqplan_t *pl, float *join_ms, float *gather_ms)
 {
 	if (!pl || !join_ms || !gather_ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(join_ms, pl->ev[0], pl->ev[1]));
+	if (const int rc = pl->elapsed(2, {{0, 1, join_ms}})) return rc;
 	*gather_ms = 0.0f;
-	if (pl->gathered) HIP_TRY(hipEventElapsedTime(gather_ms, pl->ev[1], pl->ev[2]));
-	return 0;
+	return pl->gathered ? pl->elapsed(2, {{1, 2, gather_ms}}) : 0;
 }
 
 int mm2c_join_mapq_batch_host(int64_t n_reads, const mm2c_mapq_opt_t *opt, int32_t max_log_arg, const int64_t *u_off, const mm2c_reg_t *regs_in,
@@ -180,34 +154,16 @@ int mm2c_join_mapq_batch_host(int64_t n_reads, const mm2c_mapq_opt_t *opt, int32
 	mm2c_mapqplan_t *pl = mm2c_mapqplan_create(n_reads, n_u, n_b, max_log_arg);
 	if (!pl) return MM2C_E_HIP;
 	const size_t nr = (size_t)n_reads, rb = (size_t)n_u * sizeof(mm2c_reg_t), ab = (size_t)n_b * 16;
-	char *d = nullptr;
-	Layout L;
-	const size_t o_off = L.take(2 * (nr + 1) * 8), o_in = L.take(rb + 8), o_out = L.take(rb + 8), o_ni = L.take(nr * 4), o_no = L.take(nr * 4), o_q = L.take(nr * 4),
-	             o_rep = L.take(nr * 4), o_b = L.take(ab + 16), o_bo = L.take(b_out ? ab + 16 : 16), o_nb = L.take(nr * 8);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs_in + ub, rb, hipMemcpyHostToDevice, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(d + o_b, b + bb, ab, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_ni, n_in, nr * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_rep, rep_len, nr * 4, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_mapqplan_run_device(pl, opt, (const int64_t *)(d + o_off), (const mm2c_reg_t *)(d + o_in), (const int32_t *)(d + o_ni),
-		                                           (const int64_t *)(d + o_off) + nr + 1, d + o_b, (const int32_t *)(d + o_q), (const int32_t *)(d + o_rep),
-		                                           (mm2c_reg_t *)(d + o_out), (int32_t *)(d + o_no), b_out ? d + o_bo : nullptr,
-		                                           b_out ? (int64_t *)(d + o_nb) : nullptr, MM2C_STREAM_LIBRARY)) return r;
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(regs_out, d + o_out, rb, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(n_out, d + o_no, nr * 4, hipMemcpyDeviceToHost, st));
-		if (b_out && n_b > 0) HIP_TRY(hipMemcpyAsync(b_out, d + o_bo, ab, hipMemcpyDeviceToHost, st));
-		if (b_out) HIP_TRY(hipMemcpyAsync(n_b_out, d + o_nb, nr * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_mapqplan_check(pl, nullptr, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	Staging stage;
+	const int i_off = stage.add(off.data(), nullptr, off.size() * 8), i_in = stage.add(n_u > 0 ? regs_in + ub : nullptr, nullptr, rb, 8), i_out = stage.add(nullptr, regs_out, rb, 8),
+	          i_ni = stage.add(n_in, nullptr, nr * 4), i_no = stage.add(nullptr, n_out, nr * 4), i_q = stage.add(qlen, nullptr, nr * 4), i_rep = stage.add(rep_len, nullptr, nr * 4),
+	          i_b = stage.add(n_b > 0 ? b + bb : nullptr, nullptr, ab, 16), i_bo = stage.add(nullptr, b_out, b_out ? ab : 0, 16), i_nb = stage.add(nullptr, n_b_out, nr * 8);
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_mapqplan_run_device(pl, opt, stage.at<int64_t>(i_off), stage.at<mm2c_reg_t>(i_in), stage.at<int32_t>(i_ni), stage.at<int64_t>(i_off) + nr + 1, stage.at<char>(i_b), stage.at<int32_t>(i_q),
+		                                stage.at<int32_t>(i_rep), stage.at<mm2c_reg_t>(i_out), stage.at<int32_t>(i_no), b_out ? stage.at<char>(i_bo) : nullptr,
+		                                b_out ? stage.at<int64_t>(i_nb) : nullptr, MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_mapqplan_check(pl, nullptr, nullptr); });
+	stage.release();
 	mm2c_mapqplan_destroy(pl);
 	return rc;
 }

@@ -1,6 +1,6 @@
 // mm2chain_regs.cpp -- C-ABI entries of the chains-to-regions step (include/mm2chain.h): region plans (mm_gen_regs on the device, chain_regs.hip),
 // the host-buffer entry built on them and the read hash of map.c:290-292.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "chain_regs.h"
 
 using namespace mm2c_api;
@@ -8,13 +8,9 @@ using namespace mm2c_api;
 static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS, "mm2c_reg_t layout");
 static_assert(offsetof(mm2c_reg_t, mlen) == 44 && offsetof(mm2c_reg_t, blen) == 48 && offsetof(mm2c_reg_t, flags) == 60 && offsetof(mm2c_reg_t, p) == 72, "mm2c_reg_t layout");
 
-struct mm2c_regplan {
+struct mm2c_regplan : PlanBase {           // d_mem: [flags | zkey | key0 | key1 | cstart | cend | val0 | val1 | crank | tiecnt | stack | moved]; events: begin, between the kernels, end
 	int64_t n_reads = 0, n_u_cap = 0, n_b_cap = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags | zkey | key0 | key1 | cstart | cend | val0 | val1 | crank | tiecnt | stack | moved]
 	mm2c::RegArgs R;
-	hipEvent_t ev[3] = {};                 // begin, between the kernels, end
-	bool ran = false;
 };
 
 extern "C" {
@@ -29,11 +25,7 @@ mm2c_regplan_t *mm2c_regplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_
 	Layout L;
 	const size_t o_fl = L.take(16), o_z = L.take(nu * 8), o_k0 = L.take(nu * 8), o_k1 = L.take(nu * 8), o_cs = L.take(nu * 8), o_ce = L.take(nu * 8),
 	             o_v0 = L.take(nu * 4), o_v1 = L.take(nu * 4), o_cr = L.take(nu * 4), o_tc = L.take(nu * 4), o_st = L.take(nu * 4 + 16), o_mv = L.take(nu * 4);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	const hipError_t e = pl->open(L.at, 3);
 	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_regplan_create: %s", hipGetErrorString(e)); mm2c_regplan_destroy(pl); return nullptr; }
 	mm2c::RegArgs &R = pl->R;
 	char *b = pl->d_mem;
@@ -47,12 +39,7 @@ mm2c_regplan_t *mm2c_regplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_
 void mm2c_regplan_destroy(mm2c_regplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -64,20 +51,16 @@ int mm2c_regplan_run_device(mm2c_regplan_t *pl, const int64_t *d_u_off, const ui
 	if (pl->n_reads == 0) return 0;
 	if (!d_u_off || !d_b_off || !d_qlen || !d_hash || (pl->n_u_cap > 0 && (!d_u || !d_regs)) || (pl->n_b_cap > 0 && !d_b)) return fail(MM2C_E_ARG, "device pointer is NULL");
 	if ((uintptr_t)d_regs & 7) return fail(MM2C_E_ARG, "d_regs is not 8-byte aligned");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::RegArgs &R = pl->R;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, R.flags, 16)) return rc;
 	R.u_off = d_u_off; R.u = d_u; R.b_off = d_b_off; R.b = (const ulonglong2 *)d_b; R.qlen = d_qlen; R.hash = d_hash; R.regs = (uint64_t *)d_regs;
-	HIP_TRY(hipMemsetAsync(R.flags, 0, 16, st));
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	int nl = 0;
 	HIP_TRY(mm2c::launch_chain_regs(R, st, pl->ev[1], &nl));
 	HIP_TRY(hipEventRecord(pl->ev[2], st));
-	pl->ran = true;
-	G.launches += (uint64_t)nl;
-	return 0;
+	return pl->end((uint64_t)nl);
 }
 
 int mm2c_regplan_check(mm2c_regplan_t *pl, int64_t *n_reads_with_ties)
@@ -85,11 +68,8 @@ int mm2c_regplan_check(mm2c_regplan_t *pl, int64_t *n_reads_with_ties)
 	if (!pl) return fail(MM2C_E_ARG, "plan is NULL");
 	if (n_reads_with_ties) *n_reads_with_ties = 0;
 	if (!pl->ran || pl->n_reads == 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
 	int32_t fl[2] = {0, 0};
-	HIP_TRY(hipMemcpy(fl, pl->R.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(2, pl->R.flags, fl, sizeof fl)) return rc;
 	if (fl[0] != 0) return fail(MM2C_E_ARG, "%d read(s): a chain without anchors, counts that do not add up to the read's extent of b, or offsets beyond the plan's capacities", fl[0]);
 	if (n_reads_with_ties) *n_reads_with_ties = fl[1];
 	return 0;
@@ -99,23 +79,14 @@ int mm2c_regplan_last_ms(mm2c_regplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[2]));
-	return 0;
+	return pl->elapsed(2, {{0, 2, ms}});
 }
 
 int mm2c_regplan_last_kernel_ms(mm2c_regplan_t *pl, float *sort_ms, float *fill_ms)
 {
 	if (!pl || !sort_ms || !fill_ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(sort_ms, pl->ev[0], pl->ev[1]));
-	HIP_TRY(hipEventElapsedTime(fill_ms, pl->ev[1], pl->ev[2]));
-	return 0;
+	return pl->elapsed(2, {{0, 1, sort_ms}, {1, 2, fill_ms}});
 }
 
 int mm2c_gen_regs_batch_host(int64_t n_reads, const int64_t *u_off, const uint64_t *u, const int64_t *b_off, const mm2c_anchor_t *b,
@@ -148,28 +119,14 @@ int mm2c_gen_regs_batch_host(int64_t n_reads, const int64_t *u_off, const uint64
 	mm2c_regplan_t *pl = mm2c_regplan_create(n_reads, n_u, n_b);
 	if (!pl) return MM2C_E_HIP;
 	const size_t nr = (size_t)n_reads;
-	char *d = nullptr;
-	Layout L;
-	const size_t o_off = L.take(2 * (nr + 1) * 8), o_u = L.take((size_t)n_u * 8), o_b = L.take((size_t)n_b * 16), o_q = L.take(nr * 4), o_h = L.take(nr * 4),
-	             o_r = L.take((size_t)n_u * sizeof(mm2c_reg_t));
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_u, u + ub, (size_t)n_u * 8, hipMemcpyHostToDevice, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(d + o_b, b + bb, (size_t)n_b * 16, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_q, qlen, nr * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_h, hash, nr * 4, hipMemcpyHostToDevice, st));
-		if (const int r = mm2c_regplan_run_device(pl, (const int64_t *)(d + o_off), (const uint64_t *)(d + o_u), (const int64_t *)(d + o_off) + nr + 1, d + o_b,
-		                                          (const int32_t *)(d + o_q), (const uint32_t *)(d + o_h), (mm2c_reg_t *)(d + o_r), MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(regs, d + o_r, (size_t)n_u * sizeof(mm2c_reg_t), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return mm2c_regplan_check(pl, nullptr);
-	};
-	const int rc = body();
-	dev_free(d);
+	Staging stage;
+	const int i_off = stage.add(off.data(), nullptr, off.size() * 8), i_u = stage.add(u + ub, nullptr, (size_t)n_u * 8), i_b = stage.add(n_b > 0 ? b + bb : nullptr, nullptr, (size_t)n_b * 16),
+	          i_q = stage.add(qlen, nullptr, nr * 4), i_h = stage.add(hash, nullptr, nr * 4), i_r = stage.add(nullptr, regs, (size_t)n_u * sizeof(mm2c_reg_t));
+	const int rc = stage.through(pl->device, [&] {
+		return mm2c_regplan_run_device(pl, stage.at<int64_t>(i_off), stage.at<uint64_t>(i_u), stage.at<int64_t>(i_off) + nr + 1, stage.at<char>(i_b), stage.at<int32_t>(i_q), stage.at<uint32_t>(i_h),
+		                               stage.at<mm2c_reg_t>(i_r), MM2C_STREAM_LIBRARY);
+	}, [&] { return mm2c_regplan_check(pl, nullptr); });
+	stage.release();
 	mm2c_regplan_destroy(pl);
 	return rc;
 }

@@ -1,6 +1,6 @@
 // mm2chain_segs.cpp -- C-ABI entries of the fragment-hits-to-segments step (include/mm2chain.h): seg plans (mm_seg_gen on the device: chain_segs.hip for the
 // per-segment chains and anchors, chain_regs.hip for their regions) and the host-buffer entry built on them.
-#include "api_internal.h"
+#include "plan_common.h"
 #include "chain_segs.h"
 #include "chain_regs.h"
 #include <cstddef>
@@ -10,17 +10,13 @@ using namespace mm2c_api;
 static_assert(sizeof(mm2c_reg_t) == 8 * mm2c::REG_WORDS && sizeof(mm2c_anchor_t) == 16 && offsetof(mm2c_reg_t, flags) == 60, "layout");
 static_assert(MM2C_MAX_SEG == mm2c::SEG_MAX && MM2C_REG_SEG_SPLIT_BIT == 15 && MM2C_REG_SEG_ID_SHIFT == 16, "constants of mm2chain.h");
 
-struct mm2c_segplan {
-	int64_t n_frags = 0, n_u_cap = 0, n_b_cap = 0, n_su_cap = 0;
+struct mm2c_segplan : PlanBase {           // d_mem: [flags, the region step's flags | cnt_u | cnt_a | state | scan | the region step's scratch]
+	int64_t n_frags = 0, n_u_cap = 0, n_b_cap = 0, n_su_cap = 0;   // events: begin, behind seg_count, the scans, seg_scatter, regs_sort, regs_fill, seg_mark
 	int32_t n_segs = 0;
-	int device = 0;
-	char *d_mem = nullptr;                 // [flags, the region step's flags | cnt_u | cnt_a | state | scan | the region step's scratch]
 	size_t scan_bytes = 0;
 	void *d_scan = nullptr;
 	mm2c::SegArgs S;
 	mm2c::RegArgs R;                       // chain_regs.hip over the segment reads
-	hipEvent_t ev[7] = {};                 // begin, behind seg_count, the scans, seg_scatter, regs_sort, regs_fill, seg_mark
-	bool ran = false;
 };
 
 static int64_t seg_chain_cap(int64_t n_segs, int64_t n_u_cap, int64_t n_b_cap)   // a segment chain holds at least one anchor
@@ -46,12 +42,8 @@ mm2c_segplan_t *mm2c_segplan_create(int64_t n_frags, int32_t n_segs, int64_t n_u
 	const size_t o_fl = L.take(48), o_cu = L.take(n1 * 8), o_ca = L.take(n1 * 8), o_st = L.take(nf * 4), o_sc = L.take(pl->scan_bytes + 16);
 	const size_t o_z = L.take(nu * 8), o_k0 = L.take(nu * 8), o_k1 = L.take(nu * 8), o_cs = L.take(nu * 8), o_ce = L.take(nu * 8),
 	             o_v0 = L.take(nu * 4), o_v1 = L.take(nu * 4), o_cr = L.take(nu * 4), o_tc = L.take(nu * 4), o_sk = L.take(nu * 4 + 16), o_mv = L.take(nu * 4);
-	pl->device = cur_device();
-	DeviceScope on(pl->device);
-	hipError_t e = on.err;
-	if (e == hipSuccess) e = dev_alloc((void **)&pl->d_mem, L.at);
-	if (e == hipSuccess) e = hipMemset(pl->d_mem + o_cu, 0, o_st - o_cu);   // the entry behind the last segment read stays 0
-	for (int i = 0; i < 7 && e == hipSuccess; ++i) e = hipEventCreate(&pl->ev[i]);
+	hipError_t e = pl->open(L.at, 7);
+	if (e == hipSuccess) e = pl->on_device([&] { return hipMemset(pl->d_mem + o_cu, 0, o_st - o_cu); });   // the entry behind the last segment read stays 0
 	if (e != hipSuccess) { fail(MM2C_E_HIP, "mm2c_segplan_create: %s", hipGetErrorString(e)); mm2c_segplan_destroy(pl); return nullptr; }
 	char *b = pl->d_mem;
 	mm2c::SegArgs &S = pl->S;
@@ -69,12 +61,7 @@ mm2c_segplan_t *mm2c_segplan_create(int64_t n_frags, int32_t n_segs, int64_t n_u
 void mm2c_segplan_destroy(mm2c_segplan_t *pl)
 {
 	if (!pl) return;
-	{
-		DeviceScope on(pl->device);
-		if (pl->ran) { ScopedNs timed(SS.free_ns); (void)hipDeviceSynchronize(); }
-		dev_free_synced(pl->d_mem);
-		for (auto &e : pl->ev) if (e) (void)hipEventDestroy(e);
-	}
+	pl->close();
 	delete pl;
 }
 
@@ -96,16 +83,14 @@ int mm2c_segplan_run_device(mm2c_segplan_t *pl, const int64_t *d_u_off, const mm
 	if (((uintptr_t)d_regs | (uintptr_t)d_seg_regs | (uintptr_t)d_su) & 7) return fail(MM2C_E_ARG, "regions or chains are not 8-byte aligned");
 	if (((uintptr_t)d_b | (uintptr_t)d_sb) & 15) return fail(MM2C_E_ARG, "anchors are not 16-byte aligned");
 	if (pl->n_b_cap > 0 && d_sb == d_b) return fail(MM2C_E_ARG, "d_sb must not alias d_b");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	hipStream_t st;
-	if (const int rc = resolve_stream(stream, pl->device, &st)) return rc;
 	mm2c::SegArgs &S = pl->S;
+	DeviceScope on(pl->device);
+	hipStream_t st;
+	if (const int rc = pl->begin(on, stream, &st, S.flags, 48)) return rc;        // its own flags and the region step's
 	S.u_off = d_u_off; S.regs = (const uint64_t *)d_regs; S.n_in = d_n_in; S.b_off = d_b_off; S.b = (const uint4 *)d_b; S.seg_len = d_seg_len; S.hash = d_hash;
 	S.rep_len = d_rep_len; S.su_off = d_su_off; S.sb_off = d_sb_off; S.su = d_su; S.sb = (uint4 *)d_sb; S.seg_hash = d_seg_hash; S.seg_rep_len = d_seg_rep_len;
 	mm2c::RegArgs &R = pl->R;
 	R.u_off = d_su_off; R.u = d_su; R.b_off = d_sb_off; R.b = (const ulonglong2 *)d_sb; R.qlen = d_seg_len; R.hash = d_seg_hash; R.regs = (uint64_t *)d_seg_regs;
-	HIP_TRY(hipMemsetAsync(S.flags, 0, 48, st));                                 // its own flags and the region step's
 	HIP_TRY(hipEventRecord(pl->ev[0], st));
 	HIP_TRY(mm2c::launch_seg_count(S, st));
 	HIP_TRY(hipEventRecord(pl->ev[1], st));
@@ -118,9 +103,7 @@ int mm2c_segplan_run_device(mm2c_segplan_t *pl, const int64_t *d_u_off, const mm
 	HIP_TRY(hipEventRecord(pl->ev[5], st));
 	HIP_TRY(mm2c::launch_seg_mark(S, (uint64_t *)d_seg_regs, st));
 	HIP_TRY(hipEventRecord(pl->ev[6], st));
-	pl->ran = true;
-	G.launches += (uint64_t)nl + 1;
-	return 0;
+	return pl->end((uint64_t)nl + 1);
 }
 
 int mm2c_segplan_check(mm2c_segplan_t *pl, int64_t *n_refused, int64_t *n_seg_chains, int64_t *n_seg_anchors)
@@ -130,11 +113,8 @@ int mm2c_segplan_check(mm2c_segplan_t *pl, int64_t *n_refused, int64_t *n_seg_ch
 	if (n_seg_chains) *n_seg_chains = 0;
 	if (n_seg_anchors) *n_seg_anchors = 0;
 	if (!pl->ran || pl->n_frags == 0) return 0;
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[6]));
 	int32_t fl[12] = {};
-	HIP_TRY(hipMemcpy(fl, pl->S.flags, sizeof fl, hipMemcpyDeviceToHost));
+	if (const int rc = pl->read_flags(6, pl->S.flags, fl, sizeof fl)) return rc;
 	int64_t tot[2];
 	memcpy(tot, fl + 2, 16);
 	if (n_refused) *n_refused = fl[0];
@@ -150,26 +130,14 @@ int mm2c_segplan_last_ms(mm2c_segplan_t *pl, float *ms)
 {
 	if (!pl || !ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[6]));
-	HIP_TRY(hipEventElapsedTime(ms, pl->ev[0], pl->ev[6]));
-	return 0;
+	return pl->elapsed(6, {{0, 6, ms}});
 }
 
 int mm2c_segplan_last_kernel_ms(mm2c_segplan_t *pl, float *count_ms, float *offsets_ms, float *scatter_ms, float *regs_ms, float *mark_ms)
 {
 	if (!pl || !count_ms || !offsets_ms || !scatter_ms || !regs_ms || !mark_ms) return fail(MM2C_E_ARG, "NULL argument");
 	if (!pl->ran) return fail(MM2C_E_ARG, "plan has not been run");
-	DeviceScope on(pl->device);
-	HIP_TRY(on.err);
-	HIP_TRY(hipEventSynchronize(pl->ev[6]));
-	HIP_TRY(hipEventElapsedTime(count_ms, pl->ev[0], pl->ev[1]));
-	HIP_TRY(hipEventElapsedTime(offsets_ms, pl->ev[1], pl->ev[2]));
-	HIP_TRY(hipEventElapsedTime(scatter_ms, pl->ev[2], pl->ev[3]));
-	HIP_TRY(hipEventElapsedTime(regs_ms, pl->ev[3], pl->ev[5]));
-	HIP_TRY(hipEventElapsedTime(mark_ms, pl->ev[5], pl->ev[6]));
-	return 0;
+	return pl->elapsed(6, {{0, 1, count_ms}, {1, 2, offsets_ms}, {2, 3, scatter_ms}, {3, 5, regs_ms}, {5, 6, mark_ms}});
 }
 
 int mm2c_seg_gen_batch_host(int64_t n_frags, int32_t n_segs, const int64_t *u_off, const mm2c_reg_t *regs, const int32_t *n_in, const int64_t *b_off,
@@ -210,43 +178,27 @@ int mm2c_seg_gen_batch_host(int64_t n_frags, int32_t n_segs, const int64_t *u_of
 	mm2c_segplan_t *pl = mm2c_segplan_create(n_frags, n_segs, n_u, n_b);
 	if (!pl) return MM2C_E_HIP;
 	const size_t rb = (size_t)n_u * sizeof(mm2c_reg_t), ab = (size_t)n_b * 16, srb = (size_t)n_su * sizeof(mm2c_reg_t);
-	char *d = nullptr;
-	Layout L;
-	const size_t o_off = L.take(off.size() * 8), o_in = L.take(rb + 8), o_ni = L.take(nf * 4), o_b = L.take(ab + 16), o_sl = L.take(ns * 4), o_h = L.take(nf * 4),
-	             o_rl = L.take(nf * 4), o_suo = L.take((ns + 1) * 8), o_sbo = L.take((ns + 1) * 8), o_su = L.take((size_t)n_su * 8 + 8), o_sb = L.take(ab + 16),
-	             o_sr = L.take(srb + 8), o_sh = L.take(ns * 4), o_srl = L.take(ns * 4);
-	auto body = [&]() -> int {
-		DeviceScope on(pl->device);
-		HIP_TRY(on.err);
-		HIP_TRY(dev_alloc((void **)&d, L.at));
-		hipStream_t st = G.stream;
-		HIP_TRY(hipMemcpyAsync(d + o_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-		if (n_u > 0) HIP_TRY(hipMemcpyAsync(d + o_in, regs + ub, rb, hipMemcpyHostToDevice, st));
-		if (n_b > 0) HIP_TRY(hipMemcpyAsync(d + o_b, b + bb, ab, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_ni, n_in, nf * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_sl, seg_len, ns * 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d + o_h, hash, nf * 4, hipMemcpyHostToDevice, st));
-		if (rep_len) HIP_TRY(hipMemcpyAsync(d + o_rl, rep_len, nf * 4, hipMemcpyHostToDevice, st));
-		const int64_t *d_off = (const int64_t *)(d + o_off);
-		if (const int r = mm2c_segplan_run_device(pl, d_off, (const mm2c_reg_t *)(d + o_in), (const int32_t *)(d + o_ni), d_off + nf + 1, d + o_b, (const int32_t *)(d + o_sl),
-		                                          (const uint32_t *)(d + o_h), rep_len ? (const int32_t *)(d + o_rl) : nullptr, (int64_t *)(d + o_suo), (uint64_t *)(d + o_su),
-		                                          (int64_t *)(d + o_sbo), d + o_sb, (mm2c_reg_t *)(d + o_sr), (uint32_t *)(d + o_sh),
-		                                          rep_len ? (int32_t *)(d + o_srl) : nullptr, MM2C_STREAM_LIBRARY)) return r;
-		HIP_TRY(hipMemcpyAsync(su_off, d + o_suo, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(sb_off, d + o_sbo, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(seg_hash, d + o_sh, ns * 4, hipMemcpyDeviceToHost, st));
-		if (rep_len) HIP_TRY(hipMemcpyAsync(seg_rep_len, d + o_srl, ns * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
+	Staging stage;
+	const int i_off = stage.add(off.data(), nullptr, off.size() * 8), i_in = stage.add(n_u > 0 ? regs + ub : nullptr, nullptr, rb, 8), i_ni = stage.add(n_in, nullptr, nf * 4),
+	          i_b = stage.add(n_b > 0 ? b + bb : nullptr, nullptr, ab, 16), i_sl = stage.add(seg_len, nullptr, ns * 4), i_h = stage.add(hash, nullptr, nf * 4), i_rl = stage.add(rep_len, nullptr, nf * 4),
+	          i_suo = stage.add(nullptr, su_off, (ns + 1) * 8), i_sbo = stage.add(nullptr, sb_off, (ns + 1) * 8), i_su = stage.add(nullptr, nullptr, (size_t)n_su * 8, 8),
+	          i_sb = stage.add(nullptr, nullptr, ab, 16), i_sr = stage.add(nullptr, nullptr, srb, 8), i_sh = stage.add(nullptr, seg_hash, ns * 4),
+	          i_srl = stage.add(nullptr, rep_len ? seg_rep_len : nullptr, ns * 4);
+	const int rc = stage.through(pl->device, [&] {
+		const int64_t *d_off = stage.at<int64_t>(i_off);
+		return mm2c_segplan_run_device(pl, d_off, stage.at<mm2c_reg_t>(i_in), stage.at<int32_t>(i_ni), d_off + nf + 1, stage.at<char>(i_b), stage.at<int32_t>(i_sl), stage.at<uint32_t>(i_h),
+		                               rep_len ? stage.at<int32_t>(i_rl) : nullptr, stage.at<int64_t>(i_suo), stage.at<uint64_t>(i_su), stage.at<int64_t>(i_sbo), stage.at<char>(i_sb),
+		                               stage.at<mm2c_reg_t>(i_sr), stage.at<uint32_t>(i_sh), rep_len ? stage.at<int32_t>(i_srl) : nullptr, MM2C_STREAM_LIBRARY);
+	}, [&]() -> int {
 		if (const int r = mm2c_segplan_check(pl, nullptr, nullptr, nullptr)) return r;
 		const int64_t tu = su_off[n_sr], ta = sb_off[n_sr];                      // only what was made comes back
 		if (tu < 0 || tu > n_su || ta < 0 || ta > n_b) return fail(MM2C_E_ARG, "segment totals beyond the capacities");
-		if (tu > 0) HIP_TRY(hipMemcpy(su, d + o_su, (size_t)tu * 8, hipMemcpyDeviceToHost));
-		if (tu > 0) HIP_TRY(hipMemcpy(seg_regs, d + o_sr, (size_t)tu * sizeof(mm2c_reg_t), hipMemcpyDeviceToHost));
-		if (ta > 0) HIP_TRY(hipMemcpy(sb, d + o_sb, (size_t)ta * 16, hipMemcpyDeviceToHost));
+		if (tu > 0) HIP_TRY(hipMemcpy(su, stage.at<char>(i_su), (size_t)tu * 8, hipMemcpyDeviceToHost));
+		if (tu > 0) HIP_TRY(hipMemcpy(seg_regs, stage.at<char>(i_sr), (size_t)tu * sizeof(mm2c_reg_t), hipMemcpyDeviceToHost));
+		if (ta > 0) HIP_TRY(hipMemcpy(sb, stage.at<char>(i_sb), (size_t)ta * 16, hipMemcpyDeviceToHost));
 		return 0;
-	};
-	const int rc = body();
-	dev_free(d);
+	});
+	stage.release();
 	mm2c_segplan_destroy(pl);
 	return rc;
 }

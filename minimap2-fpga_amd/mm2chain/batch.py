@@ -43,7 +43,7 @@ def device_count():
 
 def split_tasks(offsets, n_parts):
     """mm2c_split_tasks: bounds of n_parts contiguous task ranges with about equal anchor counts (no GPU involved)"""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    off = _i64(offsets)
     bounds = np.zeros(n_parts + 1, dtype=np.int64)
     N.check(N.load().mm2c_split_tasks(off.size - 1, off.ctypes.data, int(n_parts), bounds.ctypes.data), "mm2c_split_tasks")
     return bounds
@@ -95,17 +95,77 @@ def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class ChainPlan:
+def _stream(stream):
+    """the stream argument of a run: the caller's, or torch's current stream (so torch.cuda.Event timing and torch.cuda.synchronize see the run)"""
+    return stream if stream is not None else torch.cuda.current_stream().cuda_stream
+
+
+def _out(t, shape, dtype, device, need_bytes, same="bytes"):
+    """an output tensor of a run: the given one, or a new one of `shape` and `dtype`; on the device, contiguous and of at least need_bytes bytes; same="dtype": of
+    that dtype, same="width": of that (integer) dtype's element size"""
+    if t is None:
+        t = torch.empty(shape, dtype=dtype, device=device)
+    assert t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= need_bytes
+    assert same == "bytes" or (t.dtype == dtype if same == "dtype" else t.element_size() * 8 == torch.iinfo(dtype).bits)
+    return t
+
+
+def _i64(x):
+    return np.ascontiguousarray(np.asarray(x, dtype=np.int64))
+
+
+def _reg_rows(regs):
+    """regions (REG_DTYPE or their bytes) as uint8 [., 80]"""
+    return np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+
+
+def _anchor_rows(b):
+    return np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+
+
+def _fit(n, *pairs):
+    """the fit test of the host entries: every (offsets, rows of the array they index) pair of a batch of n reads stays inside its array"""
+    return n <= 0 or all(o[0] >= 0 and o.max() <= rows for o, rows in pairs)
+
+
+class _Handle:
+    """owner of one native handle: create or raise, close() (more than once is fine; handle is None afterwards), and a __del__ that swallows"""
+    _destroy = None                                                            # the C entry that frees the handle
+
+    def _create(self, fn, *args, code=-1, what=None):
+        self.lib = N.load()
+        self.handle = getattr(self.lib, fn)(*args)
+        if not self.handle:
+            N.check(code, what or fn)
+
+    def _ms(self, fn, n=1):
+        """n floats out of the C entry `fn`, which takes n float pointers behind the handle"""
+        v = [C.c_float(0) for _ in range(n)]
+        N.check(getattr(self.lib, fn)(self.handle, *[C.byref(x) for x in v]), fn)
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ChainPlan(_Handle):
     """mm2c_plan_t: offsets + longest-first order + workspace on the device; run() enqueues the DP."""
 
+    _destroy = "mm2c_plan_destroy"
+
     def __init__(self, params: Params, offsets):
-        self.lib = N.load()
-        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        off = _i64(offsets)
         self.n_tasks = off.size - 1
         self.params = params
-        self.handle = self.lib.mm2c_plan_create(C.byref(params), self.n_tasks, _np_ptr(off))
-        if not self.handle:
-            N.check(-1, "mm2c_plan_create")
+        self._create("mm2c_plan_create", C.byref(params), self.n_tasks, _np_ptr(off))
         self.total = self.lib.mm2c_plan_total_anchors(self.handle)
 
     def run(self, anchors: torch.Tensor, f: torch.Tensor, p: torch.Tensor, avg: torch.Tensor = None, stream=None):
@@ -116,7 +176,7 @@ class ChainPlan:
         assert f.is_contiguous() and p.is_contiguous()
         if avg is not None:
             assert avg.is_cuda and avg.dtype == torch.float32 and avg.is_contiguous()
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         # the extents of the tensors go with the pointers: the library refuses buffers shorter than the plan (cf. chain_hardware.cpp:34-37)
         N.check(self.lib.mm2c_plan_run_device_n(self.handle, anchors.data_ptr(), anchors.numel() // 2, avg.data_ptr() if avg is not None else None,
                                                 avg.numel() if avg is not None else 0, f.data_ptr(), f.numel(), p.data_ptr(), p.numel(), st),
@@ -145,7 +205,7 @@ class ChainPlan:
         ns = torch.empty(self.total, dtype=torch.uint8, device=anchors.device)
         ts = torch.empty(self.n_tasks, dtype=torch.int64, device=anchors.device)
         tt = torch.empty(self.n_tasks, dtype=torch.int64, device=anchors.device)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_plan_predict_device(self.handle, anchors.data_ptr(), ns.data_ptr(), ts.data_ptr(), tt.data_ptr(), st),
                 "mm2c_plan_predict_device")
         return ns, ts, tt
@@ -160,21 +220,17 @@ class ChainPlan:
         b_off = torch.empty(self.n_tasks + 1, dtype=torch.int64, device=dev)
         u = torch.empty(max(self.total, 1), dtype=torch.int64, device=dev)
         b = torch.empty((max(self.total, 1), 2), dtype=torch.int64, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_plan_chains_device_n(self.handle, anchors.data_ptr(), anchors.numel() // 2, f.data_ptr(), f.numel(), p.data_ptr(), p.numel(),
                                                    min_cnt, min_sc, u_off.data_ptr(), u_off.numel(), u.data_ptr(), u.numel(), b_off.data_ptr(),
                                                    b_off.numel(), b.data_ptr(), b.numel() // 2, st), "mm2c_plan_chains_device_n")
         return u_off, u, b_off, b
 
     def last_epilogue_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_plan_last_epilogue_ms(self.handle, C.byref(ms)), "mm2c_plan_last_epilogue_ms")
-        return ms.value
+        return self._ms("mm2c_plan_last_epilogue_ms")[0]
 
     def last_kernel_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_plan_last_kernel_ms(self.handle, C.byref(ms)), "mm2c_plan_last_kernel_ms")
-        return ms.value
+        return self._ms("mm2c_plan_last_kernel_ms")[0]
 
     def last_route(self):
         """(pieces, pieces run with one wave each, pieces run with sixteen waves each) of the last run -- mm2c_plan_last_route"""
@@ -195,20 +251,7 @@ class ChainPlan:
         return bytes(buf)[:self.n_tasks]
 
     def last_prepass_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_plan_last_prepass_ms(self.handle, C.byref(ms)), "mm2c_plan_last_prepass_ms")
-        return ms.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_plan_last_prepass_ms")[0]
 
 
 class PinnedArray:
@@ -236,7 +279,7 @@ class PinnedArray:
 def chain_batch_host_into(params: Params, offsets, anchors, f, p, avg=None):
     """as chain_batch_host, but into caller-provided int32 arrays (e.g. PinnedArray.array); anchors may be pinned too"""
     lib = N.load()
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    off = _i64(offsets)
     a = anchors.view(np.uint64).reshape(-1, 2)
     assert a.flags.c_contiguous and f.flags.c_contiguous and p.flags.c_contiguous and f.dtype == np.int32 and p.dtype == np.int32
     if off.size and (off[0] < 0 or off[-1] > a.shape[0] or off[-1] > f.size or off[-1] > p.size):
@@ -252,7 +295,7 @@ def chain_batch_host_into(params: Params, offsets, anchors, f, p, avg=None):
 def chain_batch_host(params: Params, offsets, anchors, avg=None):
     """Whole batch from host numpy arrays (uint64 [total,2]); returns (f, p) int32 arrays.  PCIe included."""
     lib = N.load()
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    off = _i64(offsets)
     a = np.ascontiguousarray(anchors).view(np.uint64).reshape(-1, 2)
     total = int(off[-1] - off[0]) if off.size else 0
     if off.size and (off[0] < 0 or off[-1] > a.shape[0]):
@@ -309,7 +352,7 @@ def mm_chain_dp_batch(params: Params, min_cnt, min_sc, offsets, anchors, epilogu
     """mm2c_mm_chain_dp_batch_host: per-task list [(u uint64 [n_u], b uint64 [n_b, 2]), ...]; epilogue_threads == 0 runs the
     epilogue on the GPU, > 0 on that many host threads"""
     lib = N.load()
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    off = _i64(offsets)
     a = np.ascontiguousarray(anchors).view(np.uint64).reshape(-1, 2)
     n_tasks, total = off.size - 1, int(off[-1] - off[0])
     if off[-1] > a.shape[0] or off[0] < 0:
@@ -324,7 +367,7 @@ def mm_chain_dp_batch(params: Params, min_cnt, min_sc, offsets, anchors, epilogu
 def chain_epilogue_host(min_cnt, min_sc, offsets, anchors, f, p, n_threads=4):
     """mm2c_chain_epilogue_host: the epilogue on host threads from f[] / p[] (no GPU involved)"""
     lib = N.load()
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    off = _i64(offsets)
     a = np.ascontiguousarray(anchors).view(np.uint64).reshape(-1, 2)
     f = np.ascontiguousarray(f, dtype=np.int32); p = np.ascontiguousarray(p, dtype=np.int32)
     n_tasks, total = off.size - 1, int(off[-1] - off[0])
@@ -341,15 +384,14 @@ REG_DTYPE = np.dtype([(k, "<i4") for k in ("id", "cnt", "rid", "score", "qs", "q
                      [("flags", "<u4"), ("hash", "<u4"), ("div", "<f4"), ("p", "<u8")])   # mm2c_reg_t = mm_reg1_t, 80 bytes
 
 
-class RegPlan:
+class RegPlan(_Handle):
     """mm2c_regplan_t: chains -> regions on the GPU (mm_gen_regs, hit.c:52-88) for batches of up to n_reads reads, n_u_cap chains, n_b_cap chain anchors"""
 
+    _destroy = "mm2c_regplan_destroy"
+
     def __init__(self, n_reads, n_u_cap, n_b_cap):
-        self.lib = N.load()
         self.n_reads, self.n_u_cap, self.n_b_cap = int(n_reads), int(n_u_cap), int(n_b_cap)
-        self.handle = self.lib.mm2c_regplan_create(self.n_reads, self.n_u_cap, self.n_b_cap)
-        if not self.handle:
-            N.check(-1, "mm2c_regplan_create")
+        self._create("mm2c_regplan_create", self.n_reads, self.n_u_cap, self.n_b_cap)
 
     def run(self, u_off: torch.Tensor, u: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, qlen: torch.Tensor, hash: torch.Tensor, regs: torch.Tensor = None,
             stream=None):
@@ -360,10 +402,8 @@ class RegPlan:
         assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1 and b_off.numel() == self.n_reads + 1
         assert u.element_size() == 8 and u.numel() >= self.n_u_cap and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
         assert qlen.dtype == torch.int32 and qlen.numel() == self.n_reads and hash.element_size() == 4 and hash.numel() == self.n_reads
-        if regs is None:
-            regs = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u.device)
-        assert regs.is_cuda and regs.is_contiguous() and regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        regs = _out(regs, (max(self.n_u_cap, 1), REG_DTYPE.itemsize), torch.uint8, u.device, self.n_u_cap * REG_DTYPE.itemsize)
+        st = _stream(stream)
         N.check(self.lib.mm2c_regplan_run_device(self.handle, u_off.data_ptr(), u.data_ptr(), b_off.data_ptr(), b.data_ptr(), qlen.data_ptr(), hash.data_ptr(),
                                                  regs.data_ptr(), st), "mm2c_regplan_run_device")
         return regs
@@ -375,37 +415,22 @@ class RegPlan:
         return n.value
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_regplan_last_ms(self.handle, C.byref(ms)), "mm2c_regplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_regplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(sort kernel, fill kernel) of the last run"""
-        a, b = C.c_float(0), C.c_float(0)
-        N.check(self.lib.mm2c_regplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_regplan_last_kernel_ms")
-        return a.value, b.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_regplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_regplan_last_kernel_ms", 2)
 
 
 def gen_regs_batch(u_off, u, b_off, b, qlen, hash):
     """mm2c_gen_regs_batch_host: host arrays in, the regions of every read out (REG_DTYPE [u_off[-1] - u_off[0]], indexed like u)"""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
+    uo = _i64(u_off); bo = _i64(b_off)
     uu = np.ascontiguousarray(u, dtype=np.uint64)
-    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    bb = _anchor_rows(b)
     q = np.ascontiguousarray(qlen, dtype=np.int32); h = np.ascontiguousarray(hash, dtype=np.uint32)
     n_reads = uo.size - 1
-    if bo.size != uo.size or q.size != n_reads or h.size != n_reads or (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > uu.size or bo.max() > bb.shape[0])):
+    if bo.size != uo.size or q.size != n_reads or h.size != n_reads or not _fit(n_reads, (uo, uu.size), (bo, bb.shape[0])):
         raise ValueError("offsets do not fit the arrays")
     regs = np.zeros(max(int(uo[-1] - uo[0]), 1) if n_reads > 0 else 1, REG_DTYPE)
     N.check(lib.mm2c_gen_regs_batch_host(n_reads, _np_ptr(uo), _np_ptr(uu), _np_ptr(bo), _np_ptr(bb), _np_ptr(q), _np_ptr(h), _np_ptr(regs)),
@@ -420,29 +445,24 @@ def read_hash(name, qlen_sum, seed=11):
     return int(N.load().mm2c_read_hash(name, int(qlen_sum), int(seed)))
 
 
-class HitPlan:
+class HitPlan(_Handle):
     """mm2c_hitplan_t: regions -> hits on the GPU (mm_set_parent hit.c:125-186, then mm_select_sub hit.c:255-272) for batches of up to n_reads reads and n_u_cap
     regions; it stands behind a RegPlan on the same stream"""
 
+    _destroy = "mm2c_hitplan_destroy"
+
     def __init__(self, n_reads, n_u_cap):
-        self.lib = N.load()
         self.n_reads, self.n_u_cap = int(n_reads), int(n_u_cap)
-        self.handle = self.lib.mm2c_hitplan_create(self.n_reads, self.n_u_cap)
-        if not self.handle:
-            N.check(-1, "mm2c_hitplan_create")
+        self._create("mm2c_hitplan_create", self.n_reads, self.n_u_cap)
 
     def run(self, opt, u_off: torch.Tensor, regs_in: torch.Tensor, regs_out: torch.Tensor = None, n_out: torch.Tensor = None, stream=None):
         """opt: params.hit_opts(); u_off int64 [n_reads + 1] and regs_in (what RegPlan.run returned) on the GPU.  Returns (regs_out uint8 [n_u_cap, 80], n_out int32
         [n_reads]): the hits of read r are rows u_off[r] .. u_off[r] + n_out[r]; the rows behind them are unspecified.  Asynchronous."""
         assert u_off.is_cuda and u_off.is_contiguous() and u_off.dtype == torch.int64 and u_off.numel() == self.n_reads + 1
         assert regs_in.is_cuda and regs_in.is_contiguous() and regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
-        if regs_out is None:
-            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
-        if n_out is None:
-            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
-        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
-        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        regs_out = _out(regs_out, (max(self.n_u_cap, 1), REG_DTYPE.itemsize), torch.uint8, u_off.device, self.n_u_cap * REG_DTYPE.itemsize)
+        n_out = _out(n_out, max(self.n_reads, 1), torch.int32, u_off.device, self.n_reads * 4, "dtype")
+        st = _stream(stream)
         N.check(self.lib.mm2c_hitplan_run_device(self.handle, C.byref(opt), u_off.data_ptr(), regs_in.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(), st),
                 "mm2c_hitplan_run_device")
         return regs_out, n_out[:self.n_reads]
@@ -456,13 +476,9 @@ class HitPlan:
         assert regs_in.is_cuda and regs_in.is_contiguous() and regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
         assert seg_len.is_cuda and seg_len.is_contiguous() and seg_len.dtype == torch.int32 and seg_len.numel() >= self.n_reads * mopt.n_segs
         assert gap_ref is None or (gap_ref.is_cuda and gap_ref.is_contiguous() and gap_ref.dtype == torch.int32 and gap_ref.numel() >= self.n_reads)
-        if regs_out is None:
-            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
-        if n_out is None:
-            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
-        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
-        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        regs_out = _out(regs_out, (max(self.n_u_cap, 1), REG_DTYPE.itemsize), torch.uint8, u_off.device, self.n_u_cap * REG_DTYPE.itemsize)
+        n_out = _out(n_out, max(self.n_reads, 1), torch.int32, u_off.device, self.n_reads * 4, "dtype")
+        st = _stream(stream)
         N.check(self.lib.mm2c_hitplan_run_device_multi(self.handle, C.byref(opt), C.byref(mopt), u_off.data_ptr(), seg_len.data_ptr(),
                                                        gap_ref.data_ptr() if gap_ref is not None else None, regs_in.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(), st),
                 "mm2c_hitplan_run_device_multi")
@@ -475,30 +491,17 @@ class HitPlan:
         return n.value
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_hitplan_last_ms(self.handle, C.byref(ms)), "mm2c_hitplan_last_ms")
-        return ms.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_hitplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_hitplan_last_ms")[0]
 
 
 def select_hits_batch(opt, u_off, regs):
     """mm2c_select_hits_batch_host: host arrays in -> (regs_out REG_DTYPE [u_off[-1] - u_off[0]], n_out int32 [n_reads]); the hits of read r are
     regs_out[u_off[r] - u_off[0] :][:n_out[r]]"""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64))
-    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    uo = _i64(u_off)
+    rr = _reg_rows(regs)
     n_reads = uo.size - 1
-    if n_reads > 0 and (uo[0] < 0 or uo.max() > rr.shape[0]):
+    if not _fit(n_reads, (uo, rr.shape[0])):
         raise ValueError("offsets do not fit the arrays")
     n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
     out = np.zeros(max(n_u, 1), REG_DTYPE)
@@ -510,12 +513,12 @@ def select_hits_batch(opt, u_off, regs):
 def select_hits_multi_batch(opt, mopt, u_off, seg_len, regs, gap_ref=None):
     """mm2c_select_hits_multi_batch_host: host arrays in -> (regs_out, n_out) as select_hits_batch, with mm_select_sub_multi in the place of mm_select_sub"""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64))
-    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
+    uo = _i64(u_off)
+    rr = _reg_rows(regs)
     sl = np.ascontiguousarray(seg_len, dtype=np.int32).reshape(-1)
     gr = None if gap_ref is None else np.ascontiguousarray(gap_ref, dtype=np.int32)
     n_reads = uo.size - 1
-    if (n_reads > 0 and (uo[0] < 0 or uo.max() > rr.shape[0])) or sl.size != n_reads * mopt.n_segs or (gr is not None and gr.size != n_reads):
+    if not _fit(n_reads, (uo, rr.shape[0])) or sl.size != n_reads * mopt.n_segs or (gr is not None and gr.size != n_reads):
         raise ValueError("offsets do not fit the arrays")
     n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
     out = np.zeros(max(n_u, 1), REG_DTYPE)
@@ -525,17 +528,16 @@ def select_hits_multi_batch(opt, mopt, u_off, seg_len, regs, gap_ref=None):
     return out[:n_u], n_out[:n_reads]
 
 
-class SegPlan:
+class SegPlan(_Handle):
     """mm2c_segplan_t: the hits of fragments of n_segs segments -> chains, anchors and regions per segment on the GPU (mm_seg_gen hit.c:373-427) for batches of up
     to n_frags fragments, n_u_cap hits and n_b_cap chain anchors; it stands behind HitPlan.run_multi on the same stream, and a HitPlan (pri_ratio 0) and a MapqPlan
     (do_join 0) over n_frags * n_segs "segment reads" stand behind it."""
 
+    _destroy = "mm2c_segplan_destroy"
+
     def __init__(self, n_frags, n_segs, n_u_cap, n_b_cap):
-        self.lib = N.load()
         self.n_frags, self.n_segs, self.n_u_cap, self.n_b_cap = int(n_frags), int(n_segs), int(n_u_cap), int(n_b_cap)
-        self.handle = self.lib.mm2c_segplan_create(self.n_frags, self.n_segs, self.n_u_cap, self.n_b_cap)
-        if not self.handle:
-            N.check(-1, "mm2c_segplan_create")
+        self._create("mm2c_segplan_create", self.n_frags, self.n_segs, self.n_u_cap, self.n_b_cap)
         self.n_seg_reads = self.n_frags * self.n_segs
         self.n_su_cap = int(self.lib.mm2c_segplan_seg_chain_cap(self.handle))
 
@@ -563,7 +565,7 @@ class SegPlan:
         assert out["sb"].numel() >= 2 * self.n_b_cap and out["seg_regs"].numel() >= self.n_su_cap * REG_DTYPE.itemsize and out["seg_hash"].numel() >= self.n_seg_reads
         for t in out.values():
             assert t is None or (t.is_cuda and t.is_contiguous())
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_segplan_run_device(self.handle, u_off.data_ptr(), regs.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(), seg_len.data_ptr(),
                                                  hash.data_ptr(), rep_len.data_ptr() if rep_len is not None else None, out["su_off"].data_ptr(), out["su"].data_ptr(),
                                                  out["sb_off"].data_ptr(), out["sb"].data_ptr(), out["seg_regs"].data_ptr(), out["seg_hash"].data_ptr(),
@@ -583,40 +585,25 @@ class SegPlan:
         return nu, na
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_segplan_last_ms(self.handle, C.byref(ms)), "mm2c_segplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_segplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(seg_count, the two scans, seg_scatter, the region kernels, seg_mark) of the last run"""
-        v = [C.c_float(0) for _ in range(5)]
-        N.check(self.lib.mm2c_segplan_last_kernel_ms(self.handle, *[C.byref(x) for x in v]), "mm2c_segplan_last_kernel_ms")
-        return tuple(x.value for x in v)
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_segplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_segplan_last_kernel_ms", 5)
 
 
 def seg_gen_batch(n_segs, u_off, regs, n_in, b_off, b, seg_len, hash, rep_len=None):
     """mm2c_seg_gen_batch_host: host arrays in -> dict(su_off, su uint64, sb_off, sb uint64 [., 2], seg_regs REG_DTYPE, seg_hash uint32, seg_rep_len int32 or None);
     segment read f * n_segs + s owns su[su_off[k] : su_off[k+1]] (and seg_regs likewise) and sb[sb_off[k] : sb_off[k+1]]"""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
-    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
-    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    uo = _i64(u_off); bo = _i64(b_off)
+    rr = _reg_rows(regs)
+    bb = _anchor_rows(b)
     ni = np.ascontiguousarray(n_in, dtype=np.int32); sl = np.ascontiguousarray(seg_len, dtype=np.int32).reshape(-1); h = np.ascontiguousarray(hash, dtype=np.uint32)
     rl = None if rep_len is None else np.ascontiguousarray(rep_len, dtype=np.int32)
     n_frags, n_segs = uo.size - 1, int(n_segs)
     if bo.size != uo.size or ni.size != n_frags or h.size != n_frags or sl.size != n_frags * n_segs or (rl is not None and rl.size != n_frags) or \
-            (n_frags > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0])):
+            not _fit(n_frags, (uo, rr.shape[0]), (bo, bb.shape[0])):
         raise ValueError("offsets do not fit the arrays")
     n_u = int(uo[-1] - uo[0]) if n_frags > 0 else 0
     n_b = int(bo[-1] - bo[0]) if n_frags > 0 else 0
@@ -653,22 +640,21 @@ def ksw_task_scratch(qlen, tlen, w, flag):
     return int(N.load().mm2c_ksw_task_scratch(int(qlen), int(tlen), int(w), int(flag)))
 
 
-class KswPlan:
+class KswPlan(_Handle):
     """mm2c_kswplan_t: ksw_extd2_sse (ksw2_extd2_sse.c) on the GPU for batches of up to n_tasks_cap independent tasks over a pool of seq_cap bases and cigar_cap
     CIGAR words, one wave per scratch slot.  Either scratch_bytes (the default cut into slots of 4 MiB, for tasks up to that size) or n_slots and slot_bytes (the
     caller's cut: a task runs in a slot of at least ksw_task_scratch(...) bytes).  Byte for byte the reference's ksw_extz_t and CIGAR."""
 
+    _destroy = "mm2c_kswplan_destroy"
+
     def __init__(self, n_tasks_cap, seq_cap, cigar_cap, scratch_bytes=None, n_slots=None, slot_bytes=None):
-        self.lib = N.load()
         self.n_tasks_cap, self.seq_cap, self.cigar_cap = int(n_tasks_cap), int(seq_cap), int(cigar_cap)
         if (scratch_bytes is None) == (n_slots is None or slot_bytes is None):
             raise ValueError("give scratch_bytes, or n_slots and slot_bytes")
         if scratch_bytes is not None:
-            self.handle = self.lib.mm2c_kswplan_create(self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(scratch_bytes))
+            self._create("mm2c_kswplan_create", self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(scratch_bytes))
         else:
-            self.handle = self.lib.mm2c_kswplan_create_slots(self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(n_slots), int(slot_bytes))
-        if not self.handle:
-            N.check(-1, "mm2c_kswplan_create")
+            self._create("mm2c_kswplan_create_slots", self.n_tasks_cap, self.seq_cap, self.cigar_cap, int(n_slots), int(slot_bytes), what="mm2c_kswplan_create")
         self.slot_bytes, self.n_slots = int(self.lib.mm2c_kswplan_slot_bytes(self.handle)), int(self.lib.mm2c_kswplan_n_slots(self.handle))
 
     def run(self, score, n_tasks, tasks: torch.Tensor, seq: torch.Tensor, cig_off: torch.Tensor, res: torch.Tensor = None, cigar: torch.Tensor = None, stream=None):
@@ -679,15 +665,10 @@ class KswPlan:
             assert t.is_cuda and t.is_contiguous()
         assert tasks.numel() * tasks.element_size() >= n_tasks * KSW_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap
         assert cig_off.dtype == torch.int64 and cig_off.numel() >= n_tasks + 1 and 0 <= n_tasks <= self.n_tasks_cap
-        dev = tasks.device
-        if res is None:
-            res = torch.empty((max(n_tasks, 1), KSW_RES_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if cigar is None:
-            cigar = torch.empty(max(self.cigar_cap, 1), dtype=torch.int32, device=dev)
-        assert res.is_cuda and res.is_contiguous() and res.numel() * res.element_size() >= n_tasks * KSW_RES_DTYPE.itemsize
-        assert cigar.is_cuda and cigar.is_contiguous() and cigar.element_size() == 4 and cigar.numel() >= self.cigar_cap
+        res = _out(res, (max(n_tasks, 1), KSW_RES_DTYPE.itemsize), torch.uint8, tasks.device, n_tasks * KSW_RES_DTYPE.itemsize)
+        cigar = _out(cigar, max(self.cigar_cap, 1), torch.int32, tasks.device, self.cigar_cap * 4, "width")
         sc = _ksw_score_bytes(score)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_kswplan_run_device(self.handle, _np_ptr(sc), n_tasks, tasks.data_ptr(), seq.data_ptr(), cig_off.data_ptr(), res.data_ptr(),
                                                  cigar.data_ptr(), st), "mm2c_kswplan_run_device")
         return res, cigar
@@ -703,26 +684,11 @@ class KswPlan:
         N.check(self.counts()[0], "mm2c_kswplan_check")
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_kswplan_last_ms(self.handle, C.byref(ms)), "mm2c_kswplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_kswplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(ksw_rows,) of the last run: rows and backtrack are one kernel"""
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_kswplan_last_kernel_ms(self.handle, C.byref(ms)), "mm2c_kswplan_last_kernel_ms")
-        return (ms.value,)
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_kswplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_kswplan_last_kernel_ms")
 
 
 def ksw_extd2_batch(score, tasks, seq, cig_off, scratch_bytes=0, res=None, cigar=None):
@@ -758,17 +724,16 @@ def _zdrop_opt_bytes(opt):
     return np.ascontiguousarray(np.array([int(x) for x in opt], np.int32))
 
 
-class ExtraPlan:
+class ExtraPlan(_Handle):
     """mm2c_extraplan_t: mm_update_extra (align.c:240-286) for batches of regions and mm_test_zdrop (align.c:47-89) on a KswPlan's device outputs, one wave per item,
     byte for byte the reference.  n_cap items, a pool of seq_cap bases, cig_in_cap input CIGAR words (for z-drop runs: the ksw plan's cigar_cap), cig_out_cap output
     words; CIGARs beyond EXTRA_LDS_WORDS words need one of n_slots scratch slots of slot_words words."""
 
+    _destroy = "mm2c_extraplan_destroy"
+
     def __init__(self, n_cap, seq_cap, cig_in_cap, cig_out_cap=0, n_slots=0, slot_words=0):
-        self.lib = N.load()
         self.n_cap, self.seq_cap, self.cig_in_cap, self.cig_out_cap = int(n_cap), int(seq_cap), int(cig_in_cap), int(cig_out_cap)
-        self.handle = self.lib.mm2c_extraplan_create(self.n_cap, self.seq_cap, self.cig_in_cap, self.cig_out_cap, int(n_slots), int(slot_words))
-        if not self.handle:
-            N.check(-1, "mm2c_extraplan_create")
+        self._create("mm2c_extraplan_create", self.n_cap, self.seq_cap, self.cig_in_cap, self.cig_out_cap, int(n_slots), int(slot_words))
 
     def update(self, score, is_eqx, n_regs, tasks: torch.Tensor, seq: torch.Tensor, in_off: torch.Tensor, cig_in: torch.Tensor, out_off: torch.Tensor,
                res: torch.Tensor = None, cig_out: torch.Tensor = None, stream=None):
@@ -780,15 +745,10 @@ class ExtraPlan:
         assert tasks.numel() * tasks.element_size() >= n * EXTRA_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap and 0 <= n <= self.n_cap
         assert in_off.dtype == torch.int64 and in_off.numel() >= n and out_off.dtype == torch.int64 and out_off.numel() >= n + 1
         assert cig_in.element_size() == 4 and cig_in.numel() >= self.cig_in_cap
-        dev = tasks.device
-        if res is None:
-            res = torch.empty((max(n, 1), EXTRA_RES_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if cig_out is None:
-            cig_out = torch.empty(max(self.cig_out_cap, 1), dtype=torch.int32, device=dev)
-        assert res.is_cuda and res.is_contiguous() and res.numel() * res.element_size() >= n * EXTRA_RES_DTYPE.itemsize
-        assert cig_out.is_cuda and cig_out.is_contiguous() and cig_out.element_size() == 4 and cig_out.numel() >= self.cig_out_cap
+        res = _out(res, (max(n, 1), EXTRA_RES_DTYPE.itemsize), torch.uint8, tasks.device, n * EXTRA_RES_DTYPE.itemsize)
+        cig_out = _out(cig_out, max(self.cig_out_cap, 1), torch.int32, tasks.device, self.cig_out_cap * 4, "width")
         sc = _ksw_score_bytes(score)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_extraplan_run_device(self.handle, _np_ptr(sc), int(bool(is_eqx)), n, tasks.data_ptr(), seq.data_ptr(), in_off.data_ptr(), cig_in.data_ptr(),
                                                    out_off.data_ptr(), res.data_ptr(), cig_out.data_ptr(), st), "mm2c_extraplan_run_device")
         return res, cig_out
@@ -802,11 +762,9 @@ class ExtraPlan:
         assert tasks.numel() * tasks.element_size() >= n * KSW_TASK_DTYPE.itemsize and seq.element_size() == 1 and seq.numel() >= self.seq_cap and 0 <= n <= self.n_cap
         assert cig_off.dtype == torch.int64 and cig_off.numel() >= n + 1 and kres.numel() * kres.element_size() >= n * KSW_RES_DTYPE.itemsize
         assert cigar.element_size() == 4 and cigar.numel() >= self.cig_in_cap
-        if zres is None:
-            zres = torch.empty((max(n, 1), ZDROP_RES_DTYPE.itemsize), dtype=torch.uint8, device=tasks.device)
-        assert zres.is_cuda and zres.is_contiguous() and zres.numel() * zres.element_size() >= n * ZDROP_RES_DTYPE.itemsize
+        zres = _out(zres, (max(n, 1), ZDROP_RES_DTYPE.itemsize), torch.uint8, tasks.device, n * ZDROP_RES_DTYPE.itemsize)
         sc, zo = _ksw_score_bytes(score), _zdrop_opt_bytes(opt)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_extraplan_zdrop_run_device(self.handle, _np_ptr(sc), _np_ptr(zo), n, tasks.data_ptr(), seq.data_ptr(), cig_off.data_ptr(), kres.data_ptr(),
                                                          cigar.data_ptr(), zres.data_ptr(), st), "mm2c_extraplan_zdrop_run_device")
         return zres
@@ -822,26 +780,11 @@ class ExtraPlan:
         N.check(self.counts()[0], "mm2c_extraplan_check")
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_extraplan_last_ms(self.handle, C.byref(ms)), "mm2c_extraplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_extraplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(extra_update, extra_zdrop) of their last runs; 0 for one that has not run"""
-        a, b = C.c_float(0), C.c_float(0)
-        N.check(self.lib.mm2c_extraplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_extraplan_last_kernel_ms")
-        return a.value, b.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_extraplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_extraplan_last_kernel_ms", 2)
 
 
 def update_extra_batch(score, is_eqx, tasks, seq, in_off, cig_in, out_off, res=None, cig_out=None):
@@ -902,43 +845,30 @@ def _aln_opt_bytes(opt):
     return np.ascontiguousarray(np.asarray(opt, dtype=ALN_OPT_DTYPE).reshape(1))
 
 
-class RefSeq:
+class RefSeq(_Handle):
     """mm2c_refseq_t: the packed reference mi->S (uint32 words, 8 bases each) with offset (uint64) and len (uint32) of every mi->seq[], resident on the GPU"""
 
+    _destroy = "mm2c_refseq_destroy"
+
     def __init__(self, offset, length, S):
-        self.lib = N.load()
         off = np.ascontiguousarray(offset, dtype=np.uint64); ln = np.ascontiguousarray(length, dtype=np.uint32); S = np.ascontiguousarray(S, dtype=np.uint32)
         if off.size != ln.size:
             raise ValueError("offset and len must have one entry per sequence")
         self.n_seq, self.n_words = int(off.size), int(S.size)
-        self.handle = self.lib.mm2c_refseq_create(self.n_seq, _np_ptr(off), _np_ptr(ln), _np_ptr(S), self.n_words)
-        if not self.handle:
-            N.check(-2, "mm2c_refseq_create")
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_refseq_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("mm2c_refseq_create", self.n_seq, _np_ptr(off), _np_ptr(ln), _np_ptr(S), self.n_words, code=-2)
 
 
-class AlnPlan:
+class AlnPlan(_Handle):
     """mm2c_alnplan_t: final regions -> the ksw tasks mm_align1 (align.c:565-771) issues when no task drops, with their items and ONE sequence pool that is the d_seq
     of a KswPlan and of an ExtraPlan, byte for byte the reference.  Capacities: regions, items, tasks, pool bytes, anchors, read bases."""
 
+    _destroy = "mm2c_alnplan_destroy"
+
     def __init__(self, n_regs_cap, n_items_cap, n_tasks_cap, pool_cap, n_b_cap, reads_cap, cig_shift=0, n_slots=0, slot_words=0):
-        self.lib = N.load()
         self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.pool_cap = int(n_regs_cap), int(n_items_cap), int(n_tasks_cap), int(pool_cap)
         self.n_b_cap, self.reads_cap, self.cig_shift = int(n_b_cap), int(reads_cap), int(cig_shift)
-        self.handle = self.lib.mm2c_alnplan_create(self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.pool_cap, self.n_b_cap, self.reads_cap, self.cig_shift,
-                                                   int(n_slots), int(slot_words))
-        if not self.handle:
-            N.check(-2, "mm2c_alnplan_create")
+        self._create("mm2c_alnplan_create", self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.pool_cap, self.n_b_cap, self.reads_cap, self.cig_shift, int(n_slots),
+                     int(slot_words), code=-2)
 
     def run(self, opt, ref: RefSeq, n_reads, n_regs, u_off: torch.Tensor, regs: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, read_off: torch.Tensor, reads: torch.Tensor,
             n_b: torch.Tensor = None, aln_regs: torch.Tensor = None, items: torch.Tensor = None, tasks: torch.Tensor = None, cig_off: torch.Tensor = None,
@@ -952,23 +882,14 @@ class AlnPlan:
         assert all(t.dtype == torch.int64 and t.numel() >= n_reads + 1 for t in (u_off, b_off, read_off)) and 0 <= n <= self.n_regs_cap
         assert regs.numel() * regs.element_size() >= n * REG_DTYPE.itemsize and b.numel() * b.element_size() >= 16 * self.n_b_cap and reads.element_size() == 1 and reads.numel() >= self.reads_cap
         dev = regs.device
-        if aln_regs is None:
-            aln_regs = torch.empty((max(n, 1), ALN_REG_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if items is None:
-            items = torch.empty((max(self.n_items_cap, 1), ALN_ITEM_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if tasks is None:
-            tasks = torch.empty((max(self.n_tasks_cap, 1), KSW_TASK_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if cig_off is None:
-            cig_off = torch.empty(self.n_tasks_cap + 1, dtype=torch.int64, device=dev)
-        if pool is None:
-            pool = torch.empty(max(self.pool_cap, 16), dtype=torch.uint8, device=dev)
-        for t in (aln_regs, items, tasks, cig_off, pool):
-            assert t.is_cuda and t.is_contiguous()
-        assert aln_regs.numel() * aln_regs.element_size() >= n * ALN_REG_DTYPE.itemsize and items.numel() * items.element_size() >= self.n_items_cap * ALN_ITEM_DTYPE.itemsize
-        assert tasks.numel() * tasks.element_size() >= self.n_tasks_cap * KSW_TASK_DTYPE.itemsize and cig_off.dtype == torch.int64 and cig_off.numel() >= self.n_tasks_cap + 1
-        assert pool.element_size() == 1 and pool.numel() >= self.pool_cap and (n_b is None or (n_b.is_cuda and n_b.dtype == torch.int64 and n_b.numel() >= n_reads))
+        aln_regs = _out(aln_regs, (max(n, 1), ALN_REG_DTYPE.itemsize), torch.uint8, dev, n * ALN_REG_DTYPE.itemsize)
+        items = _out(items, (max(self.n_items_cap, 1), ALN_ITEM_DTYPE.itemsize), torch.uint8, dev, self.n_items_cap * ALN_ITEM_DTYPE.itemsize)
+        tasks = _out(tasks, (max(self.n_tasks_cap, 1), KSW_TASK_DTYPE.itemsize), torch.uint8, dev, self.n_tasks_cap * KSW_TASK_DTYPE.itemsize)
+        cig_off = _out(cig_off, self.n_tasks_cap + 1, torch.int64, dev, (self.n_tasks_cap + 1) * 8, "dtype")
+        pool = _out(pool, max(self.pool_cap, 16), torch.uint8, dev, self.pool_cap, "width")
+        assert n_b is None or (n_b.is_cuda and n_b.dtype == torch.int64 and n_b.numel() >= n_reads)
         o = _aln_opt_bytes(opt)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_alnplan_run_device(self.handle, _np_ptr(o), ref.handle, n_reads, n, u_off.data_ptr(), regs.data_ptr(), b_off.data_ptr(),
                                                  n_b.data_ptr() if n_b is not None else None, b.data_ptr(), read_off.data_ptr(), reads.data_ptr(), aln_regs.data_ptr(),
                                                  items.data_ptr(), tasks.data_ptr(), cig_off.data_ptr(), pool.data_ptr(), st), "mm2c_alnplan_run_device")
@@ -994,17 +915,6 @@ class AlnPlan:
 
     def last_ms(self):
         return sum(self.last_kernel_ms())
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_alnplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def align_tasks_batch(opt, ref_offset, ref_len, S, u_off, regs, b_off, b, read_off, reads, n_items_cap, n_tasks_cap, pool_cap, cig_shift=0, fill=None):
@@ -1039,17 +949,16 @@ def align_tasks_batch(opt, ref_offset, ref_len, S, u_off, regs, b_off, b, read_o
                 totals=tuple(int(x) for x in tot), rc=rc)
 
 
-class MapqPlan:
+class MapqPlan(_Handle):
     """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
     reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the
     plan's table holds -- the host's own logf, filled at creation; 2^22 (16 MB) by default, at most 2^24 - 1."""
 
+    _destroy = "mm2c_mapqplan_destroy"
+
     def __init__(self, n_reads, n_u_cap, n_b_cap, max_log_arg=1 << 22):
-        self.lib = N.load()
         self.n_reads, self.n_u_cap, self.n_b_cap, self.max_log_arg = int(n_reads), int(n_u_cap), int(n_b_cap), int(max_log_arg)
-        self.handle = self.lib.mm2c_mapqplan_create(self.n_reads, self.n_u_cap, self.n_b_cap, self.max_log_arg)
-        if not self.handle:
-            N.check(-1, "mm2c_mapqplan_create")
+        self._create("mm2c_mapqplan_create", self.n_reads, self.n_u_cap, self.n_b_cap, self.max_log_arg)
 
     def run(self, opt, u_off: torch.Tensor, regs_in: torch.Tensor, n_in: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, qlen: torch.Tensor,
             rep_len: torch.Tensor, regs_out: torch.Tensor = None, n_out: torch.Tensor = None, anchors=False, b_out: torch.Tensor = None,
@@ -1064,20 +973,13 @@ class MapqPlan:
         assert regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
         assert n_in.dtype == torch.int32 and n_in.numel() >= self.n_reads and qlen.dtype == torch.int32 and qlen.numel() == self.n_reads
         assert rep_len.dtype == torch.int32 and rep_len.numel() == self.n_reads
-        if regs_out is None:
-            regs_out = torch.empty((max(self.n_u_cap, 1), REG_DTYPE.itemsize), dtype=torch.uint8, device=u_off.device)
-        if n_out is None:
-            n_out = torch.empty(max(self.n_reads, 1), dtype=torch.int32, device=u_off.device)
-        if (anchors or n_b_out is not None) and b_out is None:
-            b_out = torch.empty((max(self.n_b_cap, 1), 2), dtype=torch.int64, device=u_off.device)
-        if b_out is not None and n_b_out is None:
-            n_b_out = torch.empty(max(self.n_reads, 1), dtype=torch.int64, device=u_off.device)
-        assert regs_out.is_cuda and regs_out.is_contiguous() and regs_out.numel() * regs_out.element_size() >= self.n_u_cap * REG_DTYPE.itemsize
-        assert n_out.is_cuda and n_out.is_contiguous() and n_out.dtype == torch.int32 and n_out.numel() >= self.n_reads
-        if b_out is not None:
-            assert b_out.is_cuda and b_out.is_contiguous() and b_out.element_size() == 8 and b_out.numel() >= 2 * self.n_b_cap
-            assert n_b_out.is_cuda and n_b_out.is_contiguous() and n_b_out.dtype == torch.int64 and n_b_out.numel() >= self.n_reads
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        dev = u_off.device
+        regs_out = _out(regs_out, (max(self.n_u_cap, 1), REG_DTYPE.itemsize), torch.uint8, dev, self.n_u_cap * REG_DTYPE.itemsize)
+        n_out = _out(n_out, max(self.n_reads, 1), torch.int32, dev, self.n_reads * 4, "dtype")
+        if anchors or b_out is not None or n_b_out is not None:
+            b_out = _out(b_out, (max(self.n_b_cap, 1), 2), torch.int64, dev, self.n_b_cap * 16, "width")
+            n_b_out = _out(n_b_out, max(self.n_reads, 1), torch.int64, dev, self.n_reads * 8, "dtype")
+        st = _stream(stream)
         N.check(self.lib.mm2c_mapqplan_run_device(self.handle, C.byref(opt), u_off.data_ptr(), regs_in.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(),
                                                   qlen.data_ptr(), rep_len.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(),
                                                   b_out.data_ptr() if b_out is not None else None, n_b_out.data_ptr() if b_out is not None else None, st),
@@ -1097,26 +999,11 @@ class MapqPlan:
         return nj
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_mapqplan_last_ms(self.handle, C.byref(ms)), "mm2c_mapqplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_mapqplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(mapq_join, mapq_gather) of the last run; the second is 0 when no anchors were asked for"""
-        a, b = C.c_float(0), C.c_float(0)
-        N.check(self.lib.mm2c_mapqplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b)), "mm2c_mapqplan_last_kernel_ms")
-        return a.value, b.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_mapqplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_mapqplan_last_kernel_ms", 2)
 
 
 def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=True, max_log_arg=1 << 22):
@@ -1124,13 +1011,13 @@ def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=Tru
     None, n_b_out int64 [n_reads] or None); the final regions of read r are regs_out[u_off[r] - u_off[0] :][:n_out[r]], its anchors
     b_out[b_off[r] - b_off[0] :][:n_b_out[r]].  Raises with code -3 when a primary lay beyond the table of max_log_arg entries."""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
-    rr = np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize)
-    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    uo = _i64(u_off); bo = _i64(b_off)
+    rr = _reg_rows(regs)
+    bb = _anchor_rows(b)
     ni = np.ascontiguousarray(n_in, dtype=np.int32); q = np.ascontiguousarray(qlen, dtype=np.int32); rl = np.ascontiguousarray(rep_len, dtype=np.int32)
     n_reads = uo.size - 1
     if bo.size != uo.size or ni.size != n_reads or q.size != n_reads or rl.size != n_reads or \
-            (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0])):
+            not _fit(n_reads, (uo, rr.shape[0]), (bo, bb.shape[0])):
         raise ValueError("offsets do not fit the arrays")
     n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
     n_b = int(bo[-1] - bo[0]) if n_reads > 0 else 0
@@ -1147,17 +1034,16 @@ def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=Tru
 ERR_DTYPE = np.dtype([("n_match", "<i4"), ("n_tot", "<i4")])                   # mm2c_err_t
 
 
-class EstErrPlan:
+class EstErrPlan(_Handle):
     """mm2c_errplan_t: the counts of mm_est_err (map.c:357, esterr.c) on the GPU for batches of up to n_reads reads, n_u_cap final regions, n_b_cap chain anchors
     and n_mini_cap minimizer positions; it stands behind a MapqPlan on the same stream.  The device makes (n_match, n_tot) per region and avg_k per read, which
     are exact by construction; est_err_apply / est_err_div turn them into div with the host's own pow."""
 
+    _destroy = "mm2c_errplan_destroy"
+
     def __init__(self, n_reads, n_u_cap, n_b_cap, n_mini_cap):
-        self.lib = N.load()
         self.n_reads, self.n_u_cap, self.n_b_cap, self.n_mini_cap = int(n_reads), int(n_u_cap), int(n_b_cap), int(n_mini_cap)
-        self.handle = self.lib.mm2c_errplan_create(self.n_reads, self.n_u_cap, self.n_b_cap, self.n_mini_cap)
-        if not self.handle:
-            N.check(-1, "mm2c_errplan_create")
+        self._create("mm2c_errplan_create", self.n_reads, self.n_u_cap, self.n_b_cap, self.n_mini_cap)
 
     def run(self, u_off: torch.Tensor, regs: torch.Tensor, n_in: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, mini_off: torch.Tensor,
             mini_pos: torch.Tensor, qlen: torch.Tensor, ref_len: torch.Tensor, err: torch.Tensor = None, avg_k: torch.Tensor = None, stream=None):
@@ -1172,13 +1058,9 @@ class EstErrPlan:
         assert regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and b.element_size() == 8 and b.numel() >= 2 * self.n_b_cap
         assert mini_pos.element_size() == 8 and mini_pos.numel() >= self.n_mini_cap and ref_len.element_size() == 4
         assert n_in.dtype == torch.int32 and n_in.numel() >= self.n_reads and qlen.dtype == torch.int32 and qlen.numel() == self.n_reads
-        if err is None:
-            err = torch.empty((max(self.n_u_cap, 1), 2), dtype=torch.int32, device=u_off.device)
-        if avg_k is None:
-            avg_k = torch.empty(max(self.n_reads, 1), dtype=torch.float32, device=u_off.device)
-        assert err.is_cuda and err.is_contiguous() and err.dtype == torch.int32 and err.numel() >= 2 * self.n_u_cap
-        assert avg_k.is_cuda and avg_k.is_contiguous() and avg_k.dtype == torch.float32 and avg_k.numel() >= self.n_reads
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        err = _out(err, (max(self.n_u_cap, 1), 2), torch.int32, u_off.device, self.n_u_cap * 8, "dtype")
+        avg_k = _out(avg_k, max(self.n_reads, 1), torch.float32, u_off.device, self.n_reads * 4, "dtype")
+        st = _stream(stream)
         N.check(self.lib.mm2c_errplan_run_device(self.handle, u_off.data_ptr(), regs.data_ptr(), n_in.data_ptr(), b_off.data_ptr(), b.data_ptr(), mini_off.data_ptr(),
                                                  mini_pos.data_ptr(), qlen.data_ptr(), int(ref_len.numel()), ref_len.data_ptr(), err.data_ptr(), avg_k.data_ptr(), st),
                 "mm2c_errplan_run_device")
@@ -1195,26 +1077,11 @@ class EstErrPlan:
         N.check(self.refused()[0], "mm2c_errplan_check")
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_errplan_last_ms(self.handle, C.byref(ms)), "mm2c_errplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_errplan_last_ms")[0]
 
     def last_kernel_ms(self):
         """(err_reads, err_walk, err_finish) of the last run"""
-        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
-        N.check(self.lib.mm2c_errplan_last_kernel_ms(self.handle, C.byref(a), C.byref(b), C.byref(c)), "mm2c_errplan_last_kernel_ms")
-        return a.value, b.value, c.value
-
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_errplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ms("mm2c_errplan_last_kernel_ms", 3)
 
 
 def est_err_div(n_match, n_tot, avg_k):
@@ -1241,14 +1108,14 @@ def est_err_batch(u_off, regs, n_in, b_off, b, mini_off, mini_pos, qlen, ref_len
     """mm2c_est_err_batch_host: host arrays in -> (regs REG_DTYPE [u_off[-1] - u_off[0]], a copy with div written, err ERR_DTYPE of the same length,
     avg_k float32 [n_reads]); the regions of read r are regs[u_off[r] - u_off[0] :][:n_in[r]]"""
     lib = N.load()
-    uo = np.ascontiguousarray(np.asarray(u_off, dtype=np.int64)); bo = np.ascontiguousarray(np.asarray(b_off, dtype=np.int64))
-    mo = np.ascontiguousarray(np.asarray(mini_off, dtype=np.int64))
-    rr = np.array(np.ascontiguousarray(regs).view(np.uint8).reshape(-1, REG_DTYPE.itemsize))
-    bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2); mp = np.ascontiguousarray(mini_pos, dtype=np.uint64).reshape(-1)
+    uo = _i64(u_off); bo = _i64(b_off)
+    mo = _i64(mini_off)
+    rr = np.array(_reg_rows(regs))
+    bb = _anchor_rows(b); mp = np.ascontiguousarray(mini_pos, dtype=np.uint64).reshape(-1)
     ni = np.ascontiguousarray(n_in, dtype=np.int32); q = np.ascontiguousarray(qlen, dtype=np.int32); rl = np.ascontiguousarray(ref_len, dtype=np.uint32)
     n_reads = uo.size - 1
     if bo.size != uo.size or mo.size != uo.size or ni.size != n_reads or q.size != n_reads or \
-            (n_reads > 0 and (uo[0] < 0 or bo[0] < 0 or mo[0] < 0 or uo.max() > rr.shape[0] or bo.max() > bb.shape[0] or mo.max() > mp.size)):
+            not _fit(n_reads, (uo, rr.shape[0]), (bo, bb.shape[0]), (mo, mp.size)):
         raise ValueError("offsets do not fit the arrays")
     n_u = int(uo[-1] - uo[0]) if n_reads > 0 else 0
     err = np.zeros(max(n_u, 1), ERR_DTYPE)
@@ -1262,17 +1129,16 @@ def est_err_batch(u_off, regs, n_in, b_off, b, mini_off, mini_pos, qlen, ref_len
 MATCH_DTYPE = np.dtype([("cr_off", "<i8"), ("n", "<u4"), ("q_pos", "<u4"), ("q_span", "<u4"), ("seg_tandem", "<u4")])   # mm2c_match_t
 
 
-class SeedPlan:
+class SeedPlan(_Handle):
     """mm2c_seedplan_t: seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) for a batch of reads"""
 
+    _destroy = "mm2c_seedplan_destroy"
+
     def __init__(self, match_off, anchor_off):
-        self.lib = N.load()
-        mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64)); ao = np.ascontiguousarray(np.asarray(anchor_off, dtype=np.int64))
+        mo = _i64(match_off); ao = _i64(anchor_off)
         assert mo.size == ao.size
         self.n_reads, self.total = mo.size - 1, int(ao[-1] - ao[0])
-        self.handle = self.lib.mm2c_seedplan_create(self.n_reads, _np_ptr(mo), _np_ptr(ao))
-        if not self.handle:
-            N.check(-1, "mm2c_seedplan_create")
+        self._create("mm2c_seedplan_create", self.n_reads, _np_ptr(mo), _np_ptr(ao))
 
     def run(self, matches: torch.Tensor, hits: torch.Tensor, qlen: torch.Tensor, anchors: torch.Tensor = None, stream=None):
         """matches: uint8 view of mm2c_match_t records on the GPU; hits: int64 pool; qlen: int32 [n_reads]; returns anchors int64 [total, 2]"""
@@ -1280,7 +1146,7 @@ class SeedPlan:
         if anchors is None:
             anchors = torch.empty((max(self.total, 1), 2), dtype=torch.int64, device=hits.device)
         assert anchors.is_cuda and anchors.dtype == torch.int64 and anchors.numel() >= 2 * self.total
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_seedplan_run_device_n(self.handle, matches.data_ptr(), matches.numel() * matches.element_size() // 24, hits.data_ptr(),
                                                     hits.numel(), qlen.data_ptr(), qlen.numel(), anchors.data_ptr(), anchors.numel() // 2, st),
                 "mm2c_seedplan_run_device_n")
@@ -1298,7 +1164,7 @@ class SeedPlan:
         off = torch.empty(self.n_reads + 1, dtype=torch.int64, device=hits.device)
         sk = N.SeedSkip(int(flag), ref_rank.data_ptr() if ref_rank is not None else None, ref_len.data_ptr() if ref_len is not None else None,
                         q_lo.data_ptr() if q_lo is not None else None, q_eq.data_ptr() if q_eq is not None else None)
-        st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        st = _stream(stream)
         N.check(self.lib.mm2c_seedplan_run_device_skip(self.handle, matches.data_ptr(), matches.numel() * matches.element_size() // 24, hits.data_ptr(),
                                                        hits.numel(), qlen.data_ptr(), qlen.numel(), C.byref(sk), anchors.data_ptr(),
                                                        anchors.numel() // 2, off.data_ptr(), st), "mm2c_seedplan_run_device_skip")
@@ -1315,9 +1181,7 @@ class SeedPlan:
         return n.value
 
     def last_ms(self):
-        ms = C.c_float(0)
-        N.check(self.lib.mm2c_seedplan_last_ms(self.handle, C.byref(ms)), "mm2c_seedplan_last_ms")
-        return ms.value
+        return self._ms("mm2c_seedplan_last_ms")[0]
 
     def last_expand_mw(self):
         """the reads the last run expanded on sixteen waves (mm2c_seedplan_last_expand_mw)"""
@@ -1325,22 +1189,11 @@ class SeedPlan:
         N.check(self.lib.mm2c_seedplan_last_expand_mw(self.handle, C.byref(n)), "mm2c_seedplan_last_expand_mw")
         return int(n.value)
 
-    def close(self):
-        if self.handle:
-            self.lib.mm2c_seedplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def seed_hits_batch(match_off, matches, hits, qlen):
     """mm2c_seed_hits_batch_host: returns (anchor_off int64 [n_reads+1], anchors uint64 [total, 2])"""
     lib = N.load()
-    mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64))
+    mo = _i64(match_off)
     m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
     h = np.ascontiguousarray(hits, dtype=np.uint64)
     q = np.ascontiguousarray(qlen, dtype=np.int32)
@@ -1357,7 +1210,7 @@ def seed_hits_batch(match_off, matches, hits, qlen):
 def seed_chain_batch(params: Params, min_cnt, min_sc, match_off, matches, hits, qlen):
     """mm2c_seed_chain_batch_host: matches in, per-read chains out [(u, b), ...] (anchors never leave the GPU)"""
     lib = N.load()
-    mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64))
+    mo = _i64(match_off)
     m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
     h = np.ascontiguousarray(hits, dtype=np.uint64)
     q = np.ascontiguousarray(qlen, dtype=np.int32)
@@ -1403,7 +1256,7 @@ class SeedSkip:
 
 
 def _seed_args(match_off, matches, qlen):
-    mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64))
+    mo = _i64(match_off)
     m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
     q = np.ascontiguousarray(qlen, dtype=np.int32)
     n_reads = mo.size - 1
@@ -1436,15 +1289,14 @@ def seed_chain_batch_skip(params: Params, min_cnt, min_sc, match_off, matches, h
     return ao, _split_chains(n_reads, u_off, u, b_off, b)
 
 
-class HitPool:
+class HitPool(_Handle):
     """mm2c_hitpool_t: the index's position arrays resident in HBM (uploaded once per index)"""
 
+    _destroy = "mm2c_hitpool_destroy"
+
     def __init__(self, hits):
-        self.lib = N.load()
         h = np.ascontiguousarray(hits, dtype=np.uint64)
-        self.handle = self.lib.mm2c_hitpool_create(_np_ptr(h), h.size)
-        if not self.handle:
-            N.check(-4, "mm2c_hitpool_create")
+        self._create("mm2c_hitpool_create", _np_ptr(h), h.size, code=-4)
         self.size = h.size
 
     _owned = True
@@ -1457,21 +1309,15 @@ class HitPool:
         return self
 
     def close(self):
-        if self.handle and self._owned:
-            self.lib.mm2c_hitpool_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if not self._owned:
+            self.handle = None
+        super().close()
 
 
 def seed_chain_batch_pool(params: Params, min_cnt, min_sc, match_off, matches, pool: HitPool, qlen):
     """mm2c_seed_chain_batch_pool: as seed_chain_batch with the hits taken from a resident pool (cr_off points into it)"""
     lib = N.load()
-    mo = np.ascontiguousarray(np.asarray(match_off, dtype=np.int64))
+    mo = _i64(match_off)
     m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
     q = np.ascontiguousarray(qlen, dtype=np.int32)
     n_reads = mo.size - 1
@@ -1533,9 +1379,11 @@ class _Result:
             pass
 
 
-class MinimizerIndex:
+class MinimizerIndex(_Handle):
     """mm2c_minidx_t: a minimizer index resident on every configured device.  keys = minimizers (x >> 8), their hits pool[cr_off : cr_off + n] of a HitPool
     (or of `hits`, uploaded as a pool owned by the index).  Lookups return what mm_idx_get returns (n = 0 for an absent key)."""
+
+    _destroy = "mm2c_minidx_destroy"
 
     def __init__(self, k, w, is_hpc, keys, cr_off, n, pool: "HitPool" = None, hits=None):
         self.lib = N.load()
@@ -1549,9 +1397,7 @@ class MinimizerIndex:
         nn = np.ascontiguousarray(n, dtype=np.uint32)
         if not (kk.size == cr.size == nn.size):
             raise ValueError("keys, cr_off and n differ in length")
-        self.handle = self.lib.mm2c_minidx_create(pool.handle, self.k, self.w, self.is_hpc, kk.size, _np_ptr(kk), _np_ptr(cr), _np_ptr(nn))
-        if not self.handle:
-            N.check(-2, "mm2c_minidx_create")
+        self._create("mm2c_minidx_create", pool.handle, self.k, self.w, self.is_hpc, kk.size, _np_ptr(kk), _np_ptr(cr), _np_ptr(nn), code=-2)
         self.size = kk.size
 
     @classmethod
@@ -1605,17 +1451,9 @@ class MinimizerIndex:
         return cr, n
 
     def close(self):
-        if self.handle:
-            self.lib.mm2c_minidx_destroy(self.handle)
-            self.handle = None
-            if not self.pool._owned:                    # a built index took its pool with it
-                self.pool.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        if self.handle and not self.pool._owned:        # a built index takes its pool with it
+            self.pool.handle = None
+        super().close()
 
 
 # what the reads-in entries return, from their result r = mm2c_read_result_t over n reads or fragments (a read is a fragment of one segment)
