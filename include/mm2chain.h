@@ -717,6 +717,80 @@ int mm2c_align_tasks_batch_host(const mm2c_aln_opt_t *opt, int64_t n_seq, const 
                                 const uint8_t *reads, int32_t cig_shift, mm2c_aln_reg_t *aln_regs, int64_t n_items_cap, mm2c_aln_item_t *items, int64_t n_tasks_cap,
                                 mm2c_ksw_task_t *tasks, int64_t *cig_off, int64_t pool_cap, uint8_t *pool, int64_t totals[4]);
 
+/* ---- ksw results -> aligned regions on the GPU: the rest of mm_align1 (align.c:698-705, 736-764, 772-783) ----
+ * mm2c_cigplan_t, a stand-alone plan wired into nothing, with two entries.  Both read the arrays of the alignment-task plan (d_aln_regs, d_items, d_tasks, d_cig_off,
+ * the pool), of the ksw plan (d_res, d_cigar) and of the z-drop entry (d_zres: only status and code are read) where those plans left them.  code is 0, 1 or 2: a host
+ * that has run ksw_ll_i16 on an inv_cand task writes 2 there before the call.
+ *
+ * mm2c_cigplan_second_run_device: the list of second passes (:736-737).  Every MM2C_ALN_GAP item with a ksw task, a z-drop status of 0 and code 1 or 2 gets a copy of
+ * its first-pass task with KSW_EZ_APPROX_MAX cleared and zdrop = (code == 2 ? zdrop_inv : zdrop), in item order, in d_tasks2 with d_cig_off2 (the slot rule of the
+ * first list, with opt->cig_shift); d_second_of[item] is its index there, -1 for an item without one, MM2C_CIG_NO_ROOM for one whose region's tasks or slots leave
+ * n_tasks2_cap or cigar2_cap (counted, MM2C_E_TOOBIG; nothing of that region is written).  The entries of a region the
+ * entry does not walk -- status not 0, item offsets leaving a capacity -- stay untouched; the join refuses such a region on its own.  The ksw plan runs the list unchanged on the same pool.  The list holds a
+ * second pass for EVERY such item, not only for those in front of its region's first drop: the reference issues a subset of them, and the join entry ignores the rest.
+ * Under MM2C_ALN_F_SR the MM2C_ALN_UNGAPPED item has no first-pass task, so its mm_test_zdrop (one M word of qe - qs bases over mat; :72 is off, the code is 0 or 1)
+ * is made here; with 1 it gets the task {reg.q_off + (qs - qs0), reg.t_off + (rs - rs0), qe - qs, re - rs, bw_ext, opt->zdrop, -1, 0}.  An ungapped item whose
+ * bases leave the pool is counted as refused, gets no task and MM2C_CIG_LOST in d_second_of, on which the join refuses its region.
+ *
+ * mm2c_cigplan_run_device: per region the cut behind the first dropped gap item, mm_append_cigar over the used items with its merge at every boundary (:303-306),
+ * dp_score, rs1 / qs1 / re1 / qe1, r->qs / r->qe on the read's strand and the split decision.  An item's ez is the second list's where d_second_of names one, else
+ * the first pass's; the reset ez with zdropped = 1 for an item over max_sw_mat; score and the word (qe - qs) << 4 for an sr ungapped item without a second pass.
+ * Outputs: one mm2c_cig_reg_t per region (n_used: items consumed; drop_item: the dropped item's index in the region, -1; split_n: the argument of mm_split_reg,
+ * 0 when the region is not split; has_p: r->p is set); the appended CIGARs in d_cig_out at cig0; and, dense and in region order for the regions that have words,
+ * d_in_off[k], d_extra_tasks[k] and d_extra_reg[k] (the region of entry k), which mm2c_extraplan_run_device takes unchanged with d_cig_out as its cig_in;
+ * d_in_off[n] is the number of words.  A region with cnt == 0 (:578) comes back with status 0, r_qs / r_qe / rs1 / re1 as the region has them and everything else 0.
+ * mm_split_reg itself stays with the host (its score is float arithmetic), as do mm_align1_inv, ksw_ll_i16, ksw_extz2_sse and splice.
+ * status (only the status word of such a region is written; its neighbours are exact): MM2C_CIG_REFUSED (counted, MM2C_E_ARG) -- an mm2c_aln_reg_t whose status is
+ * not 0; on a consumed item a code outside 0 .. 2, a z-drop record whose status is not 0, a second pass where the code is 0; item, task or CIGAR offsets leaving a
+ * capacity; an appended CIGAR whose op lengths do not add up to qe1 - qs1 and re1 - rs1 (:284); qs1 < 0, rs1 < 0, qe1 > qlen or re1 - rs1 > re0 - rs0 (:707, 779, 785).
+ * MM2C_CIG_INCOMPLETE (counted, MM2C_E_TOOBIG) -- a consumed task whose ksw status is not 0, an n_cigar beyond its slot, a code that is not 0 without a second pass.
+ * A task behind the cut may have any status.  MM2C_CIG_OVER_CAP (counted, MM2C_E_TOOBIG): the region's words or extra task leave words_cap or n_extra_cap; its record
+ * holds what the region came to (cig0 is 0), none of its words and no extra task is written, nothing is written behind a capacity and totals[] say what the batch takes.  With n_regs == 0 only in_off[0] = 0 is written. */
+#define MM2C_CIG_REFUSED 1
+#define MM2C_CIG_INCOMPLETE 2
+#define MM2C_CIG_OVER_CAP 3
+#define MM2C_CIG_PIECE 256             /* items and CIGAR words a workgroup of cig_gather takes at a time */
+#define MM2C_CIG_NO_ROOM (-2)
+#define MM2C_CIG_LOST (-3)
+typedef struct { int32_t zdrop, zdrop_inv, bw_ext, min_cnt, flag, cig_shift; } mm2c_cig_opt_t;    /* flag: MM2C_ALN_F_*; cig_shift: that of the alignment-task plan */
+typedef struct {
+	int32_t status, n_used, dropped, drop_item, zdrop_code, split_n, split_inv, has_p, n_cigar, dp_score, rs1, re1, qs1, qe1, r_qs, r_qe;
+	int64_t cig0;
+} mm2c_cig_reg_t;
+typedef struct mm2c_cigplan mm2c_cigplan_t;
+/* capacities: regions, items, first-list tasks and CIGAR words (the ksw plan's cigar_cap), second-list tasks and CIGAR words, pool bytes, anchors, output words,
+ * extra tasks */
+mm2c_cigplan_t *mm2c_cigplan_create(int64_t n_regs_cap, int64_t n_items_cap, int64_t n_tasks_cap, int64_t cigar_cap, int64_t n_tasks2_cap, int64_t cigar2_cap, int64_t pool_cap,
+                                    int64_t n_b_cap, int64_t words_cap, int64_t n_extra_cap);
+void mm2c_cigplan_destroy(mm2c_cigplan_t *plan);
+/* asynchronous on `stream`; all pointers are device memory except opt and sc (mat is read).  d_cig_off2: n_tasks2_cap + 1 entries; d_second_of: n_items_cap; d_seq is
+ * read under MM2C_ALN_F_SR only */
+int mm2c_cigplan_second_run_device(mm2c_cigplan_t *plan, const mm2c_cig_opt_t *opt, const mm2c_ksw_score_t *sc, int64_t n_regs, const mm2c_aln_reg_t *d_aln_regs,
+                                   const mm2c_aln_item_t *d_items, const mm2c_ksw_task_t *d_tasks, const mm2c_zdrop_res_t *d_zres, const uint8_t *d_seq,
+                                   mm2c_ksw_task_t *d_tasks2, int64_t *d_cig_off2, int32_t *d_second_of, void *stream);
+/* waits for the last second-pass run; totals (may be NULL): tasks and CIGAR words of the second list */
+int mm2c_cigplan_second_check(mm2c_cigplan_t *plan, int64_t *n_refused, int64_t *n_over_cap, int64_t totals[2]);
+/* asynchronous on `stream`.  d_u_off, d_b_off, d_read_off: n_reads + 1 entries; d_n_b may be NULL; d_b is read only.  d_in_off: n_extra_cap + 1 entries.  d_cig_out may
+ * overlap neither d_cigar nor d_cigar2 (MM2C_E_ARG) */
+int mm2c_cigplan_run_device(mm2c_cigplan_t *plan, const mm2c_cig_opt_t *opt, int64_t n_reads, int64_t n_regs, const int64_t *d_u_off, const mm2c_reg_t *d_regs,
+                            const int64_t *d_b_off, const int64_t *d_n_b, const void *d_b, const int64_t *d_read_off, const mm2c_aln_reg_t *d_aln_regs,
+                            const mm2c_aln_item_t *d_items, const int64_t *d_cig_off, const mm2c_ksw_res_t *d_res, const uint32_t *d_cigar, const mm2c_zdrop_res_t *d_zres,
+                            const int32_t *d_second_of, const int64_t *d_cig_off2, const mm2c_ksw_res_t *d_res2, const uint32_t *d_cigar2, mm2c_cig_reg_t *d_cig_regs,
+                            uint32_t *d_cig_out, int64_t *d_in_off, mm2c_extra_task_t *d_extra_tasks, int32_t *d_extra_reg, void *stream);
+/* waits for the last join run; totals (may be NULL): CIGAR words and extra tasks the batch takes */
+int mm2c_cigplan_check(mm2c_cigplan_t *plan, int64_t *n_refused, int64_t *n_incomplete, int64_t *n_over_cap, int64_t totals[2]);
+/* milliseconds between HIP events of the last runs: cig_second_count with its scan, cig_second_emit, cig_cut, cig_scan, cig_gather; 0 for an entry that has not run */
+int mm2c_cigplan_last_kernel_ms(mm2c_cigplan_t *plan, float ms[5]);
+/* host arrays in and out; argument checks (under MM2C_ALN_F_SR every base code of the pool too) come before any device work.  cig_off2: n_tasks2_cap + 1 entries */
+int mm2c_second_pass_batch_host(const mm2c_cig_opt_t *opt, const mm2c_ksw_score_t *sc, int64_t n_regs, const mm2c_aln_reg_t *aln_regs, int64_t n_items,
+                                const mm2c_aln_item_t *items, int64_t n_tasks, const mm2c_ksw_task_t *tasks, const mm2c_zdrop_res_t *zres, int64_t pool_len, const uint8_t *pool,
+                                int64_t n_tasks2_cap, mm2c_ksw_task_t *tasks2, int64_t *cig_off2, int32_t *second_of, int64_t totals[2]);
+int mm2c_assemble_regions_batch_host(const mm2c_cig_opt_t *opt, int64_t n_reads, const int64_t *u_off, const mm2c_reg_t *regs, const int64_t *b_off, const mm2c_anchor_t *b,
+                                     const int64_t *read_off, const mm2c_aln_reg_t *aln_regs, int64_t n_items, const mm2c_aln_item_t *items, int64_t n_tasks, const int64_t *cig_off,
+                                     const mm2c_ksw_res_t *res, const uint32_t *cigar, const mm2c_zdrop_res_t *zres, const int32_t *second_of, int64_t n_tasks2,
+                                     const int64_t *cig_off2, const mm2c_ksw_res_t *res2, const uint32_t *cigar2, mm2c_cig_reg_t *cig_regs, int64_t words_cap, uint32_t *cig_out,
+                                     int64_t n_extra_cap, int64_t *in_off, mm2c_extra_task_t *extra_tasks, int32_t *extra_reg, int64_t totals[2]);
+
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits
  * are hits[cr_off .. cr_off + n) of a hit pool (the arrays mm_idx_get returns: rid<<32 | pos<<1 | strand).  The anchors of read r are

@@ -209,6 +209,17 @@ C_SYMBOLS = {
     "mm2c_alnplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 13),
     "mm2c_alnplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mm2c_alnplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_cigplan_create": (C.c_void_p, [C.c_int64] * 10),
+    "mm2c_cigplan_destroy": (None, [C.c_void_p]),
+    "mm2c_cigplan_second_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9),
+    "mm2c_cigplan_second_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_cigplan_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 22),
+    "mm2c_cigplan_check": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int64)] * 4),
+    "mm2c_cigplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_second_pass_batch_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mm2c_assemble_regions_batch_host": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64] + [C.c_void_p] * 4 +
+                                                   [C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
     "mm2c_align_tasks_batch_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int64,
                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "mm2c_mapqplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),

@@ -949,6 +949,187 @@ def align_tasks_batch(opt, ref_offset, ref_len, S, u_off, regs, b_off, b, read_o
                 totals=tuple(int(x) for x in tot), rc=rc)
 
 
+CIG_OPT_DTYPE = np.dtype([(n, "<i4") for n in ("zdrop", "zdrop_inv", "bw_ext", "min_cnt", "flag", "cig_shift")])
+CIG_REG_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_used", "dropped", "drop_item", "zdrop_code", "split_n", "split_inv", "has_p", "n_cigar", "dp_score", "rs1", "re1",
+                                               "qs1", "qe1", "r_qs", "r_qe")] + [("cig0", "<i8")])
+CIG_REFUSED, CIG_INCOMPLETE, CIG_OVER_CAP = 1, 2, 3
+CIG_PIECE = 256
+CIG_NO_ROOM = -2
+CIG_LOST = -3
+
+
+def _cig_opt_bytes(opt):
+    """a dict with the fields of CIG_OPT_DTYPE (those an aln_opts() dict has are taken from it; cig_shift defaults to 0) or a record -> the 24 bytes of mm2c_cig_opt_t"""
+    if isinstance(opt, dict):
+        o = np.zeros(1, CIG_OPT_DTYPE)
+        for k in CIG_OPT_DTYPE.names:
+            o[k] = int(opt.get(k, 0))
+        return o
+    return np.ascontiguousarray(np.asarray(opt, dtype=CIG_OPT_DTYPE).reshape(1))
+
+
+class CigPlan(_Handle):
+    """mm2c_cigplan_t: the rest of mm_align1 (align.c:698-705, 736-764, 772-783) on the arrays an AlnPlan, a KswPlan and ExtraPlan.zdrop leave on the GPU: second() lists
+    the second passes, join() cuts each region behind its first drop, appends and merges the CIGARs, sums dp_score, takes rs1 .. qe1 and decides the split; its extra
+    tasks, in_off and CIGAR buffer go into ExtraPlan.update unchanged.  Capacities: regions, items, first-list tasks and CIGAR words, second-list tasks and CIGAR
+    words, pool bytes, anchors, output words, extra tasks."""
+
+    _destroy = "mm2c_cigplan_destroy"
+
+    def __init__(self, n_regs_cap, n_items_cap, n_tasks_cap, cigar_cap, n_tasks2_cap, cigar2_cap, pool_cap, n_b_cap, words_cap, n_extra_cap):
+        self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.cigar_cap = int(n_regs_cap), int(n_items_cap), int(n_tasks_cap), int(cigar_cap)
+        self.n_tasks2_cap, self.cigar2_cap, self.pool_cap, self.n_b_cap = int(n_tasks2_cap), int(cigar2_cap), int(pool_cap), int(n_b_cap)
+        self.words_cap, self.n_extra_cap = int(words_cap), int(n_extra_cap)
+        self._create("mm2c_cigplan_create", self.n_regs_cap, self.n_items_cap, self.n_tasks_cap, self.cigar_cap, self.n_tasks2_cap, self.cigar2_cap, self.pool_cap, self.n_b_cap,
+                     self.words_cap, self.n_extra_cap, code=-2)
+
+    def second(self, opt, score, n_regs, aln_regs: torch.Tensor, items: torch.Tensor, tasks: torch.Tensor, zres: torch.Tensor, seq: torch.Tensor = None,
+               tasks2: torch.Tensor = None, cig_off2: torch.Tensor = None, second_of: torch.Tensor = None, stream=None):
+        """the arrays of AlnPlan.run (aln_regs, items, tasks, pool as seq) and of ExtraPlan.zdrop (zres) as they lie on the GPU -> (tasks2 uint8 [n_tasks2_cap, 40],
+        cig_off2 int64 [n_tasks2_cap + 1], second_of int32 [n_items_cap]) GPU tensors (given ones are written into).  Asynchronous."""
+        n = int(n_regs)
+        for t in (aln_regs, items, tasks, zres):
+            assert t.is_cuda and t.is_contiguous()
+        assert 0 <= n <= self.n_regs_cap and aln_regs.numel() * aln_regs.element_size() >= n * ALN_REG_DTYPE.itemsize
+        assert items.numel() * items.element_size() >= self.n_items_cap * ALN_ITEM_DTYPE.itemsize and tasks.numel() * tasks.element_size() >= self.n_tasks_cap * KSW_TASK_DTYPE.itemsize
+        assert zres.numel() * zres.element_size() >= self.n_tasks_cap * ZDROP_RES_DTYPE.itemsize
+        assert seq is None or (seq.is_cuda and seq.element_size() == 1 and seq.numel() >= self.pool_cap)
+        dev = aln_regs.device
+        tasks2 = _out(tasks2, (max(self.n_tasks2_cap, 1), KSW_TASK_DTYPE.itemsize), torch.uint8, dev, self.n_tasks2_cap * KSW_TASK_DTYPE.itemsize)
+        cig_off2 = _out(cig_off2, self.n_tasks2_cap + 1, torch.int64, dev, (self.n_tasks2_cap + 1) * 8, "dtype")
+        second_of = _out(second_of, max(self.n_items_cap, 1), torch.int32, dev, self.n_items_cap * 4, "dtype")
+        o, sc = _cig_opt_bytes(opt), _ksw_score_bytes(score)
+        st = _stream(stream)
+        N.check(self.lib.mm2c_cigplan_second_run_device(self.handle, _np_ptr(o), _np_ptr(sc), n, aln_regs.data_ptr(), items.data_ptr(), tasks.data_ptr(), zres.data_ptr(),
+                                                        seq.data_ptr() if seq is not None else None, tasks2.data_ptr(), cig_off2.data_ptr(), second_of.data_ptr(), st),
+                "mm2c_cigplan_second_run_device")
+        return tasks2, cig_off2, second_of
+
+    def join(self, opt, n_reads, n_regs, u_off: torch.Tensor, regs: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, read_off: torch.Tensor, aln_regs: torch.Tensor,
+             items: torch.Tensor, cig_off: torch.Tensor, res: torch.Tensor, cigar: torch.Tensor, zres: torch.Tensor, second_of: torch.Tensor, cig_off2: torch.Tensor,
+             res2: torch.Tensor, cigar2: torch.Tensor, n_b: torch.Tensor = None, cig_regs: torch.Tensor = None, cig_out: torch.Tensor = None, in_off: torch.Tensor = None,
+             extra_tasks: torch.Tensor = None, extra_reg: torch.Tensor = None, stream=None):
+        """the batch (u_off, regs, b_off, b, read_off), the arrays of AlnPlan.run, KswPlan.run and ExtraPlan.zdrop, and those of second() with the KswPlan.run over its list,
+        all on the GPU -> (cig_regs uint8 [n_regs, 72], cig_out int32 [words_cap], in_off int64 [n_extra_cap + 1], extra_tasks uint8 [n_extra_cap, 32], extra_reg int32
+        [n_extra_cap]) GPU tensors (given ones are written into).  Asynchronous."""
+        n_reads, n = int(n_reads), int(n_regs)
+        for t in (u_off, regs, b_off, b, read_off, aln_regs, items, cig_off, res, cigar, zres, second_of, cig_off2, res2, cigar2):
+            assert t.is_cuda and t.is_contiguous()
+        assert all(t.dtype == torch.int64 and t.numel() >= n_reads + 1 for t in (u_off, b_off, read_off)) and 0 <= n <= self.n_regs_cap
+        assert regs.numel() * regs.element_size() >= n * REG_DTYPE.itemsize and b.numel() * b.element_size() >= 16 * self.n_b_cap
+        assert aln_regs.numel() * aln_regs.element_size() >= n * ALN_REG_DTYPE.itemsize and items.numel() * items.element_size() >= self.n_items_cap * ALN_ITEM_DTYPE.itemsize
+        assert cig_off.dtype == torch.int64 and cig_off.numel() >= self.n_tasks_cap + 1 and cig_off2.dtype == torch.int64 and cig_off2.numel() >= self.n_tasks2_cap + 1
+        assert res.numel() * res.element_size() >= self.n_tasks_cap * KSW_RES_DTYPE.itemsize and res2.numel() * res2.element_size() >= self.n_tasks2_cap * KSW_RES_DTYPE.itemsize
+        assert zres.numel() * zres.element_size() >= self.n_tasks_cap * ZDROP_RES_DTYPE.itemsize and second_of.dtype == torch.int32 and second_of.numel() >= self.n_items_cap
+        assert cigar.element_size() == 4 and cigar.numel() >= self.cigar_cap and cigar2.element_size() == 4 and cigar2.numel() >= self.cigar2_cap
+        assert n_b is None or (n_b.is_cuda and n_b.dtype == torch.int64 and n_b.numel() >= n_reads)
+        dev = regs.device
+        cig_regs = _out(cig_regs, (max(n, 1), CIG_REG_DTYPE.itemsize), torch.uint8, dev, n * CIG_REG_DTYPE.itemsize)
+        cig_out = _out(cig_out, max(self.words_cap, 1), torch.int32, dev, self.words_cap * 4, "width")
+        in_off = _out(in_off, self.n_extra_cap + 1, torch.int64, dev, (self.n_extra_cap + 1) * 8, "dtype")
+        extra_tasks = _out(extra_tasks, (max(self.n_extra_cap, 1), EXTRA_TASK_DTYPE.itemsize), torch.uint8, dev, self.n_extra_cap * EXTRA_TASK_DTYPE.itemsize)
+        extra_reg = _out(extra_reg, max(self.n_extra_cap, 1), torch.int32, dev, self.n_extra_cap * 4, "dtype")
+        o = _cig_opt_bytes(opt)
+        st = _stream(stream)
+        N.check(self.lib.mm2c_cigplan_run_device(self.handle, _np_ptr(o), n_reads, n, u_off.data_ptr(), regs.data_ptr(), b_off.data_ptr(), n_b.data_ptr() if n_b is not None else None,
+                                                 b.data_ptr(), read_off.data_ptr(), aln_regs.data_ptr(), items.data_ptr(), cig_off.data_ptr(), res.data_ptr(), cigar.data_ptr(),
+                                                 zres.data_ptr(), second_of.data_ptr(), cig_off2.data_ptr(), res2.data_ptr(), cigar2.data_ptr(), cig_regs.data_ptr(),
+                                                 cig_out.data_ptr(), in_off.data_ptr(), extra_tasks.data_ptr(), extra_reg.data_ptr(), st), "mm2c_cigplan_run_device")
+        return cig_regs, cig_out, in_off, extra_tasks, extra_reg
+
+    def second_counts(self):
+        """waits for the last second() -> (return code, refused, regions beyond a capacity, (tasks, CIGAR words) of the second list)"""
+        a, b, t = C.c_int64(0), C.c_int64(0), (C.c_int64 * 2)()
+        rc = self.lib.mm2c_cigplan_second_check(self.handle, C.byref(a), C.byref(b), t)
+        return rc, a.value, b.value, tuple(int(x) for x in t)
+
+    def second_check(self):
+        rc, _, _, tot = self.second_counts()
+        N.check(rc, "mm2c_cigplan_second_check")
+        return tot
+
+    def counts(self):
+        """waits for the last join() -> (return code, regions refused, incomplete, beyond a capacity, (CIGAR words, extra tasks) the batch takes)"""
+        a, b, c, t = C.c_int64(0), C.c_int64(0), C.c_int64(0), (C.c_int64 * 2)()
+        rc = self.lib.mm2c_cigplan_check(self.handle, C.byref(a), C.byref(b), C.byref(c), t)
+        return rc, a.value, b.value, c.value, tuple(int(x) for x in t)
+
+    def check(self):
+        """waits for the last join(); raises (code -2) if a region was refused, (code -3) if one was incomplete or left a capacity; returns the totals"""
+        rc, _, _, _, tot = self.counts()
+        N.check(rc, "mm2c_cigplan_check")
+        return tot
+
+    def last_kernel_ms(self):
+        """(cig_second_count with its scan, cig_second_emit, cig_cut, cig_scan, cig_gather) of the last runs; 0 for an entry that has not run"""
+        ms = (C.c_float * 5)()
+        N.check(self.lib.mm2c_cigplan_last_kernel_ms(self.handle, ms), "mm2c_cigplan_last_kernel_ms")
+        return tuple(float(x) for x in ms)
+
+    def last_ms(self):
+        return sum(self.last_kernel_ms())
+
+
+def second_pass_batch(opt, score, aln_regs, items, tasks, zres, pool, n_tasks2_cap, fill=None):
+    """mm2c_second_pass_batch_host: host arrays in (aln_regs ALN_REG_DTYPE, items ALN_ITEM_DTYPE, tasks KSW_TASK_DTYPE, zres ZDROP_RES_DTYPE, pool uint8) ->
+    dict(tasks2, cig_off2, second_of, totals, rc); rc is 0 or -3 (the second list leaves n_tasks2_cap).  Raises for any other failure.  fill: a byte the outputs are
+    filled with beforehand (tests)."""
+    lib = N.load()
+    ar = np.ascontiguousarray(aln_regs, dtype=ALN_REG_DTYPE); it = np.ascontiguousarray(items, dtype=ALN_ITEM_DTYPE); tk = np.ascontiguousarray(tasks, dtype=KSW_TASK_DTYPE)
+    zr = np.ascontiguousarray(zres, dtype=ZDROP_RES_DTYPE); pl = np.ascontiguousarray(pool, dtype=np.uint8)
+    if zr.size < tk.size:
+        raise ValueError("zres must hold one record per task")
+    f = 0 if fill is None else int(fill)
+    cap = int(n_tasks2_cap)
+    tasks2 = np.full(max(cap, 1) * KSW_TASK_DTYPE.itemsize, f, np.uint8).view(KSW_TASK_DTYPE)
+    cig_off2 = np.full((cap + 1) * 8, f, np.uint8).view(np.int64)
+    second_of = np.full(max(it.size, 1) * 4, f, np.uint8).view(np.int32)
+    tot = (C.c_int64 * 2)()
+    o, sc = _cig_opt_bytes(opt), _ksw_score_bytes(score)
+    rc = lib.mm2c_second_pass_batch_host(_np_ptr(o), _np_ptr(sc), ar.size, _np_ptr(ar), it.size, _np_ptr(it), tk.size, _np_ptr(tk), _np_ptr(zr), pl.size, _np_ptr(pl), cap,
+                                         _np_ptr(tasks2), _np_ptr(cig_off2), _np_ptr(second_of), tot)
+    if rc not in (0, -3):
+        N.check(rc, "mm2c_second_pass_batch_host")
+    return dict(tasks2=tasks2[:cap], cig_off2=cig_off2, second_of=second_of[:it.size], totals=tuple(int(x) for x in tot), rc=rc)
+
+
+def assemble_regions_batch(opt, u_off, regs, b_off, b, read_off, aln_regs, items, cig_off, res, cigar, zres, second_of, cig_off2, res2, cigar2, words_cap, n_extra_cap, fill=None):
+    """mm2c_assemble_regions_batch_host: host arrays in -> dict(cig_regs CIG_REG_DTYPE, cig_out uint32 [words_cap], in_off int64 [n_extra_cap + 1], extra_tasks
+    EXTRA_TASK_DTYPE, extra_reg int32, totals, rc); rc is 0 or -3 (a region incomplete or beyond a capacity: the rest is complete all the same).  Raises for any other
+    failure.  fill: a byte the outputs are filled with beforehand (tests)."""
+    lib = N.load()
+    uo = np.ascontiguousarray(u_off, dtype=np.int64); bo = np.ascontiguousarray(b_off, dtype=np.int64); ro = np.ascontiguousarray(read_off, dtype=np.int64)
+    rg = np.ascontiguousarray(regs, dtype=REG_DTYPE); bb = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 2)
+    ar = np.ascontiguousarray(aln_regs, dtype=ALN_REG_DTYPE); it = np.ascontiguousarray(items, dtype=ALN_ITEM_DTYPE)
+    co = np.ascontiguousarray(cig_off, dtype=np.int64); rs = np.ascontiguousarray(res, dtype=KSW_RES_DTYPE); cg = np.ascontiguousarray(cigar, dtype=np.uint32)
+    zr = np.ascontiguousarray(zres, dtype=ZDROP_RES_DTYPE); so = np.ascontiguousarray(second_of, dtype=np.int32)
+    c2 = np.ascontiguousarray(cig_off2, dtype=np.int64); r2 = np.ascontiguousarray(res2, dtype=KSW_RES_DTYPE); g2 = np.ascontiguousarray(cigar2, dtype=np.uint32)
+    n_reads = uo.size - 1
+    if bo.size != n_reads + 1 or ro.size != n_reads + 1:
+        raise ValueError("u_off, b_off and read_off must hold n_reads + 1 offsets")
+    n_regs = int(uo[-1]) if n_reads > 0 else 0
+    n_tasks, n_tasks2 = rs.size, r2.size
+    if rg.size < n_regs or ar.size < n_regs or bb.shape[0] < int(bo[-1]) or co.size < n_tasks + 1 or c2.size < n_tasks2 + 1 or zr.size < n_tasks or so.size < it.size:
+        raise ValueError("an array is shorter than its offsets say")
+    if cg.size < int(co[n_tasks]) or g2.size < int(c2[n_tasks2]):
+        raise ValueError("a CIGAR buffer is shorter than its offsets say")
+    f = 0 if fill is None else int(fill)
+    wc, xc = int(words_cap), int(n_extra_cap)
+    cig_regs = np.full(max(n_regs, 1) * CIG_REG_DTYPE.itemsize, f, np.uint8).view(CIG_REG_DTYPE)
+    cig_out = np.full(max(wc, 1) * 4, f, np.uint8).view(np.uint32)
+    in_off = np.full((xc + 1) * 8, f, np.uint8).view(np.int64)
+    extra_tasks = np.full(max(xc, 1) * EXTRA_TASK_DTYPE.itemsize, f, np.uint8).view(EXTRA_TASK_DTYPE)
+    extra_reg = np.full(max(xc, 1) * 4, f, np.uint8).view(np.int32)
+    tot = (C.c_int64 * 2)()
+    o = _cig_opt_bytes(opt)
+    rc = lib.mm2c_assemble_regions_batch_host(_np_ptr(o), n_reads, _np_ptr(uo), _np_ptr(rg), _np_ptr(bo), _np_ptr(bb), _np_ptr(ro), _np_ptr(ar), it.size, _np_ptr(it), n_tasks,
+                                              _np_ptr(co), _np_ptr(rs), _np_ptr(cg), _np_ptr(zr), _np_ptr(so), n_tasks2, _np_ptr(c2), _np_ptr(r2), _np_ptr(g2), _np_ptr(cig_regs),
+                                              wc, _np_ptr(cig_out), xc, _np_ptr(in_off), _np_ptr(extra_tasks), _np_ptr(extra_reg), tot)
+    if rc not in (0, -3):
+        N.check(rc, "mm2c_assemble_regions_batch_host")
+    return dict(cig_regs=cig_regs[:n_regs], cig_out=cig_out[:wc], in_off=in_off, extra_tasks=extra_tasks[:xc], extra_reg=extra_reg[:xc], totals=tuple(int(x) for x in tot), rc=rc)
+
+
 class MapqPlan(_Handle):
     """mm2c_mapqplan_t: hits -> final regions with mapping quality on the GPU (mm_join_long hit.c:295-371, mm_set_mapq hit.c:463-508) for batches of up to n_reads
     reads, n_u_cap regions and n_b_cap chain anchors; it stands behind a HitPlan on the same stream.  max_log_arg: the largest score (and n_sub + 1) whose logf the
