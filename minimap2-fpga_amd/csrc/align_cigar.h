@@ -38,7 +38,7 @@ struct CigArgs {
 	const ZdropRes *zres;
 	// the batch
 	const int64_t *u_off;
-	const AlnRegIn *regs;
+	const Reg *regs;
 	const int64_t *b_off, *n_b;
 	const ulonglong2 *b;
 	const int64_t *read_off;

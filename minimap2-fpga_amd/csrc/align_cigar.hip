@@ -8,6 +8,7 @@
 //   cig_gather  streaming over the words of the used items, a region taken by one workgroup of 256 lanes in pieces: mm_append_cigar with its merge (:303-306)
 // Placement comes from the scans; every store is a plain vector store; the only atomics are the adds of the refusal counters; no floating point.
 #include "align_cigar.h"
+#include "wave_ops.h"
 #include <limits.h>
 
 namespace mm2c {
@@ -15,32 +16,12 @@ namespace {
 
 constexpr int KSW_EZ_APPROX_MAX = 0x08;
 
-__device__ inline int32_t lo32(uint64_t v) { return (int32_t)(uint32_t)v; }
 __device__ inline int64_t slot_of(int64_t s, int shift) { const int64_t c = (s >> shift) + 16; return s < c ? s : c; }   // a task's CIGAR slot, the rule of the first list
-
-__device__ inline int w_incl_sum(int v, int lane)
-{
-	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
-	return v;
-}
-__device__ inline int w_incl_max(int v, int lane)
-{
-	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d && o > v) v = o; }
-	return v;
-}
-// the latest value >= 0 at or in front of the lane, -1 if there is none
-__device__ inline int w_incl_last(int v, int lane)
-{
-	for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d && v < 0) v = o; }
-	return v;
-}
-__device__ inline int w_max(int v) { for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(v, d); v = o > v ? o : v; } return v; }
-__device__ inline int64_t w_sum64(int64_t v) { for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d); return v; }
 
 // the same over a workgroup of 256 lanes; sw: 4 words of LDS
 __device__ inline int b_incl_sum(int v, int lane, int wv, int *sw)
 {
-	v = w_incl_sum(v, lane);
+	v = wave_incl_sum(v, lane);
 	if (lane == 63) sw[wv] = v;
 	__syncthreads();
 	int add = 0;
@@ -50,7 +31,7 @@ __device__ inline int b_incl_sum(int v, int lane, int wv, int *sw)
 }
 __device__ inline int b_incl_last(int v, int lane, int wv, int *sw)
 {
-	v = w_incl_last(v, lane);
+	v = wave_incl_last(v, lane);
 	if (lane == 63) sw[wv] = v;
 	__syncthreads();
 	if (v < 0) for (int i = wv - 1; i >= 0; --i) if (sw[i] >= 0) { v = sw[i]; break; }
@@ -63,16 +44,9 @@ struct Ctx { int64_t na; const ulonglong2 *a; int32_t qlen; };
 // the read of region g, its anchors and its length; false when an offset leaves a capacity
 __device__ bool locate(const CigArgs &A, int64_t g, Ctx &C)
 {
-	const int64_t base = A.u_off[0];
-	int64_t lo = 0, hi = A.n_reads;
-	while (lo < hi) {
-		const int64_t mid = (lo + hi) >> 1;
-		if (A.u_off[mid + 1] - base <= g) lo = mid + 1; else hi = mid;
-	}
-	if (lo >= A.n_reads || A.u_off[lo] - base > g) return false;
-	const int64_t b0 = A.b_off[lo], na = A.n_b ? A.n_b[lo] : A.b_off[lo + 1] - b0, r0 = A.read_off[lo], r1 = A.read_off[lo + 1];
-	if (b0 < 0 || na < 0 || na > INT32_MAX || b0 > A.b_cap - na || r0 < 0 || r1 < r0 || r1 - r0 > INT32_MAX) return false;
-	C.na = na; C.a = A.b + b0; C.qlen = (int32_t)(r1 - r0);
+	RegionRead Q;
+	if (!read_of_region(A, g, Q)) return false;
+	C.na = Q.na; C.a = A.b + Q.b0; C.qlen = Q.qlen;
 	return true;
 }
 
@@ -131,10 +105,10 @@ __device__ int sr_test(const CigArgs &A, int64_t qo, int64_t to, int32_t len, in
 		const bool on = j < len;
 		int d = 0;
 		if (on) { const int ct = A.seq[to + j], cq = A.seq[qo + j]; d = A.mat[(ct > 4 ? 4 : ct) * 5 + (cq > 4 ? 4 : cq)]; }
-		const int S = carry_s + w_incl_sum(d, lane);
-		int v = w_incl_max(on ? S : INT32_MIN, lane);
+		const int S = carry_s + wave_incl_sum(d, lane);
+		int v = wave_incl_max(on ? S : INT32_MIN, lane);
 		if (mv > v) v = mv;
-		best = max(best, w_max(on ? v - S : 0));
+		best = max(best, wave_max(on ? v - S : 0));
 		carry_s = __shfl(S, 63); mv = __shfl(v, 63);
 	}
 	return best > A.opt.zdrop ? 1 : 0;
@@ -188,7 +162,7 @@ __device__ void second_walk(const CigArgs &A, int lane)
 			const int64_t words = want ? slot_of((int64_t)T.qlen + T.tlen, A.opt.cig_shift) : 0;
 			const uint64_t m = __ballot(want);
 			// slots of up to 2^21 words, 64 of them: below 2^31
-			const int inc = w_incl_sum((int)words, lane);
+			const int inc = wave_incl_sum((int)words, lane);
 			if (EMIT && on) {
 				const int64_t idx = tk + __popcll(m & ((1ull << lane) - 1));
 				A.second_of[R.item0 + k] = lost ? CIG_LOST : !want ? -1 : room ? (int32_t)idx : CIG_NO_ROOM;
@@ -210,24 +184,15 @@ __global__ __launch_bounds__(1024) void cig_second_scan(const CigArgs A)
 	int64_t carry[2] = {0, 0};
 	for (int64_t base = 0; base < A.n_regs; base += 1024) {
 		const int64_t g = base + tid;
-		int64_t v[2] = {0, 0};
+		int64_t v[2] = {0, 0}, in[2], tot[2];
 		if (g < A.n_regs) { const CigSec s = A.sec[g]; v[0] = s.tk0; v[1] = s.cg0; }
-		for (int c = 0; c < 2; ++c) sh[c][tid] = v[c];
-		__syncthreads();
-		for (int d = 1; d < 1024; d <<= 1) {
-			int64_t t[2];
-			for (int c = 0; c < 2; ++c) t[c] = tid >= d ? sh[c][tid - d] : 0;
-			__syncthreads();
-			for (int c = 0; c < 2; ++c) sh[c][tid] += t[c];
-			__syncthreads();
-		}
+		block_incl_sum_1024(sh, tid, v, in, tot);
 		if (g < A.n_regs) {
-			CigSec s = {carry[0] + sh[0][tid] - v[0], carry[1] + sh[1][tid] - v[1]};
+			CigSec s = {carry[0] + in[0] - v[0], carry[1] + in[1] - v[1]};
 			if (v[0] > 0 && (s.tk0 + v[0] > A.tasks2_cap || s.cg0 + v[1] > A.cig2_cap)) { s.tk0 = -1; atomicAdd(A.flags + 2, 1); }
 			A.sec[g] = s;
 		}
-		for (int c = 0; c < 2; ++c) carry[c] += sh[c][1023];
-		__syncthreads();
+		for (int c = 0; c < 2; ++c) carry[c] += tot[c];
 	}
 	if (tid == 0) {
 		A.totals[0] = carry[0]; A.totals[1] = carry[1];
@@ -250,7 +215,7 @@ __global__ __launch_bounds__(64) void cig_cut(const CigArgs A)
 			if (R.status != 0) break;
 			Ctx C;
 			if (!locate(A, g, C)) break;
-			const AlnRegIn r = A.regs[g];
+			const Reg r = A.regs[g];
 			if (R.cnt1 == 0 && R.n_items == 0) {                                           // :578: the region stays as it is
 				O.rs1 = r.rs; O.re1 = r.re; O.r_qs = r.qs; O.r_qe = r.qe;
 				status = 0;
@@ -277,14 +242,14 @@ __global__ __launch_bounds__(64) void cig_cut(const CigArgs A)
 				// a boundary merges when the item's first op is the last op of the item with words in front of it (:303)
 				uint32_t fw = 0, lw = 0;
 				if (n > 0) { fw = E.p ? E.p[0] : E.synth; lw = E.p ? E.p[n - 1] : E.synth; }
-				const int il = w_incl_last(n > 0 ? (int)(lw & 0xf) : -1, lane);
+				const int il = wave_incl_last(n > 0 ? (int)(lw & 0xf) : -1, lane);
 				int prev = __shfl_up(il, 1);
 				if (lane == 0 || prev < 0) prev = carry_op;
 				merges += __popcll(__ballot(n > 0 && prev == (int)(fw & 0xf)));
 				const int last = __shfl(il, 63);
 				if (last >= 0) carry_op = last;
 				// the lengths of :284, over the words of the step's items
-				const int pin = w_incl_sum(n, lane), tot = __shfl(pin, 63);
+				const int pin = wave_incl_sum(n, lane), tot = __shfl(pin, 63);
 				if (lane == 0) sP[0] = 0;
 				sP[lane + 1] = pin; sp[lane] = E.p; ssyn[lane] = E.synth;
 				__syncthreads();
@@ -300,8 +265,8 @@ __global__ __launch_bounds__(64) void cig_cut(const CigArgs A)
 			}
 			if (ref) break;
 			if (inc) { status = CIG_INCOMPLETE; break; }
-			qsum = w_sum64(qsum); tsum = w_sum64(tsum);
-			for (int d = 32; d >= 1; d >>= 1) dp += __shfl_xor(dp, d);
+			qsum = wave_sum(qsum); tsum = wave_sum(tsum);
+			dp = wave_sum(dp);
 			// every lane takes the same scalars
 			int32_t rs1 = R.rs, qs1 = R.qs;
 			Eff first = {}, lastE = {};

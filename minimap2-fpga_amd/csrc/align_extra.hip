@@ -12,17 +12,12 @@
 //                       (T, C, P, M) with s' = max(s + T, C), max' = max(max, s + P, M); the z-drop by a prefix sum and a prefix maximum where the later point wins.
 // Stores are plain vector stores; the only atomics are the adds of the three counters; every loop's bound is known at its entry or falls with every step.
 #include "align_extra.h"
+#include "wave_ops.h"
 
 namespace mm2c {
 
 constexpr int XNEG = -0x40000000;
 constexpr int XINF = 0x20000000;
-
-__device__ static inline int x_incl_sum(int v, int lane) { for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; } return v; }
-__device__ static inline int x_incl_max(int v, int lane) { for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d && o > v) v = o; } return v; }
-__device__ static inline int x_sum(int v) { for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m); return v; }
-__device__ static inline int64_t x_sum64(int64_t v) { for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m); return v; }
-__device__ static inline int x_below(uint64_t mask, int lane) { return __popcll(mask & ((1ull << lane) - 1)); }
 
 // inclusive scan of the maps x -> min(a, b + x) in lane order, applied to `carry`: what comes out of each lane's map
 __device__ static inline int x_map_scan(int a, int b, int carry, int lane)
@@ -102,11 +97,11 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 				if (on) { W[k] = w; badop |= op > 3 || (op == 3 && len == 0); anyzero |= len == 0; anynz |= len != 0; }
 				const uint32_t dq = on && op <= 1 ? len : 0u, dt = on && (op == 0 || op == 2 || op == 3) ? len : 0u;
 				sq += dq; stt += dt;
-				const uint32_t iq = (uint32_t)x_incl_sum((int)dq, lane), it = (uint32_t)x_incl_sum((int)dt, lane);
+				const uint32_t iq = (uint32_t)wave_incl_sum((int)dq, lane), it = (uint32_t)wave_incl_sum((int)dt, lane);
 				if (on) { QP[k] = (int32_t)(cq + iq - dq); TP[k] = (int32_t)(ct + it - dt); }
 				cq += (uint32_t)__shfl((int)iq, 63); ct += (uint32_t)__shfl((int)it, 63);
 			}
-			sq = x_sum64(sq); stt = x_sum64(stt);
+			sq = wave_sum(sq); stt = wave_sum(stt);
 			anyzero = __any(anyzero); anynz = __any(anynz); badop = __any(badop);
 			if (badop || sq != T.qlen || stt != T.tlen || (n >= 2 && !anynz)) {
 				if (lane == 0) { A.res[i].status = EXTRA_REFUSED; atomicAdd(&A.flags[0], 1); }
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 						const uint32_t w = k < n ? W[k] : 0u;
 						const bool keep = (w >> 4) != 0;
 						const uint64_t mask = __ballot(keep);
-						if (keep) W[cnt + x_below(mask, lane)] = w;
+						if (keep) W[cnt + lanes_below(mask)] = w;
 						cnt += __popcll(mask);
 					}
 					m = cnt;
@@ -215,13 +210,13 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 						const uint32_t w = on ? W[j] : 0u, op = w & 0xf;
 						const uint32_t nop = j + 1 < m ? W[j + 1] & 0xf : 16u;
 						const bool end = on && op != nop;
-						const int P = carry_p + x_incl_sum(on ? (int)(w >> 4) : 0, lane);
-						const int ei = x_incl_max(end ? P : 0, lane);
+						const int P = carry_p + wave_incl_sum(on ? (int)(w >> 4) : 0, lane);
+						const int ei = wave_incl_max(end ? P : 0, lane);
 						int ex = __shfl_up(ei, 1);
 						if (lane == 0) ex = 0;
 						if (ex < prev_end) ex = prev_end;
 						const uint64_t mask = __ballot(end);
-						if (end) W[outn + x_below(mask, lane)] = (uint32_t)(P - ex) << 4 | op;
+						if (end) W[outn + lanes_below(mask)] = (uint32_t)(P - ex) << 4 | op;
 						outn += __popcll(mask);
 						carry_p = __shfl(P, 63);
 						const int el = __shfl(ei, 63);
@@ -248,14 +243,14 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 					const int len = (int)(w >> 4);
 					const int dq = on && op <= 1 ? len : 0, dt = on && op != 1 ? len : 0;
 					const int dc = !on ? 0 : op == 0 ? len : op == 3 ? 1 : (len > 0 ? len : 1);
-					const int iq = x_incl_sum(dq, lane), it = x_incl_sum(dt, lane), ic = x_incl_sum(dc, lane);
+					const int iq = wave_incl_sum(dq, lane), it = wave_incl_sum(dt, lane), ic = wave_incl_sum(dc, lane);
 					__syncthreads();                                         // QP, TP of the words in front of w0 + k are not read any more
 					if (on) { QP[k] = cq2 + iq - dq; TP[k] = ct2 + it - dt; CP[k] = cc + ic - dc; }
 					cq2 += __shfl(iq, 63); ct2 += __shfl(it, 63); cc += __shfl(ic, 63);
 					nm += on && op == 0; sm += on && op == 0 ? len : 0; sid += on && (op == 1 || op == 2) ? len : 0;
 					if (!A.is_eqx && on && k < room) out[k] = w;
 				}
-				n_cols = cc; n_M = x_sum(nm); sum_M = x_sum(sm); sum_ID = x_sum(sid);
+				n_cols = cc; n_M = wave_sum(nm); sum_M = wave_sum(sm); sum_ID = wave_sum(sid);
 			}
 			__syncthreads();
 			// :249-282 and :175-193,210-234 over the columns
@@ -307,8 +302,8 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 					const bool sev = on && (op != 0 ? j == 0 : (j == 0 || eq != eq_prev));   // the column at which an output word begins
 					const bool rs = sev && op == 0;
 					n_eqx += rs;
-					const int ev = carry_ev + x_incl_sum(sev, lane);
-					int ls = x_incl_max(rs ? c : -1, lane);
+					const int ev = carry_ev + wave_incl_sum((int)sev, lane);
+					int ls = wave_incl_max(rs ? c : -1, lane);
 					if (ls < carry_ls) ls = carry_ls;
 					int ls_ex = __shfl_up(ls, 1);
 					if (lane == 0) ls_ex = carry_ls;
@@ -318,7 +313,7 @@ __global__ __launch_bounds__(64) void extra_update(const ExtraArgs A)
 					carry_eq = __shfl(eq, 63); carry_ev = __shfl(ev, 63); carry_ls = __shfl(ls, 63);
 				}
 			}
-			n_amb = x_sum(n_amb); n_nm = x_sum(n_nm); n_eqx = x_sum(n_eqx);
+			n_amb = wave_sum(n_amb); n_nm = wave_sum(n_nm); n_eqx = wave_sum(n_eqx);
 			int dp_max = 0;
 			if (cP > dp_max) dp_max = cP;
 			if (cM > dp_max) dp_max = cM;
@@ -378,12 +373,12 @@ __global__ __launch_bounds__(64) void extra_zdrop(const ExtraArgs A)
 				const uint32_t di = on && (op == 0 || op == 2 || op == 3) ? len : 0u, dj = on && op <= 1 ? len : 0u;
 				const int dc = !on ? 0 : op == 0 ? (int)len : op <= 3 ? 1 : 0;     // a point per base of M and per gap word; other ops are passed over as at :56,62
 				si += di; sj += dj;
-				const uint32_t ii = (uint32_t)x_incl_sum((int)di, lane), ij = (uint32_t)x_incl_sum((int)dj, lane);
-				const int ic = x_incl_sum(dc, lane);
+				const uint32_t ii = (uint32_t)wave_incl_sum((int)di, lane), ij = (uint32_t)wave_incl_sum((int)dj, lane);
+				const int ic = wave_incl_sum(dc, lane);
 				if (on) { IP[k] = (int32_t)(ci + ii - di); JP[k] = (int32_t)(cj + ij - dj); CP[k] = cc + ic - dc; }
 				ci += (uint32_t)__shfl((int)ii, 63); cj += (uint32_t)__shfl((int)ij, 63); cc += __shfl(ic, 63);
 			}
-			si = x_sum64(si); sj = x_sum64(sj);
+			si = wave_sum(si); sj = wave_sum(sj);
 			if (si > T.tlen || sj > T.qlen) {                                // the walk would leave the sequences
 				if (lane == 0) { A.zres[i].status = EXTRA_REFUSED; atomicAdd(&A.flags[0], 1); }
 				continue;
@@ -410,7 +405,7 @@ __global__ __launch_bounds__(64) void extra_zdrop(const ExtraArgs A)
 					pi = IP[w] + (op == 1 ? 0 : len); pj = JP[w] + (op == 1 ? len : 0);
 				}
 			}
-			const int S = carry_s + x_incl_sum(d, lane);
+			const int S = carry_s + wave_incl_sum(d, lane);
 			int v = on ? S : INT32_MIN, vi = pi, vj = pj;                    // the inclusive maximum, the later point winning a tie (:34,44)
 			for (int dd = 1; dd < 64; dd <<= 1) {
 				const int ov = __shfl_up(v, dd), oi = __shfl_up(vi, dd), oj = __shfl_up(vj, dd);

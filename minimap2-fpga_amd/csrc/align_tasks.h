@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "ksw_extd2.h"
+#include "chain_regs.h"
 
 namespace mm2c {
 
@@ -25,17 +26,14 @@ struct AlnReg {                            // mm2c_aln_reg_t
 	int64_t item0, task0, cig0, q_off, t_off, left_off;
 };
 struct AlnItem { int32_t reg, kind, anchor, rs, re, qs, qe, task, score, reserved; };   // mm2c_aln_item_t
-struct AlnRegIn {                          // mm2c_reg_t
-	int32_t id, cnt, rid, score, qs, qe, rs, re, parent, subsc, as, mlen, blen, n_sub, score0;
-	uint32_t flags, hash; float div; uint64_t p;
-};
+using AlnRegIn = Reg;                      // mm2c_reg_t (chain_regs.h); the name the host files cast to
 
 struct AlnArgs {
 	int64_t n_reads, n_regs, items_cap, tasks_cap, pool_cap, b_cap, reads_cap;
 	AlnOpt opt;
 	int32_t cig_shift;
 	const int64_t *u_off;                  // n_reads + 1; region g belongs to the read r with u_off[r] - u_off[0] <= g < u_off[r + 1] - u_off[0]
-	const AlnRegIn *regs;
+	const Reg *regs;
 	const int64_t *b_off, *n_b;            // the read's anchors start at b[b_off[r]]; n_b (may be NULL): how many it has, else b_off[r + 1] - b_off[r]
 	ulonglong2 *b;                         // in/out: MM_SEED_IGNORE / MM_SEED_LONG_JOIN
 	const int64_t *read_off;               // n_reads + 1
@@ -54,6 +52,25 @@ struct AlnArgs {
 	int32_t *flags;                        // [0]: refused, [1]: too big, [2]: regions beyond a capacity
 	int64_t *totals;                       // items, tasks, CIGAR words, pool bytes
 };
+// The read of region g in a batch (AlnArgs, or CigArgs of align_cigar.h): region g belongs to the read with u_off[read] - u_off[0] <= g < u_off[read + 1] -
+// u_off[0]; its anchors are b[b0 .. b0 + na), its bases lie at [r0, r0 + qlen).  false when g belongs to no read or an offset leaves b_cap or int32.
+struct RegionRead { int64_t read, b0, na, r0; int32_t qlen; };
+template <typename Args>
+__device__ inline bool read_of_region(const Args &A, int64_t g, RegionRead &Q)
+{
+	const int64_t base = A.u_off[0];
+	int64_t lo = 0, hi = A.n_reads;
+	while (lo < hi) {
+		const int64_t mid = (lo + hi) >> 1;
+		if (A.u_off[mid + 1] - base <= g) lo = mid + 1; else hi = mid;
+	}
+	if (lo >= A.n_reads || A.u_off[lo] - base > g) return false;
+	const int64_t b0 = A.b_off[lo], na = A.n_b ? A.n_b[lo] : A.b_off[lo + 1] - b0, r0 = A.read_off[lo], r1 = A.read_off[lo + 1];
+	if (b0 < 0 || na < 0 || na > INT32_MAX || b0 > A.b_cap - na || r0 < 0 || r1 < r0 || r1 - r0 > INT32_MAX) return false;
+	Q.read = lo; Q.b0 = b0; Q.na = na; Q.r0 = r0; Q.qlen = (int32_t)(r1 - r0);
+	return true;
+}
+
 hipError_t launch_aln_plan(const AlnArgs &A, hipStream_t st);     // aln_plan, then aln_scan
 hipError_t launch_aln_emit(const AlnArgs &A, hipStream_t st);     // aln_emit
 hipError_t launch_aln_gather(const AlnArgs &A, hipStream_t st);   // aln_gather

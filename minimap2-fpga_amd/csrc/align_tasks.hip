@@ -5,6 +5,7 @@
 //   aln_gather streaming over bases, a region dealt in pieces of 16-base units: the spans from the reads and the packed reference, the reversed left copies
 // Placement comes from the scan; every store is a plain vector store; the only atomics are the adds of the refusal counters.
 #include "align_tasks.h"
+#include "wave_ops.h"
 
 namespace mm2c {
 namespace {
@@ -14,11 +15,8 @@ constexpr int KSW_EZ_RIGHT = 0x02, KSW_EZ_APPROX_MAX = 0x08, KSW_EZ_EXTZ_ONLY = 
 
 // a flag word another lane of the wave may just have written (see `Ordering` in aln_plan)
 __device__ inline uint64_t ld_y(const ulonglong2 *p) { return __hip_atomic_load(&p->y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int32_t lo32(uint64_t v) { return (int32_t)(uint32_t)v; }
 __device__ inline int32_t span_of(uint64_t y) { return (int32_t)(y >> 32 & 0xff); }
 __device__ inline int64_t r16(int64_t n) { return (n + 15) & ~(int64_t)15; }   // every pool segment starts at a multiple of 16
-__device__ inline int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
-__device__ inline int32_t imax(int32_t a, int32_t b) { return a > b ? a : b; }
 // y_i - y_{i-1} - (x_i - x_{i-1}) as the reference's int: modulo 2^32 whichever of its three spellings (:372, :402, :430)
 __device__ inline int32_t gap_at(const ulonglong2 *a, int32_t i)
 {
@@ -31,17 +29,9 @@ struct RegCtx { int64_t read, na; ulonglong2 *a; int32_t qlen; const uint8_t *fw
 // the read of region g and its arrays; false when an offset leaves a capacity
 __device__ bool locate(const AlnArgs &A, int64_t g, RegCtx &C)
 {
-	const int64_t base = A.u_off[0];
-	int64_t lo = 0, hi = A.n_reads;
-	while (lo < hi) {
-		const int64_t mid = (lo + hi) >> 1;
-		if (A.u_off[mid + 1] - base <= g) lo = mid + 1; else hi = mid;
-	}
-	if (lo >= A.n_reads || A.u_off[lo] - base > g) return false;
-	C.read = lo;
-	const int64_t b0 = A.b_off[lo], na = A.n_b ? A.n_b[lo] : A.b_off[lo + 1] - b0, r0 = A.read_off[lo], r1 = A.read_off[lo + 1];
-	if (b0 < 0 || na < 0 || na > INT32_MAX || b0 > A.b_cap - na || r0 < 0 || r1 < r0 || r1 > A.reads_cap || r1 - r0 > INT32_MAX) return false;
-	C.na = na; C.a = A.b + b0; C.qlen = (int32_t)(r1 - r0); C.fwd = A.reads + r0;
+	RegionRead Q;
+	if (!read_of_region(A, g, Q) || Q.r0 + Q.qlen > A.reads_cap) return false;
+	C.read = Q.read; C.na = Q.na; C.a = A.b + Q.b0; C.qlen = Q.qlen; C.fwd = A.reads + Q.r0;
 	return true;
 }
 
@@ -257,7 +247,7 @@ __device__ void walk(const AlnArgs &A, const RegCtx &C, int64_t t0, const ulongl
 				const uint32_t qb = qbase(C, R.rev != 0, qs + j), tb = sget(A.S, t0 + rs + j);
 				sc += qb >= 4 || tb >= 4 ? o.e2 : qb == tb ? o.a : -o.b;
 			}
-			for (int d = 32; d >= 1; d >>= 1) sc += __shfl_xor(sc, d);
+			sc = wave_sum(sc);
 			if (lane == 0) A.items[c.it] = AlnItem{(int32_t)g, ALN_UNGAPPED, R.as1 + R.cnt1 - 1, rs, R.re, qs, R.qe, -1, sc, 0};
 		}
 		++c.it;
@@ -302,7 +292,7 @@ __global__ __launch_bounds__(64) void aln_plan(const AlnArgs A)
 			const bool is_sr = (o.flag & ALN_F_SR) != 0;
 			if ((o.flag & ALN_F_SPLICE) || (is_sr && (o.idx_flag & ALN_I_HPC))) break;             // :575
 			if (!locate(A, g, C)) break;
-			const AlnRegIn r = A.regs[g];
+			const Reg r = A.regs[g];
 			if (r.cnt == 0) { status = 0; break; }                                         // :578
 			if (r.cnt < 0 || r.as < 0 || (int64_t)r.as + r.cnt > C.na) break;
 			ulonglong2 *a = C.a;
@@ -445,7 +435,7 @@ __global__ __launch_bounds__(64) void aln_plan(const AlnArgs A)
 			R.as1 = as1; R.cnt1 = cnt1; R.rs = rs; R.qs = qs; R.re = re; R.qe = qe; R.rs0 = rs0; R.qs0 = qs0; R.re0 = re0; R.qe0 = qe0;
 			R.rev = (int32_t)(a0.x >> 63);
 			Cursor c = {0, 0, 0};
-			walk<false>(A, C, t0, a, R, (r.flags >> 24 & 1) != 0, g, c, lane);
+			walk<false>(A, C, t0, a, R, (r.flags >> REG_SPLIT_INV_BIT & 1) != 0, g, c, lane);
 			R.n_items = (int32_t)c.it; R.n_tasks = (int32_t)c.tk;
 			// until aln_scan: the counts where the offsets go
 			R.item0 = c.it; R.task0 = c.tk; R.cig0 = c.cig;
@@ -507,7 +497,7 @@ __global__ __launch_bounds__(64) void aln_emit(const AlnArgs A)
 		RegCtx C;
 		if (R.status != 0 || R.n_items == 0 || !locate(A, g, C)) continue;
 		Cursor c = {R.item0, R.task0, R.cig0};
-		walk<true>(A, C, (int64_t)A.ref_off[(int64_t)(C.a[R.as1].x << 1 >> 33)], C.a, R, (A.regs[g].flags >> 24 & 1) != 0, g, c, lane);
+		walk<true>(A, C, (int64_t)A.ref_off[(int64_t)(C.a[R.as1].x << 1 >> 33)], C.a, R, (A.regs[g].flags >> REG_SPLIT_INV_BIT & 1) != 0, g, c, lane);
 	}
 }
 

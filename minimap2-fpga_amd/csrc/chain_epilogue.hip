@@ -50,12 +50,6 @@ __device__ __forceinline__ int wg_load(const int *addr)   // a load that sees th
 	return __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-__device__ __forceinline__ int wave_sum(int x)
-{
-	for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-	return x;
-}
-
 // wave_sort64 -- the stable LSD radix sort of one task's records by one wave -- lives in wave_sort.h (chain_regs.hip sorts with it too)
 
 // The three chunked passes below walk a task in chunks of W = 64*K anchors (K per lane), because the passes are sequential from chunk
@@ -156,7 +150,7 @@ __global__ __launch_bounds__(64) void epi_ends(EpiArgs A)
 			const int i = c0 + lane + 64 * k;
 			if (i < n) mark[i] = NONE;                                         // from here on: the chain that takes the anchor (kernel B)
 			const uint64_t m = __ballot(is_end[k]);
-			if (is_end[k]) keys[cnt + lanes_before(m)] = (uint64_t)(uint32_t)fpk[k] << 32 | (uint32_t)pk[k];
+			if (is_end[k]) keys[cnt + lanes_below(m)] = (uint64_t)(uint32_t)fpk[k] << 32 | (uint32_t)pk[k];
 			cnt += __popcll(m);
 		}
 	}
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(64) void epi_claim(EpiArgs A)
 			keep = (stop < 0 || sc >= A.min_sc) && len >= A.min_cnt;
 		}
 		const uint64_t m = __ballot(keep);
-		const int kk = kept + lanes_before(m);
+		const int kk = kept + lanes_below(m);
 		if (keep) {
 			u2[kk] = (uint64_t)(uint32_t)sc << 32 | (uint32_t)len;
 			rkey[kk] = A.d_a[base + top].x;
@@ -397,7 +391,7 @@ void epi_fused(EpiArgs A, int n_above)
 			int at = 0;
 			if (m != 0 && lane == 0) at = atomicAdd(&s_n, __popcll(m));
 			at = __shfl(at, 0);
-			if (is_end[k]) s_a[at + lanes_before(m)] = key[k];
+			if (is_end[k]) s_a[at + lanes_below(m)] = key[k];
 		}
 	}
 	__syncthreads();
@@ -687,7 +681,7 @@ void epi_fused(EpiArgs A, int n_above)
 				keep = (stop < 0 || sc >= A.min_sc) && len >= A.min_cnt;
 			}
 			const uint64_t m = __ballot(keep);
-			const int kk = kept + lanes_before(m);
+			const int kk = kept + lanes_below(m);
 			if (keep) {
 				u2[kk] = (uint64_t)(uint32_t)sc << 32 | (uint32_t)len;
 				rkey[kk] = A.d_a[base + top].x;
@@ -751,7 +745,7 @@ __global__ __launch_bounds__(1024) void epi_offsets(EpiArgs A)
 	const int64_t nt = A.n_tasks, t0 = (int64_t)blockIdx.x * 1024;
 	int64_t pre_u = 0, pre_b = 0;
 	for (int64_t t = tid; t < t0; t += 1024) { pre_u += A.cnt_u[t]; pre_b += A.cnt_b[t]; }
-	for (int o = 32; o > 0; o >>= 1) { pre_u += __shfl_xor(pre_u, o); pre_b += __shfl_xor(pre_b, o); }
+	pre_u = wave_sum(pre_u); pre_b = wave_sum(pre_b);
 	if (lane == 0) { s_u[wave] = pre_u; s_b[wave] = pre_b; }
 	__syncthreads();
 	int64_t carry_u = 0, carry_b = 0;
@@ -796,7 +790,7 @@ __global__ __launch_bounds__(64) void epi_tiesort(EpiArgs A)
 	for (int i0 = 0; i0 < nk; i0 += 64) {
 		const int i = i0 + lane;
 		const int flag = (i + 1 < nk && sx[i] == sx[i + 1]) ? 1 : 0;
-		const int incl = wave_incl_scan(flag, lane);
+		const int incl = wave_incl_sum(flag, lane);
 		if (i < nk) tiecnt[i] = run + incl - flag;
 		run += __shfl(incl, 63);
 	}
@@ -844,7 +838,7 @@ __global__ __launch_bounds__(64) void epi_emit(EpiArgs A)
 		const int kk = valid ? ord[i] : 0;
 		const uint64_t uu = valid ? u2[kk] : 0;
 		const int len = valid ? (int32_t)uu : 0;
-		const int incl = wave_incl_scan(len, lane);
+		const int incl = wave_incl_sum(len, lane);
 		if (valid) { dest[kk] = run + incl - len; u_out[i] = uu; }
 		run += __shfl(incl, 63);
 	}
@@ -897,7 +891,7 @@ __global__ __launch_bounds__(64) void epi_emit_cd(EpiArgs A)
 		const int kk = valid ? ord[i] : 0;
 		const uint64_t uu = valid ? u2[kk] : 0;
 		const int len = valid ? (int32_t)uu : 0;
-		const int incl = wave_incl_scan(len, lane);
+		const int incl = wave_incl_sum(len, lane);
 		if (valid) { dest[kk] = run + incl - len; u_out[i] = uu; }
 		run += __shfl(incl, 63);
 	}

@@ -33,12 +33,11 @@
 #include <climits>
 #include "chain_esterr.h"
 #include "chain_regs.h"
+#include "wave_ops.h"
 
 namespace mm2c {
 
 namespace {
-
-constexpr int REV_BIT = 10;                                                    // minimap.h:96: mapq:8, split:2, rev:1
 
 // get_for_qpos (esterr.c:7-14) on an anchor as four 32-bit words: x = .y << 32 | .x, y = .w << 32 | .z
 __device__ __forceinline__ int32_t for_qpos(const int32_t qlen, const uint4 a)
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(ERR_READS_LANES) void err_reads(ErrArgs A)
 			}
 		}
 	}
-	for (int o = 32; o > 0; o >>= 1) sum_k += __shfl_xor(sum_k, o);
+	sum_k = wave_sum(sum_k);
 	const bool wbad = __ballot(bad) != 0;
 	if (lane == 0) { s_sum[tid >> 6] = sum_k; s_bad[tid >> 6] = wbad; }
 	__syncthreads();
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(ERR_READS_LANES) void err_reads(ErrArgs A)
 	// ---- every region's anchors and reference sequence, before anything is read through them ----
 	for (int i = lane; i < n; i += 64) {
 		const uint64_t *g = regs + (int64_t)i * REG_WORDS;
-		const int32_t cnt = (int32_t)(g[0] >> 32), rid = (int32_t)g[1], as = (int32_t)g[5];
+		const int32_t cnt = reg_get<REG_CNT>(g), rid = reg_get<REG_RID>(g), as = reg_get<REG_AS>(g);
 		bad |= cnt < 0 || as < 0 || (int64_t)as + cnt > bl || rid < 0 || rid >= A.n_ref;
 	}
 	if (__ballot(bad)) { refuse(A, r, lane); return; }
@@ -131,14 +130,14 @@ __global__ __launch_bounds__(ERR_READS_LANES) void err_reads(ErrArgs A)
 		int32_t cnt = 0, as = 0, rev = 0;
 		if (i < n) {
 			const uint64_t *g = regs + (int64_t)i * REG_WORDS;
-			cnt = (int32_t)(g[0] >> 32); as = (int32_t)g[5]; rev = (int32_t)(g[7] >> (32 + REV_BIT)) & 1;
+			cnt = reg_get<REG_CNT>(g); as = reg_get<REG_AS>(g); rev = reg_rev(g);
 			A.first_fail[base + i] = cnt;
 		}
 		if (cnt > 0) {
 			int rank = 0;
 			for (int j = 0; j < n; ++j) {
 				const uint64_t *h = regs + (int64_t)j * REG_WORDS;
-				const int32_t cj = (int32_t)(h[0] >> 32), aj = (int32_t)h[5];
+				const int32_t cj = reg_get<REG_CNT>(h), aj = reg_get<REG_AS>(h);
 				rank += cj > 0 && (aj < as || (aj == as && j < i));
 			}
 			A.tab[base + rank] = make_int4(as, cnt, i, rev);
@@ -189,8 +188,7 @@ __device__ __forceinline__ void post_fail(const ErrArgs &A, const int64_t reg, c
 	if (!m) return;
 	const int64_t reg0 = __shfl(reg, __ffsll(m) - 1);
 	if (__all(!fail || reg == reg0)) {
-		int mn = kf;
-		for (int o = 32; o > 0; o >>= 1) { const int v = __shfl_xor(mn, o); mn = v < mn ? v : mn; }
+		const int mn = wave_min(kf);
 		if ((threadIdx.x & 63) == 0) atomicMin(&A.first_fail[reg0], mn);
 	} else if (fail) atomicMin(&A.first_fail[reg], kf);
 }
@@ -246,8 +244,8 @@ __global__ __launch_bounds__(64) void err_finish(ErrArgs A)
 	const float avg_k = A.avg_k[r];
 	for (int i = lane; i < n; i += 64) {
 		const uint64_t *g = A.regs + (base + i) * REG_WORDS;
-		const int32_t cnt = (int32_t)(g[0] >> 32), rid = (int32_t)g[1], qs = (int32_t)g[2], rs = (int32_t)g[3], re = (int32_t)(g[3] >> 32), as = (int32_t)g[5];
-		const int rev = (int32_t)(g[7] >> (32 + REV_BIT)) & 1;
+		const int32_t cnt = reg_get<REG_CNT>(g), rid = reg_get<REG_RID>(g), qs = reg_get<REG_QS>(g), rs = reg_get<REG_RS>(g), re = reg_get<REG_RE>(g), as = reg_get<REG_AS>(g);
+		const int rev = reg_rev(g);
 		int2 e = make_int2(0, 0);                                                // esterr.c:44-51: div = -1
 		if (cnt > 0) {
 			const int32_t st = mini_idx(mp, ml, for_qpos(qlen, A.b[bo + as + (rev ? cnt - 1 : 0)]));

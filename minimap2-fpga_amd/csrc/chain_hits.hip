@@ -30,23 +30,16 @@
 #include <climits>
 #include "chain_hits.h"
 #include "chain_regs.h"
+#include "wave_ops.h"
 
 namespace mm2c {
 
 namespace {
 
-constexpr uint32_t SAM_PRI = 1u << 12;                                         // minimap.h:96: mapq:8, split:2, rev:1, inv:1, sam_pri:1
-
 struct HitTab {
 	int32_t *qs, *qe, *score, *cnt, *subsc, *nsub, *parent, *rid, *rs, *re, *w, *rev;   // rev: hits_select_multi only
 	int2 *pq, *cov;
 };
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
 
 // what mm_select_sub_multi knows of the fragment: qlens[0] and max_dist (pe.c:10)
 struct MultiFrag { int32_t q0, max_dist; bool two; };
@@ -56,12 +49,12 @@ __device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, cons
                                           const MultiFrag F)
 {
 	for (int i = lane; i < n; i += 64) {
-		const uint64_t *r = in + (int64_t)i * REG_WORDS;
-		const uint64_t w0 = r[0], w1 = r[1], w2 = r[2], w3 = r[3], w4 = r[4], w6 = r[6];
-		T.cnt[i] = (int32_t)(w0 >> 32); T.rid[i] = (int32_t)w1; T.score[i] = (int32_t)(w1 >> 32);
-		T.qs[i] = (int32_t)w2; T.qe[i] = (int32_t)(w2 >> 32); T.rs[i] = (int32_t)w3; T.re[i] = (int32_t)(w3 >> 32);
-		T.parent[i] = (int32_t)w4; T.subsc[i] = (int32_t)(w4 >> 32); T.nsub[i] = (int32_t)(w6 >> 32);
-		if constexpr (MULTI) T.rev[i] = (int32_t)(r[7] >> (32 + 10)) & 1;
+		uint64_t w[8];                                                           // the 64-bit loads first (those of words nobody asks for are dropped)
+		for (int k = 0; k < 8; ++k) w[k] = in[(int64_t)i * REG_WORDS + k];
+		T.cnt[i] = reg_get<REG_CNT>(w); T.rid[i] = reg_get<REG_RID>(w); T.score[i] = reg_get<REG_SCORE>(w);
+		T.qs[i] = reg_get<REG_QS>(w); T.qe[i] = reg_get<REG_QE>(w); T.rs[i] = reg_get<REG_RS>(w); T.re[i] = reg_get<REG_RE>(w);
+		T.parent[i] = reg_get<REG_PARENT>(w); T.subsc[i] = reg_get<REG_SUBSC>(w); T.nsub[i] = reg_get<REG_N_SUB>(w);
+		if constexpr (MULTI) T.rev[i] = reg_rev(w);
 	}
 	__syncthreads();
 
@@ -189,10 +182,10 @@ __device__ __forceinline__ void hits_read(const HitArgs &A, const HitTab T, cons
 	for (int e = lane; e < kept * REG_WORDS; e += 64) {
 		const int t = e / REG_WORDS, wd = e - t * REG_WORDS, s = src[t];
 		uint64_t v = in[(int64_t)s * REG_WORDS + wd];
-		if (wd == 0) v = (v & 0xffffffff00000000ull) | (uint32_t)(sync ? t : s);
-		else if (wd == 4) v = (uint64_t)(uint32_t)(sync ? newidx[T.parent[s]] : T.parent[s]) | (uint64_t)(uint32_t)T.subsc[s] << 32;
-		else if (wd == 6) v = (v & 0xffffffffull) | (uint64_t)(uint32_t)T.nsub[s] << 32;
-		else if (wd == 7 && sync) v = (v & ~((uint64_t)SAM_PRI << 32)) | (uint64_t)(t == 0 ? SAM_PRI : 0u) << 32;   // hit.c:220-229: region 0 is the first primary
+		if (wd == reg_word(REG_ID)) v = reg_with<REG_ID>(v, (uint32_t)(sync ? t : s));
+		else if (wd == reg_word(REG_PARENT)) v = reg_put<REG_PARENT>((uint32_t)(sync ? newidx[T.parent[s]] : T.parent[s])) | reg_put<REG_SUBSC>((uint32_t)T.subsc[s]);
+		else if (wd == reg_word(REG_N_SUB)) v = reg_with<REG_N_SUB>(v, (uint32_t)T.nsub[s]);
+		else if (wd == reg_word(REG_FLAGS) && sync) v = (v & ~reg_put<REG_FLAGS>(REG_SAM_PRI)) | reg_put<REG_FLAGS>(t == 0 ? REG_SAM_PRI : 0u);   // hit.c:220-229: region 0 is the first primary
 		out[(int64_t)t * REG_WORDS + wd] = v;
 	}
 	if (lane == 0) { *n_out = kept; atomicAdd(A.total, (unsigned long long)kept); }

@@ -83,8 +83,7 @@ __global__ __launch_bounds__(64) void regs_sort(RegArgs A)
 		const int32_t cnt = (int32_t)uu;
 		bad |= valid && cnt <= 0;
 		const int64_t c = cnt > 0 ? cnt : 0;
-		int64_t incl = c;
-		for (int o = 1; o < 64; o <<= 1) { const int64_t y = __shfl_up(incl, o); if (lane >= o) incl += y; }
+		const int64_t incl = wave_incl_sum(c, lane);
 		const int64_t pre = run + incl - c;                                      // = as
 		if (valid) {
 			cstart[i] = bbase + (pre < nb ? pre : nb);
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(64) void regs_sort(RegArgs A)
 	for (int i0 = 0; i0 < nu; i0 += 64) {
 		const int i = i0 + lane;
 		const int flag = (i + 1 < nu && key1[i] == key1[i + 1]) ? 1 : 0;
-		const int incl = wave_incl_scan(flag, lane);
+		const int incl = wave_incl_sum(flag, lane);
 		if (i < nu) tiecnt[i] = ties + incl - flag;
 		ties += __shfl(incl, 63);
 	}
@@ -147,16 +146,16 @@ __global__ __launch_bounds__(64) void regs_sort(RegArgs A)
 		const uint32_t qs = rev ? (uint32_t)qlen - y1 : y0, qe = rev ? (uint32_t)qlen - y0 : y1;
 		const uint32_t score = (uint32_t)(z >> 32);
 		uint64_t *o = A.regs + (base + j) * REG_WORDS;
-		o[0] = (uint64_t)(uint32_t)j | (uint64_t)(uint32_t)cnt << 32;             // id, cnt
-		o[1] = (uint64_t)rid | (uint64_t)score << 32;                            // rid, score
-		o[2] = (uint64_t)qs | (uint64_t)qe << 32;
-		o[3] = (uint64_t)rs | (uint64_t)re << 32;
-		o[4] = 0xffffffffull;                                                    // parent = MM_PARENT_UNSET, subsc
-		o[5] = (uint64_t)(uint32_t)as;                                           // as, mlen (regs_fill)
-		o[6] = 0;                                                                // blen (regs_fill), n_sub
-		o[7] = (uint64_t)score | (uint64_t)(rev << 10) << 32;                    // score0, the bit-field word: rev is bit 10
-		o[8] = (uint64_t)(uint32_t)z | 0xbf800000ull << 32;                      // hash, div = -1.0f
-		o[9] = 0;                                                                // p
+		o[reg_word(REG_ID)] = reg_put<REG_ID>((uint32_t)j) | reg_put<REG_CNT>((uint32_t)cnt);
+		o[reg_word(REG_RID)] = reg_put<REG_RID>(rid) | reg_put<REG_SCORE>(score);
+		o[reg_word(REG_QS)] = reg_put<REG_QS>(qs) | reg_put<REG_QE>(qe);
+		o[reg_word(REG_RS)] = reg_put<REG_RS>(rs) | reg_put<REG_RE>(re);
+		o[reg_word(REG_PARENT)] = reg_put<REG_PARENT>(0xffffffffu);                 // parent = MM_PARENT_UNSET, subsc = 0
+		o[reg_word(REG_AS)] = reg_put<REG_AS>((uint32_t)as);                        // mlen: regs_fill
+		o[reg_word(REG_BLEN)] = 0;                                                  // blen: regs_fill; n_sub
+		o[reg_word(REG_SCORE0)] = reg_put<REG_SCORE0>(score) | reg_put<REG_FLAGS>(rev << REG_REV_BIT);
+		o[reg_word(REG_HASH)] = reg_put<REG_HASH>((uint32_t)z) | reg_put<REG_DIV>(0xbf800000u);   // div = -1.0f
+		o[REG_WORDS - 1] = 0;                                                       // p
 		A.crank[base + c] = (int32_t)(base + j);
 	}
 }
@@ -211,7 +210,7 @@ __device__ __forceinline__ void fill_flush(const RegArgs &A, const SliceTab &T, 
 {
 	const int rk = A.crank[c];
 	if ((uint32_t)rk >= (uint32_t)A.n_u_cap) return;                             // (every chain looked up here had its rank written by this run: the bound of the write all the same)
-	int32_t *p = (int32_t *)A.regs + (int64_t)rk * (2 * REG_WORDS) + 11;          // mlen, blen
+	int32_t *p = (int32_t *)A.regs + (int64_t)rk * (2 * REG_WORDS) + REG_MLEN;    // mlen, blen
 	if (T.start<LDS>(c) >= 0 && T.end<LDS>(c) <= len) { p[0] = vm; p[1] = vb; }  // the whole chain lies in this wave's slice
 	else { atomicAdd(p, vm); atomicAdd(p + 1, vb); }
 }

@@ -32,9 +32,6 @@ namespace mm2c {
 
 namespace {
 
-constexpr uint64_t SEG_SPLIT = 1ull << (32 + 15);                               // minimap.h:96: ..., seg_split:1 (bit 15), seg_id:8 (bits 16-23)
-constexpr int SEG_ID_SHIFT = 32 + 16;
-
 template <bool WRITE>
 __global__ __launch_bounds__(64) void seg_walk(SegArgs A)
 {
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(64) void seg_walk(SegArgs A)
 	int64_t sum_cnt = 0;
 	for (int i = 0; i < n && !bad; ++i) {
 		const uint64_t *g = A.regs + (base + i) * REG_WORDS;
-		const int32_t cnt = (int32_t)(g[0] >> 32), score = (int32_t)(g[1] >> 32), as = (int32_t)g[5];
+		const int32_t cnt = reg_get<REG_CNT>(g), score = reg_get<REG_SCORE>(g), as = reg_get<REG_AS>(g);
 		if (!WRITE) {
 			sum_cnt += cnt > 0 ? cnt : 0;
 			if (cnt < 0 || as < 0 || (int64_t)as + cnt > bl || sum_cnt > bl) { bad = true; break; }   // a region that leaves the fragment's anchors, or more than it has
@@ -135,8 +132,8 @@ __global__ __launch_bounds__(256) void seg_mark(SegArgs A, uint64_t *seg_regs)
 	if (sr >= A.n_frags * A.n_segs) return;
 	const int64_t lo = A.su_off[sr], hi = A.su_off[sr + 1];
 	if (lo < 0 || hi > A.n_su_cap) return;                                       // (the scans of counted chains: inside the capacity when seg_walk stored them all)
-	const uint64_t bits = SEG_SPLIT | (uint64_t)(sr % A.n_segs) << SEG_ID_SHIFT;
-	for (int64_t i = lo + lane; i < hi; i += 64) seg_regs[i * REG_WORDS + 7] |= bits;
+	const uint64_t bits = reg_put<REG_FLAGS>(REG_SEG_SPLIT | (uint32_t)(sr % A.n_segs) << REG_SEG_ID_SHIFT);   // seg_id < n_segs <= SEG_MAX: eight bits
+	for (int64_t i = lo + lane; i < hi; i += 64) seg_regs[i * REG_WORDS + reg_word(REG_FLAGS)] |= bits;
 }
 
 } // namespace

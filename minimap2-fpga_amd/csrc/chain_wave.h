@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <limits.h>
 #include "chain_kernel.h"
+#include "wave_ops.h"
 
 namespace mm2c {
 
@@ -39,10 +40,6 @@ __device__ __forceinline__ int prefix_max_incl(int v)
 }
 
 #define BALLOT(c) ((mask_t)__builtin_amdgcn_ballot_w64(c))
-__device__ __forceinline__ int lanes_below(mask_t m)   // number of set bits of m in lanes below this one
-{
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
 __device__ __forceinline__ int rdlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 // per-lane select by a scalar lane mask: bit set -> b, clear -> a
 __device__ __forceinline__ int sel(mask_t m, int a, int b)

@@ -9,23 +9,14 @@
 // which its keys differ (clz of smallest ^ largest); buckets without equal keys, passes in which all keys share the digit, and buckets of
 // <= 64 records (insertion sort in the reference = stable; the caller's final stable sort of the replayed arrangement does the same) need
 // no replay.  A pass over two buckets has a closed form (all lanes); a pass over more buckets is the reference's loop as a walk on one lane
-// that reads digits only (replay_walk).
+// that reads digits only (replay_walk).  The wave primitives (lanes_below, wave_incl_sum, wave_sum) are those of wave_ops.h; rp_wave_sync is this file's own.
 #ifndef MM2C_RADIX_REPLAY_H
 #define MM2C_RADIX_REPLAY_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave_ops.h"
 
 namespace mm2c {
-
-__device__ __forceinline__ int rp_lanes_before(uint64_t m)
-{
-	return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-__device__ __forceinline__ int rp_incl_scan(int x, int lane)
-{
-	for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-	return x;
-}
 
 // un_x / sorted_x: the keys of the unsorted and of the (stably) sorted array, `stride` 64-bit words apart; tiecnt[i] = number of positions
 // j < i of the sorted array with key[j] == key[j+1]; id: position -> record (any memory); dg: one byte per position, with at least one
@@ -246,13 +237,13 @@ __device__ __forceinline__ void replay_bucket(const uint64_t *un_x, int un_strid
 		int h[4], sum = 0;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) { h[k] = s_cur[4 * lane + k]; sum += h[k]; n_buckets += h[k] > 0; }
-		int at = lo + rp_incl_scan(sum, lane) - sum;
+		int at = lo + wave_incl_sum(sum, lane) - sum;
 #pragma unroll
 		for (int k = 0; k < 4; ++k) { s_lo[4 * lane + k] = at; at += h[k]; }
 		if (lane == 63) s_lo[256] = at;                                      // = hi
 	}
 	rp_wave_sync();
-	for (int o = 32; o > 0; o >>= 1) n_buckets += __shfl_xor(n_buckets, o);
+	n_buckets = wave_sum(n_buckets);
 	if (TWO_BUCKET && n_buckets == 2) {
 		// Two buckets A | B (the strand byte, often the top position byte): the distribution has a closed form, no walk.
 		// Bucket A is filled first (ksort.h:118).  Its t-th misplaced record starts a cycle: it is dropped at B's cursor, the records
@@ -267,7 +258,7 @@ __device__ __forceinline__ void replay_bucket(const uint64_t *un_x, int un_strid
 			const int q = q0 + lane;
 			const bool in = q < mid, foreign = in && dg[q] != da;
 			const uint64_t m = __ballot(foreign);
-			if (foreign) fposA[F + rp_lanes_before(m)] = q;
+			if (foreign) fposA[F + lanes_below(m)] = q;
 			else if (in) moved[q] = q;
 			F += __popcll(m);
 		}
@@ -276,7 +267,7 @@ __device__ __forceinline__ void replay_bucket(const uint64_t *un_x, int un_strid
 			const int q = q0 + lane;
 			const bool in = q < hi, foreign = in && dg[q] != db;
 			const uint64_t m = __ballot(foreign);
-			const int t = FB + rp_lanes_before(m);                              // misplaced slots of B before q
+			const int t = FB + lanes_below(m);                              // misplaced slots of B before q
 			if (foreign) fposB[t] = q;
 			else if (in) moved[q + (t < F ? 1 : 0)] = q;
 			FB += __popcll(m);

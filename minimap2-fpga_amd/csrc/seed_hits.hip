@@ -23,21 +23,6 @@ namespace mm2c {
 
 namespace {
 
-__device__ __forceinline__ int lanes_before(uint64_t m)
-{
-	return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-__device__ __forceinline__ int wave_incl_scan(int x, int lane)
-{
-	for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-	return x;
-}
-__device__ __forceinline__ uint64_t wave_or(uint64_t v)
-{
-	for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-	return v;
-}
-
 // where a read's anchors are: the plan's offsets give the CAPACITY of a read (every hit kept); with skip_seed (map.c:122-147) a read keeps
 // cnt[read] <= capacity anchors, the work arrays (unsorted, scratch, tiecnt) stay laid out by capacity and the result is packed by out_off
 struct ReadGeom { int64_t a0, o0; int na; };
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(64) void seed_expand(SeedArgs A)
 			if (lane == 0) { A.status[read] = 2; if (A.d_count) A.d_count[read] = 0; }   // a match reaches beyond the hit pool the caller declared
 			return;
 		}
-		const int incl = wave_incl_scan((int)q.n, lane);
+		const int incl = wave_incl_sum((int)q.n, lane);
 		const int total = __shfl(incl, 63);
 		__syncthreads();
 		s_start[lane] = incl - (int)q.n; s_cr[lane] = q.cr_off; s_qpos[lane] = q.q_pos; s_span[lane] = q.q_span; s_segt[lane] = q.seg_tandem;
@@ -138,7 +123,7 @@ __global__ __launch_bounds__(64) void seed_expand(SeedArgs A)
 			}
 			const uint64_t km = __ballot(keep);                                 // kept hits stay in hit order (the order collect_seed_hits fills a[])
 			if (keep) {
-				out[run + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0))] = a;
+				out[run + lanes_below(km)] = a;
 				x_or |= a.x; x_and &= a.x;
 			}
 			run += (int)__builtin_popcountll(km);
@@ -184,7 +169,7 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 	__syncthreads();
 	// the rows of one chunk of the wave's matches (owner search and encoding) and the chunk's hit total; a wave's own rows: no workgroup barrier
 	auto load_rows = [&](const Match &q) -> int {
-		const int incl = wave_incl_scan((int)q.n, lane);
+		const int incl = wave_incl_sum((int)q.n, lane);
 		const int total = __shfl(incl, 63);
 		s_start[wave][lane] = incl - (int)q.n; s_cr[wave][lane] = q.cr_off; s_qpos[wave][lane] = q.q_pos; s_span[wave][lane] = q.q_span; s_segt[wave][lane] = q.seg_tandem;
 		if (lane == 63) s_start[wave][64] = total;
@@ -208,7 +193,7 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 		const bool outside = A.n_hits > 0 && i < nm && (q.cr_off < 0 || q.cr_off + (int64_t)q.n > A.n_hits);
 		if (outside) s_bad = 2;
 		unsigned long long n64 = q.n;                                               // the chunk's hits in 64 bits: a chunk with more than the read's anchors is an error (and keeps the int sums exact)
-		for (int d = 1; d < 64; d <<= 1) n64 += (unsigned long long)__shfl_xor((long long)n64, d);
+		n64 = wave_sum(n64);
 		if (n64 > (unsigned long long)na) { if (!s_bad) s_bad = 1; n64 = 0; }
 		if constexpr (SKIP) {
 			int kept = 0;
@@ -244,7 +229,7 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 	{
 		// (an int suffices for the places: the grand total must equal na < 2^31, checked below; a partial sum that overflowed shows up as a mismatch there)
 		int v = (int)min(mine, (long long)INT_MAX);
-		const int incl = wave_incl_scan(v, lane);
+		const int incl = wave_incl_sum(v, lane);
 		if (lane == 63) s_part[wave] = incl;
 		__syncthreads();
 		int before = 0;
@@ -274,7 +259,7 @@ __global__ __launch_bounds__(64 * NW) void seed_expand_mw(SeedArgs A)
 			const bool keep = t < total && hit_at(t, a);
 			if constexpr (SKIP) {
 				const uint64_t km = __ballot(keep);                                   // kept hits stay in hit order (the order collect_seed_hits fills a[])
-				if (keep) { out[run + lanes_before(km)] = a; x_or |= a.x; x_and &= a.x; }
+				if (keep) { out[run + lanes_below(km)] = a; x_or |= a.x; x_and &= a.x; }
 				run += (int)__builtin_popcountll(km);
 			} else if (keep) {
 				out[run + t] = a;
@@ -335,7 +320,7 @@ __device__ void wave_sort_anchors(const ulonglong2 *src, ulonglong2 *alt, ulongl
 			int h[4], sum = 0;
 #pragma unroll
 			for (int k = 0; k < 4; ++k) { h[k] = s_cnt[4 * lane + k]; sum += h[k]; }
-			int at = wave_incl_scan(sum, lane) - sum;
+			int at = wave_incl_sum(sum, lane) - sum;
 			__syncthreads();
 #pragma unroll
 			for (int k = 0; k < 4; ++k) { s_cnt[4 * lane + k] = at; at += h[k]; }
@@ -355,7 +340,7 @@ __device__ void wave_sort_anchors(const ulonglong2 *src, ulonglong2 *alt, ulongl
 					const uint64_t bal = __ballot((d >> b) & 1);
 					peers &= ((d >> b) & 1) ? bal : ~bal;
 				}
-				const int rank = lanes_before(peers);
+				const int rank = lanes_below(peers);
 				if (valid) to[s_cnt[d] + rank] = rec[k];
 				__syncthreads();
 				if (valid && rank == 0) s_cnt[d] += __popcll(peers);
@@ -396,7 +381,7 @@ __device__ uint64_t *wave_sort_keys(uint64_t *a, uint64_t *b, int n, int bit_lo,
 			int h[4], sum = 0;
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { h[u] = s_cnt[4 * lane + u]; sum += h[u]; }
-			int at = wave_incl_scan(sum, lane) - sum;
+			int at = wave_incl_sum(sum, lane) - sum;
 			__syncthreads();
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { s_cnt[4 * lane + u] = at; at += h[u]; }
@@ -416,7 +401,7 @@ __device__ uint64_t *wave_sort_keys(uint64_t *a, uint64_t *b, int n, int bit_lo,
 					const uint64_t bal = __ballot((d >> bb) & 1);
 					peers &= ((d >> bb) & 1) ? bal : ~bal;
 				}
-				const int rank = lanes_before(peers);
+				const int rank = lanes_below(peers);
 				if (valid) to[s_cnt[d] + rank] = k[u];
 				__syncthreads();
 				if (valid && rank == 0) s_cnt[d] += __popcll(peers);
@@ -477,7 +462,7 @@ __global__ __launch_bounds__(64 * NW) void seed_sort_lds(SeedArgs A, int blk0)
 			int h[4], sum = 0;
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { h[u] = s_hist[32 * shift + 4 * lane + u]; sum += h[u]; }
-			int at = wave_incl_scan(sum, lane) - sum;
+			int at = wave_incl_sum(sum, lane) - sum;
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { s_cnt[4 * lane + u] = at; at += h[u]; }
 		}
@@ -493,7 +478,7 @@ __global__ __launch_bounds__(64 * NW) void seed_sort_lds(SeedArgs A, int blk0)
 				const uint64_t bal = __ballot((d >> bb) & 1);
 				peers &= ((d >> bb) & 1) ? bal : ~bal;
 			}
-			const int rank = lanes_before(peers);
+			const int rank = lanes_below(peers);
 			if (valid && rank == 0) s_w[256 * wave + d] = __popcll(peers);
 			__syncthreads();
 			if (valid) {
@@ -516,7 +501,7 @@ __global__ __launch_bounds__(64 * NW) void seed_sort_lds(SeedArgs A, int blk0)
 		const int id = i < na ? (int)from[i] : 0, idn = i + 1 < na ? (int)from[i + 1] : 0;
 		if (i < na) { out[i] = un[id]; srt[i] = (uint32_t)id; }
 		const int flag = (i + 1 < na && s_key[id] == s_key[idn]) ? 1 : 0;
-		const int incl = wave_incl_scan(flag, lane);
+		const int incl = wave_incl_sum(flag, lane);
 		if (lane == 63) s_carry[wave + 1] = incl;
 		__syncthreads();
 		int before = run;
@@ -576,7 +561,7 @@ __global__ __launch_bounds__(64) void seed_sort(SeedArgs A)
 			const uint64_t k = i < na ? ks[i] : 0, kn = i + 1 < na ? ks[i + 1] : ~0ull;
 			if (i < na) { out[i] = un[(int)(k & idm)]; srt[i] = (uint32_t)(k & idm); }   // srt: which anchor of the unsorted array stands here (seed_ties reorders equal x by it)
 			const int flag = (i + 1 < na && (k >> idb) == (kn >> idb)) ? 1 : 0;
-			const int incl = wave_incl_scan(flag, lane);
+			const int incl = wave_incl_sum(flag, lane);
 			if (i < na) tiecnt[i] = run + incl - flag;
 			run += __shfl(incl, 63);
 		}
@@ -585,7 +570,7 @@ __global__ __launch_bounds__(64) void seed_sort(SeedArgs A)
 		for (int i0 = 0; i0 < na; i0 += 64) {
 			const int i = i0 + lane;
 			const int flag = (i + 1 < na && out[i].x == out[i + 1].x) ? 1 : 0;
-			const int incl = wave_incl_scan(flag, lane);
+			const int incl = wave_incl_sum(flag, lane);
 			if (i < na) tiecnt[i] = run + incl - flag;
 			run += __shfl(incl, 63);
 		}
@@ -612,7 +597,7 @@ __device__ uint64_t *block_sort_keys(uint64_t *a, uint64_t *b, int n, int bit_lo
 			int h[4], sum = 0;
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { h[u] = s_cnt[4 * lane + u]; sum += h[u]; }
-			int at = wave_incl_scan(sum, lane) - sum;
+			int at = wave_incl_sum(sum, lane) - sum;
 #pragma unroll
 			for (int u = 0; u < 4; ++u) { s_cnt[4 * lane + u] = at; at += h[u]; }
 		}
@@ -628,7 +613,7 @@ __device__ uint64_t *block_sort_keys(uint64_t *a, uint64_t *b, int n, int bit_lo
 				const uint64_t bal = __ballot((d >> bb) & 1);
 				peers &= ((d >> bb) & 1) ? bal : ~bal;
 			}
-			const int rank = lanes_before(peers);
+			const int rank = lanes_below(peers);
 			if (valid && rank == 0) s_w[256 * wave + d] = __popcll(peers);
 			__syncthreads();
 			if (valid) {
@@ -689,7 +674,7 @@ __global__ __launch_bounds__(64 * NW) void seed_sort_mw(SeedArgs A)
 		const uint64_t k = i < na ? ks[i] : 0, kn = i + 1 < na ? ks[i + 1] : ~0ull;
 		if (i < na) { out[i] = un[(int)(k & idm)]; srt[i] = (uint32_t)(k & idm); }
 		const int flag = (i + 1 < na && (k >> idb) == (kn >> idb)) ? 1 : 0;
-		const int incl = wave_incl_scan(flag, lane);
+		const int incl = wave_incl_sum(flag, lane);
 		if (lane == 63) s_carry[wave + 1] = incl;
 		__syncthreads();
 		int before = run;

@@ -19,6 +19,7 @@
 //      joined; the lookups then run per fragment.  The max_occ re-chain (map.c:318-340) is decided per fragment from the chains on the device, and the flagged
 //      fragments' minimizers are compacted for a second pass.  DESIGN.md section 3.11.
 #include "api_internal.h"
+#include "wave_ops.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -342,12 +343,6 @@ struct RcArgs {
 	uint8_t *flag; int64_t *sel_cnt, *mini_cnt;                // per fragment (n_frags + 1, the last 0): 1 / its minimizers when flagged, then their exclusive scans
 };
 
-template <class T> __device__ __forceinline__ T wave_sum(T v)
-{
-	for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-	return v;
-}
-
 // one wave per fragment: rechain = rep_len > 0 && (no chain || the best chain misses a segment), map.c:318-331 (the caller has tested max_occ > mid_occ)
 __global__ void __launch_bounds__(TPB) rc_decide(RcArgs A)
 {
@@ -371,11 +366,11 @@ __global__ void __launch_bounds__(TPB) rc_decide(RcArgs A)
 			if (best_i >= 0) {
 				int64_t off = 0;
 				for (int64_t i = lane; i < best_i; i += 64) off += (int64_t)(uint32_t)A.u[u0 + i];
-				off = A.b_off[g] + wave_sum(off);
+				off = A.b_off[g] + mm2c::wave_sum(off);
 				const int64_t cnt = (int64_t)(int32_t)A.u[u0 + best_i];
 				int diff = 0;
 				for (int64_t i = 1 + lane; i < cnt; i += 64) diff += (A.b[off + i].y & SEG_MASK) != (A.b[off + i - 1].y & SEG_MASK);
-				n_chained_segs += wave_sum(diff);
+				n_chained_segs += mm2c::wave_sum(diff);
 			}
 			rechain = n_chained_segs < A.n_segs;
 		}

@@ -1,24 +1,14 @@
 // wave_sort.h -- stable LSD radix sort of one task's records by one wave, shared by the device epilogue (chain_epilogue.hip) and the
-// chains-to-regions step (chain_regs.hip).
+// chains-to-regions step (chain_regs.hip).  The wave primitives it uses (lanes_below, wave_incl_sum, wave_or) are those of wave_ops.h.
 #ifndef MM2C_WAVE_SORT_H
 #define MM2C_WAVE_SORT_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave_ops.h"
 
 namespace mm2c {
 
 namespace {
-
-__device__ __forceinline__ int lanes_before(uint64_t m)
-{
-	return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-__device__ __forceinline__ int wave_incl_scan(int x, int lane)
-{
-	for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(x, o); if (lane >= o) x += y; }
-	return x;
-}
 
 // ---- stable LSD radix sort of one task's records by one wave (8-bit digits, ping-pong between two global buffers) ----
 // Bytes in which all keys agree are skipped, so (score << 32 | index) keys cost about four passes.  Per 64 records: the lanes with
@@ -40,7 +30,7 @@ __device__ void wave_sort64(uint64_t *k0, uint64_t *k1, int32_t *v0, int32_t *v1
 	uint64_t diff = 0;
 	const uint64_t first = k0[0];
 	for (int i = lane; i < m; i += 64) diff |= k0[i] ^ first;
-	for (int o = 32; o > 0; o >>= 1) diff |= __shfl_xor(diff, o);
+	diff = wave_or(diff);
 	uint64_t *src = k0, *dst = k1;
 	int32_t *vsrc = v0, *vdst = v1;
 	for (int shift = 0; shift < 64; shift += 8) {
@@ -56,7 +46,7 @@ __device__ void wave_sort64(uint64_t *k0, uint64_t *k1, int32_t *v0, int32_t *v1
 			int h[4], sum = 0;
 #pragma unroll
 			for (int k = 0; k < 4; ++k) { h[k] = s_cnt[4 * lane + k]; sum += h[k]; }
-			int at = wave_incl_scan(sum, lane) - sum;
+			int at = wave_incl_sum(sum, lane) - sum;
 			__syncthreads_sort();
 #pragma unroll
 			for (int k = 0; k < 4; ++k) { s_cnt[4 * lane + k] = at; at += h[k]; }
@@ -76,13 +66,13 @@ __device__ void wave_sort64(uint64_t *k0, uint64_t *k1, int32_t *v0, int32_t *v1
 				peers &= ((d >> b) & 1) ? bal : ~bal;
 			}
 			if (valid) {
-				const int rank = lanes_before(peers);
+				const int rank = lanes_below(peers);
 				const int pos = s_cnt[d] + rank;
 				dst[pos] = key;
 				if (vdst) vdst[pos] = val;
 			}
 			__syncthreads_sort();
-			if (valid && lanes_before(peers) == 0) s_cnt[d] += __popcll(peers);
+			if (valid && lanes_below(peers) == 0) s_cnt[d] += __popcll(peers);
 			__syncthreads_sort();
 		}
 		{ uint64_t *t = src; src = dst; dst = t; }

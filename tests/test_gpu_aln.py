@@ -148,6 +148,31 @@ def test_every_region_in_batches_both_orders(name, fx, ref, model):
     plan.close()
 
 
+def repeat(c, k):
+    """the reads of a batch k times over in one call"""
+    u_off, regs, b_off, b, read_off, fwd, names = c
+    off = lambda o: np.concatenate([[0], np.cumsum(np.tile(np.diff(o), k))]).astype(np.int64)
+    return off(u_off), np.tile(regs, k), off(b_off), np.tile(b, (k, 1)), off(read_off), np.tile(fwd, k), list(names) * k
+
+
+def test_more_regions_than_one_scan_chunk(ref, model):
+    """the asm20 batch five times over in one call, 1 285 regions: aln_scan takes them in chunks of 1 024, so the offsets of the second chunk are the first chunk's
+    totals plus its own prefix sums.  Every byte equals the model's, and every copy plans the tasks of the batch run once (which
+    test_every_region_in_batches_both_orders holds against the reference's record)."""
+    o, c, want1 = model["asm20"]
+    c5 = repeat(c, 5)
+    n = int(c5[0][-1])
+    assert n > 1024 and n % 1024 != 0
+    want = M.run(o, D.reference(), *c5[:6], slot_words=SLOT_WORDS)
+    plan = plan_for(c5, want)
+    got, guards = run_plan(plan, ref, opt_of(o), c5)
+    assert got["rc"] == 0 and guards
+    same(got, want, "asm20 x 5")
+    n1 = int(c[0][-1])
+    assert all(M.task_records(got, g) == M.task_records(want1, g % n1) for g in range(n))
+    plan.close()
+
+
 def one_region(c, g):
     """region g of a batch alone in a call, with its read"""
     u_off, regs, b_off, b, read_off, fwd, names = c

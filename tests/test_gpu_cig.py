@@ -194,6 +194,15 @@ def both(B, m, what):
         plan.close()
 
 
+def test_more_regions_than_one_scan_chunk():
+    """the planted regions 43 times over in one call, 1 075 regions: cig_second_scan and cig_scan take them in chunks of 1 024, so the offsets of the second chunk are
+    the first chunk's totals plus its own prefix sums"""
+    names = D.planted_batch()[0] * 43
+    _, B = D.planted_batch(names)
+    assert len(B["aregs"]) > 1024 and len(B["aregs"]) % 1024 != 0 and B["second"]["totals"][0] > 0
+    assert both(B, D.model(B), "1075 regions")["rc"] == 0
+
+
 def test_reverse_order_option_sets_and_a_shift_that_cuts():
     """the planted regions in reverse order; under the z-drop, band and min_cnt scalars of every option set of aln_data.OPTS with q != q2 (sr has its own batch); and at
     cig_shift 4, where the slot rule of the second list differs from qlen + tlen and the long CIGARs of the word limits no longer fit their slots: those regions are
