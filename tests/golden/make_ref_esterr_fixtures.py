@@ -3,7 +3,8 @@ esterr.o, with klib's sorts from misc.o and the host's own pow and logf) on ever
 reference objects build() leaves in oracle/_ref/.
 Output: tests/golden/ref_esterr.npz (data only): reg_size, names, libm (the C library's version string the fixture was made with), n_out / out_off / regs_out (the raw
 mm_reg1_t arrays behind mm_set_mapq, div included), n_b_out / a_off / a_out (the final a[] of every case: uint64 [., 2]).  The chains, anchors, mini_pos and ref_len
-are not stored: esterr_data.cases() makes them again."""
+are not stored: esterr_data.cases() makes them again.
+With arguments `<data module> <file name>` the cases() of another module under tests/ go into another file: `anchor_space_limit_data ref_esterr_limits.npz`."""
 import os
 import platform
 import struct
@@ -17,15 +18,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF_OBJ = os.path.join(ROOT, "oracle", "_ref")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import esterr_data  # noqa: E402
+import importlib  # noqa: E402
 
 
-def main(out_name="ref_esterr.npz"):
+def main(module="esterr_data", out_name="ref_esterr.npz"):
+    """module: the data module under tests/ whose cases() to run (by default esterr_data, into ref_esterr.npz)"""
     tmp = tempfile.mkdtemp()
     dump = os.path.join(tmp, "esterr_dump")
     objs = [os.path.join(REF_OBJ, o + ".o") for o in ("hit", "esterr", "misc", "kalloc")]
     subprocess.check_call(["gcc", "-O2", "-w", "-DHAVE_KALLOC", "-I/root/reference", os.path.join(HERE, "esterr_dump.c")] + objs + ["-o", dump, "-lm", "-lpthread"])
-    cs = esterr_data.cases()
+    cs = importlib.import_module(module).cases()
     fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<i", len(cs)))
@@ -64,4 +66,4 @@ def main(out_name="ref_esterr.npz"):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:2])
+    main(*sys.argv[1:3])

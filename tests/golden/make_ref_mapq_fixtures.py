@@ -3,7 +3,8 @@
 against the reference objects build() leaves in oracle/_ref/.
 Output: tests/golden/ref_mapq.npz (data only): reg_size, names, libm (the C library's version string the fixture was made with), n_in / in_off / hits_in (the raw
 mm_reg1_t arrays in front of mm_join_long: the plan's input), n_out / out_off / hits_out (the arrays behind mm_set_mapq), n_b_out / a_off / a_out (the final a[] of
-every case: uint64 [., 2]).  The chains and anchors are not stored: mapq_data.cases() makes them again."""
+every case: uint64 [., 2]).  The chains and anchors are not stored: mapq_data.cases() makes them again.
+With arguments `<data module> <file name>` the cases() of another module under tests/ go into another file: `anchor_space_limit_data ref_mapq_limits.npz`."""
 import os
 import platform
 import struct
@@ -17,15 +18,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF_OBJ = os.path.join(ROOT, "oracle", "_ref")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import mapq_data  # noqa: E402
+import importlib  # noqa: E402
 
 
-def main(out_name="ref_mapq.npz"):
+def main(module="mapq_data", out_name="ref_mapq.npz"):
+    """module: the data module under tests/ whose cases() to run (by default mapq_data, into ref_mapq.npz)"""
     tmp = tempfile.mkdtemp()
     dump = os.path.join(tmp, "mapq_dump")
     objs = [os.path.join(REF_OBJ, o + ".o") for o in ("hit", "misc", "kalloc")]
     subprocess.check_call(["gcc", "-O2", "-w", "-DHAVE_KALLOC", "-I/root/reference", os.path.join(HERE, "mapq_dump.c")] + objs + ["-o", dump, "-lm", "-lpthread"])
-    cs = mapq_data.cases()
+    cs = importlib.import_module(module).cases()
     fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<i", len(cs)))
@@ -66,4 +68,4 @@ def main(out_name="ref_mapq.npz"):
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:2])
+    main(*sys.argv[1:3])
