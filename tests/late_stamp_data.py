@@ -1,5 +1,5 @@
 """Seeded inputs for the fold order of the tile kernel's hand-written loop (csrc/chain_dp_tile.h: a chunk stamps only once its fold knows that the scan goes on; the
-model: tests/tile_model_late_stamps.py).  tests/test_cpu_late_stamps.py shows on the CPU, from the oracle and the model alone, that each input holds what it is named
+model: tests/tile_model.py).  tests/test_cpu_late_stamps.py shows on the CPU, from the oracle and the model alone, that each input holds what it is named
 for; tests/test_gpu_late_stamps.py runs the same inputs through the library."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""Seeded inputs for the score-bound exit of the tile kernel's hand-written loop (csrc/chain_dp_tile.h, MM2C_EXIT_TEST; the model: tests/tile_model_exit.py).
+"""Seeded inputs for the score-bound exit of the tile kernel's hand-written loop (csrc/chain_dp_tile.h, MM2C_EXIT_TEST; the model: tests/tile_model.py).
 tests/test_cpu_score_exit.py shows on the CPU, from the oracle and the model alone, that each input holds what it is named for; tests/test_gpu_score_exit.py runs
 the same inputs through the library."""
 import numpy as np

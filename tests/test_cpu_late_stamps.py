@@ -1,31 +1,24 @@
 """The fold order of the tile kernel's hand-written loop (csrc/chain_dp_tile.h: stamps and marks of a scored chunk behind the fold's decision, MM2C_ST_LEAN /
-MM2C_ST_FAR) on the CPU: the model of the loop in that order (tests/tile_model_late_stamps.py) against the oracle, and the inputs of tests/late_stamp_data.py against
+MM2C_ST_FAR) on the CPU: the model of the loop in that order (tests/tile_model.py, its default) against the oracle, and the inputs of tests/late_stamp_data.py against
 what they are named for.  A chunk whose fold B0 takes the score-bound exit leaves before any of its stamps is written; every other fold stamps before it reads a mark.
 A. the standard inputs at max_skip 0, 1 and 25: the model equals the oracle, exits without stamps happen in the own tile and are followed, in the same tile, by
 anchors whose fold reads own-tile marks, and a fold B0 that stays reaches the `break` at each max_skip (late stamps are still counted); B. windows of 1 .. 6 whole older
 tiles with and without a partly covered one: the best candidate is the deepest, on either side of the end of the f / p ring; C. first tile and short last tile;
-D. the device-cut task; E. with the exit off nothing leaves without stamps and the counters are those of tests/tile_model_exit.py."""
+D. the device-cut task; E. with the exit off nothing leaves without stamps and the counters are those of the model with the stamps before the fold (late_stamps=False)."""
 import numpy as np
 import pytest
 
 import late_stamp_data as ls
 import oracle_binding as ob
 import score_exit_data as sx
-from tile_model_exit import chain_tile_model_exit
-from tile_model_late_stamps import chain_tile_model_late_stamps
+from tile_loop_harness import run_model, same as _same
+from tile_model import chain_tile_model
 
 
 def _run(P, t, **kw):
     """(oracle f, p), (model f, p), stats, events"""
-    avg = ob.avg_qspan(t)
-    f, p, _ = ob.chain_fpv(P, t, avg)
-    st, ev = {}, dict(unstamped=[], own_marks=[])
-    fm, pm = chain_tile_model_late_stamps(P, t, avg, stats=st, events=ev, **kw)
-    return (f, p), (fm, pm), st, ev
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    ref, got, st, _, ev = run_model(P, t, **kw)
+    return ref, got, st, ev
 
 
 @pytest.mark.parametrize("form", list(ls.FORMS))
@@ -85,7 +78,7 @@ def test_d_the_pieces_of_the_device_cut_task():
     f, p, _ = ob.chain_fpv(P, t, avg)
     for s, e in sx.cut_pieces(P, t):
         st = {}
-        fm, pm = chain_tile_model_late_stamps(P, t[s:e], avg, NX=16, NF=4, compact=True, stats=st)
+        fm, pm = chain_tile_model(P, t[s:e], avg, NX=16, NF=4, compact=True, stats=st)
         assert np.array_equal(fm, f[s:e]) and np.array_equal(np.where(pm >= 0, pm + s, pm), p[s:e]), (s, e)
         assert st["exits_unstamped"] > 0
 
@@ -97,8 +90,8 @@ def test_e_exit_off_and_the_counters_of_the_earlier_model():
         avg = ob.avg_qspan(t)
         for mode in ("auto", "off"):
             a, b = {}, {}
-            ra = chain_tile_model_exit(P, t, avg, NX=16, NF=4, compact=True, stats=a, score_exit=mode)
-            rb = chain_tile_model_late_stamps(P, t, avg, NX=16, NF=4, compact=True, stats=b, score_exit=mode)
+            ra = chain_tile_model(P, t, avg, NX=16, NF=4, compact=True, stats=a, score_exit=mode, late_stamps=False)
+            rb = chain_tile_model(P, t, avg, NX=16, NF=4, compact=True, stats=b, score_exit=mode)
             assert _same(ra, rb)
             assert all(a[k] == b[k] for k in a if k != "far_stamp"), {k: (a[k], b[k]) for k in a if a[k] != b[k]}   # (far stamps: an exit without stamps writes none)
             assert b["far_stamp"] <= a["far_stamp"]

@@ -155,7 +155,7 @@ def test_tile_formulation_model_equals_oracle(profile):
             avg = ob.avg_qspan(t)
             f, p, _ = ob.chain_fpv(par, t, avg)
             st = {}
-            fm, pm = chain_tile_model(par, t, avg, stats=st)
+            fm, pm = chain_tile_model(par, t, avg, stats=st, score_exit="off", late_stamps=False)
             assert np.array_equal(f, fm) and np.array_equal(p, pm)
             assert st["anchors"] == t.shape[0] and st["fold_a"] + st["fold_b0"] + st["fold_b1"] + st["fold_b2_closed"] + st["fold_b2_scan"] == \
                 st["own_pass"] + st["ring_pass"] + st["far_pass"]
@@ -184,7 +184,7 @@ def test_model_of_the_hand_written_loop_reaches_every_label():
                 avg = ob.avg_qspan(t)
                 f, p, _ = ob.chain_fpv(par, t, avg)
                 st = {}
-                fm, pm = chain_tile_model(par, t, avg, NX=NX, stats=st, compact=compact)
+                fm, pm = chain_tile_model(par, t, avg, NX=NX, stats=st, compact=compact, score_exit="off", late_stamps=False)
                 assert np.array_equal(f, fm) and np.array_equal(p, pm), (form, max_skip)
                 for k in LABEL_KEYS:
                     S[k] += st[k]

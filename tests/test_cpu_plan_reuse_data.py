@@ -73,7 +73,7 @@ def test_scored_tiles_come_from_beyond_the_packed_ring(name):
         t = rd.get(name)[k]
         avg = float(np.float32(.01 * float(np.float32(rd.span_sum(t))) / t.shape[0]))
         st = {}
-        chain_tile_model(P, t, avg, stats=st, NX=16, NF=4)
+        chain_tile_model(P, t, avg, stats=st, NX=16, NF=4, score_exit="off", late_stamps=False)
         deep += st["deep_fp"]; ring += st["ring_pass"]
     print(f"set {name}: deep_fp {deep}, ring_pass {ring}")
     assert deep > 0 and ring > deep

@@ -1,5 +1,5 @@
 """The score-bound exit of the tile kernel's hand-written loop (csrc/chain_dp_tile.h, MM2C_EXIT_TEST) on the CPU: the model of the loop with the exit
-(tests/tile_model_exit.py) against the oracle.  An anchor's scan ends once pfx + span_i <= best, pfx being the largest f before the tile in progress: a pair scores
+(tests/tile_model.py with late_stamps=False: the loop as it was when it got the exit) against the oracle.  An anchor's scan ends once pfx + span_i <= best, pfx being the largest f before the tile in progress: a pair scores
 at most f[j] + span_i while the gap cost is not a gain, so f / p cannot change -- the exit only replaces the rest of a scan that would have counted skip events.
 A. the standard inputs; B. the equality edge (f[j] + span_i == best leaves, == best + 1 does not); C. first tile and short last tile; D. gap_scale < 0, where the
 bound does not hold and the exit stays off; E. the task the GPU test has cut into pieces on the device."""
@@ -8,21 +8,13 @@ import pytest
 
 import oracle_binding as ob
 import score_exit_data as sx
-from tile_model import LABEL_KEYS
-from tile_model_exit import chain_tile_model_exit
+from tile_loop_harness import run_model, same as _same
+from tile_model import LABEL_KEYS, chain_tile_model
 
 
 def _run(P, t, **kw):
     """(oracle f, p), (model f, p), stats, anchors that left early"""
-    avg = ob.avg_qspan(t)
-    f, p, _ = ob.chain_fpv(P, t, avg)
-    st, ex = {}, []
-    fm, pm = chain_tile_model_exit(P, t, avg, stats=st, exit_anchors=ex, **kw)
-    return (f, p), (fm, pm), st, ex
-
-
-def _same(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    return run_model(P, t, late_stamps=False, **kw)[:4]
 
 
 @pytest.mark.parametrize("form", list(sx.FORMS))
@@ -102,7 +94,7 @@ def test_e_the_device_cut_task_is_cut_and_its_pieces_exit():
     exits = []
     for s, e in pieces:
         st, ex = {}, []
-        fm, pm = chain_tile_model_exit(P, t[s:e], avg, NX=16, compact=True, stats=st, exit_anchors=ex)
+        fm, pm = chain_tile_model(P, t[s:e], avg, NX=16, compact=True, stats=st, exit_anchors=ex, late_stamps=False)
         assert np.array_equal(fm, f[s:e]) and np.array_equal(np.where(pm >= 0, pm + s, pm), p[s:e]), (s, e)
         assert all(i >= 64 for i in ex)                           # a piece starts its own pfx: nothing leaves during its first tile
         exits.append(st["exits"])

@@ -92,7 +92,7 @@ def test_scored_tiles_at_every_depth_of_the_ring_and_beyond(gap_scale, knobs):
         avg = float(np.float32(.01 * float(np.float32(span_sum(t))) / t.shape[0]))
         for nf in (2, 4):
             st = {}
-            chain_tile_model(P, t, avg, stats=st, NX=16, NF=nf)
+            chain_tile_model(P, t, avg, stats=st, NX=16, NF=nf, score_exit="off", late_stamps=False)
             got[f"deep{nf}"] += st["deep_fp"]
         got["ring"] += st["ring_pass"]
     assert got["deep4"] > 0 and got["deep2"] > got["deep4"] and got["ring"] > got["deep2"], got

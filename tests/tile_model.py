@@ -1,10 +1,37 @@
-"""NumPy model of the control flow of the round-2 HIP kernel (csrc/chain_dp_tile.h), lane for lane: tile-aligned chunks scanned
-nearest-first (own tile from "registers", NX - 1 older tiles from the x / q ring, f / p of the NF nearest from the ring and deeper ones
-from the task's own stores, anything older from "global" memory), the three-instruction filter, equal-x runs found per tile, 16-bit
-stamps in a ring of 64 NX slots with 32-bit stamps beyond it, and the fold paths (A: no lane beats the running best, B0: the first surviving
-lane is the only new maximum, B1: a single candidate, B2: prefix max + closed-form or max-plus skip counter).  It exists so that the formulation can be checked against the oracle
-WITHOUT a GPU (-m "not gpu"), and so that tools/chunk_stats.py can count how often each path of the hand-written loop is taken
-(profiles/r2_isa_budget.md); the GPU tests check the real kernel.  One segment, no cDNA (the variant the hand-written loop covers)."""
+"""NumPy model of the control flow of the tile kernel's hand-written anchor loop (csrc/chain_dp_tile.h, MM2C_SCAN_TILE_ASM), lane for lane: tile-aligned chunks
+scanned nearest-first (own tile from "registers", NX - 1 older tiles from the x / q ring, f / p of the NF nearest from the ring and deeper ones from the task's
+own stores, anything older from "global" memory), the three-instruction filter, equal-x runs found per tile, 16-bit stamps in a ring of 64 NX slots with 32-bit
+stamps beyond it, and the fold paths (A: no lane beats the running best, B0: the first surviving lane is the only new maximum, B1: a single candidate, B2: prefix
+max + closed-form or max-plus skip counter).  It exists so that the formulation can be checked against the oracle WITHOUT a GPU (-m "not gpu"), and so that
+tools/chunk_stats.py can count how often each path of the loop is taken; the GPU tests check the real kernel and hold the label-counting build against these
+counters.  One segment, no cDNA (the variant the hand-written loop covers).  The defaults are the loop as it ships; two switches give the loops it was before.
+
+score_exit: the score-bound exit (MM2C_EXIT_TEST).  pfx is the maximum of f over the finished tiles of the task (a piece cut on the device is a task of its own),
+and wherever a fold has raised the best -- fold B0 once the new best and its j are set, and the common way back of B1 / B1M / B2 / take -- the scan of the anchor
+ends when best - (span_i - 1) > pfx, i.e. pfx + span_i <= best: a pair scores at most f[j] + span_i while the gap cost is not a gain (chain.c:207-220,
+gap_scale >= 0), so no anchor still to be scanned can raise the best, and what is left of the scan would only decide where it ends (chain.c:231).  During the
+first tile of a task there is no pfx (the kernel passes INT_MAX).  "auto": on where the host turns it on (gap_scale >= 0); "force": on whatever gap_scale is (to
+show that the host's condition has teeth); "off": the loop before it had the exit.
+
+late_stamps: where the stamps and marks of a scored own-tile or ring chunk stand against its fold (the order of MM2C_ST_LEAN / MM2C_ST_FAR against the folds).
+True: the chunk adds f, looks whether any lane beats the best, and writes its stamps and reads its marks only once it knows that the scan goes on -- fold A and
+the general folds (Lslow / Lslow2) stamp before anything reads the marks, fold B0 takes the score-bound exit first and stamps only if it stays.  On that way out
+neither marks nor stamps have been used: B0 tests `valid` and the scores only, the skip counter and the marks are first touched after the exit test, and stamps
+are private to the anchor that wrote them (the ring is wiped per tile and the value is the anchor's own).  Stamps written later within the same chunk are
+equivalent: a stamp's target lies farther back than its writer, and every stamp of a chunk is written before the chunk's marks are read.  False: every scored
+chunk stamps and reads its marks before its fold, as the loop did before.  f / p are the same either way; a chunk from memory stamps before its fold in both.
+
+stats receives the paths by name and the sub-paths of the fold by the names of the assembly's labels (LABEL_KEYS; tests/test_cpu_oracle.py keeps them warm,
+tests/test_gpu_labels.py counts the real ones), `exits`, and `futile_scores` (the scored chunks whose candidates could not have beaten the best); with
+late_stamps additionally (LATE_KEYS)
+  exits_unstamped   exits taken before any stamp of the chunk (fold B0's),
+  stamped_chunks    scored own-tile and ring chunks that wrote their stamps (every scored one less exits_unstamped), of the anchors the hand-written loop handles,
+  cpp_chunks        ... and of the anchors it hands to the C++ path (an equal-x run that reaches into the tile before), which stamps as it always did,
+  near_pass / deep_pass   scored ring tiles by phase: within the NF tiles of the f / p ring, and beyond them (the deep fetch),
+  phase_changes     anchors whose ring scan visits a tile beyond the f / p ring;
+and with tile_skip (tools/chunk_stats.py --tile-skip, profiles/r6_tile_skip.md) what a 256-bit occupancy bitmap of each tile's diagonal buckets would have
+rejected (skip_tested / skip_rejects / skip_wrong / skip_missed).  exit_anchors (a list) receives the anchors that left early; events (a dict of lists) receives
+`unstamped`: (anchor, "own" / "ring") of each exit before any stamp, and `own_marks`: the anchors whose fold read a mark in their own tile."""
 import numpy as np
 
 INT_MIN = -(2**31)
@@ -22,12 +49,14 @@ def _score(P, avg, dr1, dq1, dd, span_i):
 
 LABEL_KEYS = ("lk", "own_pass", "lloop", "lold", "lfg", "lpart", "part_pass", "limp", "fold_b0", "lslow2", "lslow", "fold_b1", "lb1m", "lb2", "b2_no_skip_events", "lli",
               "li_closed", "lcfb", "lgen", "lbk", "break_in_fold_a", "break_in_b0", "lend", "far_chunks", "far_pass", "far_stamp", "lspec")
+LATE_KEYS = ("exits_unstamped", "stamped_chunks", "cpp_chunks", "near_pass", "deep_pass", "phase_changes")
+SKIP_KEYS = ("skip_tested", "skip_rejects", "skip_wrong", "skip_missed")
 
 
-def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, compact=False):
+def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, compact=False,
+                     score_exit="auto", late_stamps=True, tile_skip=False, exit_anchors=None, events=None):
     """compact: the x / q ring holds the low 16 bits of x and q (Lds<..., C16>), differences taken mod 2^16 and zero-extended, as the SDWA subtractions of the
-    compact instantiations do (the caller checks the task's q span, as the prepass does).  stats additionally receives the sub-paths of the fold by the names of
-    the assembly's labels (LABEL_KEYS; tests/test_cpu_oracle.py keeps them warm, tests/test_gpu_labels.py counts the real ones)."""
+    compact instantiations do (the caller checks the task's q span, as the prepass does)."""
     a = np.ascontiguousarray(anchors).view(np.uint64).reshape(-1, 2)
     n = a.shape[0]
     x64 = a[:, 0].astype(np.uint64)
@@ -48,14 +77,24 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
     if P.bw < 0:
         max_dq = 0                                                                # chain.c:205: dd >= 0 > bw, nothing passes
     lane = np.arange(64)
-    S = dict(anchors=0, no_window=0, own_chunks=0, own_pass=0, ring_chunks=0, ring_pass=0, deep_fp=0, far_chunks=0, far_pass=0,
-             fold_a=0, fold_b0=0, fold_b1=0, fold_b2_closed=0, fold_b2_scan=0, breaks=0, eq_run_anchors=0)
-    S.update(dict.fromkeys(LABEL_KEYS, 0), fold_b0=0, fold_b1=0, own_pass=0, far_chunks=0, far_pass=0)
-    S.update(skip_tested=0, skip_rejects=0, skip_wrong=0, skip_missed=0)
+    S = dict.fromkeys(("anchors", "no_window", "own_chunks", "own_pass", "ring_chunks", "ring_pass", "deep_fp", "far_chunks", "far_pass", "fold_a", "fold_b0", "fold_b1",
+                       "fold_b2_closed", "fold_b2_scan", "breaks", "eq_run_anchors", "exits", "futile_scores") + LABEL_KEYS + LATE_KEYS + SKIP_KEYS, 0)
+    assert score_exit in ("auto", "force", "off")
+    exit_on = score_exit == "force" or (score_exit == "auto" and np.float32(P.gap_scale) >= 0)
+    f_done = INT_MIN                                                              # maximum of f over the finished tiles
+
+    def leaves(best, sp_i, pfx, i):
+        if pfx is None or not best - (sp_i - 1) > pfx:                            # s_sub_i32 t, best, span1; s_cmp_gt_i32 t, pfx
+            return False
+        S["exits"] += 1
+        if exit_anchors is not None:
+            exit_anchors.append(i)
+        return True
     CM = 0xffff
     for i0 in range(0, n, 64):
         cnt = min(64, n - i0)
         stamp_lo = i0 - 64 * (NX - 1)
+        pfx = f_done if exit_on and i0 > 0 else None
         idx = i0 + 63 - lane                                                      # lane L holds anchor i0 + 63 - L
         m = idx < n
         s_x[idx[m] % SN] = xlo[idx[m]] & CM if compact else xlo[idx[m]]
@@ -81,6 +120,7 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                 S["eq_run_anchors"] += 1
                 if e > i - i0:
                     S["lspec"] += 1                                                # the run reaches into the tile before: the C++ path takes the anchor
+            pfx_i = None if e > i - i0 else pfx                                    # (the C++ path, which takes such an anchor, has no exit)
             s16 = 1 + (i & 63)
             broke = False
             base = i0
@@ -92,10 +132,13 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                 own = base == i0
                 ring = (not own) and base >= stamp_lo
                 part = bool((j < lo).any())
+                depth = (i0 - base) // 64
                 if own:
                     S["own_chunks"] += 1
                 elif ring:
                     S["ring_chunks"] += 1
+                    if depth == NF + 1:
+                        S["phase_changes"] += 1
                     S["lpart" if part else "lloop"] += 1
                 else:
                     S["far_chunks"] += 1
@@ -116,9 +159,9 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                 else:
                     ok = (dq1 >= 0) & (dq1 + 1 <= max_dq) & (dd <= P.bw)
                 valid = ok & inwin & (j < i - e)
-                if ring:
-                    # (round 6, tools/chunk_stats.py --tile-skip: would a 256-bit occupancy bitmap of the tile's diagonal buckets ((x - q) >> 9 mod 256) have rejected this
-                    # visit before its 13 instructions?  A pair passes only with |dr - dq| <= bw <= 511: the candidate's bucket is the anchor's or a neighbour)
+                if ring and tile_skip:
+                    # would a 256-bit occupancy bitmap of the tile's diagonal buckets ((x - q) >> 9 mod 256) have rejected this visit before its 13 instructions?
+                    # A pair passes only with |dr - dq| <= bw <= 511: the candidate's bucket is the anchor's or a neighbour
                     bj = (((xlo[jj] - q[jj]) >> 9) & 255)[j >= max(base, 0)]
                     bi = ((int(xlo[i]) - int(q[i])) >> 9) & 255
                     hit = np.isin(bj, [(bi - 1) & 255, bi, (bi + 1) & 255]).any()
@@ -131,7 +174,6 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                         S["skip_missed"] += 1
                 if not valid.any():
                     base -= 64; continue
-                depth = (i0 - base) // 64
                 if own:
                     S["own_pass"] += 1
                     fj, pj = f[jj], p[jj]
@@ -139,32 +181,47 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                     S["ring_pass"] += 1
                     S["part_pass" if part else "lold"] += 1
                     if depth <= NF:
+                        S["near_pass"] += 1
                         fj, pj = s_f[j % (64 * NF)], s_p[j % (64 * NF)]
                     else:
+                        S["deep_pass"] += 1
                         S["deep_fp"] += 1
                         S["lfg"] += 1
                         fj, pj = f[jj], p[jj]
                 else:
                     S["far_pass"] += 1
                     fj, pj = f[jj], p[jj]
-                # stamps (chain.c:226-233): scatter by p, gather by j; 16 bits inside the ring, 32 bits beyond
-                do_mark = valid & (pj >= lo)
-                for L in np.nonzero(do_mark)[0]:
-                    if pj[L] >= stamp_lo:
-                        s_t[pj[L] % SN] = s16
-                    else:
-                        t_glob[pj[L]] = i + 1
-                        S["far_stamp"] += 1
-                if own or ring:
-                    marked = valid & (s_t[j % SN] == s16)
+                if int(fj[valid].max()) + sp_i <= best:
+                    S["futile_scores"] += 1                                        # a scored chunk none of whose candidates can beat the best: only its marks matter
+
+                # stamps (chain.c:226-233): scatter by p, gather by j; 16 bits inside the ring, 32 bits beyond.  With late_stamps, written and read only where the fold asks
+                def stamps_and_marks():
+                    do_mark = valid & (pj >= lo)
+                    for L in np.nonzero(do_mark)[0]:
+                        if pj[L] >= stamp_lo:
+                            s_t[pj[L] % SN] = s16
+                        else:
+                            t_glob[pj[L]] = i + 1
+                            S["far_stamp"] += 1
+                    if own or ring:
+                        S["cpp_chunks" if e > i - i0 else "stamped_chunks"] += 1
+                        mk = valid & (s_t[j % SN] == s16)
+                        if events is not None and own and mk.any():
+                            events["own_marks"].append(i)                          # an anchor whose fold reads a mark in its own tile
+                        return mk
+                    return valid & (t_glob[jj] == i + 1)
+                if late_stamps and (own or ring):
+                    marked = None
                 else:
-                    marked = valid & (t_glob[jj] == i + 1)
+                    marked = stamps_and_marks()                                    # a chunk from memory stamps in memory before its fold in either order
                 sc = _score(P, avg, dr1, dq1, dd, sp_i) + fj
                 scv = np.where(valid, sc, INT_MIN)
                 cand = scv > best
                 last = 63
                 if not cand.any():                                                 # fold A
                     S["fold_a"] += 1
+                    if marked is None:
+                        marked = stamps_and_marks()
                     n_skip += int(marked.sum())
                     if marked.any() and n_skip > P.max_skip:                       # the break of chain.c:231; nothing before it changes the best
                         broke = True
@@ -182,6 +239,15 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                 if scv[l0] > best and not (scv > scv[l0]).any():                   # fold B0: the first surviving lane is the only new maximum
                     S["fold_b0"] += 1
                     best, best_j = int(scv[l0]), base + 63 - l0
+                    if leaves(best, sp_i, pfx_i, i):
+                        if marked is None:
+                            S["exits_unstamped"] += 1                              # the way out before any stamp of the chunk
+                            if events is not None:
+                                events["unstamped"].append((i, "own" if own else "ring"))
+                        broke = True
+                        continue
+                    if marked is None:
+                        marked = stamps_and_marks()
                     n_skip = max(n_skip - 1, 0)
                     se = marked.copy(); se[l0] = False                             # every marked lane behind it is a skip event
                     n_skip += int(se.sum())
@@ -191,12 +257,15 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                         S["break_in_b0"] += 1
                     base -= 64
                     continue
+                if marked is None:
+                    marked = stamps_and_marks()                                    # Lslow / Lslow2: the general folds read the marks first thing
                 incl = np.maximum.accumulate(scv)
                 if not marked.any() and n_skip == 0 and int(cand.sum()) == 1:      # fold B1
                     S["fold_b1"] += 1
                     L = int(np.argmax(cand))
                     best, best_j = int(scv[L]), base + 63 - L
                     base -= 64
+                    broke = leaves(best, sp_i, pfx_i, i)
                     continue
                 if not marked.any() and n_skip == 0:
                     S["lb1m"] += 1                                                 # several candidates, nothing to count: prefix max only
@@ -236,12 +305,17 @@ def chain_tile_model(P, anchors, avg, NX=8, NF=2, span_override=-1, stats=None, 
                     if mc > best:
                         best = mc
                         best_j = base + 63 - int(np.argmax(valid & (sc == mc)))
+                if not broke:                                                      # (the take went through the whole chunk: Lretx)
+                    broke = leaves(best, sp_i, pfx_i, i)
                 base -= 64
             if not broke and base + 63 < lo and i0 - lo > 0:
                 S["lend"] += 1                                                     # the window ran out (in the assembly: its ring part, Lend)
             f[i], p[i] = best, best_j
         sl = slice(i0, i0 + cnt)
         s_f[np.arange(i0, i0 + cnt) % (64 * NF)] = f[sl]; s_p[np.arange(i0, i0 + cnt) % (64 * NF)] = p[sl]
+        f_done = max(f_done, int(f[sl].max()))
     if stats is not None:
+        for k in (() if late_stamps else LATE_KEYS) + (() if tile_skip else SKIP_KEYS):
+            del S[k]                                                              # (reported only where they were asked for)
         stats.update(S)
     return f.astype(np.int32), p.astype(np.int32)
