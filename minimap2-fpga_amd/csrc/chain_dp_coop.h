@@ -397,7 +397,7 @@ chain_dp_coop(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 			const int e_l = above ? (int)__builtin_ctzll(above) : 64;
 			const int w_l = min(rl, idx - lo_l);
 			const int bef_l = max(i0 - lo_c, 0);
-			tw_l = max(w_l - e_l, 0) | (min(lane + 1 + e_l, 64) << 8) | (bef_l << 15);
+			tw_l = pack_tw(max(w_l - e_l, 0), min(lane + 1 + e_l, 64), bef_l);
 			if (lo_l >= idx) tw_l |= (int)0xa0000000;
 			if (FAR && lo_l < stamp_lo) tw_l |= 1 << 30;
 			if (e_l > rl) tw_l |= (int)0x80000000;

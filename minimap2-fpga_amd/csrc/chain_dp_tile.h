@@ -122,6 +122,17 @@ __device__ __forceinline__ int pack_fp(int f_biased, int p) { return (int)(((uns
 __device__ __forceinline__ int packed_f(int w) { return (int)((unsigned)w << (32 - PK_FBITS)) >> (32 - PK_FBITS); }   // f - FBIAS
 __device__ __forceinline__ int packed_p(int w) { return w >> PK_FBITS; }
 
+// The per-anchor word of the hand-written loop (MM2C_SCAN_TILE_ASM; the operand tw) without its flag bits, laid out for the loop: bits 0-9 bef, the anchors of older
+// tiles inside the window clamped to the ring (bef & 0x3c0 is 64 x its whole tiles: the loop counts tiles and their depth in anchors; bef & 63 the lanes of the partly
+// covered tile behind them), bits 10-15 the own-tile lanes to scan, bits 16-22 the first of them (1 .. 64).  Bit 28 is the loop's own (the scan goes on from memory),
+// bits 29-31 are the caller's: no window at all / window clamped / not for the loop.  Every caller of the loop packs here (chain_dp_tile, chain_dp_coop's walker).
+__device__ __forceinline__ int pack_tw(int own_lanes, int first_lane, int bef)
+{
+	int h = own_lanes | (first_lane << 6);
+	asm("" : "+v"(h));       // (made before bef is: one register less at the peak of the 32-bit far forms; not volatile, so it goes where the word is not used)
+	return (h << 10) | bef;
+}
+
 struct AnchorCtx {
 	int xi1, qi1;            // x_i - 1, q_i - 1 (so that dr - 1 and dq - 1 come out of one subtraction each)
 	int span_i, seg_i;
@@ -356,7 +367,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 // max_skip on, one segment, max_dq - 1 >= bw; gap cost computed (gap_scale 1) or read from the per-task table.  One instruction sequence
 // per TILE: anchors k_start .. of the tile with first anchor i0, one after the other; lane L = 63 - k holds anchor i0 + k in the per-tile
 // registers: tx / tq = x, q; tx1 / tq1 = x - 1, q - 1; tspan = span; tlo = window start, tbef = anchors of older tiles inside the window
-// (both clamped to what the ring holds; tbef travels in bits 15-24 of tw); 64 - L = LDS stamp; tw = number of own-tile predecessors inside the window, bit 29: no window at
+// (both clamped to what the ring holds; tbef travels in bits 0-9 of tw: pack_tw); 64 - L = LDS stamp; tw = number of own-tile predecessors inside the window, bit 29: no window at
 // all, bit 30: window clamped, bit 31: anchor not handled here.  Results go into the anchor's lane of own_f / own_p.  Returns the position
 // of the first anchor it did not process (cnt when the tile is done, else a bit-31 anchor).  A clamped window that the ring part of the scan
 // does not end (no `break` of chain.c:231) goes on tile by tile from L2 / HBM: x, q from the anchor array, f / p from the task's own
@@ -432,15 +443,41 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 // ---- what depends on the slot size of the f / p ring (Lds<>::FS): the request of a scored ring tile's f / p, what follows its arrival, the bit at which the
 // stamp slot starts in the address OLDADDR made, and what a deep tile's values from memory need before they join the ring path
 #define MM2C_RDFP_8 "ds_read_b64 " MM2C_R_FP ", %[u2] offset:%[FPOFF]\n\t"
-#define MM2C_RDFP_4 "ds_read_b32 " MM2C_R_F ", %[u2] offset:%[FPOFF]\n\t"
-#define MM2C_UNPACK_8 ""
-#define MM2C_UNPACK_4 "v_ashrrev_i32 " MM2C_R_P ", %[FBITS], " MM2C_R_F "\n\t" "v_bfe_i32 " MM2C_R_F ", " MM2C_R_F ", 0, %[FBITS]\n\t"
+#define MM2C_RDFP_4 "ds_read_b32 " MM2C_R_P ", %[u2] offset:%[FPOFF]\n\t"
 #define MM2C_FGFIX_8 "v_subrev_u32 " MM2C_R_P ", %[pbase], " MM2C_R_P "\n\t" "v_max_i32 " MM2C_R_P ", -1, " MM2C_R_P "\n\t" "v_add_u32 " MM2C_R_F ", -14, " MM2C_R_F "\n\t"
-#define MM2C_FGFIX_4 MM2C_UNPACK_4
+// The packed word of a scored tile (FS4; from the ring or, deeper, from the side array) arrives in the register of p.  Only the stamps read p of a scored chunk, so the
+// lean form never unpacks it: f leaves the word by one v_bfe_i32, and the stamp slot is made from the word as it is (MM2C_STSLOT_FS4) -- p sits in the word's top bits,
+// so the signed comparison of two words is the comparison of their p wherever those differ, and a word whose p equals the threshold's is not below the threshold
+// with a zero f field: max(word, (lo - 1) << FBITS) >> FBITS = max(p, lo - 1), and the slot is ten bits of it from bit FBITS on.  The tile's own predecessors enter
+// with p << FBITS for that (MM2C_OWNP_FS4_LEANF: a shift where the other forms move), and the kernel hands the lean form its threshold shifted likewise.  The far form
+// compares p with per-anchor scalars and makes addresses of it: it unpacks both halves where the word arrives, as before.  The forms with 8-byte f / p slots (FS8)
+// have nothing to unpack.  (The two tags are names, pasted here: FS8 / FS4 from the ring's list, LEANF / FARF from the instantiation's.)
+#define MM2C_UNPK_FS8_LEANF ""
+#define MM2C_UNPK_FS8_FARF ""
+#define MM2C_UNPK_FS4_LEANF "v_bfe_i32 " MM2C_R_F ", " MM2C_R_P ", 0, %[FBITS]\n\t"
+#define MM2C_UNPK_FS4_FARF MM2C_UNPK_FS4_LEANF "v_ashrrev_i32 " MM2C_R_P ", %[FBITS], " MM2C_R_P "\n\t"
+#define MM2C_UNPK(FST, LFT) MM2C_UNPK_##FST##_##LFT
+#define MM2C_FGFIX_FS8_LEANF MM2C_FGFIX_8
+#define MM2C_FGFIX_FS8_FARF MM2C_FGFIX_8
+#define MM2C_FGFIX_FS4_LEANF MM2C_UNPK_FS4_LEANF
+#define MM2C_FGFIX_FS4_FARF MM2C_UNPK_FS4_FARF
+#define MM2C_FGFIX(FST, LFT) MM2C_FGFIX_##FST##_##LFT
+#define MM2C_OWNP_FS8_LEANF "v_mov_b32 " MM2C_R_P ", %[own_p]\n\t"
+#define MM2C_OWNP_FS8_FARF MM2C_OWNP_FS8_LEANF
+#define MM2C_OWNP_FS4_LEANF "v_lshlrev_b32 " MM2C_R_P ", %[FBITS], %[own_p]\n\t"
+#define MM2C_OWNP_FS4_FARF MM2C_OWNP_FS8_LEANF
+#define MM2C_OWNP(FST, LFT) MM2C_OWNP_##FST##_##LFT
+#define MM2C_STSLOT_FS8 "v_max_i32 %[u2], " MM2C_R_P ", %[lomc]\n\t" "v_and_b32 %[u2], %[SNM1], %[u2]\n\t"
+#define MM2C_STSLOT_FS4 "v_max_i32 %[u2], " MM2C_R_P ", %[lomc]\n\t" "v_bfe_u32 %[u2], %[u2], %[FBITS], %[SBITS]\n\t"
+#define MM2C_STSLOT(FST) MM2C_STSLOT_##FST
 // x / q of the tile with first anchor fb from memory (anchors are 16 bytes: x low word at 0, q at 8), fb one tile back afterwards
 #define MM2C_FAR_REQ "v_add_u32 %[u2], %[fb], %[rl]\n\t" "v_max_i32 %[u2], 0, %[u2]\n\t" "v_lshlrev_b32 %[u2], 4, %[u2]\n\t" \
 	"global_load_dword %[fx], %[u2], %[aptr]\n\t" "global_load_dword %[fq], %[u2], %[aptr] offset:8\n\t" "s_sub_i32 %[fb], %[fb], 64\n\t"
-#define MM2C_SCORE_CMP "v_or_b32 %[va], 1, %[dd]\n\t" "v_ffbh_u32 %[va], %[va]\n\t" "v_lshrrev_b32 %[va], 1, %[va]\n\t" "v_cvt_f32_u32 %[vc], %[dd]\n\t" \
+// The log term clz(dd | 1) >> 1 (chain.c:209 through FBIAS) in two instructions: v_ffbh_u32 counts the leading zeros of dd itself, and bits 1-4 of the count are the
+// count shifted right by one.  For 1 <= dd < 2^31 the count is 1 .. 31 = clz(dd | 1), and (count >> 1) <= 15 fits the four bits; for dd = 0 the instruction returns all
+// ones, whose bits 1-4 are 15 = clz(1) >> 1.  The filter has bounded dd by bw in every lane whose score is looked at (a lane that failed it may hold any dd: a dd with
+// bit 31 set gives 0 either way).
+#define MM2C_SCORE_CMP "v_ffbh_u32 %[va], %[dd]\n\t" "v_bfe_u32 %[va], %[va], 1, 4\n\t" "v_cvt_f32_u32 %[vc], %[dd]\n\t" \
 	"v_mul_f32 %[vc], %[avg], %[vc]\n\t" "v_cvt_i32_f32 %[vc], %[vc]\n\t" "v_min3_i32 %[sc], %[dq], %[dr], %[span1]\n\t" "v_sub_u32 %[sc], %[sc], %[vc]\n\t"
 #define MM2C_ADDF_CMP "v_add3_u32 %[sc], %[sc], %[va], " MM2C_R_F "\n\t"   /* vf = f[j] - 14 */
 #define MM2C_SCORE_TAB "v_min_u32 %[va], 0x1ff, %[dd]\n\t" "v_lshlrev_b32 %[va], 1, %[va]\n\t" "ds_read_i16 %[va], %[va] offset:%[GAPOFF]\n\t" \
@@ -487,7 +524,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"ds_write_b8 %[u2], %[s16v] offset:%[STOFF]\n\t" \
 	"s_mov_b64 exec, %[valid]\n\t" \
 	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n\t"
-#define MM2C_ST_FAR(SITE) \
+#define MM2C_ST_FAR(SITE, FST) \
 	"s_bitcmp1_b32 %[pk], 30\n\t" \
 	"s_cbranch_scc1 Lstc" SITE "_%=\n\t" \
 	MM2C_ST_LDS_FAR \
@@ -510,10 +547,9 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"global_store_dword %[u2], %[u1], %[tptr] sc0\n\t" \
 	"s_mov_b64 exec, %[valid]\n\t" \
 	"s_branch Lstm" SITE "_%=\n"
-#define MM2C_ST_LEAN(SITE) \
+#define MM2C_ST_LEAN(SITE, FST) \
 	MM2C_LC(MM2C_LB_HF) \
-	"v_max_i32 %[u2], " MM2C_R_P ", %[lomc]\n\t" \
-	"v_and_b32 %[u2], %[SNM1], %[u2]\n\t" \
+	MM2C_STSLOT(FST) \
 	"ds_write_b8 %[u2], %[s16v] offset:%[STOFF]\n\t" \
 	"ds_read_i8 %[vb], %[vb] offset:%[STOFF]\n\t" \
 	"s_waitcnt lgkmcnt(0)\n\t" \
@@ -549,13 +585,13 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"s_and_b32 %[part], %[t0], 63\n\t" \
 	"s_lshr_b32 %[nfull], %[t0], 6\n\t" \
 	"s_sub_i32 %[n], %[nfull], %[NXM1]\n\t" \
-	"s_mov_b32 %[d], %[NXM1]\n\t" \
+	"s_mov_b32 %[d], %[REACHM64]\n\t"           /* the depth in anchors, as in the ring part of the scan; n counts the tiles from memory one by one */ \
 	"s_mov_b32 %[lo], %[lo0]\n\t" \
 	"s_add_i32 %[s16], %[icnt1], %[c]\n\t" \
 	"v_mov_b32 %[s16v], %[s16]\n" \
 	"Lfloop_%=:\n\t" \
 	MM2C_LC(MM2C_LB_FLOOP) \
-	"s_add_u32 %[d], %[d], 1\n\t" \
+	"s_add_u32 %[d], %[d], 64\n\t" \
 	"s_sub_u32 %[n], %[n], 1\n\t" \
 	"s_cbranch_scc1 Lfpart_%=\n\t" \
 	"s_waitcnt vmcnt(0)\n\t" \
@@ -577,8 +613,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"s_cbranch_scc0 Ldone_%=\n" \
 	"Lfold_%=:\n\t" \
 	MM2C_LC(MM2C_LB_FOLD) \
-	"s_lshl_b32 %[t0], %[d], 6\n\t" \
-	"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+	"s_sub_i32 %[base], %[i0], %[d]\n\t" \
 	"v_add_u32 %[u2], %[base], %[rl]\n\t" \
 	"v_max_i32 %[u2], 0, %[u2]\n\t" \
 	"v_lshlrev_b32 %[u2], 2, %[u2]\n\t" \
@@ -614,8 +649,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"s_cbranch_vccnz Lslow2m_%=\n\t" \
 	MM2C_LC(MM2C_LB_B0) \
 	"s_mov_b32 %[best], %[t1]\n\t" \
-	"s_lshl_b32 %[t1], %[d], 6\n\t" \
-	"s_sub_i32 %[bestj], %[i063], %[t1]\n\t" \
+	"s_sub_i32 %[bestj], %[i063], %[d]\n\t" \
 	"s_sub_i32 %[bestj], %[bestj], %[t0]\n\t" \
 	MM2C_EXIT_TEST("%[t1]") \
 	"s_branch Lb0s_%=\n" \
@@ -695,8 +729,7 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 #define MM2C_FG_CLOB_PF2 , MM2C_R_F2, MM2C_R_P2
 #define MM2C_FG_CLOB(SEL) MM2C_FG_CLOB_##SEL      /* (a name, pasted here: a clobber list as a macro argument would fall apart at its commas) */
 #define MM2C_FG_PLAIN(SCORE) \
-	"s_lshl_b32 %[t0], %[d], 6\n\t" \
-	"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+	"s_sub_i32 %[base], %[i0], %[d]\n\t" \
 	"v_add_u32 %[u2], %[base], %[rl]\n\t" \
 	"v_max_i32 %[u2], 0, %[u2]\n\t" \
 	"v_lshlrev_b32 %[u2], 2, %[u2]\n\t" \
@@ -707,18 +740,16 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 // packed f / p: the tile's words from the side array -- one load, and the values are the ring's own (piece-relative p, biased f).  (wptr is an input operand of
 // every instantiation of the block -- the others are handed f -- which costs those two SGPRs and nothing else: VGPRs, LDS and waves per SIMD are what they were.)
 #define MM2C_FG_PACKED(SCORE) \
-	"s_lshl_b32 %[t0], %[d], 6\n\t" \
-	"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+	"s_sub_i32 %[base], %[i0], %[d]\n\t" \
 	"v_add_u32 %[u2], %[base], %[rl]\n\t" \
 	"v_max_i32 %[u2], 0, %[u2]\n\t" \
 	"v_lshlrev_b32 %[u2], 2, %[u2]\n\t" \
-	"global_load_dword " MM2C_R_F ", %[u2], %[wptr] sc0\n\t" \
+	"global_load_dword " MM2C_R_P ", %[u2], %[wptr] sc0\n\t" \
 	SCORE \
 	"s_waitcnt vmcnt(0)\n\t"
 #if MM2C_DEEP_PREFETCH
 #define MM2C_FG_W(SCORE) \
-	"s_lshl_b32 %[t0], %[d], 6\n\t" \
-	"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+	"s_sub_i32 %[base], %[i0], %[d]\n\t" \
 	"s_cmp_eq_u32 %[base], %[bpre]\n\t" \
 	"s_cbranch_scc1 Lfgh_%=\n\t" \
 	"v_add_u32 %[u2], %[base], %[rl]\n\t" \
@@ -735,7 +766,10 @@ __device__ __forceinline__ void scan_anchor(const KParams &P, const AnchorCtx &X
 	"v_mov_b32 " MM2C_R_P ", " MM2C_R_P2 "\n\t" \
 	"v_mov_b32 " MM2C_R_F ", " MM2C_R_F2 "\n" \
 	"Lfgp_%=:\n\t" \
-	"s_or_b32 %[t0], %[n], %[part]\n\t"            /* whole tiles left + lanes of the partly covered one: anything further back in this window? */ \
+	"s_bitcmp1_b32 %[pk], 28\n\t"                /* whole tiles left + lanes of the partly covered one (ring part: still in the anchor's word; from memory: in part): anything further back in this window? */ \
+	"s_cselect_b32 %[t0], %[part], %[pk]\n\t" \
+	"s_and_b32 %[t0], %[t0], 63\n\t" \
+	"s_or_b32 %[t0], %[t0], %[n]\n\t" \
 	"s_cbranch_scc0 Lfgx_%=\n\t" \
 	"s_sub_i32 %[bpre], %[base], 64\n\t" \
 	"v_add_u32 %[u2], %[bpre], %[rl]\n\t" \
@@ -805,7 +839,7 @@ __device__ unsigned long long g_label_hits[8 * 32];   // row = compact << 2 | ta
 // value.  Tested wherever a fold has just raised the best (fold A leaves it alone); the way out is the `break`'s.  pfx = INT_MAX (the first tile of a piece, gap_scale
 // < 0, mm2c_tune("score_bound_exit", 0)) never passes.  T: a free scalar.
 #define MM2C_EXIT_TEST(T) "s_sub_i32 " T ", %[best], %[span1]\n\t" "s_cmp_gt_i32 " T ", %[pfx]\n\t" MM2C_LC_BR_SCC1("Ldone_%=", MM2C_LB_EXIT)
-#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, UNPACK, FGFIX, STSH, SCORE, ADDF, SWAIT, SEG_RD, SEG_LK, SEG_ST, SEG_TAIL, SEG_END, SEG_DONE, LNEXT) \
+#define MM2C_SCAN_TILE_ASM(NAME, TABV, C16V, XQ1, NEXT_XQ, RFILTER, OLDADDR, BACK, OWNFILTER, FARFILTER, RDXQ, SEG_FG, CLOB, RDFP, FST, STSH, SCORE, ADDF, SWAIT, SEG_RD, SEG_LK, SEG_ST, SEG_TAIL, SEG_END, SEG_DONE, LNEXT, LFT) \
 template <int NX, int NF> \
 __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, float avg, const int32_t *f, const int32_t *p, const int32_t *wq, int pbase, const uint4 *a, \
                                     int32_t *tg, int tx, int tx1, int tq, int tq1, int tspan, int tlo, int tlo0, int tw, int &own_f, int &own_p, \
@@ -834,17 +868,16 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_cmp_lt_i32 %[pk], 0\n\t" \
 		"s_cbranch_scc1 Lspec_%=\n\t"              /* bit 31: not for this loop, or (bit 29 too) no window at all */ \
 		SEG_LK \
-		"s_bfe_u32 %[n], %[pk], 0x40015\n\t"       /* whole older tiles inside the window */ \
+		"s_and_b32 %[n], %[pk], 0x3c0\n\t"         /* 64 x the whole older tiles inside the window: the loop counts them, and their depth, in anchors */ \
 		XQ1 \
 		"v_mov_b32 %[addr], %[addr2]\n\t" \
 		"s_add_i32 %[span1], %[best], -1\n\t" \
 		"s_mov_b32 %[nskip], 0\n\t" \
-		"s_bfe_u32 %[part], %[pk], 0x6000f\n\t"    /* lanes of the partly covered tile behind them */ \
 		"s_mov_b32 %[nfull], %[n]\n\t" \
 		"v_mov_b32 %[s16v], %[c]\n\t" \
-		"s_and_b32 %[t0], %[pk], 63\n\t" \
+		"s_bfe_u32 %[t0], %[pk], 0x6000a\n\t"      /* own-tile lanes to scan (SCC: any) ... */ \
 		"s_cbranch_scc0 Lloop_%=\n\t" \
-		"s_bfe_u32 %[t1], %[pk], 0x70008\n\t" \
+		"s_bfe_u32 %[t1], %[pk], 0x70010\n\t"      /* ... and the first of them */ \
 		"s_bfm_b64 %[mask], %[t0], %[t1]\n\t" \
 		OWNFILTER MM2C_FILTER2 \
 		"s_and_b64 %[valid], vcc, %[mask]\n\t" \
@@ -852,7 +885,7 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		MM2C_LC(MM2C_LB_OWN) \
 		"s_mov_b32 %[d], 0\n\t" \
 		"v_add_u32 " MM2C_R_F ", -14, %[own_f]\n\t" \
-		"v_mov_b32 " MM2C_R_P ", %[own_p]\n\t" \
+		MM2C_OWNP(FST, LFT) \
 		"v_mov_b32 %[vb], %[ownst]\n\t" \
 		SCORE \
 		SWAIT \
@@ -860,54 +893,54 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"Lloop_%=:\n\t" \
 		MM2C_LC(MM2C_LB_LOOP) \
 		MM2C_PROBE_LOOP \
-		"s_sub_u32 %[n], %[n], 1\n\t" \
+		"s_sub_u32 %[n], %[n], 64\n\t"             /* (n is a multiple of 64: the borrow comes when no whole tile is left) */ \
 		"s_cbranch_scc1 Lpart_%=\n\t" \
 		"s_waitcnt lgkmcnt(0)\n\t" \
 		RFILTER NEXT_XQ MM2C_FILTER2 \
 		"s_cbranch_vccz Lloop_%=\n\t" \
 		"s_mov_b64 %[valid], vcc\n\t" \
-		"s_sub_i32 %[d], %[nfull], %[n]\n" \
+		"s_sub_i32 %[d], %[nfull], %[n]\n"          /* 64 x the tile's depth */ \
 		"Lold_%=:\n\t" \
 		MM2C_LC(MM2C_LB_OLD) \
 		OLDADDR                                        /* the running address is two tiles further on: back to this tile's (in units of 8-byte slots; of 4-byte slots in the packed form, whose STSH is 2) */ \
 		"v_and_b32 %[u2], %[FMASK], %[vb]\n\t"          /* its slot in the f / p ring */ \
 		"v_bfe_u32 %[vb], %[vb], " STSH ", %[SBITS]\n\t"   /* its slot in the stamp ring */ \
-		"s_cmp_gt_u32 %[d], %[NFI]\n\t" \
+		"s_cmp_gt_u32 %[d], %[NFI64]\n\t" \
 		"s_cbranch_scc1 Lfg_%=\n\t" \
 		RDFP \
 		SCORE \
 		"s_waitcnt lgkmcnt(0)\n\t" \
-		UNPACK \
+		MM2C_UNPK(FST, LFT) \
 		"\n" \
 		"Lhf_%=:\n\t" \
 		"s_mov_b64 exec, %[valid]\n\t"                /* exec = the lanes that passed the filters, until the fold has looked at the scores and the marks */ \
 		ADDF \
 		"v_cmp_lt_i32 vcc, %[best], %[sc]\n\t" \
 		"s_cbranch_vccnz Limp_%=\n\t" \
-		SEG_ST("a")                                    /* fold A: no lane beats the best, the scan goes on (or ends by the marks) */ \
+		SEG_ST("a", FST)                                    /* fold A: no lane beats the best, the scan goes on (or ends by the marks) */ \
 		"Lfat_%=:\n\t" \
 		"s_mov_b64 exec, %[ex]\n\t" \
 		SEG_TAIL \
 		"Lfg_%=:\n\t" \
 		MM2C_LC(MM2C_LB_FG) \
 		SEG_FG(SCORE) \
-		FGFIX \
+		MM2C_FGFIX(FST, LFT) \
 		SWAIT \
 		"s_branch Lhf_%=\n" \
 		"Lpart_%=:\n\t" \
 		MM2C_LC(MM2C_LB_PART) \
 		"s_mov_b32 %[n], 0\n\t" \
-		"s_cmp_eq_u32 %[part], 0\n\t" \
-		"s_cbranch_scc1 Lend_%=\n\t" \
+		"s_and_b32 %[part], %[pk], 63\n\t"          /* lanes of the partly covered tile: taken from the anchor's word only here ... */ \
+		"s_cbranch_scc0 Lend_%=\n\t" \
 		"s_waitcnt lgkmcnt(0)\n\t" \
 		RFILTER MM2C_FILTER2 \
 		"s_sub_i32 %[t0], 64, %[part]\n\t" \
 		"s_lshr_b64 %[mask], -1, %[t0]\n\t" \
-		"s_mov_b32 %[part], 0\n\t" \
+		"s_andn2_b32 %[pk], %[pk], 63\n\t"          /* ... and taken out of it: the tile is behind the scan */ \
 		"s_and_b64 %[valid], vcc, %[mask]\n\t" \
 		"s_cbranch_scc0 Lend_%=\n\t" \
 		MM2C_LC(MM2C_LB_PARTPASS) \
-		"s_add_i32 %[d], %[nfull], 1\n\t" \
+		"s_add_i32 %[d], %[nfull], 64\n\t" \
 		BACK \
 		"s_branch Lold_%=\n" \
 		"Limp_%=:\n\t" \
@@ -920,11 +953,10 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"s_cbranch_vccnz Lslow2_%=\n\t" \
 		MM2C_LC(MM2C_LB_B0) \
 		"s_mov_b32 %[best], %[t1]\n\t" \
-		"s_lshl_b32 %[t1], %[d], 6\n\t" \
-		"s_sub_i32 %[bestj], %[i063], %[t1]\n\t"   /* i0 + 63 - 64 d - lane */ \
+		"s_sub_i32 %[bestj], %[i063], %[d]\n\t"    /* i0 + 63 - 64 depth - lane */ \
 		"s_sub_i32 %[bestj], %[bestj], %[t0]\n\t" \
 		MM2C_EXIT_TEST("%[t1]")                        /* the way out that owes no stamp: nothing so far has looked at a mark, Ldone sets exec itself */ \
-		SEG_ST("b") \
+		SEG_ST("b", FST) \
 		"Lb0s_%=:\n\t" \
 		"s_mov_b64 exec, %[ex]\n\t" \
 		"s_sub_i32 %[nskip], %[nskip], 1\n\t" \
@@ -941,13 +973,12 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		"\n" \
 		"Lslow_%=:\n\t" \
 		MM2C_LC(MM2C_LB_SLOW) \
-		SEG_ST("s") \
+		SEG_ST("s", FST) \
 		"Lsls_%=:\n\t" \
 		"v_cmp_lt_i32 vcc, %[best], %[sc]\n\t"        /* (again: the stamps went through VCC) */ \
 		"s_mov_b64 exec, %[ex]\n\t"                     /* the general folds work on all lanes: the lanes that did not pass get the sentinel score */ \
 		"v_cndmask_b32_e64 %[sc], %[sent], %[sc], %[valid]\n\t" \
-		"s_lshl_b32 %[t0], %[d], 6\n\t" \
-		"s_sub_i32 %[base], %[i0], %[t0]\n\t" \
+		"s_sub_i32 %[base], %[i0], %[d]\n\t" \
 		"s_cmp_lg_u64 %[marked], 0\n\t" \
 		"s_cbranch_scc1 Lb2_%=\n\t" \
 		"s_cmp_lg_u32 %[nskip], 0\n\t" \
@@ -1098,19 +1129,19 @@ __device__ __forceinline__ int NAME(int i0, int k_start, int cnt, int max_skip, 
 		  [addr1] "v"(addr1), [addr2] "v"(addr2), [lomc] "v"(lomc), [ownst] "v"(ownst), [rl] "v"(rl), [mdqbw] "v"(mdqbw_v), [bw] "v"(bw_v), [sent] "v"(sent_v), \
 		  [addr1q] "v"(addr1q), [selq] "v"(selq_v), [QHOFF] "n"(LY::QH), \
 		  [XQOFF] "n"(LY::XQ), [FPOFF] "n"(LY::FP), [STOFF] "n"(LY::ST), [RBM1] "n"(LY::RB - 1), [FMASK] "n"(LY::FMASK), \
-		  [SNM1] "n"(LY::SN - 1), [RMASK] "n"(64 * NX - 1), [SBITS] "n"(LY::SBITS), [NFI] "n"(NF), [GAPOFF] "n"(LYT::GAP), [NXM1] "n"(NX - 1), [REACH] "n"(64 * NX), [FBITS] "n"(PK_FBITS) \
+		  [SNM1] "n"(LY::SN - 1), [RMASK] "n"(64 * NX - 1), [SBITS] "n"(LY::SBITS), [NFI64] "n"(64 * NF), [GAPOFF] "n"(LYT::GAP), [NXM1] "n"(NX - 1), [REACHM64] "n"(64 * (NX - 1)), [REACH] "n"(64 * NX), [FBITS] "n"(PK_FBITS) \
 		: "memory", "vcc", "scc", MM2C_R_X, MM2C_R_Q, MM2C_R_F, MM2C_R_P MM2C_FG_CLOB(CLOB)); \
 	return cnt + c; \
 }
 
 // two instantiations of each: `lean` for tiles in which no window reaches beyond the LDS ring (no test for it anywhere in the loop, stamps written
 // without touching exec), `far` for the others
-#define MM2C_RING_W MM2C_XQ1_W, MM2C_NEXT_XQ_W, MM2C_RFILTER_W, MM2C_OLDADDR_W, MM2C_BACK_W, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_W, PF2, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
-#define MM2C_RING_C MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
-#define MM2C_RING_P MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_P, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PACKED, PF0, MM2C_RDFP_4, MM2C_UNPACK_4, MM2C_FGFIX_4, "2"
+#define MM2C_RING_W MM2C_XQ1_W, MM2C_NEXT_XQ_W, MM2C_RFILTER_W, MM2C_OLDADDR_W, MM2C_BACK_W, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_W, PF2, MM2C_RDFP_8, FS8, "3"
+#define MM2C_RING_C MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, FS8, "3"
+#define MM2C_RING_P MM2C_XQ1_C, MM2C_NEXT_XQ_C, MM2C_RFILTER_C, MM2C_OLDADDR_P, MM2C_BACK_C, MM2C_OWNFILTER_C, MM2C_FARFILTER_C, MM2C_RDXQ_C, MM2C_FG_PACKED, PF0, MM2C_RDFP_4, FS4, "2"
 #define MM2C_SCAN_TILE_ASM_(...) MM2C_SCAN_TILE_ASM(__VA_ARGS__)
-#define MM2C_LEAN MM2C_RD_LEAN, MM2C_LK_LEAN, MM2C_ST_LEAN, MM2C_TAIL_LEAN, MM2C_END_LEAN, "", "Lloop_%="
-#define MM2C_FARS MM2C_RD_FAR, MM2C_LK_FAR, MM2C_ST_FAR, MM2C_TAIL_FAR, MM2C_END_FAR, MM2C_DONE_FAR, "Lret_%="
+#define MM2C_LEAN MM2C_RD_LEAN, MM2C_LK_LEAN, MM2C_ST_LEAN, MM2C_TAIL_LEAN, MM2C_END_LEAN, "", "Lloop_%=", LEANF
+#define MM2C_FARS MM2C_RD_FAR, MM2C_LK_FAR, MM2C_ST_FAR, MM2C_TAIL_FAR, MM2C_END_FAR, MM2C_DONE_FAR, "Lret_%=", FARF
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab, true, false, MM2C_RING_W, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far, false, false, MM2C_RING_W, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
@@ -1126,7 +1157,7 @@ MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, M
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_p, false, 3, MM2C_RING_P, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_far_p, true, 3, MM2C_RING_P, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_FARS)
 // ... and over the q24 ring (the long ring of class-1 tasks): everything but a ring tile's request and filter is the 32-bit form's or the compact form's
-#define MM2C_RING_Q MM2C_XQ1_Q, MM2C_NEXT_XQ_Q, MM2C_RFILTER_Q, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, MM2C_UNPACK_8, MM2C_FGFIX_8, "3"
+#define MM2C_RING_Q MM2C_XQ1_Q, MM2C_NEXT_XQ_Q, MM2C_RFILTER_Q, MM2C_OLDADDR_C, MM2C_BACK_C, MM2C_OWNFILTER_W, MM2C_FARFILTER_W, MM2C_RDXQ_W, MM2C_FG_PLAIN, PF0, MM2C_RDFP_8, FS8, "3"
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_tab_q, true, 2, MM2C_RING_Q, MM2C_SCORE_TAB, MM2C_ADDF_TAB, MM2C_SWAIT_TAB, MM2C_LEAN)
 MM2C_SCAN_TILE_ASM_(scan_tile_asm_cmp_far_q, false, 2, MM2C_RING_Q, MM2C_SCORE_CMP, MM2C_ADDF_CMP, "", MM2C_FARS)
@@ -1151,7 +1182,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 	static_assert(!C16 || (SKIP && !GEN && (GS1 || TAB)), "the compact and the q24 ring belong to the variants of the hand-written loop");
 	static_assert(NF >= 1 && NF < NX && (NF & (NF - 1)) == 0 && (NX & (NX - 1)) == 0, "rings of a power of two of tiles, addressed with masks");
 	static_assert(NF <= NX, "the f / p ring holds a prefix of the tiles of the x / q ring");
-	static_assert(64 * (NX - 1) < 1024, "bef (anchors of older tiles inside the ring window) travels in the 10-bit field bits 15-24 of the per-anchor word");
+	static_assert(64 * (NX - 1) < 1024, "bef (anchors of older tiles inside the ring window) travels in the 10-bit field bits 0-9 of the per-anchor word");
 	typedef Lds<NX, NF, GEN, TAB, C16> LY;
 	constexpr int SN = LY::SN;
 	constexpr bool ASMV = SKIP && !GEN && (GS1 || TAB);        // the hand-written scan covers this variant ...
@@ -1237,8 +1268,18 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 			if (BALLOT(rl < cnt && own_g != seg0)) { if (lane == 0) status[task] = 1; return; }
 		}
 		// stamps are one byte: 1 + the anchor's position in its tile.  They only mean something during the scan of the anchor that wrote them, so
-		// the whole ring is wiped when a tile starts (two dword stores per lane) and a value identifies its anchor within the tile
-		for (int s = lane; s < SN / 4; s += 64) ((int *)(lds + LY::ST))[s] = 0;
+		// the whole ring is wiped when a tile starts (one 16-byte store per lane for a ring of 16 tiles) and a value identifies its anchor within the tile
+		static_assert(LY::ST % 16 == 0 && SN % 16 == 0, "the stamp ring is wiped in 16-byte stores");
+		if (SN == 1024) {
+			// a ring of 16 tiles: 16 bytes per lane in one LDS instruction.  The zeros and the address are made here and live for as long as the store takes (four
+			// zeros kept across the tile loop would cost the compact forms their seventh wave); the zeros are written twice, side by side, and which lane wipes
+			// which 16 bytes does not matter
+			long long z = 0;
+			int ta;
+			asm volatile("" : "+v"(z));
+			asm volatile("v_lshlrev_b32 %0, 4, %1\n\tv_add_u32 %0, %3, %0\n\tds_write2_b64 %0, %2, %2 offset1:1" : "=&v"(ta) : "v"(rl), "v"(z), "n"(LY::ST) : "memory");
+		} else
+			for (int s = lane; s < SN / 4; s += 64) ((int *)(lds + LY::ST))[s] = 0;
 		const int stamp_lo = i0 - 64 * (NX - 1);   // oldest anchor reachable without global memory while this tile is processed
 		{
 			const int o = (idx & (SN - 1)) * LY::XS;   // the tile enters the x / q ring (its slot held the tile NX tiles back)
@@ -1271,7 +1312,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 		// lean tiles (every window inside the ring): a stamp may go to any slot the ring holds, also one before the anchor's own window -- nothing
 		// reads it during this anchor's scan and its value is this anchor's alone -- so the threshold below which a target is diverted is a constant of
 		// the tile, the ring's oldest anchor; the sink, stamp_lo - 1 = i0 + 63 (mod SN), is the slot of the tile's last anchor, which no scan of this tile reads
-		int lomc_v = stamp_lo - 1;
+		int lomc_v = C16 == 3 ? (stamp_lo - 1) * (1 << PK_FBITS) : stamp_lo - 1;   // (the packed forms compare it with the packed word: MM2C_STSLOT_FS4; |stamp_lo - 1| < PK_MAX_N)
 		asm volatile("" : "+v"(lomc_v));
 
 		// per-anchor scalars of the tile, kept per lane (the hand-written loop fetches them with v_readlane): window start, LDS stamp, number
@@ -1285,7 +1326,7 @@ chain_dp_tile(KParams P, int64_t n_tasks, const int64_t *__restrict__ offsets, c
 		const int e_l = above ? (int)__builtin_ctzll(above) : 64;
 		const int w_l = min(rl, idx - lo_l);                      // own-tile predecessors inside the window: lanes lane + 1 .. lane + w
 		const int lo_c = max(lo_l, stamp_lo), bef_l = max(i0 - lo_c, 0);   // the window clamped to what the ring holds; its anchors in older tiles (<= 64 (NX - 1))
-		int tw_l = max(w_l - e_l, 0) | (min(lane + 1 + e_l, 64) << 8) | (bef_l << 15);   // bits 0-5: lanes to scan, bits 8-14: the first of them, bits 15-24: bef
+		int tw_l = pack_tw(max(w_l - e_l, 0), min(lane + 1 + e_l, 64), bef_l);
 		if (lo_l >= idx) tw_l |= (int)0xa0000000;             // no window at all: bit 29, and bit 31 so that the loop needs one test for both rare cases
 		if (FAR && lo_l < stamp_lo) tw_l |= 1 << 30;
 		if (e_l > rl) tw_l |= (int)0x80000000;
