@@ -114,6 +114,11 @@ int  mm2c_device_identity(int *ordinal, char *pci_bus_id, size_t bus_len, char *
  * "score_bound_exit" 1 = the hand-written loop of the tile kernel ends an anchor's scan once the largest f before its tile plus its span cannot beat its best (the rest of such a scan only
  * decides where the scan ends, chain.c:231: same f / p; default; a call with gap_scale < 0 runs without it, and the variant text says score_exit=0), 0 = never. */
 int  mm2c_tune(const char *key, int value);
+/* What mm2c_tune set, and the table it goes by (csrc/knobs.def: each knob's key, environment variable, range, default and meaning).  Neither needs a device.
+ * mm2c_tune_get: the knob's current value and its default (either pointer may be NULL), so that a caller can put back what it found; MM2C_E_ARG for an unknown key
+ * ("trim" is a command, not a knob).  mm2c_tune_key: key and environment variable of knob i = 0 .. n-1 (*env is NULL for a knob without one); MM2C_E_ARG beyond the table. */
+int  mm2c_tune_get(const char *key, int64_t *value, int64_t *dflt);
+int  mm2c_tune_key(int i, const char **key, const char **env);
 
 /* HW/SW split model of the reference for this hardware (chain.c:80-81,101; constants in the form of chain_hardware.h:19-30 live in
  * include/mm2chain_split.h): hw_ms = k1_hw * n + k2_hw * total_subparts + c_hw for one synchronous per-read call into this library,

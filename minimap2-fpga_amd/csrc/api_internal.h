@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -34,50 +35,15 @@ struct Global {
 	std::atomic<bool> ready{false};         // written under `mu`; read without it by lib_ready()
 	int device = -1;                        // primary device (= devices[0])
 	std::vector<int> devices;               // every device the library drives (mm2c_init_devices); entries may repeat
-	std::atomic<int64_t> multi_min_anchors{1 << 20};   // host batches of at least this many anchors are split across the devices
-	// tuning knobs: written by mm2c_tune / mm2c_init under `mu`, read by compute entries on other threads (atomics: no torn or stale-forever reads)
-	std::atomic<int> ring_class{3};
-	std::atomic<int> far_thr10{7};                      // ... from this many tenths of an expected far tile per anchor
-	std::atomic<int> noskip_loop{1};                    // max_skip >= max_iter: through the hand-written loop with max_skip = max_iter - 1 (same results)
-	std::atomic<int> heap_sort{0};                      // seed plans created from now on leave collect_seed_hits_heap's order among equal x (MM_F_HEAP_SORT)
-	std::atomic<int> wide_pct{40};                      // plans: tasks with the 32-bit ring hold more than this % of the anchors -> no task takes the compact ring
-	std::atomic<int> split_streams{1};                  // plans: the instantiations a batch is split over (32-bit / compact ring) run side by side on two streams
-	std::atomic<int> compact_ring{1};                   // tile kernel: the compact x / q ring for the tasks whose q values allow it (0: never; the parity tests run both)
-	std::atomic<int> packed_fp{1};                      // tile kernel: the packed f / p ring for the plan tasks it can hold (0: the routing without it; the tests run both)
-	std::atomic<int> score_bound_exit{1};               // tile kernel: the hand-written loop ends an anchor's scan once no older score can beat its best (0: never; the tests run both)
-	std::atomic<int> q24_ring{1};                       // tile kernel: the long ring of class-1 tasks in the q24 form (0: 32-bit slots; the parity tests run both)
-	std::atomic<int> force_tab{0};                      // tile kernel: gap cost from the LDS table also when gap_scale == 1 (tests; slower)
-	std::atomic<int> far_ring{1};                       // plans: tasks whose scans are expected to leave the short LDS ring run with a ring twice as long (0: never, 2: all)
-	std::atomic<int> epi_fused{1};                      // device epilogue: tasks that fit the LDS take the fused kernel (0: kernels A, B, C for every task)
-	std::atomic<size_t> combine_max_anchors{1u << 17};   // host paths: calls up to this many anchors are combined with concurrent callers' calls
+	// tuning knobs: written by mm2c_tune / mm2c_init under `mu`, read by compute entries on other threads (atomics: no torn or stale-forever reads).  The ones with a
+	// key are declared from csrc/knobs.def, which holds each one's key, environment variable, range, default and meaning
+#define KNOB(type, member, key, env, lo, hi, dflt, flags, meaning) std::atomic<type> member{dflt};
+#include "knobs.def"
+#undef KNOB
+	// ... and the ones without
 	std::atomic<size_t> stage_max_anchors{1u << 21};     // host paths: calls up to this many anchors go through pinned staging buffers
-	std::atomic<int64_t> pipeline_chunk_anchors{20 << 20};  // host paths: batches of at least twice this size are pipelined in chunks of this size
-	std::atomic<int64_t> pipeline_pieces{8}, pipeline_min_chunk{4 << 20};   // host paths: a batch of a few chunks' worth is cut into about `pieces` chunks of at least `min_chunk` anchors
-	std::atomic<int64_t> pipeline_taper{0};             // host paths: the last chunks of a pipelined batch halve in size this many times (0, the default: equal chunks -- the sweep of
-	                                                    // round 6, profiles/r6_hoststream.md, shows nothing to gain: 16.4-16.7 ms for 0 .. 4 halvings)
 	std::atomic<int64_t> cut_below_tasks{4096};         // host paths: passes with at least this many tasks are not cut (they fill the GPU anyway)
-	std::atomic<int> seg_min{256};                      // shortest piece a task is cut into at empty-window positions (0 = never cut)
-	std::atomic<int> coop_waves{16};                    // passes of at most coop_max_tasks tasks: several waves per task (chain_dp_coop; 0 or 1: never; the value only switches, the width -- 16 or 8 -- goes by coop_w8_above)
-	std::atomic<int64_t> coop_max_tasks{1024};
-	std::atomic<int> single_launch{1};                  // per-read passes of short tasks: ONE launch -- the cooperative kernel reads the pass from the pinned arena itself (no stage_in)
-	std::atomic<int> fuse_st{1};                        // per-read passes: the window starts inside the cooperative kernel (no prepass launch)
-	std::atomic<int> seg_prepass{1};                    // plans with long tasks: the window-start prepass with a block per segment of a task instead of a block per task
-	std::atomic<int> coop_w8_above{256};                // the cooperative kernel: eight waves per piece (two workgroups per CU) in passes of more pieces than this, sixteen up to it
-	std::atomic<int> pin_workers{1};                    // the worker thread of a device slot is pinned to the CPUs of the device's NUMA node (sysfs; 0: left to the scheduler)
-	std::atomic<int> decline_when_busy{0};              // mm2c_chain_task_host_pred / run_chaining_on_hw: the reference's busy protocol (chain_hardware.cpp:54-75).  0 (default since round 6):
-	                                                    // always accept -- a chain.o built without PROCESS_ON_SW_IF_HW_BUSY ignores the answer 1 (chain.c:105,163-169) and would chain from
-	                                                    // uninitialised f / p, and no decline rule beat "never" on the measured run (profiles/r6_per_read.md); 1: decline by the measured
-	                                                    // service time of the slot; 2: round 5's rule (booked predictions).  MM2C_DECLINE_WHEN_BUSY / mm2c_tune opt in.
-	std::atomic<int> direct_pass{1};                    // small staged passes: the two copies are kernels and the host polls a flag word (host_stage.hip; 0: copy commands + stream wait)
-	std::atomic<size_t> direct_max_anchors{1u << 18};   // ... passes of up to this many anchors
-	std::atomic<int> host_st{0};                        // ... bring their window starts along, computed by the host while it stages the anchors (no prepass launch).  Off: measured on the
-	                                                    // end-to-end run it trades 4.3 us of submission for 8 us of host sweep per pass (profiles/r6_per_read.md); mm2c_tune("host_st", 1) turns it on
-	std::atomic<int> fused_out{1};                      // ... that end in the cooperative kernel: the kernel writes f / p to the result buffer and raises the flag itself (no stage_out launch)
-	std::atomic<int> pipe_coop_chunks{1};               // pipelined host batches: this many of the LAST chunks run with several waves per piece when they have few enough pieces
-	std::atomic<int> combiner_lanes{4};                 // passes of the call combiner in flight at once (1 .. 16; round 5, with direct passes: 4.60 / 4.55 / 4.65 / 4.67 / 4.78 / 4.83 s for 3 / 4 / 6 / 8 / 12 / 16 on the 120 000-read run)
-	std::atomic<int> coop_plans{2};                     // plans and the cooperative kernel: 2 (default) per run, by coop_pays (few long pieces); 1: every plan of few tasks (tests); 0: never
-	std::atomic<int> plan_cut{1};                       // plans: cut long tasks into pieces on the device (chain_cut) before the DP
-	std::atomic<int> plan_cut_min{8192};                // ... tasks of at least this many anchors (the ones that make the tail of a batch)
+	std::atomic<size_t> direct_max_anchors{1u << 18};   // direct passes (direct_pass): passes of up to this many anchors
 	hipStream_t stream = nullptr;           // library stream for plan runs with stream == NULL
 	std::vector<ThreadCtx *> thread_ctxs;   // owned; released in mm2c_shutdown
 	std::atomic<uint64_t> tasks{0}, anchors{0}, launches{0}, segments{0}, host_call_ns{0}, passes{0};
@@ -92,8 +58,6 @@ inline void knobs_into(mm2c::LaunchArgs &L, bool cls_arrays = true)
 	L.coop_w8_above = G.coop_w8_above.load(); L.fuse_st = G.fuse_st.load();
 	if (cls_arrays) { L.far_ring = G.far_ring; L.far_thr10 = G.far_thr10; L.wide_pct = G.wide_pct; }
 }
-extern std::atomic<int64_t> read_chunk_bases;   // mm2c_read_chain_batch: bases per chunk of whole reads (mm2c_tune("read_chunk_bases"); mm2chain_sketch.cpp)
-extern std::atomic<int64_t> index_chunk_bases;  // mm2c_minidx_build: bases per chunk of whole sequences (mm2c_tune("index_chunk_bases"); mm2chain_sketch.cpp)
 // mm2c_init_async: the initialisation runs on a thread of its own while the host does something else (a minimap2 host loads its index, main.c:371-399, before the
 // first chaining call); every entry that needs the device joins that thread first.  async_init_join is a no-op when none is pending and on the thread itself.
 void async_init_join();

@@ -479,6 +479,28 @@ int epilogue_debug_phases() { const char *dbg = getenv("MM2C_EPI_PHASES"); retur
 
 using namespace mm2c_api;
 
+// the tuning knobs (csrc/knobs.def), as rows that mm2c_tune, mm2c_tune_get, mm2c_tune_key and mm2c_init walk; the compute entries load G.<member> themselves
+enum { KNOB_ANY = 1, KNOB_CLAMP_HI = 2, KNOB_ENV_LO = 4, KNOB_ENV_INIT = 8 };
+struct Knob {
+	const char *key, *env;
+	int64_t lo, hi, dflt;
+	int flags;
+	const char *meaning;
+	int64_t (*get)();
+	void (*set)(int64_t);
+};
+static const Knob KNOBS[] = {
+#define KNOB(type, member, key, env, lo, hi, dflt, flags, meaning) \
+	{key, env, lo, hi, dflt, flags, meaning, []() -> int64_t { return (int64_t)G.member.load(); }, [](int64_t v) { G.member = (type)v; }},
+#include "knobs.def"
+#undef KNOB
+};
+static const Knob *find_knob(const char *key)
+{
+	for (const Knob &k : KNOBS) if (key && strcmp(key, k.key) == 0) return &k;
+	return nullptr;
+}
+
 struct mm2c_plan {
 	mm2c_params_t par;
 	int device = 0;                         // the device the plan's workspace lives on
@@ -555,38 +577,12 @@ int mm2c_init(int device_ordinal)
 	G.device = dev;
 	if (!env_devices.empty()) G.devices = env_devices;
 	if (G.devices.empty()) G.devices.assign(1, dev);
-	const char *rc = getenv("MM2C_RING_CLASS");
-	G.ring_class = rc ? std::max(0, std::min(4, atoi(rc))) : 3;
-	const char *ef = getenv("MM2C_EPI_FUSED");           // 0: the device epilogue works in HBM for every task (kernels A, B, C)
-	if (ef) G.epi_fused = atoi(ef) != 0;
-	const char *fr = getenv("MM2C_FAR_RING");            // 0: one LDS ring size for every task; 2: the long ring for every task (tests)
-	if (fr) G.far_ring = std::max(0, std::min(2, atoi(fr)));
-	const char *ss = getenv("MM2C_SPLIT_STREAMS");       // 0: the instantiations of a split batch run one after the other on the caller's stream
-	if (ss) G.split_streams = std::max(0, std::min(2, atoi(ss)));
-	const char *wp = getenv("MM2C_WIDE_SHARE_THRESHOLD"); // % of the anchors in tasks that need the 32-bit ring from which every task takes it
-	if (wp) G.wide_pct = std::max(0, std::min(100, atoi(wp)));
-	const char *cm = getenv("MM2C_COMBINE_MAX");         // experiments: 0 = no call combiner
-	if (cm) G.combine_max_anchors = (size_t)std::max(0, atoi(cm));
-	const char *cl = getenv("MM2C_COMBINER_LANES");      // experiments: passes of the call combiner in flight
-	if (cl) G.combiner_lanes = std::max(1, std::min(16, atoi(cl)));
-	const char *dp = getenv("MM2C_DIRECT_PASS");         // 0: small per-read passes use copy commands and a stream wait instead of the staging kernels and the polled flag (experiments)
-	if (dp) G.direct_pass = atoi(dp) != 0;
-	const char *cw = getenv("MM2C_COOP_WAVES");          // 0: the host-buffer entries never use several waves per task (experiments; the tests use mm2c_tune)
-	if (cw) G.coop_waves = std::max(0, atoi(cw));
-	const char *pc = getenv("MM2C_PIPE_COOP_CHUNKS");    // experiments: the last chunks of a pipelined host batch with several waves per piece
-	if (pc) G.pipe_coop_chunks = std::max(0, atoi(pc));
-	const char *q4 = getenv("MM2C_Q24_RING");            // 0: the long ring of class-1 tasks keeps its 32-bit slots (experiments; the tests use mm2c_tune)
-	if (q4) G.q24_ring = atoi(q4) != 0;
-	const char *cr = getenv("MM2C_COMPACT_RING");        // 0: never the compact x / q ring of the tile kernel (experiments; the tests use mm2c_tune)
-	if (cr) G.compact_ring = atoi(cr) != 0;
-	const char *sl = getenv("MM2C_SINGLE_LAUNCH");       // 0: per-read passes keep stage_in (experiments)
-	if (sl) G.single_launch = atoi(sl) != 0;
-	const char *fs = getenv("MM2C_FUSE_ST");             // 0: per-read passes keep the prepass launch for the window starts (experiments)
-	if (fs) G.fuse_st = atoi(fs) != 0;
-	const char *dwb = getenv("MM2C_DECLINE_WHEN_BUSY");  // a path-A host (no mm2c_tune call site) opts into the busy protocol here: 1 / 2 = the rules of mm2chain_host.cpp, book_pred
-	if (dwb) G.decline_when_busy = std::max(0, std::min(2, atoi(dwb)));
-	const char *ft = getenv("MM2C_FAR_RING_THRESHOLD");  // tenths of an expected far tile per anchor from which a task takes the long ring
-	if (ft) G.far_thr10 = std::max(0, atoi(ft));
+	for (const Knob &k : KNOBS) {                    // the knobs' environment variables: out-of-range values are clamped, not refused
+		const char *e = k.env ? getenv(k.env) : nullptr;
+		if (!e) { if (k.flags & KNOB_ENV_INIT) k.set(k.dflt); continue; }
+		const int64_t v = atoi(e);
+		k.set(k.hi == 1 ? v != 0 : std::max(k.lo, (k.flags & KNOB_ENV_LO) ? v : std::min(k.hi, v)));
+	}
 	G.ready = true;
 	return 0;
 }
@@ -778,181 +774,35 @@ int mm2c_tune(const char *key, int value)
 {
 	std::lock_guard<std::mutex> lk(G.mu);
 	if (key && strcmp(key, "trim") == 0) { dev_cache_release(); return 0; }   // give the cached device memory back to the runtime
-	if (!key) return fail(MM2C_E_ARG, "key is NULL");
-	if (strcmp(key, "ring_class") == 0) {
-		if (value < 0 || value > 4) return fail(MM2C_E_ARG, "ring_class must be 0 .. 4");
-		G.ring_class = value;
-		return 0;
-	}
-	if (strcmp(key, "far_ring") == 0) {
-		if (value < 0 || value > 2) return fail(MM2C_E_ARG, "far_ring must be 0, 1 or 2");
-		G.far_ring = value;
-		return 0;
-	}
-	if (strcmp(key, "far_ring_threshold") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "far_ring_threshold (tenths of a far tile per anchor) must be >= 0");
-		G.far_thr10 = value;
-		return 0;
-	}
-	if (strcmp(key, "noskip_loop") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "noskip_loop must be 0 or 1");
-		G.noskip_loop = value;
-		return 0;
-	}
-	if (strcmp(key, "read_chunk_bases") == 0) {              // mm2c_read_chain_batch: bases per chunk of whole reads
-		if (value < 1) return fail(MM2C_E_ARG, "read_chunk_bases must be >= 1");
-		read_chunk_bases = value;
-		return 0;
-	}
-	if (strcmp(key, "index_chunk_bases") == 0) {             // mm2c_minidx_build: bases per chunk of whole sequences
-		if (value < 1) return fail(MM2C_E_ARG, "index_chunk_bases must be >= 1");
-		index_chunk_bases = value;
-		return 0;
-	}
-	if (strcmp(key, "heap_sort") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "heap_sort must be 0 or 1");
-		G.heap_sort = value;
-		return 0;
-	}
-	if (strcmp(key, "wide_share_threshold") == 0) {
-		if (value < 0 || value > 100) return fail(MM2C_E_ARG, "wide_share_threshold is a percentage");
-		G.wide_pct = value;
-		return 0;
-	}
-	if (strcmp(key, "split_streams") == 0) {
-		if (value < 0 || value > 2) return fail(MM2C_E_ARG, "split_streams must be 0, 1 (batches of mixed task sizes) or 2 (every batch)");
-		G.split_streams = value;
-		return 0;
-	}
-	if (strcmp(key, "compact_ring") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "compact_ring must be 0 or 1");
-		G.compact_ring = value;
-		return 0;
-	}
-	if (strcmp(key, "force_tab") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "force_tab must be 0 or 1");
-		G.force_tab = value;
-		return 0;
-	}
-	if (strcmp(key, "epi_fused") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "epi_fused must be 0 or 1");
-		G.epi_fused = value;
-		return 0;
-	}
-	if (strcmp(key, "pipeline_chunk_anchors") == 0) {
-		if (value < 1024) return fail(MM2C_E_ARG, "pipeline_chunk_anchors must be >= 1024");
-		G.pipeline_chunk_anchors = value;
-		return 0;
-	}
-	if (strcmp(key, "pipeline_pieces") == 0) {
-		if (value < 1) return fail(MM2C_E_ARG, "pipeline_pieces must be >= 1");
-		G.pipeline_pieces = value;
-		return 0;
-	}
-	if (strcmp(key, "pipeline_taper") == 0) {
-		if (value < 0 || value > 6) return fail(MM2C_E_ARG, "pipeline_taper must be 0 .. 6");
-		G.pipeline_taper = value;
-		return 0;
-	}
-	if (strcmp(key, "pipeline_min_chunk") == 0) {
-		if (value < 1024) return fail(MM2C_E_ARG, "pipeline_min_chunk must be >= 1024");
-		G.pipeline_min_chunk = value;
-		return 0;
-	}
-	if (strcmp(key, "coop_waves") == 0) {
-		if (value < 0 || value > 64) return fail(MM2C_E_ARG, "coop_waves must be 0 .. 64 (0 / 1: one wave per task always; any other value: the cooperative kernel, which is built for 16 waves per task)");
-		G.coop_waves = value;
-		return 0;
-	}
-	if (strcmp(key, "combine_max_anchors") == 0) {            // calls of up to this many anchors go through the call combiner (0: every call runs a pass of its own on its thread's stream)
-		if (value < 0) return fail(MM2C_E_ARG, "combine_max_anchors must be >= 0");
-		G.combine_max_anchors = (size_t)value;
-		return 0;
-	}
-	if (strcmp(key, "combiner_lanes") == 0) {
-		if (value < 1 || value > 16) return fail(MM2C_E_ARG, "combiner_lanes must be 1 .. 16");
-		G.combiner_lanes = value;
-		return 0;
-	}
-	if (strcmp(key, "pipe_coop_chunks") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "pipe_coop_chunks must be >= 0");
-		G.pipe_coop_chunks = value;
-		return 0;
-	}
-	if (strcmp(key, "q24_ring") == 0) {
-		G.q24_ring = value != 0;
-		return 0;
-	}
-	if (strcmp(key, "packed_fp") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "packed_fp must be 0 or 1");
-		G.packed_fp = value;
-		return 0;
-	}
-	if (strcmp(key, "score_bound_exit") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "score_bound_exit must be 0 or 1");
-		G.score_bound_exit = value;
-		return 0;
-	}
-	if (strcmp(key, "pin_workers") == 0) {
-		G.pin_workers = value != 0;
-		return 0;
-	}
-	if (strcmp(key, "decline_when_busy") == 0) {
-		if (value < 0 || value > 2) return fail(MM2C_E_ARG, "decline_when_busy must be 0 (never decline), 1 (by the slot's measured service time) or 2 (round 5's rule: booked predictions)");
-		G.decline_when_busy = value;
-		return 0;
-	}
-	if (strcmp(key, "direct_pass") == 0) {
-		G.direct_pass = value != 0;
-		return 0;
-	}
-	if (strcmp(key, "coop_plans") == 0) {
-		if (value < 0 || value > 2) return fail(MM2C_E_ARG, "coop_plans must be 0 (never), 1 (every plan of at most coop_max_tasks tasks) or 2 (per run: few long pieces)");
-		G.coop_plans = value;
-		return 0;
-	}
-	if (strcmp(key, "host_st") == 0) {
-		G.host_st = value != 0;
-		return 0;
-	}
-	if (strcmp(key, "fused_out") == 0) {
-		G.fused_out = value != 0;
-		return 0;
-	}
-	if (strcmp(key, "single_launch") == 0) { G.single_launch = value != 0; return MM2C_OK; }   // per-read passes of short tasks: the cooperative kernel reads the pinned arena itself (1) or stage_in uploads it first (0)
-	if (strcmp(key, "fuse_st") == 0) { G.fuse_st = value != 0; return MM2C_OK; }   // passes of few tasks of at most 7 168 anchors: the sixteen-wave kernel makes the window starts itself (1) or a prepass launch does (0)
-	if (strcmp(key, "seg_prepass") == 0) { G.seg_prepass = value != 0; return MM2C_OK; }   // plans with tasks of 65 536 anchors or more: a prepass block per 32 768 anchors (1) or per task (0)
-	if (strcmp(key, "coop_w8_above") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "coop_w8_above must be >= 0 (pieces beyond which the cooperative kernel takes eight waves per piece instead of sixteen)");
-		G.coop_w8_above = (int)std::min<int64_t>(value, 1 << 30);
-		return MM2C_OK;
-	}
-	if (strcmp(key, "coop_max_tasks") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "coop_max_tasks must be >= 0");
-		G.coop_max_tasks = value;
-		return 0;
-	}
-	if (strcmp(key, "plan_cut") == 0) {
-		if (value < 0 || value > 1) return fail(MM2C_E_ARG, "plan_cut must be 0 or 1");
-		G.plan_cut = value;
-		return 0;
-	}
-	if (strcmp(key, "plan_cut_min") == 0) {
-		if (value < 1) return fail(MM2C_E_ARG, "plan_cut_min must be >= 1");
-		G.plan_cut_min = value;
-		return 0;
-	}
-	if (strcmp(key, "multi_min_anchors") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "multi_min_anchors must be >= 0");
-		G.multi_min_anchors = value;
-		return 0;
-	}
-	if (strcmp(key, "seg_min") == 0) {
-		if (value < 0) return fail(MM2C_E_ARG, "seg_min must be >= 0");
-		G.seg_min = value;
-		return 0;
-	}
-	return fail(MM2C_E_ARG, "unknown tuning key '%s'", key);
+	const Knob *k = find_knob(key);
+	if (!k) return key ? fail(MM2C_E_ARG, "unknown tuning key '%s'", key) : fail(MM2C_E_ARG, "key is NULL");
+	int64_t v = value;
+	if (k->flags & KNOB_ANY) v = v != 0;
+	else if ((k->flags & KNOB_CLAMP_HI) && v > k->hi) v = k->hi;
+	if (v < k->lo || v > k->hi)
+		return k->hi == INT_MAX ? fail(MM2C_E_ARG, "%s must be >= %lld (%s)", k->key, (long long)k->lo, k->meaning)
+		                        : fail(MM2C_E_ARG, "%s must be %lld .. %lld (%s)", k->key, (long long)k->lo, (long long)k->hi, k->meaning);
+	k->set(v);
+	return 0;
+}
+
+int mm2c_tune_get(const char *key, int64_t *value, int64_t *dflt)
+{
+	std::lock_guard<std::mutex> lk(G.mu);
+	const Knob *k = find_knob(key);
+	if (!k) return key ? fail(MM2C_E_ARG, "unknown tuning key '%s'", key) : fail(MM2C_E_ARG, "key is NULL");
+	if (value) *value = k->get();
+	if (dflt) *dflt = k->dflt;
+	return 0;
+}
+
+int mm2c_tune_key(int i, const char **key, const char **env)
+{
+	std::lock_guard<std::mutex> lk(G.mu);
+	if (i < 0 || i >= (int)(sizeof(KNOBS) / sizeof(KNOBS[0]))) return fail(MM2C_E_ARG, "no tuning knob %d", i);
+	if (key) *key = KNOBS[i].key;
+	if (env) *env = KNOBS[i].env;
+	return 0;
 }
 
 int mm2c_split_model(const char *preset, float *k1_hw, float *k2_hw, float *c_hw, float *k_sw, float *c_sw)

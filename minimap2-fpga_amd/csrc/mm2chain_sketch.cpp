@@ -37,8 +37,6 @@ int index_sort(uint64_t *key, const uint64_t *y, uint64_t *key_tmp, uint64_t *y_
 int index_heads(const uint64_t *key, const uint64_t *y, int64_t n, int64_t *head, int64_t *row, int *bad, void *tmp, size_t tmp_bytes, hipStream_t st);
 int index_rows(const uint64_t *key, const int64_t *head, const int64_t *row, int64_t n, int64_t n_keys, char *img, int *bad, hipStream_t st);
 int index_count_select(const uint32_t *d_n, int64_t n_keys, int64_t i, uint32_t *h_val, hipStream_t st);
-std::atomic<int64_t> read_chunk_bases{1 << 27};                             // mm2c_tune("read_chunk_bases")
-std::atomic<int64_t> index_chunk_bases{1 << 27};                            // mm2c_tune("index_chunk_bases")
 }
 
 namespace {
@@ -497,7 +495,7 @@ int build_index(mm2c_minidx *ix, int64_t n_seqs, const int64_t *seq_off, const u
 
 	// 1. sketch in chunks of whole sequences, tag, append
 	PairList P;
-	const int64_t chunk_bases = std::max<int64_t>(index_chunk_bases.load(), 1);
+	const int64_t chunk_bases = std::max<int64_t>(G.index_chunk_bases.load(), 1);
 	for (int64_t r0 = 0; r0 < n_seqs;) {
 		int64_t r1 = r0 + 1;
 		while (r1 < n_seqs && seq_off[r1 + 1] - seq_off[r0] <= chunk_bases) ++r1;
@@ -780,7 +778,7 @@ int mm2c_read_chain_batch(const mm2c_params_t *par, int min_cnt, int min_sc, con
 		HIP_TRY(refs.take((void **)&d_ref, 2 * n_ref * 4));
 		HIP_TRY(skip_upload_refs(skip, d_ref, d_ref + n_ref, st));
 	}
-	const int64_t chunk_bases = std::max<int64_t>(read_chunk_bases.load(), 1);
+	const int64_t chunk_bases = std::max<int64_t>(G.read_chunk_bases.load(), 1);
 	int64_t A = 0, U = 0, B = 0, M = 0;
 	for (int64_t r0 = 0; r0 < n_reads;) {
 		int64_t r1 = r0 + 1;
@@ -1004,7 +1002,7 @@ static int frag_chain_impl(const mm2c_params_t *par, int min_cnt, int min_sc, co
 		HIP_TRY(skip_upload_refs(skip, d_ref, d_ref + n_ref, st));
 	}
 	const bool two_pass = max_occ > mid_occ;                   // map.c:318
-	const int64_t chunk_bases = std::max<int64_t>(read_chunk_bases.load(), 1);
+	const int64_t chunk_bases = std::max<int64_t>(G.read_chunk_bases.load(), 1);
 	auto bases = [&](int64_t g0, int64_t g1) { return seq_off[frag_off[g1]] - seq_off[frag_off[g0]]; };
 	int64_t A = 0, U = 0, B = 0, M = 0, n_rechained = 0;
 	for (int64_t g0 = 0; g0 < n_frags;) {                      // chunks of whole fragments

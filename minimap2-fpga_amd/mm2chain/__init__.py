@@ -2,7 +2,7 @@
 dispatch surface.  The compute lives in libmm2chain_hip.so (HIP, gfx950); this package is the host-side mirror."""
 from ._native import Params, Mm2cError, LIB_PATH, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL, load
 from . import params, synth, sharding, stream
-from .batch import (device_identity, last_host_variant, init, split_model, init_devices, device_count, split_tasks, shutdown, device_info, tune, ChainPlan, chain_batch_host, chain_batch_host_into, PinnedArray, chain_task, hardware_init, cleanup,
+from .batch import (device_identity, last_host_variant, init, split_model, init_devices, device_count, split_tasks, shutdown, device_info, tune, tune_get, tune_keys, tuned, ChainPlan, chain_batch_host, chain_batch_host_into, PinnedArray, chain_task, hardware_init, cleanup,
                     run_chaining_on_hw, mm_chain_dp, mm_chain_dp_batch, chain_epilogue_host, SeedPlan, seed_hits_batch, seed_chain_batch, MATCH_DTYPE,
                     HitPool, seed_chain_batch_pool, stage_stats, slot_stats, chain_task_pred, SeedSkip, seed_hits_batch_skip, seed_chain_batch_skip,
                     seed_chain_batch_pool_skip, MinimizerIndex, sketch_batch, sketch_match_batch, read_chain_batch, sketch_stats, index_stats,
@@ -16,7 +16,7 @@ from .batch import (device_identity, last_host_variant, init, split_model, init_
                     CigPlan, second_pass_batch, assemble_regions_batch, CIG_OPT_DTYPE, CIG_REG_DTYPE, CIG_REFUSED, CIG_INCOMPLETE, CIG_OVER_CAP, CIG_PIECE, CIG_NO_ROOM, CIG_LOST)
 
 __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE_GENERAL", "load", "params", "synth",
-           "sharding", "stream", "device_identity", "last_host_variant", "init", "split_model", "init_devices", "device_count", "split_tasks", "shutdown", "device_info", "tune", "ChainPlan", "chain_batch_host", "chain_batch_host_into", "PinnedArray", "chain_task", "hardware_init",
+           "sharding", "stream", "device_identity", "last_host_variant", "init", "split_model", "init_devices", "device_count", "split_tasks", "shutdown", "device_info", "tune", "tune_get", "tune_keys", "tuned", "ChainPlan", "chain_batch_host", "chain_batch_host_into", "PinnedArray", "chain_task", "hardware_init",
            "cleanup", "run_chaining_on_hw", "mm_chain_dp", "mm_chain_dp_batch", "chain_epilogue_host", "SeedPlan", "seed_hits_batch", "seed_chain_batch", "MATCH_DTYPE",
            "HitPool", "seed_chain_batch_pool", "stage_stats", "slot_stats", "chain_task_pred", "SeedSkip", "seed_hits_batch_skip", "seed_chain_batch_skip",
            "seed_chain_batch_pool_skip", "MinimizerIndex", "sketch_batch", "sketch_match_batch", "read_chain_batch", "sketch_stats", "index_stats",

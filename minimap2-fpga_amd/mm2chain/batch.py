@@ -6,6 +6,7 @@ run_chaining_on_hw / hardware_init / cleanup : the reference's own entry points,
 mm_chain_dp : the whole reference function (mmpriv.h:65), DP on the GPU, epilogue on the host.
 torch is plumbing only: device memory, streams.
 """
+import contextlib
 import ctypes as C
 import os
 import numpy as np
@@ -66,6 +67,35 @@ def shutdown():
 
 def tune(key, value):
     N.check(N.load().mm2c_tune(key.encode(), int(value)), "mm2c_tune")
+
+
+def tune_get(key):
+    """(value, default) of a tuning knob; needs no device"""
+    value, dflt = C.c_int64(0), C.c_int64(0)
+    N.check(N.load().mm2c_tune_get(key.encode(), C.byref(value), C.byref(dflt)), "mm2c_tune_get")
+    return value.value, dflt.value
+
+
+def tune_keys():
+    """{key: environment variable or None} of every tuning knob, in the order of the library's table (csrc/knobs.def)"""
+    lib, keys, k = N.load(), {}, 0
+    key, env = C.c_char_p(), C.c_char_p()
+    while lib.mm2c_tune_key(k, C.byref(key), C.byref(env)) == 0:
+        keys[key.value.decode()] = env.value.decode() if env.value else None
+        k += 1
+    return keys
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """with tuned(coop_plans=1, fuse_st=0): ... -- sets the knobs in the order given and, on the way out (also by an exception, also when a later knob of the
+    list is refused), puts back in reverse order what each of them held before"""
+    with contextlib.ExitStack() as undo:
+        for key, value in knobs.items():
+            before = tune_get(key)[0]
+            tune(key, value)
+            undo.callback(tune, key, before)
+        yield
 
 
 def device_info():

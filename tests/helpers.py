@@ -1,5 +1,8 @@
 """shared test helpers: task construction and GPU-vs-oracle comparison"""
+import contextlib
+
 import numpy as np
+import pytest
 import torch
 
 import oracle_binding as ob
@@ -33,6 +36,31 @@ PINNED_ROUTE = None
 ROUTE_LOG = []
 
 
+@contextlib.contextmanager
+def knob_setter():
+    """tune(key, val) for a block that flips knobs as it goes (mm2chain.tuned, one level per call): when the block ends, also by an exception, every knob is back at
+    what it held before, whatever the library's defaults are"""
+    import mm2chain
+    with contextlib.ExitStack() as undo:
+        yield lambda key, val: undo.enter_context(mm2chain.tuned(**{key: val}))
+
+
+@pytest.fixture
+def knobs():
+    """a test's own knob_setter (`from helpers import knobs` makes it a fixture of the importing module); setting "coop_plans" pins gpu_batch's route for the test"""
+    global PINNED_ROUTE
+    with knob_setter() as tune:
+        def tune_and_pin(key, val):
+            global PINNED_ROUTE
+            if key == "coop_plans":
+                PINNED_ROUTE = val                            # (gpu_batch then runs the input once, as pinned, instead of on both routes)
+            tune(key, val)
+        try:
+            yield tune_and_pin
+        finally:
+            PINNED_ROUTE = None
+
+
 def _run_plan(par, offsets, d_a, d_avg, variant):
     import mm2chain
     total = d_a.shape[0]
@@ -58,11 +86,8 @@ def gpu_batch(par, offsets, anchors, avg=None, variant=None):
     if PINNED_ROUTE is not None:
         f, p, _ = _run_plan(par, offsets, d_a, d_avg, variant)
         return f, p
-    try:
-        mm2chain.tune("coop_plans", 0)
+    with mm2chain.tuned(coop_plans=0):
         f, p, _ = _run_plan(par, offsets, d_a, d_avg, variant)
-    finally:
-        mm2chain.tune("coop_plans", 2)
     f2, p2, route = _run_plan(par, offsets, d_a, d_avg, None)
     ROUTE_LOG.append(route)
     bad = np.nonzero((f != f2) | (p != p2))[0]

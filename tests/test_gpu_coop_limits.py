@@ -10,7 +10,7 @@ import torch
 
 import coop_limit_data as cd
 import oracle_binding as ob
-from helpers import assert_same, gpu_batch, oracle_batch
+from helpers import assert_same, gpu_batch, knobs, oracle_batch  # noqa: F401 (knobs: a fixture)
 from reuse_data import batch
 
 pytestmark = pytest.mark.gpu
@@ -26,23 +26,6 @@ def _init():
     mm2chain.init()
     yield
     mm2chain.shutdown()
-
-
-@pytest.fixture
-def knobs():
-    """tuning knobs a test changes, put back afterwards (results never depend on them; the instantiation that runs does)"""
-    import helpers
-    import mm2chain
-
-    def tune(key, val):
-        if key == "coop_plans":
-            helpers.PINNED_ROUTE = val
-        return mm2chain.tune(key, val)
-    yield tune
-    helpers.PINNED_ROUTE = None
-    for key, val in (("force_tab", 0), ("plan_cut", 1), ("plan_cut_min", 8192), ("seg_min", 256), ("coop_plans", 2), ("coop_waves", 16), ("coop_w8_above", 256),
-                     ("fuse_st", 1), ("single_launch", 1)):
-        mm2chain.tune(key, val)
 
 
 _CASES = {}
@@ -168,9 +151,9 @@ def _per_read(P, t, f_ref, p_ref, what):
     Pr = params.make_params(P.max_dist_x, P.max_dist_y, P.bw, P.max_skip, P.max_iter, P.gap_scale, P.is_cdna, P.n_segs, P.q_span_override, P.flags | mm2chain.MM2C_F_IGNORE_SEG)
     avg = ob.avg_qspan(t)
     for single in (1, 0, 1):
-        mm2chain.tune("single_launch", single)
-        f, p = mm2chain.chain_task(Pr, t, avg)
-        v = mm2chain.last_host_variant()
+        with mm2chain.tuned(single_launch=single):
+            f, p = mm2chain.chain_task(Pr, t, avg)
+            v = mm2chain.last_host_variant()
         assert_same(f, p, f_ref, p_ref, None, f"{what}, per-read entry, single_launch {single}: {v}")
         assert v.startswith("chain_dp_coop<W=16,") and f"FAR={int(P.max_iter > 960)},TAB=0>" in v and "loop=asm" in v, (what, v)
 

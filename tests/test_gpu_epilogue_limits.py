@@ -24,11 +24,8 @@ def _init():
 def epi_path(request):
     """the two forms of the device epilogue: tasks that fit the LDS in the fused kernel (default), or kernels A / B / C for every task"""
     import mm2chain
-    mm2chain.tune("epi_fused", request.param)
-    try:
+    with mm2chain.tuned(epi_fused=request.param):
         yield request.param
-    finally:
-        mm2chain.tune("epi_fused", 1)
 
 
 def _compare(cases, task, got, min_cnt, min_sc, what):

@@ -9,6 +9,7 @@ import torch
 
 import frag_model as fm
 import sketch_model as sm
+from helpers import knobs  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_frag.npz")
@@ -27,8 +28,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("heap_sort", 0)
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -104,9 +103,9 @@ def _check_final(fx, variant, got, ids, first=False):
 
 
 @pytest.mark.parametrize("variant", ["heap", "radix", "heap_for"])
-def test_frag_chain_equals_the_reference(fx, variant):
+def test_frag_chain_equals_the_reference(fx, variant, knobs):
     import mm2chain
-    mm2chain.tune("heap_sort", 0 if variant == "radix" else 1)
+    knobs("heap_sort", 0 if variant == "radix" else 1)
     skip = mm2chain.SeedSkip(FOR_ONLY) if variant == "heap_for" else None
     idx = _index(fx)
     n_re = 0
@@ -118,9 +117,9 @@ def test_frag_chain_equals_the_reference(fx, variant):
     idx.close()
 
 
-def test_max_occ_equal_mid_occ_is_the_first_pass(fx):
+def test_max_occ_equal_mid_occ_is_the_first_pass(fx, knobs):
     import mm2chain
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     idx = _index(fx)
     for h, ids in _groups(fx).items():
         got = mm2chain.frag_chain_batch(_params(h), h[5], h[6], _sub(fx, ids), idx, int(fx["mid_occ"]), int(fx["mid_occ"]))
@@ -169,15 +168,15 @@ def test_single_segment_fragments_equal_the_sketch_and_match_entries(fx, hpc):
     idx.close()
 
 
-def test_chunks_are_cut_between_fragments(fx):
+def test_chunks_are_cut_between_fragments(fx, knobs):
     import mm2chain
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     idx = _index(fx)
     h, ids = max(_groups(fx).items(), key=lambda kv: len(kv[1]))          # the pairs of 2 x 150: every kind but (f) is among them
     frags = _sub(fx, ids)
     one = mm2chain.frag_chain_batch(_params(h), h[5], h[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]))
     before = mm2chain.sketch_stats()
-    mm2chain.tune("read_chunk_bases", 700)                                 # two fragments of 300 bases a chunk
+    knobs("read_chunk_bases", 700)                                 # two fragments of 300 bases a chunk
     many = mm2chain.frag_chain_batch(_params(h), h[5], h[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]))
     n_chunks = mm2chain.sketch_stats()["chunks"] - before["chunks"]
     assert n_chunks >= len(ids) // 2
@@ -191,19 +190,19 @@ def test_chunks_are_cut_between_fragments(fx):
     idx.close()
 
 
-def test_every_fragment_a_chunk_of_its_own(fx):
+def test_every_fragment_a_chunk_of_its_own(fx, knobs):
     """read_chunk_bases = 1: a chunk boundary on both sides of every fragment of every kind, (f) included -- chunks whose segment range begins or ends with a
     zero-length segment, and one re-chained fragment per chunk.  Every group of fragments that may share a call; equal to the one-chunk run and to the reference"""
     import mm2chain
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     idx = _index(fx)
     seen = []
     for h, ids in _groups(fx).items():
         frags = _sub(fx, ids)
-        mm2chain.tune("read_chunk_bases", 1 << 27)
+        knobs("read_chunk_bases", 1 << 27)
         one = mm2chain.frag_chain_batch(_params(h), h[5], h[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]))
         before = mm2chain.sketch_stats()["chunks"]
-        mm2chain.tune("read_chunk_bases", 1)
+        knobs("read_chunk_bases", 1)
         many = mm2chain.frag_chain_batch(_params(h), h[5], h[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]))
         assert mm2chain.sketch_stats()["chunks"] - before == len(ids)
         for key in ("anchor_off", "u_off", "u", "b_off", "b", "rep_len", "mini_off", "mini_pos", "rechained", "n_rechained"):
@@ -248,9 +247,9 @@ def _equal_model(got, want):
 
 
 @pytest.mark.parametrize("shape", ["all_empty", "empty_first", "empty_last", "alone", "255_one_base"])
-def test_edge_shapes(fx, shape):
+def test_edge_shapes(fx, shape, knobs):
     import mm2chain
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     idx = _index(fx)
     g = int(fx["kind_b"][0])                                               # a pair that re-chains
     s = [fx["seq"][fx["seq_off"][i]:fx["seq_off"][i + 1]].tobytes() for i in range(fx["frag_off"][g], fx["frag_off"][g + 1])]
@@ -288,11 +287,11 @@ def test_refusals(fx):
     idx.close()
 
 
-def test_best_chain_tie_takes_the_first(fx):
+def test_best_chain_tie_takes_the_first(fx, knobs):
     """two chains of equal score, only the second spanning both segments: the reference's `max < score` scan keeps the first, which misses a segment, so the
     fragment re-chains.  Built by hand: an index over the pair's own minimizers whose hits lie on one diagonal each"""
     import mm2chain
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     k, w, mid_occ, max_occ = int(fx["k"]), int(fx["w"]), 8, 40
     rng = np.random.default_rng(5)
     segs = [rng.choice(np.frombuffer(b"ACGT", np.uint8), 300).tobytes() for _ in range(2)]

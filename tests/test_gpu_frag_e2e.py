@@ -17,8 +17,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("heap_sort", 0)
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -30,19 +28,17 @@ def sets():
 def _calls(cpu, idx, heap, mid_occ, max_occ, chunk_bases=None):
     """one call per group; returns [(ids, result)] and the chunks the calls made"""
     import mm2chain
-    mm2chain.tune("heap_sort", int(heap))
     out, n_chunks = [], 0
     for h, ids in cpu.groups:
         frags = [cpu.frags[g] for g in ids]
         cb = chunk_bases(frags) if chunk_bases else 1 << 27
-        mm2chain.tune("read_chunk_bases", int(cb))
-        before = mm2chain.sketch_stats()["chunks"]
-        got = mm2chain.frag_chain_batch(fd.params_of(h), h[5], h[6], frags, idx, mid_occ, max_occ)
-        made = mm2chain.sketch_stats()["chunks"] - before
+        with mm2chain.tuned(heap_sort=int(heap), read_chunk_bases=int(cb)):
+            before = mm2chain.sketch_stats()["chunks"]
+            got = mm2chain.frag_chain_batch(fd.params_of(h), h[5], h[6], frags, idx, mid_occ, max_occ)
+            made = mm2chain.sketch_stats()["chunks"] - before
         rule = len(fd.frag_chunks(frags, cb))
         assert made == rule, f"read_chunk_bases {cb}: {made} chunks, the host's rule gives {rule}"
         out.append((ids, got))
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     return out
 
 

@@ -27,10 +27,8 @@ def _init():
     import mm2chain
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
-    mm2chain.tune("heap_sort", 1)
-    yield
-    mm2chain.tune("heap_sort", 0)
-    mm2chain.tune("read_chunk_bases", 1 << 27)
+    with mm2chain.tuned(heap_sort=1):
+        yield
     mm2chain.shutdown()
 
 
@@ -113,11 +111,8 @@ def test_chunks_of_a_few_fragments(fx, n_segs):
     ids = _ids(fx, n_segs)
     one = _call(fx, idx, ids)
     before = mm2chain.sketch_stats()["chunks"]
-    mm2chain.tune("read_chunk_bases", 900)
-    try:
+    with mm2chain.tuned(read_chunk_bases=900):
         many = _call(fx, idx, ids)
-    finally:
-        mm2chain.tune("read_chunk_bases", 1 << 27)
     assert mm2chain.sketch_stats()["chunks"] - before >= len(ids) // 4
     for key in KEYS:
         assert np.array_equal(one[key], many[key]), key

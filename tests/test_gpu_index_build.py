@@ -18,6 +18,7 @@ import torch
 import index_model as im
 import oracle_binding as ob
 from helpers import assert_table as _assert_table
+from helpers import knobs  # noqa: F401 (knobs: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +40,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("index_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -212,23 +212,21 @@ def test_sweep_against_the_numpy_model(k, w, hpc):
 
 # ---- 3. chunking ---------------------------------------------------------------------------------------------------------------------------------------
 
-def test_chunking_does_not_change_the_index(refs):
+def test_chunking_does_not_change_the_index(refs, knobs):
     import mm2chain
     lens = [len(s) for s in refs]
     short = min(l for l in lens if l > 0)
     out = {}
     for name, cb in (("below the longest sequence", max(lens) // 3), ("one short sequence", short), ("default", None)):
-        if cb is not None:
-            mm2chain.tune("index_chunk_bases", cb)
-        else:
-            mm2chain.tune("index_chunk_bases", 1 << 27)
+        lim = mm2chain.tune_get("index_chunk_bases")[1] if cb is None else cb
+        knobs("index_chunk_bases", lim)
         mm2chain.index_stats(reset=True)
         idx = mm2chain.MinimizerIndex.build(refs, 15, 10)
         out[name] = idx.export() + (idx.mid_occ,)
         st = mm2chain.index_stats()
         # the host's rule: a chunk takes whole sequences while its bases stay within index_chunk_bases, at least one sequence
         off = np.concatenate([[0], np.cumsum(lens)])
-        want, r0, lim = 0, 0, (1 << 27) if cb is None else cb
+        want, r0 = 0, 0
         while r0 < len(lens):
             r1 = r0 + 1
             while r1 < len(lens) and off[r1 + 1] - off[r0] <= lim:
@@ -247,7 +245,7 @@ def test_chunking_does_not_change_the_index(refs):
 
 # ---- 4. scale -------------------------------------------------------------------------------------------------------------------------------------------
 
-def test_scale_2e7_bases():
+def test_scale_2e7_bases(knobs):
     import mm2chain
     rng = np.random.default_rng(4242)
     lens = [9_000_000, 6_500_000, 0, 5_000_000, 3_000_000, 499_999, 1]
@@ -257,7 +255,7 @@ def test_scale_2e7_bases():
         s[p:p + rep.size] = rep
     assert sum(lens) >= 20_000_000
     k, w = 15, 10
-    mm2chain.tune("index_chunk_bases", 8_000_000)                                     # several chunks, one of them a sequence longer than the chunk
+    knobs("index_chunk_bases", 8_000_000)                                     # several chunks, one of them a sequence longer than the chunk
     mm2chain.index_stats(reset=True)
     idx = mm2chain.MinimizerIndex.build(seqs, k, w)
     st = mm2chain.index_stats()

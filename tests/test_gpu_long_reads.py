@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import oracle_binding as ob
-from helpers import oracle_batch, assert_same
+from helpers import oracle_batch, assert_same, knob_setter
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -147,10 +147,10 @@ def test_window_starts_made_inside_the_sixteen_wave_kernel(preset):
     a = np.concatenate([x[1] for x in parts])
     off = np.concatenate([[0]] + [x[0][1:] + sum(y[0][-1] for y in parts[:k]) for k, x in enumerate(parts)]).astype(np.int64)
     f_ref, p_ref = oracle_batch(P, off, a)
-    try:
-        mm2chain.tune("coop_plans", 1)
+    with knob_setter() as tune:
+        tune("coop_plans", 1)
         for fuse, want in ((1, "st=kernel"), (0, "st=prepass"), (1, "st=kernel")):
-            mm2chain.tune("fuse_st", fuse)
+            tune("fuse_st", fuse)
             f, p, route, variant = _plan_run(P, off, a)
             assert_same(f, p, f_ref, p_ref, off, f"{preset}, fuse_st {fuse}: {variant}")
             assert variant.startswith("chain_dp_coop<W=16") and want in variant, variant
@@ -164,15 +164,13 @@ def test_window_starts_made_inside_the_sixteen_wave_kernel(preset):
         # the per-read host entry (a staged pass -> the same kernel): as ONE launch -- the kernel copies the anchors from the pinned arena itself -- and with stage_in first;
         # alternating, so that the counter of finished workgroups is handed from one kind of pass to the other
         for single in (1, 0, 1, 1, 0):
-            mm2chain.tune("single_launch", single)
+            tune("single_launch", single)
             for k in (3, 6, 10, 0, 9):
                 t_k = a[off[k]:off[k + 1]]
                 avg = ob.avg_qspan(t_k)
                 f, p = mm2chain.chain_task(P, t_k, avg)
                 assert_same(f, p, f_ref[off[k]:off[k + 1]], p_ref[off[k]:off[k + 1]], None,
                             f"{preset}, single_launch {single}, chain_task of {t_k.shape[0]} anchors: {mm2chain.last_host_variant()}")
-    finally:
-        mm2chain.tune("coop_plans", 2); mm2chain.tune("fuse_st", 1); mm2chain.tune("single_launch", 1)
 
 
 @pytest.mark.parametrize("loci", [31, 32, 33, 70])
@@ -187,13 +185,10 @@ def test_single_launch_pass_with_its_metadata_in_the_arguments_and_in_the_arena(
     avg = ob.avg_qspan(t)
     f_ref, p_ref, _ = ob.chain_fpv(P, t, avg)
     for single in (1, 0):
-        mm2chain.tune("single_launch", single)
-        try:
+        with mm2chain.tuned(single_launch=single):
             for rep in range(2):
                 f, p = mm2chain.chain_task(P, t, avg)
                 assert_same(f, p, f_ref, p_ref, None, f"{loci} loci, single_launch {single}, run {rep}: {mm2chain.last_host_variant()}")
-        finally:
-            mm2chain.tune("single_launch", 1)
     assert int(p_ref.max()) > 300 * (loci - 1) - 1                                                 # (a predecessor inside the last locus: index relative to the task)
     assert "st=kernel" in mm2chain.last_host_variant(), mm2chain.last_host_variant()
 
@@ -213,17 +208,15 @@ def test_prepass_of_long_tasks_by_segments_and_by_task_alike():
     off = np.concatenate([[0]] + [x[0][1:] + sum(y[0][-1] for y in parts[:k]) for k, x in enumerate(parts)]).astype(np.int64)
     f_ref, p_ref = oracle_batch(P, off, a)
     seen = {}
-    try:
+    with knob_setter() as tune:
         for seg in (1, 0, 1):
-            mm2chain.tune("seg_prepass", seg)
+            tune("seg_prepass", seg)
             for rep in range(2):
                 f, p, route, variant = _plan_run(P, off, a)
                 assert_same(f, p, f_ref, p_ref, off, f"seg_prepass {seg}, run {rep}: {variant}, route {route}")
                 seen.setdefault(seg, (route, variant))
                 assert (route, variant) == seen[seg]
         assert seen[0] == seen[1], seen                                                            # the same pieces, the same kernels either way
-    finally:
-        mm2chain.tune("seg_prepass", 1)
 
 
 def test_one_task_at_the_references_buffer_limit():
@@ -302,10 +295,8 @@ def test_one_read_of_a_million_anchors_among_short_ones_on_both_routes():
     off = np.concatenate([o2[:151], o2[150] + o1[1:], o2[151:] + o1[-1]])
     assert np.diff(off).max() == 1_000_000 and off[-1] == a.shape[0]
     f_ref, p_ref = oracle_batch(P, off, a)
-    try:
+    with knob_setter() as tune:
         for coop in (2, 0):
-            mm2chain.tune("coop_plans", coop)
+            tune("coop_plans", coop)
             f, p, route, variant = _plan_run(P, off, a)
             assert_same(f, p, f_ref, p_ref, off, f"coop_plans {coop}: {variant}, route {route}")
-    finally:
-        mm2chain.tune("coop_plans", 2)

@@ -91,11 +91,8 @@ def _run_both_knob_values(knobs, gap_scale, what, want_asm):
 @pytest.mark.parametrize("ring_class", [0, 1, 2, 3, 4])
 def test_ring_classes(ring_class, gap_scale, knobs):
     import mm2chain
-    mm2chain.tune("ring_class", ring_class)
-    try:
+    with mm2chain.tuned(ring_class=ring_class):
         _run_both_knob_values(knobs, gap_scale, f"ring_class={ring_class}", want_asm=ring_class >= 3)
-    finally:
-        mm2chain.tune("ring_class", 3)
 
 
 @pytest.mark.parametrize("gap_scale", GAP_SCALES)

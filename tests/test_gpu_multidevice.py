@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import oracle_binding as ob
-from helpers import oracle_batch, assert_same
+from helpers import oracle_batch, assert_same, knob_setter, knobs  # noqa: F401 (knobs: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,7 @@ def _stream(profile, n_reads, n_per, seed):
 
 
 @pytest.mark.parametrize("n_ctx", [2, 3])
-def test_host_batches_split_across_device_contexts(n_ctx):
+def test_host_batches_split_across_device_contexts(n_ctx, knobs):
     import mm2chain
     from mm2chain import params, synth
     assert torch.cuda.is_available()
@@ -33,7 +33,7 @@ def test_host_batches_split_across_device_contexts(n_ctx):
     mm2chain.init_devices([0] * n_ctx)
     try:
         assert mm2chain.device_count() == n_ctx
-        mm2chain.tune("multi_min_anchors", 1000)
+        knobs("multi_min_anchors", 1000)
         # f / p through the host-buffer path
         f, p = mm2chain.chain_batch_host(P, off, a_all)
         assert_same(f[5:], p[5:], f_ref, p_ref, off - 5, "split chain_batch_host")
@@ -68,7 +68,7 @@ def test_host_batches_split_across_device_contexts(n_ctx):
         assert np.array_equal(out[k][0], res1[k][0]), k          # seeds -> chains == anchors -> chains (scores and counts; the order among equal x is the sort's)
 
 
-def test_small_ranges_of_a_split_batch_stay_on_their_own_device_context():
+def test_small_ranges_of_a_split_batch_stay_on_their_own_device_context(knobs):
     """ranges of at most combine_max_anchors (2^17) anchors used to go through the call combiner, whose stream and arenas belong to the primary
     device, from worker threads bound to other devices; a worker now always runs on the context of its own device slot.  Small batch, three
     contexts, per-read calls (which do use the combiner) before and after, passes counted."""
@@ -81,7 +81,7 @@ def test_small_ranges_of_a_split_batch_stay_on_their_own_device_context():
     mm2chain.shutdown()
     mm2chain.init_devices([0, 0, 0])
     try:
-        mm2chain.tune("multi_min_anchors", 1000)
+        knobs("multi_min_anchors", 1000)
         k = 7
         f1, p1 = mm2chain.chain_task(P, a[off[k]:off[k + 1]], ob.avg_qspan(a[off[k]:off[k + 1]]))       # creates the combiner's context
         assert_same(f1, p1, f_ref[off[k]:off[k + 1]], p_ref[off[k]:off[k + 1]], None, "per-read call before the split batch")
@@ -97,7 +97,7 @@ def test_small_ranges_of_a_split_batch_stay_on_their_own_device_context():
         mm2chain.init(0)
 
 
-def test_devices_named_in_the_environment_for_hosts_whose_init_hook_carries_no_ordinals(monkeypatch):
+def test_devices_named_in_the_environment_for_hosts_whose_init_hook_carries_no_ordinals(monkeypatch, knobs):
     """hardware_init(long, char *) (chain_hardware.h:69) -> mm2c_init(-1): MM2C_DEVICES names the devices"""
     import mm2chain
     from mm2chain import params
@@ -109,7 +109,7 @@ def test_devices_named_in_the_environment_for_hosts_whose_init_hook_carries_no_o
         monkeypatch.setenv("MM2C_DEVICES", "0,0")
         mm2chain.init(-1)
         assert mm2chain.device_count() == 2
-        mm2chain.tune("multi_min_anchors", 1000)
+        knobs("multi_min_anchors", 1000)
         f, p = mm2chain.chain_batch_host(P, off, a)
         assert_same(f, p, f_ref, p_ref, off, "MM2C_DEVICES=0,0")
         mm2chain.shutdown()
@@ -148,7 +148,7 @@ def test_bench_gpus_2_starts_two_ranks_on_the_gpu():
 
 
 @pytest.mark.parametrize("n_ctx", [2, 3])
-def test_per_read_calls_are_served_by_every_device_context(n_ctx):
+def test_per_read_calls_are_served_by_every_device_context(n_ctx, knobs):
     """The reference's dispatch surface -- one blocking call per read from many host threads (map.c:561 -> chain.c:103 -> run_chaining_on_hw) -- with several
     devices configured: every device slot has its own call combiner (lanes, streams, arenas on that device) and a call goes to the least loaded slot
     (chain_hardware.cpp:9-23,58-72: a queue, a lock, a buffer set per kernel, one picked per call).  The box has one GPU, listed n_ctx times.  Twelve threads,
@@ -166,8 +166,6 @@ def test_per_read_calls_are_served_by_every_device_context(n_ctx):
     errs = []
     try:
         assert mm2chain.device_count() == n_ctx
-        mm2chain.tune("multi_min_anchors", 1 << 20)                 # (the library's default; the tests above lower it, and knobs outlive a shutdown)
-
         def worker(tid):
             try:
                 for rep in range(3):
@@ -221,8 +219,8 @@ def test_busy_protocol_of_the_reference_symbol():
     ret, f, p = mm2chain.run_chaining_on_hw(t.shape[0], 5000, 5000, 500, 15, avg, t, None, 0, tid=3, hw_time_pred=2.0, sw_time_pred=0.5)
     assert ret == 0 and mm2chain.slot_stats(0)["declined"] == d0
     assert_same(f, p, f_ref, p_ref, None, "default: the protocol is off")
-    try:
-        mm2chain.tune("decline_when_busy", 2)
+    with knob_setter() as tune:
+        tune("decline_when_busy", 2)
         ret, f, p = mm2chain.run_chaining_on_hw(t.shape[0], 5000, 5000, 500, 15, avg, t, None, 0, tid=3, hw_time_pred=2.0, sw_time_pred=0.5)
         assert ret == 1 and mm2chain.slot_stats(0)["declined"] == d0 + 1
         ret, f, p = mm2chain.run_chaining_on_hw(t.shape[0], 5000, 5000, 500, 15, avg, t, None, 0, tid=3, hw_time_pred=0.4, sw_time_pred=0.5)
@@ -234,7 +232,7 @@ def test_busy_protocol_of_the_reference_symbol():
         rc, f, p = mm2chain.chain_task_pred(P, t, avg, 0, 9.0, 1.0)
         assert rc == 1 and np.all(f == -77) and np.all(p == -77)          # declined: nothing written
         # rule 1: the slot has served passes by now, so it knows what one takes (tens of microseconds to a millisecond)
-        mm2chain.tune("decline_when_busy", 1)
+        tune("decline_when_busy", 1)
         for _ in range(12):                                               # (the estimate leaves out a slot's first eight passes: they pay for code loading and arena growth)
             mm2chain.chain_task(P, t, avg)
         rc, f, p = mm2chain.chain_task_pred(P, t, avg, 0, 0.05, 1e-6)     # the caller's loop: a nanosecond -- waiting for a pass cannot beat it
@@ -245,8 +243,6 @@ def test_busy_protocol_of_the_reference_symbol():
         rc, f, p = mm2chain.chain_task_pred(P, t, avg, 0, 0.0, 0.0)       # no model
         assert rc == 0
         assert_same(f, p, f1, p1, None, "rule 1, no model: never declined")
-    finally:
-        mm2chain.tune("decline_when_busy", 0)
     rc, f, p = mm2chain.chain_task_pred(P, t, avg, 0, 9.0, 1.0)
     assert rc == 0
     assert_same(f, p, f1, p1, None, "protocol off")
@@ -264,8 +260,7 @@ def test_small_host_passes_staged_by_kernels_or_by_copy_commands(direct):
     P = params.map_ont()
     # 2 (round 6, the default): as 1, and a pass that ends in the cooperative kernel has no fourth launch -- that kernel stores f / p to the result buffer as it goes and its
     # last workgroup raises the flag; 1: the copy back as a kernel of its own (stage_out)
-    mm2chain.tune("direct_pass", 1 if direct else 0); mm2chain.tune("fused_out", 1 if direct == 2 else 0)
-    try:
+    with mm2chain.tuned(direct_pass=1 if direct else 0, fused_out=1 if direct == 2 else 0):
         for n_reads, n_per, seed in [(1, 1, 1), (1, 7, 2), (3, (1, 9), 3), (5, (200, 3000), 4), (40, (50, 700), 5)]:
             off, a = _stream("mixed", n_reads, n_per, seed=700 + seed)
             f_ref, p_ref = oracle_batch(P, off, a)
@@ -298,5 +293,3 @@ def test_small_host_passes_staged_by_kernels_or_by_copy_commands(direct):
         for t in th:
             t.join()
         assert not errs, errs[:3]
-    finally:
-        mm2chain.tune("direct_pass", 1); mm2chain.tune("fused_out", 1)

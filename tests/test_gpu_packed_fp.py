@@ -5,7 +5,7 @@ Every case is compared element for element with the CPU oracle, with the knob on
 import numpy as np
 import pytest
 
-from helpers import assert_same, gpu_batch, oracle_batch
+from helpers import assert_same, gpu_batch, knobs, oracle_batch  # noqa: F401 (knobs: a fixture)
 from reuse_data import PK_MAX_F, PK_MAX_N, batch, chain_with_noise, span_sum, task_of
 
 pytestmark = pytest.mark.gpu
@@ -19,21 +19,6 @@ def _init():
     mm2chain.init()
     yield
     mm2chain.shutdown()
-
-
-@pytest.fixture
-def knobs():
-    import helpers
-    import mm2chain
-
-    def tune(key, val):
-        if key == "coop_plans":
-            helpers.PINNED_ROUTE = val
-        return mm2chain.tune(key, val)
-    yield tune
-    helpers.PINNED_ROUTE = None
-    for key, val in (("packed_fp", 1), ("coop_plans", 2), ("plan_cut", 1), ("plan_cut_min", 8192)):
-        mm2chain.tune(key, val)
 
 
 def run_both(P, tasks, knobs, what, ref_tasks=None):

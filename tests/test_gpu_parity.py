@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import oracle_binding as ob
-from helpers import mk_anchor, pack, oracle_batch, gpu_batch, assert_same
+from helpers import mk_anchor, pack, oracle_batch, gpu_batch, assert_same, knob_setter, knobs  # noqa: F401 (knobs: a fixture)
 from helpers import steep_colinear_task as _steep_colinear_task
 
 pytestmark = pytest.mark.gpu
@@ -75,15 +75,12 @@ def test_ring_classes_and_far_lookback(ring_class):
     kernel (the default), 0 / 1 / 2 = the first-generation kernel with 256 / 512 / 1024 anchors of ring"""
     import mm2chain
     from mm2chain import params
-    mm2chain.tune("ring_class", ring_class)
-    try:
+    with mm2chain.tuned(ring_class=ring_class):
         for P in (params.make_params(max_skip=400, max_iter=3000), params.map_ont(), params.make_params(max_skip=INT32_MAX, max_iter=1500)):
             off, a = _stream("dense", 6, 4000, seed=21, locus=6000)
             f_ref, p_ref = oracle_batch(P, off, a)
             f, p = gpu_batch(P, off, a)
             assert_same(f, p, f_ref, p_ref, off, f"ring {ring_class}")
-    finally:
-        mm2chain.tune("ring_class", 3)
 
 
 @pytest.mark.parametrize("max_skip", [25, 1000, INT32_MAX])
@@ -269,11 +266,8 @@ def test_ring_size_classes_in_one_batch(far_ring):
     a = np.concatenate(parts)
     off = np.concatenate(([0], np.cumsum([t.shape[0] for t in parts]))).astype(np.int64)
     f_ref, p_ref = oracle_batch(P, off, a)
-    mm2chain.tune("far_ring", far_ring)
-    try:
+    with mm2chain.tuned(far_ring=far_ring):
         f, p = gpu_batch(P, off, a)
-    finally:
-        mm2chain.tune("far_ring", 1)
     assert_same(f, p, f_ref, p_ref, off, f"far_ring={far_ring}")
 
 
@@ -433,9 +427,8 @@ def _multiseg_task(rng, n, n_segs):
 def general_kernel(request):
     """the segment / cDNA variant runs in the first-generation kernel by default (ring_class 3) and in the tile kernel on request (4)"""
     import mm2chain
-    mm2chain.tune("ring_class", request.param)
-    yield request.param
-    mm2chain.tune("ring_class", 3)
+    with mm2chain.tuned(ring_class=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("is_cdna,n_segs", [(0, 2), (1, 1), (1, 2), (0, 3)])
@@ -556,15 +549,13 @@ def test_host_paths_cut_tasks_at_empty_windows():
     off = np.concatenate(([0], np.cumsum([t.shape[0] for t in tasks]))).astype(np.int64)
     P = params.make_params(max_skip=300)           # long scans: windows of up to ~1200 anchors, beyond the ring
     f_ref, p_ref = oracle_batch(P, off, a)
-    try:
+    with knob_setter() as tune:
         for seg_min in (0, 1, 64, 1000):
-            mm2chain.tune("seg_min", seg_min)
+            tune("seg_min", seg_min)
             f, p = mm2chain.chain_batch_host(P, off, a)
             assert_same(f, p, f_ref, p_ref, off, f"seg_min {seg_min}")
             f1, p1 = mm2chain.chain_task(P, tasks[0], ob.avg_qspan(tasks[0]))
             assert_same(f1, p1, f_ref[: off[1]], p_ref[: off[1]], None, f"task seg_min {seg_min}")
-    finally:
-        mm2chain.tune("seg_min", 256)
 
 
 def _multi_locus_tasks(seed, n_tasks, loci=(3, 30), per_locus=(1, 700), seg_ids=False):
@@ -591,8 +582,7 @@ def test_plans_cut_long_tasks_on_the_device(seg_min, cut_min):
     tasks = _multi_locus_tasks(123, 9) + [_stream("mixed", 1, (700, 700), seed=5)[1], np.zeros((0, 2), np.uint64)] + _multi_locus_tasks(124, 3, seg_ids=True)
     a = np.concatenate(tasks)
     off = np.concatenate(([0], np.cumsum([t.shape[0] for t in tasks]))).astype(np.int64)
-    try:
-        mm2chain.tune("seg_min", seg_min); mm2chain.tune("plan_cut_min", cut_min)
+    with mm2chain.tuned(seg_min=seg_min, plan_cut_min=cut_min):
         for P in (params.map_ont(), params.make_params(max_skip=300), params.make_params(n_segs=2)):
             f_ref, p_ref = oracle_batch(P, off, a)
             f, p = gpu_batch(P, off, a)
@@ -610,8 +600,6 @@ def test_plans_cut_long_tasks_on_the_device(seg_min, cut_min):
         for k in range(off.size - 1):
             u_ref, b_ref = ob.mm_chain_dp(P, 3, 40, a[off[k]:off[k + 1]])
             assert np.array_equal(u[uo[k]:uo[k + 1]], u_ref) and np.array_equal(b[bo[k]:bo[k + 1]], b_ref), f"task {k}: chains differ"
-    finally:
-        mm2chain.tune("seg_min", 256); mm2chain.tune("plan_cut_min", 8192)
 
 
 def test_plan_with_one_very_long_task_is_cut_by_default():
@@ -712,9 +700,8 @@ def _assert_chains(res, P, min_cnt, min_sc, off, a, what):
 def epi_path(request):
     """the two forms of the device epilogue: tasks that fit the LDS in the fused kernel (default), or kernels A / B / C for every task"""
     import mm2chain
-    mm2chain.tune("epi_fused", request.param)
-    yield request.param
-    mm2chain.tune("epi_fused", 1)
+    with mm2chain.tuned(epi_fused=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("epilogue_threads", [0, 1, 5])
@@ -739,13 +726,10 @@ def test_batched_mm_chain_dp_pipelined_in_chunks():
     off, a = _mixed_batch_with_gaps()
     from mm2chain import _native as N
     st0, st1 = N.Stats(), N.Stats()
-    mm2chain.tune("pipeline_chunk_anchors", 6000)
-    try:
+    with mm2chain.tuned(pipeline_chunk_anchors=6000):
         mm2chain.load().mm2c_get_stats(C.byref(st0))
         res = mm2chain.mm_chain_dp_batch(P, 3, 40, off, a, epilogue_threads=0)
         mm2chain.load().mm2c_get_stats(C.byref(st1))
-    finally:
-        mm2chain.tune("pipeline_chunk_anchors", 20 << 20)
     assert st1.passes - st0.passes > 8, "the batch was not cut into chunks"
     assert _assert_chains(res, P, 3, 40, off, a, "chunked") > 40
 
@@ -944,23 +928,6 @@ def test_hip_equals_the_references_own_device_kernel(knobs):
         # and the stock CPU semantics (V1) restricted to what V2 can express: same vectors
         f, p = gpu_batch(params.make_params(mdx, mdy, bw, max_skip=INT32_MAX, max_iter=1024), off, a)
         assert_same(f, p, f_ref, p_ref, off, f"plan with V1 kernel, max_skip = inf, max_iter = 1024, {(mdx, mdy, bw)}")
-
-
-@pytest.fixture
-def knobs():
-    """tuning knobs a test changes, put back afterwards (results never depend on them; the instantiation that runs does)"""
-    import mm2chain
-    import helpers
-
-    def tune(key, val):
-        if key == "coop_plans":
-            helpers.PINNED_ROUTE = val                        # (gpu_batch then runs the input once, as pinned, instead of on both routes)
-        return mm2chain.tune(key, val)
-    yield tune
-    helpers.PINNED_ROUTE = None
-    for key, val in (("ring_class", int(os.environ.get("MM2C_RING_CLASS", "3"))), ("far_ring", int(os.environ.get("MM2C_FAR_RING", "1"))), ("force_tab", 0), ("noskip_loop", 1), ("compact_ring", 1), ("wide_share_threshold", 40), ("split_streams", 1),
-                     ("plan_cut", 1), ("plan_cut_min", 8192), ("seg_min", 256), ("coop_plans", 2), ("coop_waves", 16), ("coop_w8_above", 256), ("fuse_st", 1), ("single_launch", 1), ("coop_max_tasks", 1024), ("q24_ring", 1)):
-        mm2chain.tune(key, val)
 
 
 @pytest.mark.parametrize("route", ["asm", "asm-32-bit-ring", "asm-tab", "asm-tab-32-bit-ring", "asm-short-ring-only", "asm-long-ring-only", "asm-device-cut", "wave-256", "wave-512", "wave-1024",
@@ -1191,15 +1158,12 @@ def test_big_host_batch_is_pipelined_in_chunks():
     off, a = _stream("mixed", 700, (2000, 5000), seed=71)
     assert a.shape[0] > (1 << 21)
     f_ref, p_ref = oracle_batch(P, off, a)
-    mm2chain.tune("pipeline_chunk_anchors", 300000)          # force the chunked two-stream path at this size
-    try:
+    with mm2chain.tuned(pipeline_chunk_anchors=300000):      # force the chunked two-stream path at this size
         f, p = mm2chain.chain_batch_host(P, off, a)          # (chunks of about 85 pieces: the default route gives each piece sixteen waves)
         assert_same(f, p, f_ref, p_ref, off, "big pageable batch, pipelined, default route")
         assert "chain_dp_coop" in mm2chain.last_host_variant(), mm2chain.last_host_variant()
-        mm2chain.tune("coop_plans", 0); mm2chain.tune("pipe_coop_chunks", 0)
-        f, p = mm2chain.chain_batch_host(P, off, a)
-    finally:
-        mm2chain.tune("pipeline_chunk_anchors", 20 << 20); mm2chain.tune("coop_plans", 2); mm2chain.tune("pipe_coop_chunks", 1)
+        with mm2chain.tuned(coop_plans=0, pipe_coop_chunks=0):
+            f, p = mm2chain.chain_batch_host(P, off, a)
     assert_same(f, p, f_ref, p_ref, off, "big pageable batch, pipelined")
     if mm2chain.device_count() == 1:                         # (with MM2C_DEVICES naming several slots the batch is split first and its parts are too small for the pipeline)
         assert "compact=1" in mm2chain.last_host_variant() and "loop=asm" in mm2chain.last_host_variant(), mm2chain.last_host_variant()   # the chunks have the prepass classes

@@ -16,7 +16,6 @@ from helpers import assert_same, oracle_batch
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_sketch.npz")
 N_LIVE = sum(n > 0 for n in rd.SIZES)      # the cut makes no piece of a task without anchors
-KNOBS = (("packed_fp", 1), ("coop_plans", 2), ("plan_cut", 1), ("plan_cut_min", 8192), ("seg_min", 256), ("compact_ring", 1), ("seg_prepass", 1))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -30,10 +29,9 @@ def _init():
 
 @pytest.fixture
 def knobs():
-    import mm2chain
-    yield mm2chain.tune
-    for key, val in KNOBS:
-        mm2chain.tune(key, val)
+    from helpers import knob_setter
+    with knob_setter() as tune:
+        yield tune
 
 
 _CHAINS = {}

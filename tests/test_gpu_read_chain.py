@@ -10,6 +10,7 @@ import torch
 
 import oracle_binding as ob
 import sketch_model as sm
+from helpers import knobs  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_sketch.npz")
@@ -28,8 +29,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("heap_sort", 0)
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -103,20 +102,20 @@ def test_read_chain_ava_ont_skip(fx):
     _compare(fx, "ava_ont", params.ava_ont(), skip=skip, skip_arrays=arrays)
 
 
-def test_read_chain_heap_sort(fx):
+def test_read_chain_heap_sort(fx, knobs):
     import mm2chain
     from mm2chain import params
-    mm2chain.tune("heap_sort", 1)
+    knobs("heap_sort", 1)
     _compare(fx, "map_ont", params.map_ont(), heap=True)
     skip, arrays = _skip(fx, "ava_ont", np.random.default_rng(10))
     _compare(fx, "ava_ont", params.ava_ont(), skip=skip, skip_arrays=arrays, heap=True)
 
 
-def test_read_chain_several_chunks(fx):
+def test_read_chain_several_chunks(fx, knobs):
     import mm2chain
     from mm2chain import params
     before = mm2chain.sketch_stats()
-    mm2chain.tune("read_chunk_bases", 20000)
+    knobs("read_chunk_bases", 20000)
     _compare(fx, "map_ont", params.map_ont(), check_oracle=False)
     skip, arrays = _skip(fx, "ava_ont", np.random.default_rng(11))
     _compare(fx, "ava_ont", params.ava_ont(), skip=skip, skip_arrays=arrays, check_oracle=False)

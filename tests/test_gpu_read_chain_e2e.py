@@ -12,6 +12,7 @@ import torch
 import index_model as im
 import oracle_binding as ob
 import sketch_model as sm
+from helpers import knobs  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 MIN_CNT, MIN_SC = 3, 40
@@ -27,7 +28,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -216,10 +216,10 @@ def _compare_matches(sm_, ref, what):
 
 def _run(cpu, mid_occ, skip=None, chunk_bases=1 << 27, idx=None):
     import mm2chain
-    mm2chain.tune("read_chunk_bases", int(chunk_bases))
-    before = mm2chain.sketch_stats()["chunks"]
-    got = mm2chain.read_chain_batch(cpu.P, MIN_CNT, MIN_SC, cpu.reads, idx, mid_occ, skip=skip)
-    n_chunks = mm2chain.sketch_stats()["chunks"] - before
+    with mm2chain.tuned(read_chunk_bases=int(chunk_bases)):
+        before = mm2chain.sketch_stats()["chunks"]
+        got = mm2chain.read_chain_batch(cpu.P, MIN_CNT, MIN_SC, cpu.reads, idx, mid_occ, skip=skip)
+        n_chunks = mm2chain.sketch_stats()["chunks"] - before
     assert n_chunks == len(_chunks(cpu.reads, chunk_bases)), f"chunk_bases {chunk_bases}: {n_chunks} chunks, the host's rule gives {len(_chunks(cpu.reads, chunk_bases))}"
     return got
 
@@ -319,13 +319,13 @@ def test_mid_occ_corners(presets):
     idx.close(); pool.close()
 
 
-def test_batches_with_nothing_to_map(presets):
+def test_batches_with_nothing_to_map(presets, knobs):
     import mm2chain
     cpu = presets["map_ont"]
     pool, idx = cpu.gpu_index()
     for reads in ([], [b"", b"N" * 5000, b"", b"nnnnNNNN", b""]):
         for cb in (1 << 27, 1):
-            mm2chain.tune("read_chunk_bases", cb)
+            knobs("read_chunk_bases", cb)
             got = mm2chain.read_chain_batch(cpu.P, MIN_CNT, MIN_SC, reads, idx, cpu.mid_occ)
             for k in ("anchor_off", "u_off", "b_off", "mini_off"):
                 assert got[k].size == len(reads) + 1 and not got[k].any(), (len(reads), k)

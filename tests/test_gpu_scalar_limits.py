@@ -10,7 +10,7 @@ import torch
 
 import limit_data as ld
 import oracle_binding as ob
-from helpers import assert_same, gpu_batch, oracle_batch
+from helpers import assert_same, gpu_batch, knobs, oracle_batch  # noqa: F401 (knobs: a fixture)
 from reuse_data import batch
 
 pytestmark = pytest.mark.gpu
@@ -23,23 +23,6 @@ def _init():
     mm2chain.init()
     yield
     mm2chain.shutdown()
-
-
-@pytest.fixture
-def knobs():
-    """tuning knobs a test changes, put back afterwards (results never depend on them; the instantiation that runs does)"""
-    import helpers
-    import mm2chain
-
-    def tune(key, val):
-        if key == "coop_plans":
-            helpers.PINNED_ROUTE = val
-        return mm2chain.tune(key, val)
-    yield tune
-    helpers.PINNED_ROUTE = None
-    for key, val in (("ring_class", 3), ("far_ring", 1), ("compact_ring", 1), ("wide_share_threshold", 40), ("coop_plans", 2), ("coop_waves", 16), ("coop_w8_above", 256),
-                     ("q24_ring", 1), ("packed_fp", 1)):
-        mm2chain.tune(key, val)
 
 
 _CASES = {}
@@ -185,9 +168,8 @@ def test_gap_cost_table_at_its_last_entry_and_largest_scale(bw, gap_scale, knobs
 @pytest.fixture(params=[3, 4], ids=["general-in-wave-kernel", "general-in-tile-kernel"])
 def general_kernel(request):
     import mm2chain
-    mm2chain.tune("ring_class", request.param)
-    yield request.param
-    mm2chain.tune("ring_class", 3)
+    with mm2chain.tuned(ring_class=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("preset", ["splice", "sr"])

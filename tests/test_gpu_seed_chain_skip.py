@@ -114,17 +114,14 @@ def test_all_vs_all_pipelined_in_chunks(mode):
         ref_anchors = [ref_anchors[k] for k in order]
     skip = mm2chain.SeedSkip(int(d["flag"]), d["ref_rank"], d["ref_len"], q_lo, q_eq)
     total = int(_capacity(mo, m)[-1])
-    mm2chain.tune("pipeline_chunk_anchors", max(1024, total // 14))
     mm2chain.stage_stats(reset=True)
-    try:
+    with mm2chain.tuned(pipeline_chunk_anchors=max(1024, total // 14)):
         if mode == "resident-pool":
             pool = mm2chain.HitPool(h)
             out = [mm2chain.seed_chain_batch_pool_skip(P, min_cnt, min_sc, mo, m, pool, ql, skip) for _ in range(2)]
             pool.close()
         else:
             out = [mm2chain.seed_chain_batch_skip(P, min_cnt, min_sc, mo, m, h, ql, skip) for _ in range(2)]
-    finally:
-        mm2chain.tune("pipeline_chunk_anchors", 20 << 20)
     st = mm2chain.stage_stats()
     assert st["calls"] == 2 and st["chunks"] >= 20 and st["seed_ns"] > 0 and st["dp_ns"] > 0 and st["epi_ns"] > 0 and st["total_ns"] > 0, st
     kept = np.array([r.shape[0] for r in ref_anchors])
@@ -241,12 +238,9 @@ def test_heap_sort_with_skip_seed_through_the_host_entries():
     q_lo = np.array([2, 0, 1], np.int32); q_eq = np.array([1, 1, 0], np.int32)
     skip = mm2chain.SeedSkip(AVA, ref_rank, ref_len, q_lo, q_eq)
     P = params.map_ont()
-    mm2chain.tune("heap_sort", 1)
-    try:
+    with mm2chain.tuned(heap_sort=1):
         ao, a = mm2chain.seed_hits_batch_skip(mo, m, h, ql, skip)
         ao2, res = mm2chain.seed_chain_batch_skip(P, 3, 40, mo, m, h, ql, skip)
-    finally:
-        mm2chain.tune("heap_sort", 0)
     n_ties = 0
     for k, (qlen, mr, hr) in enumerate(reads):
         ref = ob.collect_seed_hits(mr, hr, qlen, AVA, ref_rank, ref_len, int(q_lo[k]), int(q_eq[k]), heap=True)
@@ -326,10 +320,9 @@ def test_split_across_two_device_contexts_equals_one():
     mm2chain.init_devices([0, 0])
     try:
         assert mm2chain.device_count() == 2
-        mm2chain.tune("multi_min_anchors", 1000)
-        ao2, res2 = mm2chain.seed_chain_batch_skip(P, min_cnt, min_sc, mo, m, h, ql, skip)
+        with mm2chain.tuned(multi_min_anchors=1000):
+            ao2, res2 = mm2chain.seed_chain_batch_skip(P, min_cnt, min_sc, mo, m, h, ql, skip)
     finally:
-        mm2chain.tune("multi_min_anchors", 1 << 20)
         mm2chain.shutdown()
         mm2chain.init(0)
     ao1, res1 = mm2chain.seed_chain_batch_skip(P, min_cnt, min_sc, mo, m, h, ql, skip)

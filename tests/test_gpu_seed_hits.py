@@ -285,9 +285,8 @@ def test_matches_in_chains_out_pipelined_in_chunks(mode):
         reads = [reads[k] for k in order]
     P = params.map_ont()
     total = sum(int(r[1]["n"].sum()) for r in reads)
-    mm2chain.tune("pipeline_chunk_anchors", max(1024, total // 7))
     mm2chain.stage_stats(reset=True)
-    try:
+    with mm2chain.tuned(pipeline_chunk_anchors=max(1024, total // 7)):
         if mode == "resident-pool":
             pool = mm2chain.HitPool(h)
             res = mm2chain.seed_chain_batch_pool(P, 3, 40, mo, m, pool, ql)
@@ -296,8 +295,6 @@ def test_matches_in_chains_out_pipelined_in_chunks(mode):
         else:
             res = mm2chain.seed_chain_batch(P, 3, 40, mo, m, h, ql)
             res2 = mm2chain.seed_chain_batch(P, 3, 40, mo, m, h, ql)
-    finally:
-        mm2chain.tune("pipeline_chunk_anchors", 20 << 20)
     st = mm2chain.stage_stats()
     assert st["calls"] == 2 and st["chunks"] >= 10 and st["seed_ns"] > 0 and st["dp_ns"] > 0 and st["epi_ns"] > 0 and st["total_ns"] > 0, st
     for k, r in enumerate(reads):
@@ -453,11 +450,8 @@ def test_heap_sort_through_the_host_batch_entry():
     d, hp = np.load(os.path.join(GOLDEN, "ref_seed_hits.npz")), np.load(os.path.join(GOLDEN, "ref_seed_hits_heap.npz"))
     reads = [(int(d[f"r{k}_qlen"]), d[f"r{k}_matches"], d[f"r{k}_hits"]) for k in range(int(d["n_reads"]))]
     mo, m, h, ql = _batch(reads)
-    mm2chain.tune("heap_sort", 1)
-    try:
+    with mm2chain.tuned(heap_sort=1):
         ao, a = mm2chain.seed_hits_batch(mo, m, h, ql)
-    finally:
-        mm2chain.tune("heap_sort", 0)
     for k in range(len(reads)):
         assert np.array_equal(a[ao[k]:ao[k + 1]], hp[f"r{k}_anchors_heap"]), k
     ao, a = mm2chain.seed_hits_batch(mo, m, h, ql)

@@ -314,12 +314,11 @@ def test_pairs_of_mixed_lengths_from_reads_to_final_segment_regions():
     hp = [int(v) for v in fx["par"][ids[0]]]
     par = params.make_params(max_dist_x=1, max_dist_y=1, bw=hp[2], max_skip=hp[3], max_iter=hp[4], gap_scale=1.0, is_cdna=hp[7], n_segs=hp[8])
     idx = mm2chain.MinimizerIndex(int(fx["k"]), int(fx["w"]), False, fx["keys"], fx["cr_off"], fx["n"], pool=mm2chain.HitPool(fx["pool"]))
-    mm2chain.tune("heap_sort", 1)
     try:
-        got = mm2chain.frag_chain_batch_gaps(par, hp[5], hp[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]),
-                                             mm2chain.frag_gaps(*(int(v) for v in fx["gaps"])))
+        with mm2chain.tuned(heap_sort=1):
+            got = mm2chain.frag_chain_batch_gaps(par, hp[5], hp[6], frags, idx, int(fx["mid_occ"]), int(fx["max_occ"]),
+                                                 mm2chain.frag_gaps(*(int(v) for v in fx["gaps"])))
     finally:
-        mm2chain.tune("heap_sort", 0)
         idx.close()
     qlens = np.array([[len(s) for s in f] for f in frags], np.int32)
     gap_ref = got["task_dists"][:, 0].astype(np.int32)

@@ -10,7 +10,7 @@ import frag_model as fm
 import index_model as im
 import sketch_limit_data as sd
 import sketch_model as sm
-from helpers import assert_table
+from helpers import assert_table, knob_setter, knobs  # noqa: F401 (knobs: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,8 +29,6 @@ def _init():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     mm2chain.init()
     yield
-    mm2chain.tune("index_chunk_bases", 1 << 27)
-    mm2chain.tune("read_chunk_bases", 1 << 27)
     mm2chain.shutdown()
 
 
@@ -148,7 +146,7 @@ def test_lookups_equal_the_model(name):
         idx.close()
 
 
-def test_a_neighbour_in_another_chunk_changes_nothing():
+def test_a_neighbour_in_another_chunk_changes_nothing(knobs):
     """[r, r, r[:len//2], r]: the last minimizer of a read and the first of the next share their key.  read_chain_batch cut between them (read_chunk_bases = one read,
     then two reads) gives the offsets, rep_len, mini_pos and chains of the uncut call, and the model's"""
     import mm2chain
@@ -161,13 +159,12 @@ def test_a_neighbour_in_another_chunk_changes_nothing():
     out = {}
     try:
         for lim in (1 << 27, one, 2 * one):
-            mm2chain.tune("read_chunk_bases", lim)
+            knobs("read_chunk_bases", lim)
             mm2chain.sketch_stats(reset=True)
             out[lim] = mm2chain.read_chain_batch(params.map_ont(), 3, 40, c["reads"], idx, c["mid_occ"])
             chunks = mm2chain.sketch_stats()["chunks"]
             assert (chunks == 1) if lim == 1 << 27 else (chunks >= 3), f"read_chunk_bases {lim}: {chunks} chunks"
     finally:
-        mm2chain.tune("read_chunk_bases", 1 << 27)
         idx.close()
     for lim, got in out.items():
         for key in ("anchor_off", "mini_off", "rep_len", "mini_pos"):
@@ -216,12 +213,10 @@ def test_chunking_of_65537_sequences_does_not_change_the_index():
     ref = im.build_from_minimizers(sd.list_minimizers(65_537, S))
     lens = [len(s) for s in seqs]
     out = {}
-    try:
+    with knob_setter() as tune:
         for name, lim in sd.CHUNKINGS:
-            mm2chain.tune("index_chunk_bases", lim)
+            tune("index_chunk_bases", lim)
             out[name] = _check_build(seqs, S, ref, f"65 537 sequences, {name}", n_chunks=len(sd.chunks(lens, lim)))
-    finally:
-        mm2chain.tune("index_chunk_bases", 1 << 27)
     for name, got in out.items():
         for a, b in zip(got, out["default"]):
             assert np.array_equal(a, b), f"{name}: the export differs from the one-chunk build"

@@ -183,15 +183,12 @@ def test_a_plan_never_given_distances_runs_what_it_ran():
     P = params.map_ont()
     off, a = synth.make_stream("mixed", 64, 2000, seed=1, device="cuda")
     f = torch.empty(a.shape[0], dtype=torch.int32, device="cuda"); p = torch.empty_like(f)
-    try:
-        mm2chain.tune("coop_plans", 0)
+    with mm2chain.tuned(coop_plans=0):
         plan = mm2chain.ChainPlan(P, off.numpy())
         plan.run(a, f, p)
         torch.cuda.synchronize()
         v = plan.last_variant()
         plan.close()
-    finally:
-        mm2chain.tune("coop_plans", 2)
     assert v.startswith("chain_dp_tile<") and "GEN=0" in v and "loop=asm" in v and "compact=1" in v and "packed_fp=1" in v, v
     f_ref, p_ref, _ = ob.chain_batch(P, off.numpy(), a.cpu().numpy().view(np.uint64), 2)
     assert np.array_equal(f.cpu().numpy(), f_ref) and np.array_equal(p.cpu().numpy(), p_ref)

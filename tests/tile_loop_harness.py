@@ -13,6 +13,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import knobs  # noqa: F401 (a fixture, handed on to the modules that import this one's)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANT = os.path.join(ROOT, "minimap2-fpga_amd", "variants", "labelcount.so")
 LABEL_SKIP = 3            # max_skip of the label-counter case
@@ -42,21 +44,6 @@ def _init():
     mm2chain.init()
     yield
     mm2chain.shutdown()
-
-
-@pytest.fixture
-def knobs():
-    import helpers
-    import mm2chain
-
-    def tune(key, val):
-        if key == "coop_plans":
-            helpers.PINNED_ROUTE = val
-        return mm2chain.tune(key, val)
-    yield tune
-    helpers.PINNED_ROUTE = None
-    for key, val in (("score_bound_exit", 1), ("compact_ring", 1), ("packed_fp", 1), ("far_ring", 1), ("coop_plans", 2)):
-        mm2chain.tune(key, val)
 
 
 def ref(refs, key, P, tasks):
