@@ -744,7 +744,7 @@ int mm2c_align_tasks_batch_host(const mm2c_aln_opt_t *opt, int64_t n_seq, const 
  * 0 when the region is not split; has_p: r->p is set); the appended CIGARs in d_cig_out at cig0; and, dense and in region order for the regions that have words,
  * d_in_off[k], d_extra_tasks[k] and d_extra_reg[k] (the region of entry k), which mm2c_extraplan_run_device takes unchanged with d_cig_out as its cig_in;
  * d_in_off[n] is the number of words.  A region with cnt == 0 (:578) comes back with status 0, r_qs / r_qe / rs1 / re1 as the region has them and everything else 0.
- * mm_split_reg itself stays with the host (its score is float arithmetic), as do mm_align1_inv, ksw_ll_i16, ksw_extz2_sse and splice.
+ * mm_split_reg itself is the finish plan's (mm2c_finplan_apply_run_device, below); mm_align1_inv, ksw_ll_i16, ksw_extz2_sse and splice stay with the host.
  * status (only the status word of such a region is written; its neighbours are exact): MM2C_CIG_REFUSED (counted, MM2C_E_ARG) -- an mm2c_aln_reg_t whose status is
  * not 0; on a consumed item a code outside 0 .. 2, a z-drop record whose status is not 0, a second pass where the code is 0; item, task or CIGAR offsets leaving a
  * capacity; an appended CIGAR whose op lengths do not add up to qe1 - qs1 and re1 - rs1 (:284); qs1 < 0, rs1 < 0, qe1 > qlen or re1 - rs1 > re0 - rs0 (:707, 779, 785).
@@ -795,6 +795,77 @@ int mm2c_assemble_regions_batch_host(const mm2c_cig_opt_t *opt, int64_t n_reads,
                                      const mm2c_ksw_res_t *res, const uint32_t *cigar, const mm2c_zdrop_res_t *zres, const int32_t *second_of, int64_t n_tasks2,
                                      const int64_t *cig_off2, const mm2c_ksw_res_t *res2, const uint32_t *cigar2, mm2c_cig_reg_t *cig_regs, int64_t words_cap, uint32_t *cig_out,
                                      int64_t n_extra_cap, int64_t *in_off, mm2c_extra_task_t *extra_tasks, int32_t *extra_reg, int64_t totals[2]);
+
+/* ---- aligned regions -> final hits on the GPU: what mm_align1 leaves in r with mm_split_reg (align.c:757-760, 781-783; hit.c:108-123), then
+ * mm_filter_regs and mm_hit_sort (align.c:917-918), mm_set_parent, mm_select_sub and mm_set_sam_pri (map.c:264-268) and mm_set_mapq (map.c:361) ----
+ * A stand-alone plan with two entries, byte for byte the reference's.  It is the only plan whose regions carry r->p: mm2c_pext_t stands for mm_extra_t without its
+ * CIGAR (ambi_strand: n_ambi:30 | trans_strand:2, as GCC lays out minimap.h:80; cig0: the first word of the region's final CIGAR in the extra plan's output), and in
+ * the regions this plan writes and reads mm2c_reg_t.p is 0 for r->p == NULL, otherwise 1 + the index of the region's mm2c_pext_t in the batch.
+ *
+ * mm2c_finplan_apply_run_device (kernels fin_apply, fin_slots, fin_children).  In, exactly as the producing plans leave them: d_u_off / d_regs (the regions that went
+ * into the alignment-task plan; d_u_off[0] == 0), d_b_off / d_b, d_read_off (for qlen), d_cig_regs of mm2c_cigplan_run_device, and n_extra, d_extra_reg, d_extra_res and
+ * the output offsets d_out_off of mm2c_extraplan_run_device.  Out: d_regs_out[g], the region as mm_align1 returns it -- rs = rs1 + tshift, re = re1, qs / qe from
+ * r_qs / r_qe with qshift on the side the extra plan names, blen, mlen from the extra result, p = g + 1; of a split region also cnt -= r2->cnt, score -= r2->score,
+ * split |= 1 -- and d_pext[g] (dp_score, n_cigar, dp_max, n_ambi from the two records, dp_max2 = 0, trans_strand = 0, cig0 = d_out_off[k]); a region with has_p == 0
+ * keeps p = 0 and gets the coordinates only (its d_pext[g] is zero).  The children r2 of mm_split_reg come dense and in region order: d_child[k], d_child_of[k] (the
+ * region it was split from), *d_n_child of them.  r2 is *r as it stood in the middle of mm_align1 -- chain-level hash, div, subsc, the split bits before |= 1 -- with
+ * id = -1, sam_pri = 0, p = 0, cnt = r->cnt - n, score = (int32_t)(r->score * ((float)r2->cnt / r->cnt) + .499) (a float quotient, a float product, a double add),
+ * as += n, parent = MM_PARENT_TMP_PRI iff r->parent == r->id, mm_reg_set_coor over its own anchors (coordinates, rid, rev, mlen, blen), split |= 2 and
+ * split_inv as the CIGAR-join plan decided it (zdrop_code == 2).  The order of the children across alignment rounds (mm_insert_reg: a child directly behind its
+ * parent) is index arithmetic on d_child_of and stays with the caller.
+ * d_status[g]: 0, or -- only the status word of such a region is written, its neighbours are exact -- MM2C_FIN_REFUSED (counted, MM2C_E_ARG from _apply_check): an
+ * mm2c_cig_reg_t or extra result with status 1, has_p without an extra entry, a region outside d_u_off, read extents that leave n_b_cap, a child whose anchors leave
+ * the read's; MM2C_FIN_INCOMPLETE (counted, MM2C_E_TOOBIG): any other status in front.  MM2C_FIN_OVER_CAP (counted, MM2C_E_TOOBIG): the region's child lies beyond
+ * n_child_cap; the region itself is written, the child is not, nothing is written behind the capacity and *d_n_child says what the batch takes.
+ *
+ * mm2c_finplan_run_device (kernel fin_select, one wave per read).  The regions of read r are d_regs_in[f_off[r] .. f_off[r] + d_n_in[r]) in the order
+ * mm_align_skeleton holds them behind its loop, every child directly behind its parent, in room for f_off[r+1] - f_off[r]; d_qlen and d_rep_len per read.  The first
+ * d_n_out[r] entries of d_regs_out from f_off[r] on are, byte for byte, the reference's array behind map.c:361; dp_max2 of the surviving regions is updated in d_pext
+ * in place and the p of every surviving region still names its record (a dropped region's record is simply no longer named).  With all_chains (MM_F_ALL_CHAINS) the
+ * three calls of map.c:265-267 are skipped.  The logarithms: two tables the HOST fills at creation with its own logf, L[i] = logf((float)i) and
+ * L2[i] = logf((float)i / match_sc), 0 <= i <= max_log_arg; a primary whose dp_max (with p), score (without) or n_sub + 1 lies beyond them gets mapq 0 and is
+ * counted (MM2C_E_TOOBIG from _check); nothing else changes.  min_dp_max < 1 or match_sc < 1 is MM2C_E_ARG: every surviving dp_max is then >= 1 and logf never sees 0.
+ * Refused and counted per read (MM2C_E_ARG from _check; nothing of that read is written, d_n_out[r] included, and its neighbours are exact): a region with inv or
+ * is_alt set (mm_align1_inv, ALT contigs, mm_set_inv_mapq and mm_alt_score are not built: nothing the device can make today sets them, and alt_drop has no counterpart
+ * in the options); offsets or d_n_in that leave the capacities or each other; a p that names no record; a read of more than one region that mixes kept regions with
+ * and without p, or keeps none with cnt > 0 (the reference asserts there, hit.c:210).  Reads of up to MM2C_FIN_LDS_REGIONS regions are worked in on-chip memory,
+ * longer ones in the plan's scratch.  d_regs_out must not alias d_regs_in; regions and records 8-byte, anchors 16-byte aligned.  Both entries are asynchronous on
+ * `stream`.  Still the host's: mm_align1_inv with ksw_ll_i16, the interleave across alignment rounds, mm_pair, ALT contigs, splice. */
+typedef struct { int32_t dp_score, dp_max, dp_max2; uint32_t ambi_strand; int32_t n_cigar, reserved; int64_t cig0; } mm2c_pext_t;
+typedef struct {
+	int32_t min_cnt, min_chain_score, min_dp_max; float max_clip_ratio;    /* mm_filter_regs, hit.c:280-284 */
+	float mask_level; int32_t mask_len, hard_mask_level, sub_diff;         /* mm_set_parent; sub_diff = opt->a * 2 + opt->b (map.c:265) */
+	float pri_ratio; int32_t min_diff, best_n;                             /* mm_select_sub; min_diff = 2k */
+	int32_t match_sc, is_sr, all_chains;                                   /* mm_set_mapq's opt->a and is_sr; MM_F_ALL_CHAINS */
+} mm2c_fin_opt_t;
+#define MM2C_FIN_LDS_REGIONS 128
+#define MM2C_FIN_REFUSED 1
+#define MM2C_FIN_INCOMPLETE 2
+#define MM2C_FIN_OVER_CAP 3
+typedef struct mm2c_finplan mm2c_finplan_t;
+/* capacities: reads, regions (of either entry), mm2c_pext_t records; the tables' largest argument (at most MM2C_MAPQ_MAX_LOG_ARG) and opt->a */
+mm2c_finplan_t *mm2c_finplan_create(int64_t n_reads, int64_t n_u_cap, int64_t n_pext_cap, int32_t max_log_arg, int32_t match_sc);
+void mm2c_finplan_destroy(mm2c_finplan_t *plan);
+int mm2c_finplan_apply_run_device(mm2c_finplan_t *plan, int64_t n_reads, int64_t n_regs, const int64_t *d_u_off, const mm2c_reg_t *d_regs, const int64_t *d_b_off,
+                                  const void *d_b, int64_t n_b_cap, const int64_t *d_read_off, const mm2c_cig_reg_t *d_cig_regs, int64_t n_extra, const int32_t *d_extra_reg,
+                                  const mm2c_extra_res_t *d_extra_res, const int64_t *d_out_off, mm2c_reg_t *d_regs_out, mm2c_pext_t *d_pext, int32_t *d_status,
+                                  int64_t n_child_cap, mm2c_reg_t *d_child, int32_t *d_child_of, int64_t *d_n_child, void *stream);
+/* waits for the last apply run.  MM2C_E_ARG if a region was refused, else MM2C_E_TOOBIG if one was incomplete or a child lay beyond n_child_cap (all three counts
+ * are filled in either way; any pointer may be NULL) */
+int mm2c_finplan_apply_check(mm2c_finplan_t *plan, int64_t *n_refused, int64_t *n_incomplete, int64_t *n_child_beyond);
+int mm2c_finplan_run_device(mm2c_finplan_t *plan, const mm2c_fin_opt_t *opt, const int64_t *d_f_off, const mm2c_reg_t *d_regs_in, const int32_t *d_n_in, mm2c_pext_t *d_pext,
+                            const int32_t *d_qlen, const int32_t *d_rep_len, mm2c_reg_t *d_regs_out, int32_t *d_n_out, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a read was refused, else MM2C_E_TOOBIG if a primary lay beyond the tables.  *n_hits_total: the sum of n_out */
+int mm2c_finplan_check(mm2c_finplan_t *plan, int64_t *n_refused, int64_t *n_beyond_table, int64_t *n_hits_total);
+/* milliseconds of the last runs between HIP events on their streams: the three kernels of the apply entry, fin_select; 0 for an entry that has not run */
+int mm2c_finplan_last_ms(mm2c_finplan_t *plan, float *apply_ms, float *select_ms);
+/* host arrays in and out; argument and offset checks (MM2C_E_ARG) come before any device work; u_off[0] and b_off[0] must be 0.  What the run does not write stays the
+ * caller's; with MM2C_E_TOOBIG the outputs are complete all the same. */
+int mm2c_apply_regions_batch_host(int64_t n_reads, const int64_t *u_off, const mm2c_reg_t *regs, const int64_t *b_off, const mm2c_anchor_t *b, const int64_t *read_off,
+                                  const mm2c_cig_reg_t *cig_regs, int64_t n_extra, const int32_t *extra_reg, const mm2c_extra_res_t *extra_res, const int64_t *out_off,
+                                  mm2c_reg_t *regs_out, mm2c_pext_t *pext, int32_t *status, int64_t n_child_cap, mm2c_reg_t *child, int32_t *child_of, int64_t *n_child);
+int mm2c_finish_regions_batch_host(int64_t n_reads, const mm2c_fin_opt_t *opt, int32_t max_log_arg, const int64_t *f_off, const mm2c_reg_t *regs_in, const int32_t *n_in,
+                                   int64_t n_pext, mm2c_pext_t *pext, const int32_t *qlen, const int32_t *rep_len, mm2c_reg_t *regs_out, int32_t *n_out);
 
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits

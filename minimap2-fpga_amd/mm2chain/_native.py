@@ -93,6 +93,14 @@ class MapqOpt(C.Structure):
                 ("min_join_flank_ratio", C.c_float), ("min_cnt", C.c_int32), ("min_chain_score", C.c_int32)]
 
 
+class FinOpt(C.Structure):
+    """mm2c_fin_opt_t: mm_filter_regs' min_cnt, min_chain_score, min_dp_max, max_clip_ratio; mm_set_parent's mask_level, mask_len, MM_F_HARD_MLEVEL, sub_diff (a * 2 + b);
+    mm_select_sub's pri_ratio, min_diff (2k), best_n; mm_set_mapq's match_sc (opt->a) and is_sr; MM_F_ALL_CHAINS"""
+    _fields_ = [("min_cnt", C.c_int32), ("min_chain_score", C.c_int32), ("min_dp_max", C.c_int32), ("max_clip_ratio", C.c_float), ("mask_level", C.c_float),
+                ("mask_len", C.c_int32), ("hard_mask_level", C.c_int32), ("sub_diff", C.c_int32), ("pri_ratio", C.c_float), ("min_diff", C.c_int32), ("best_n", C.c_int32),
+                ("match_sc", C.c_int32), ("is_sr", C.c_int32), ("all_chains", C.c_int32)]
+
+
 class Err(C.Structure):
     """mm2c_err_t: the counts of mm_est_err per final region (esterr.c:53-61); n_match 0: div = -1, n_match -1: the read has no mini_pos"""
     _fields_ = [("n_match", C.c_int32), ("n_tot", C.c_int32)]
@@ -105,6 +113,7 @@ MM2C_MAX_SEG = 255
 MM2C_REG_SEG_SPLIT_BIT = 15
 MM2C_REG_SEG_ID_SHIFT = 16
 MM2C_SEED_LONG_JOIN_BIT = 40
+MM2C_FIN_LDS_REGIONS = 128
 
 C_SYMBOLS = {
     "mm2c_init": (C.c_int, [C.c_int]),
@@ -231,6 +240,16 @@ C_SYMBOLS = {
     "mm2c_mapqplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mm2c_mapqplan_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mm2c_join_mapq_batch_host": (C.c_int, [C.c_int64, C.POINTER(MapqOpt), C.c_int32] + [C.c_void_p] * 11),
+    "mm2c_finplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "mm2c_finplan_destroy": (None, [C.c_void_p]),
+    "mm2c_finplan_apply_run_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 +
+                                      [C.c_int64] + [C.c_void_p] * 4),
+    "mm2c_finplan_apply_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_finplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(FinOpt)] + [C.c_void_p] * 9),
+    "mm2c_finplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_finplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mm2c_apply_regions_batch_host": (C.c_int, [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 3),
+    "mm2c_finish_regions_batch_host": (C.c_int, [C.c_int64, C.POINTER(FinOpt), C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 5),
     "mm2c_errplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mm2c_errplan_destroy": (None, [C.c_void_p]),
     "mm2c_errplan_run_device": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] + [C.c_void_p] * 4),

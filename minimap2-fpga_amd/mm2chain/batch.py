@@ -1242,6 +1242,189 @@ def join_mapq_batch(opt, u_off, regs, n_in, b_off, b, qlen, rep_len, anchors=Tru
     return out[:n_u], n_out[:n_reads], (b_out[:n_b] if anchors else None), (n_b_out[:n_reads] if anchors else None)
 
 
+PEXT_DTYPE = np.dtype([("dp_score", "<i4"), ("dp_max", "<i4"), ("dp_max2", "<i4"), ("ambi_strand", "<u4"), ("n_cigar", "<i4"), ("reserved", "<i4"), ("cig0", "<i8")])   # mm2c_pext_t
+FIN_REFUSED, FIN_INCOMPLETE, FIN_OVER_CAP = 1, 2, 3
+
+
+class FinPlan(_Handle):
+    """mm2c_finplan_t: aligned regions -> final hits on the GPU for batches of up to n_reads reads, n_u_cap regions and n_pext_cap mm2c_pext_t records.  apply():
+    what mm_align1 leaves in a region, with mm_split_reg (align.c:757-760, 781-783; hit.c:108-123).  run(): mm_filter_regs, mm_hit_sort, mm_set_parent, mm_select_sub,
+    mm_set_sam_pri and mm_set_mapq (align.c:917-918, map.c:264-268, 361).  max_log_arg: the largest dp_max, score and n_sub + 1 whose logf the plan's two tables hold
+    -- the host's own logf, filled at creation; match_sc: opt->a, the divisor of the second table."""
+
+    _destroy = "mm2c_finplan_destroy"
+
+    def __init__(self, n_reads, n_u_cap, n_pext_cap, max_log_arg=1 << 20, match_sc=2):
+        self.n_reads, self.n_u_cap, self.n_pext_cap, self.max_log_arg, self.match_sc = int(n_reads), int(n_u_cap), int(n_pext_cap), int(max_log_arg), int(match_sc)
+        self._create("mm2c_finplan_create", self.n_reads, self.n_u_cap, self.n_pext_cap, self.max_log_arg, self.match_sc, code=-2)
+
+    def apply(self, n_reads, n_regs, u_off: torch.Tensor, regs: torch.Tensor, b_off: torch.Tensor, b: torch.Tensor, read_off: torch.Tensor, cig_regs: torch.Tensor,
+              n_extra, extra_reg: torch.Tensor, extra_res: torch.Tensor, out_off: torch.Tensor, n_child_cap, regs_out: torch.Tensor = None, pext: torch.Tensor = None,
+              status: torch.Tensor = None, child: torch.Tensor = None, child_of: torch.Tensor = None, n_child: torch.Tensor = None, stream=None):
+        """u_off, regs, b_off, b, read_off as AlnPlan.run took them, cig_regs as CigPlan.join wrote them, extra_reg (CigPlan.join), extra_res and out_off (ExtraPlan.update)
+        of the first n_extra entries; all on the GPU.  Returns (regs_out uint8 [n_regs, 80], pext uint8 [n_regs, 32], status int32 [n_regs], child uint8
+        [n_child_cap, 80], child_of int32 [n_child_cap], n_child int64 [1]).  Asynchronous."""
+        n_reads, n_regs, n_extra, cap = int(n_reads), int(n_regs), int(n_extra), int(n_child_cap)
+        for t in (u_off, regs, b_off, b, read_off, cig_regs, extra_reg, extra_res, out_off):
+            assert t.is_cuda and t.is_contiguous()
+        assert u_off.dtype == torch.int64 and b_off.dtype == torch.int64 and read_off.dtype == torch.int64 and out_off.dtype == torch.int64 and extra_reg.dtype == torch.int32
+        assert u_off.numel() >= n_reads + 1 and b_off.numel() >= n_reads + 1 and read_off.numel() >= n_reads + 1 and out_off.numel() >= n_extra + 1 and extra_reg.numel() >= n_extra
+        assert regs.numel() * regs.element_size() >= n_regs * REG_DTYPE.itemsize and cig_regs.numel() * cig_regs.element_size() >= n_regs * CIG_REG_DTYPE.itemsize
+        assert extra_res.numel() * extra_res.element_size() >= n_extra * EXTRA_RES_DTYPE.itemsize and b.element_size() == 8
+        dev = u_off.device
+        regs_out = _out(regs_out, (max(n_regs, 1), REG_DTYPE.itemsize), torch.uint8, dev, n_regs * REG_DTYPE.itemsize)
+        pext = _out(pext, (max(n_regs, 1), PEXT_DTYPE.itemsize), torch.uint8, dev, n_regs * PEXT_DTYPE.itemsize)
+        status = _out(status, max(n_regs, 1), torch.int32, dev, n_regs * 4, "dtype")
+        child = _out(child, (max(cap, 1), REG_DTYPE.itemsize), torch.uint8, dev, cap * REG_DTYPE.itemsize)
+        child_of = _out(child_of, max(cap, 1), torch.int32, dev, cap * 4, "dtype")
+        n_child = _out(n_child, 1, torch.int64, dev, 8, "dtype")
+        N.check(self.lib.mm2c_finplan_apply_run_device(self.handle, n_reads, n_regs, u_off.data_ptr(), regs.data_ptr(), b_off.data_ptr(), b.data_ptr(), b.numel() // 2,
+                                                       read_off.data_ptr(), cig_regs.data_ptr(), n_extra, extra_reg.data_ptr(), extra_res.data_ptr(), out_off.data_ptr(),
+                                                       regs_out.data_ptr(), pext.data_ptr(), status.data_ptr(), cap, child.data_ptr(), child_of.data_ptr(), n_child.data_ptr(),
+                                                       _stream(stream)), "mm2c_finplan_apply_run_device")
+        return regs_out[:n_regs], pext[:n_regs], status[:n_regs], child[:cap], child_of[:cap], n_child
+
+    def run(self, opt, f_off: torch.Tensor, regs_in: torch.Tensor, n_in: torch.Tensor, pext: torch.Tensor, qlen: torch.Tensor, rep_len: torch.Tensor,
+            regs_out: torch.Tensor = None, n_out: torch.Tensor = None, stream=None):
+        """opt: params.fin_opts(); the regions of read r are rows f_off[r] .. f_off[r] + n_in[r] of regs_in, every child directly behind its parent; pext the
+        mm2c_pext_t records their p names (dp_max2 is updated in place); qlen and rep_len int32 per read; all on the GPU.  Returns (regs_out uint8 [n_u_cap, 80],
+        n_out int32 [n_reads]): the final hits of read r are rows f_off[r] .. f_off[r] + n_out[r].  Asynchronous."""
+        for t in (f_off, regs_in, n_in, pext, qlen, rep_len):
+            assert t.is_cuda and t.is_contiguous()
+        assert f_off.dtype == torch.int64 and f_off.numel() == self.n_reads + 1 and n_in.dtype == torch.int32 and n_in.numel() >= self.n_reads
+        assert regs_in.numel() * regs_in.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and pext.numel() * pext.element_size() >= self.n_pext_cap * PEXT_DTYPE.itemsize
+        assert qlen.dtype == torch.int32 and qlen.numel() == self.n_reads and rep_len.dtype == torch.int32 and rep_len.numel() == self.n_reads
+        dev = f_off.device
+        regs_out = _out(regs_out, (max(self.n_u_cap, 1), REG_DTYPE.itemsize), torch.uint8, dev, self.n_u_cap * REG_DTYPE.itemsize)
+        n_out = _out(n_out, max(self.n_reads, 1), torch.int32, dev, self.n_reads * 4, "dtype")
+        N.check(self.lib.mm2c_finplan_run_device(self.handle, C.byref(opt), f_off.data_ptr(), regs_in.data_ptr(), n_in.data_ptr(), pext.data_ptr(), qlen.data_ptr(),
+                                                 rep_len.data_ptr(), regs_out.data_ptr(), n_out.data_ptr(), _stream(stream)), "mm2c_finplan_run_device")
+        return regs_out, n_out[:self.n_reads]
+
+    def counts(self):
+        """waits for the last run() -> (return code, reads refused, primaries beyond the tables, final hits of all reads) without raising"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_finplan_check(self.handle, C.byref(a), C.byref(b), C.byref(c))
+        return rc, a.value, b.value, c.value
+
+    def apply_counts(self):
+        """waits for the last apply() -> (return code, regions refused, regions incomplete, children beyond n_child_cap) without raising"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_finplan_apply_check(self.handle, C.byref(a), C.byref(b), C.byref(c))
+        return rc, a.value, b.value, c.value
+
+    def check(self):
+        """waits for the last run(); raises if a read was refused (code -2) or a primary lay beyond the tables (code -3); returns the number of final hits"""
+        rc, _, _, n = self.counts()
+        N.check(rc, "mm2c_finplan_check")
+        return n
+
+    def apply_check(self):
+        rc = self.apply_counts()[0]
+        N.check(rc, "mm2c_finplan_apply_check")
+
+    def last_ms(self):
+        """(the apply entry's kernels, fin_select) of the last runs; 0 for an entry that has not run"""
+        return self._ms("mm2c_finplan_last_ms", 2)
+
+
+def apply_regions_batch(u_off, regs, b_off, b, read_off, cig_regs, extra_reg, extra_res, out_off, n_child_cap, fill=None):
+    """mm2c_apply_regions_batch_host: host arrays in -> dict(regs REG_DTYPE, pext PEXT_DTYPE, status int32, child REG_DTYPE [n_child_cap], child_of int32, n_child, rc);
+    rc is 0, -2 (a region refused) or -3 (a region incomplete, or children beyond n_child_cap): the rest is complete all the same.  Raises for any other failure, an argument
+    refused before the device ran included.  fill: a byte the outputs are filled with beforehand (tests)."""
+    lib = N.load()
+    uo = _i64(u_off); bo = _i64(b_off); ro = _i64(read_off); oo = _i64(out_off)
+    rg = np.ascontiguousarray(regs, dtype=REG_DTYPE); bb = _anchor_rows(b); cr = np.ascontiguousarray(cig_regs, dtype=CIG_REG_DTYPE)
+    xr = np.ascontiguousarray(extra_reg, dtype=np.int32); xe = np.ascontiguousarray(extra_res, dtype=EXTRA_RES_DTYPE)
+    n_reads = uo.size - 1
+    if bo.size != n_reads + 1 or ro.size != n_reads + 1:
+        raise ValueError("u_off, b_off and read_off must hold n_reads + 1 offsets")
+    n_regs = int(uo[-1]) if n_reads > 0 else 0
+    n_extra = xr.size
+    if rg.size < n_regs or cr.size < n_regs or (n_reads > 0 and bb.shape[0] < int(bo[-1])) or xe.size < n_extra or (n_extra > 0 and oo.size < n_extra + 1):
+        raise ValueError("an array is shorter than its offsets say")
+    f = 0 if fill is None else int(fill)
+    cap = int(n_child_cap)
+    out = np.full(max(n_regs, 1) * REG_DTYPE.itemsize, f, np.uint8).view(REG_DTYPE)
+    pext = np.full(max(n_regs, 1) * PEXT_DTYPE.itemsize, f, np.uint8).view(PEXT_DTYPE)
+    status = np.full(max(n_regs, 1) * 4, f, np.uint8).view(np.int32)
+    child = np.full(max(cap, 1) * REG_DTYPE.itemsize, f, np.uint8).view(REG_DTYPE)
+    child_of = np.full(max(cap, 1) * 4, f, np.uint8).view(np.int32)
+    n_child = np.zeros(1, np.int64)
+    rc = lib.mm2c_apply_regions_batch_host(n_reads, _np_ptr(uo), _np_ptr(rg), _np_ptr(bo), _np_ptr(bb), _np_ptr(ro), _np_ptr(cr), n_extra, _np_ptr(xr), _np_ptr(xe), _np_ptr(oo),
+                                           _np_ptr(out), _np_ptr(pext), _np_ptr(status), cap, _np_ptr(child), _np_ptr(child_of), _np_ptr(n_child))
+    if rc not in (0, -3) and not (rc == -2 and b"only their status is written" in (lib.mm2c_last_error() or b"")):
+        N.check(rc, "mm2c_apply_regions_batch_host")
+    return dict(regs=out[:n_regs], pext=pext[:n_regs], status=status[:n_regs], child=child[:cap], child_of=child_of[:cap], n_child=int(n_child[0]), rc=rc)
+
+
+def interleave_rounds(rounds):
+    """The order mm_align_skeleton holds a read's regions in behind its loop (mm_insert_reg, align.c:905: a child directly behind its parent, a grandchild behind the
+    child), from the outputs of FinPlan.apply / apply_regions_batch over the alignment rounds: index arithmetic on child_of, on the host.
+    rounds: one dict per round, in order: u_off (int64 [n_reads + 1]: the round's regions per read; round 0's are the reads' own, a later round's are the children of the
+    round before, in order), regs (REG_DTYPE [n]: as apply wrote them, p = index + 1 or 0), pext (PEXT_DTYPE [n]) and child_of (int32 [n_child]: the region of this
+    round every child was split from; absent or empty in the last round).  A region whose apply status is not 0 has no place in a list: the caller leaves such a
+    read out or mends it first.
+    -> (f_off int64 [n_reads + 1], regs REG_DTYPE, pext PEXT_DTYPE): the lists FinPlan.run / finish_regions_batch take (n_in = f_off[1:] - f_off[:-1]); pext is
+    the rounds' records one after another, and every p is 1 + its record's index there."""
+    if not rounds:
+        return np.zeros(1, np.int64), np.zeros(0, REG_DTYPE), np.zeros(0, PEXT_DTYPE)
+    R = [np.ascontiguousarray(r["regs"]).reshape(-1).view(REG_DTYPE) for r in rounds]
+    P = [np.ascontiguousarray(r["pext"]).reshape(-1).view(PEXT_DTYPE) for r in rounds]
+    base = np.concatenate([[0], np.cumsum([r.size for r in R])])
+    child = []                                                                 # per round: region -> its child in the next round, -1
+    for k, r in enumerate(rounds):
+        c = np.full(R[k].size, -1, np.int64)
+        of = np.asarray(r.get("child_of", ()), np.int64).reshape(-1)
+        if of.size:
+            if k + 1 >= len(rounds) or of.size != R[k + 1].size or (of < 0).any() or (of >= R[k].size).any() or (np.diff(of) <= 0).any():
+                raise ValueError(f"round {k}: child_of does not name the regions of round {k + 1} in ascending order")
+            c[of] = np.arange(of.size)
+        child.append(c)
+    u_off = _i64(rounds[0]["u_off"])
+    n_reads = u_off.size - 1
+    order, f_off = [], [0]
+    for rd in range(n_reads):
+        for g in range(int(u_off[rd]), int(u_off[rd + 1])):
+            k = 0
+            while g >= 0:
+                order.append(int(base[k]) + g)
+                g, k = int(child[k][g]), k + 1
+        f_off.append(len(order))
+    if len(order) != int(base[-1]):
+        raise ValueError("regions of a later round that no child_of names")
+    allr, order = np.concatenate(R), np.array(order, np.int64)
+    src_base = base[np.searchsorted(base, order, side="right") - 1]
+    out = allr[order].copy()
+    has = out["p"] != 0
+    out["p"][has] += src_base[has].astype(np.uint64)
+    return np.array(f_off, np.int64), out, np.concatenate(P)
+
+
+def finish_regions_batch(opt, f_off, regs, n_in, pext, qlen, rep_len, max_log_arg=1 << 20, fill=None):
+    """mm2c_finish_regions_batch_host: host arrays in -> dict(regs REG_DTYPE [f_off[-1] - f_off[0]], n_out int32 [n_reads], pext (a copy, dp_max2 updated), rc); the final
+    hits of read r are regs[f_off[r] - f_off[0] :][:n_out[r]].  rc is 0, -2 (a read refused on the device: nothing of it is written) or -3 (a primary beyond the
+    tables): the rest is complete all the same.  Raises for any other failure.  fill: a byte regs and n_out are filled with beforehand (tests)."""
+    lib = N.load()
+    fo = _i64(f_off)
+    rr = _reg_rows(regs)
+    ni = np.ascontiguousarray(n_in, dtype=np.int32); q = np.ascontiguousarray(qlen, dtype=np.int32); rl = np.ascontiguousarray(rep_len, dtype=np.int32)
+    px = np.array(pext, dtype=PEXT_DTYPE, copy=True).reshape(-1)
+    n_reads = fo.size - 1
+    if ni.size != n_reads or q.size != n_reads or rl.size != n_reads or not _fit(n_reads, (fo, rr.shape[0])):
+        raise ValueError("offsets do not fit the arrays")
+    n_u = int(fo[-1] - fo[0]) if n_reads > 0 else 0
+    f = 0 if fill is None else int(fill)
+    out = np.full(max(n_u, 1) * REG_DTYPE.itemsize, f, np.uint8).view(REG_DTYPE)
+    n_out = np.full(max(n_reads, 1) * 4, f, np.uint8).view(np.int32)
+    pp = px if px.size else np.zeros(1, PEXT_DTYPE)
+    rc = lib.mm2c_finish_regions_batch_host(n_reads, C.byref(opt), int(max_log_arg), _np_ptr(fo), _np_ptr(rr), _np_ptr(ni), px.size, _np_ptr(pp), _np_ptr(q), _np_ptr(rl),
+                                            _np_ptr(out), _np_ptr(n_out))
+    if rc not in (0, -3) and not (rc == -2 and b"refused, nothing of them written" in (lib.mm2c_last_error() or b"")):
+        N.check(rc, "mm2c_finish_regions_batch_host")
+    return dict(regs=out[:n_u], n_out=n_out[:n_reads], pext=px, rc=rc)
+
+
 ERR_DTYPE = np.dtype([("n_match", "<i4"), ("n_tot", "<i4")])                   # mm2c_err_t
 
 

@@ -1,5 +1,5 @@
 """Chaining parameter presets, mirroring options.c of the reference (file:line cited per preset)."""
-from ._native import Params, HitOpt, HitMultiOpt, MapqOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
+from ._native import Params, HitOpt, HitMultiOpt, MapqOpt, FinOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
 
 INT32_MAX = 2**31 - 1
 
@@ -70,6 +70,29 @@ def mapq_opts(**kw):
         raise TypeError(f"mapq_opts: unknown field(s) {sorted(unknown)}")
     v.update(kw)
     return MapqOpt(int(bool(v["do_join"])), v["max_join_long"], v["max_join_short"], v["min_join_flank_sc"], v["min_join_flank_ratio"], v["min_cnt"], v["min_chain_score"])
+
+
+FIN_PRESETS = {   # min_cnt, min_chain_score, min_dp_max, pri_ratio, best_n, a, b, k, is_sr, all_chains (options.c:24-25, 33-36, 45, 49, 52 and the presets of :82-151)
+    "map-ont": (3, 40, 80, 0.8, 5, 2, 4, 15, 0, 0), "map-pb": (3, 40, 80, 0.8, 5, 2, 4, 19, 0, 0), "ava-ont": (3, 100, 80, 0.0, 5, 2, 4, 15, 0, 1),
+    "ava-pb": (3, 100, 80, 0.0, 5, 2, 4, 19, 0, 1),
+    "asm5": (3, 40, 200, 0.8, 50, 1, 19, 19, 0, 0), "asm10": (3, 40, 200, 0.8, 50, 1, 9, 19, 0, 0), "asm20": (3, 40, 200, 0.8, 50, 1, 4, 19, 0, 0),
+    "sr": (2, 25, 40, 0.5, 20, 2, 8, 21, 1, 0),
+}
+
+
+def fin_opts(preset="map-ont", **over):
+    """mm2c_fin_opt_t as align_regs and mm_map_frag hand their options on (align.c:917, map.c:264-268, 361): min_cnt, min_chain_score, min_dp_max (options.c:49:
+    min_chain_score * a = 80 at init; asm*: 200, sr: 40), max_clip_ratio 1.0 (:52), mask_level 0.5, mask_len INT_MAX, hard_mask_level 0, sub_diff = a * 2 + b,
+    pri_ratio, min_diff = 2k (the index's k), best_n, match_sc = a, is_sr, all_chains (MM_F_ALL_CHAINS: ava-ont).  Keywords override single fields."""
+    min_cnt, mcs, mdm, pri, best_n, a, b, k, is_sr, all_chains = FIN_PRESETS[preset]
+    v = dict(min_cnt=min_cnt, min_chain_score=mcs, min_dp_max=mdm, max_clip_ratio=1.0, mask_level=0.5, mask_len=INT32_MAX, hard_mask_level=0, sub_diff=a * 2 + b,
+             pri_ratio=pri, min_diff=2 * k, best_n=best_n, match_sc=a, is_sr=is_sr, all_chains=all_chains)
+    unknown = set(over) - set(v)
+    if unknown:
+        raise TypeError(f"fin_opts: unknown field(s) {sorted(unknown)}")
+    v.update(over)
+    return FinOpt(v["min_cnt"], v["min_chain_score"], v["min_dp_max"], v["max_clip_ratio"], v["mask_level"], v["mask_len"], int(bool(v["hard_mask_level"])), v["sub_diff"],
+                  v["pri_ratio"], v["min_diff"], v["best_n"], v["match_sc"], int(bool(v["is_sr"])), int(bool(v["all_chains"])))
 
 
 KSW_PRESETS = {   # a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus, bw (options.c:26,45-48 and the presets of :82-151)
