@@ -375,6 +375,8 @@ typedef struct {
 	float pri_ratio; int32_t min_diff; int32_t best_n;             /* mm_select_sub: opt->pri_ratio, mi->k * 2, opt->best_n */
 } mm2c_hit_opt_t;
 #define MM2C_REG_SAM_PRI_BIT 12
+#define MM2C_REG_PROPER_FRAG_BIT 13    /* set by the pair plan (mm_pair, pe.c:138) */
+#define MM2C_REG_PE_THRU_BIT 14        /* set by the pair plan (mm_set_pe_thru, pe.c:60) */
 #define MM2C_HIT_LDS_REGIONS 128
 typedef struct mm2c_hitplan mm2c_hitplan_t;
 mm2c_hitplan_t *mm2c_hitplan_create(int64_t n_reads, int64_t n_u_cap);
@@ -830,7 +832,8 @@ int mm2c_assemble_regions_batch_host(const mm2c_cig_opt_t *opt, int64_t n_reads,
  * in the options); offsets or d_n_in that leave the capacities or each other; a p that names no record; a read of more than one region that mixes kept regions with
  * and without p, or keeps none with cnt > 0 (the reference asserts there, hit.c:210).  Reads of up to MM2C_FIN_LDS_REGIONS regions are worked in on-chip memory,
  * longer ones in the plan's scratch.  d_regs_out must not alias d_regs_in; regions and records 8-byte, anchors 16-byte aligned.  Both entries are asynchronous on
- * `stream`.  Still the host's: mm_align1_inv with ksw_ll_i16, the interleave across alignment rounds, mm_pair, ALT contigs, splice. */
+ * `stream`.  Still the host's: mm_align1_inv with ksw_ll_i16, the interleave across alignment rounds, ALT contigs, splice; mm_pair is the pair
+ * plan's (mm2c_pairplan_run_device, below). */
 typedef struct { int32_t dp_score, dp_max, dp_max2; uint32_t ambi_strand; int32_t n_cigar, reserved; int64_t cig0; } mm2c_pext_t;
 typedef struct {
 	int32_t min_cnt, min_chain_score, min_dp_max; float max_clip_ratio;    /* mm_filter_regs, hit.c:280-284 */
@@ -866,6 +869,44 @@ int mm2c_apply_regions_batch_host(int64_t n_reads, const int64_t *u_off, const m
                                   mm2c_reg_t *regs_out, mm2c_pext_t *pext, int32_t *status, int64_t n_child_cap, mm2c_reg_t *child, int32_t *child_of, int64_t *n_child);
 int mm2c_finish_regions_batch_host(int64_t n_reads, const mm2c_fin_opt_t *opt, int32_t max_log_arg, const int64_t *f_off, const mm2c_reg_t *regs_in, const int32_t *n_in,
                                    int64_t n_pext, mm2c_pext_t *pext, const int32_t *qlen, const int32_t *rep_len, mm2c_reg_t *regs_out, int32_t *n_out);
+
+/* ---- the two ends of a fragment paired on the GPU: mm_pair with mm_set_pe_thru (pe.c:45-63, 76-177; map.c:373-374) and the flip of the mate that
+ * was reverse-complemented before mapping (map.c:455-466) ----
+ * A stand-alone plan (kernel pair_select, one wave per fragment), byte for byte the reference's, wired into nothing.  Fragment f is the two segment reads 2f and
+ * 2f + 1 (the numbering f * n_segs + s of the fragment plans).  In: the final regions of segment read r, d_regs[d_f_off[r] .. d_f_off[r] + d_n[r]) in room for
+ * d_f_off[r+1] - d_f_off[r], as mm2c_finplan_run_device wrote them (its d_regs_out / d_n_out, with the f_off it took); d_pext, the records their p names (read
+ * only); d_seg_len[r], the qlens; d_gap_ref[f], max_chain_gap_ref per fragment, or NULL for opt->max_gap_ref (the convention of mm2c_hitplan_run_device_multi).
+ * Out: the regions in place -- only parent and the bits mapq, sam_pri, proper_frag, pe_thru of flags change, and with opt->flip qs, qe and rev of the mate j with
+ * (j == 0 && pe_ori >> 1 & 1) || (j == 1 && pe_ori & 1) (qs, qe = qlen - qe, qlen - qs; map.c:455-466) -- and d_status[f].  The flip runs last, whether or not a
+ * pair was found and also when one mate has no region; a fragment with one mate empty is otherwise untouched (pe.c:97-100: mm_set_pe_thru is behind the return).
+ * logf((float)n_sub) of pe.c:159 comes from a table the HOST fills at creation with its own logf, 0 <= i <= max_log_arg; a fragment whose n_sub lies beyond it
+ * keeps both winners' mapq as they came in, everything else of it is done, and it is counted (MM2C_E_TOOBIG from _check).
+ * Refused at the entry (MM2C_E_ARG): sub_diff < 0, match_sc < 1, pe_ori outside 0..3.
+ * Refused and counted per fragment (d_status[f] = 1, MM2C_E_ARG from _check; nothing else of that fragment is written and its neighbours are exact), whether or not
+ * both mates have regions: a region with p == 0 or a p that names no record (the reference dereferences it); rid < 0; rs < 0 or rs >= 2^30 (the int shift of the
+ * key); id not equal to the region's position, or parent outside the mate (the reference indexes regs[s][parent]); offsets or counts that leave the capacities or
+ * each other.  Fragments of up to MM2C_PAIR_LDS_REGIONS regions (both mates) are worked in on-chip memory, longer ones in the plan's scratch.  Regions and records
+ * 8-byte aligned; asynchronous on `stream`.  Not built: MM_F_INDEPEND_SEG, fragments of more than two segments (the reference does not pair them). */
+typedef struct {
+	int32_t max_gap_ref, pe_bonus;         /* opt->max_gap_ref (one scalar, when d_gap_ref is NULL), opt->pe_bonus */
+	int32_t sub_diff, match_sc;            /* opt->a * 2 + opt->b, opt->a (map.c:374) */
+	int32_t pe_ori, flip;                  /* opt->pe_ori; flip != 0: run map.c:455-466 */
+} mm2c_pair_opt_t;
+#define MM2C_PAIR_LDS_REGIONS 128
+typedef struct mm2c_pairplan mm2c_pairplan_t;
+/* capacities: fragments, regions, mm2c_pext_t records; the table's largest argument (at most MM2C_MAPQ_MAX_LOG_ARG) */
+mm2c_pairplan_t *mm2c_pairplan_create(int64_t n_frags, int64_t n_u_cap, int64_t n_pext_cap, int32_t max_log_arg);
+void mm2c_pairplan_destroy(mm2c_pairplan_t *plan);
+int mm2c_pairplan_run_device(mm2c_pairplan_t *plan, const mm2c_pair_opt_t *opt, const int64_t *d_f_off, mm2c_reg_t *d_regs, const int32_t *d_n, const mm2c_pext_t *d_pext,
+                             const int32_t *d_seg_len, const int32_t *d_gap_ref, int32_t *d_status, void *stream);
+/* waits for the last run.  MM2C_E_ARG if a fragment was refused, else MM2C_E_TOOBIG if an n_sub lay beyond the table.  *n_proper: fragments with a proper pair */
+int mm2c_pairplan_check(mm2c_pairplan_t *plan, int64_t *n_refused, int64_t *n_beyond_table, int64_t *n_proper);
+/* milliseconds of the last run between HIP events on its stream */
+int mm2c_pairplan_last_ms(mm2c_pairplan_t *plan, float *select_ms);
+/* host arrays in and out (regs in place); argument and offset checks (MM2C_E_ARG) come before any device work.  With MM2C_E_TOOBIG, or MM2C_E_ARG for fragments
+ * refused on the device, the rest is complete all the same. */
+int mm2c_pair_ends_batch_host(int64_t n_frags, const mm2c_pair_opt_t *opt, int32_t max_log_arg, const int64_t *f_off, mm2c_reg_t *regs, const int32_t *n, int64_t n_pext,
+                              const mm2c_pext_t *pext, const int32_t *seg_len, const int32_t *gap_ref, int32_t *status);
 
 /* ---- seed hits -> sorted anchors on the GPU (collect_seed_hits, map.c:215-247) ----
  * One match = one query minimizer found in the index (mm_match_t, map.c:76-81, as collect_matches map.c:84-120 fills it); its hits

@@ -14,7 +14,7 @@ from .batch import (device_identity, last_host_variant, init, split_model, init_
                     EXTRA_CIGAR_CUT, EXTRA_LDS_WORDS,
                     RefSeq, AlnPlan, align_tasks_batch, ALN_OPT_DTYPE, ALN_REG_DTYPE, ALN_ITEM_DTYPE, ALN_REFUSED, ALN_TOO_BIG, ALN_OVER_CAP, ALN_LDS_GAPS,
                     CigPlan, second_pass_batch, assemble_regions_batch, CIG_OPT_DTYPE, CIG_REG_DTYPE, CIG_REFUSED, CIG_INCOMPLETE, CIG_OVER_CAP, CIG_PIECE, CIG_NO_ROOM, CIG_LOST,
-                    FinPlan, apply_regions_batch, finish_regions_batch, interleave_rounds, PEXT_DTYPE, FIN_REFUSED, FIN_INCOMPLETE, FIN_OVER_CAP)
+                    FinPlan, apply_regions_batch, finish_regions_batch, interleave_rounds, PEXT_DTYPE, FIN_REFUSED, FIN_INCOMPLETE, FIN_OVER_CAP, PairPlan, pair_ends_batch)
 
 __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE_GENERAL", "load", "params", "synth",
            "sharding", "stream", "device_identity", "last_host_variant", "init", "split_model", "init_devices", "device_count", "split_tasks", "shutdown", "device_info", "tune", "tune_get", "tune_keys", "tuned", "ChainPlan", "chain_batch_host", "chain_batch_host_into", "PinnedArray", "chain_task", "hardware_init",
@@ -30,4 +30,4 @@ __all__ = ["Params", "Mm2cError", "LIB_PATH", "MM2C_F_IGNORE_SEG", "MM2C_F_FORCE
            "EXTRA_CIGAR_CUT", "EXTRA_LDS_WORDS",
            "RefSeq", "AlnPlan", "align_tasks_batch", "ALN_OPT_DTYPE", "ALN_REG_DTYPE", "ALN_ITEM_DTYPE", "ALN_REFUSED", "ALN_TOO_BIG", "ALN_OVER_CAP", "ALN_LDS_GAPS",
            "CigPlan", "second_pass_batch", "assemble_regions_batch", "CIG_OPT_DTYPE", "CIG_REG_DTYPE", "CIG_REFUSED", "CIG_INCOMPLETE", "CIG_OVER_CAP", "CIG_PIECE", "CIG_NO_ROOM", "CIG_LOST",
-           "FinPlan", "apply_regions_batch", "finish_regions_batch", "interleave_rounds", "PEXT_DTYPE", "FIN_REFUSED", "FIN_INCOMPLETE", "FIN_OVER_CAP"]
+           "FinPlan", "apply_regions_batch", "finish_regions_batch", "interleave_rounds", "PEXT_DTYPE", "FIN_REFUSED", "FIN_INCOMPLETE", "FIN_OVER_CAP", "PairPlan", "pair_ends_batch"]

@@ -101,12 +101,21 @@ class FinOpt(C.Structure):
                 ("match_sc", C.c_int32), ("is_sr", C.c_int32), ("all_chains", C.c_int32)]
 
 
+class PairOpt(C.Structure):
+    """mm2c_pair_opt_t: mm_pair's max_gap_ref (one scalar, for a run without per-fragment values), pe_bonus, sub_diff (a * 2 + b), match_sc (a); opt->pe_ori and
+    whether the flip of map.c:455-466 runs"""
+    _fields_ = [(k, C.c_int32) for k in ("max_gap_ref", "pe_bonus", "sub_diff", "match_sc", "pe_ori", "flip")]
+
+
 class Err(C.Structure):
     """mm2c_err_t: the counts of mm_est_err per final region (esterr.c:53-61); n_match 0: div = -1, n_match -1: the read has no mini_pos"""
     _fields_ = [("n_match", C.c_int32), ("n_tot", C.c_int32)]
 
 
 MM2C_REG_SAM_PRI_BIT = 12
+MM2C_REG_PROPER_FRAG_BIT = 13
+MM2C_REG_PE_THRU_BIT = 14
+MM2C_PAIR_LDS_REGIONS = 128
 MM2C_HIT_LDS_REGIONS = 128
 MM2C_MAPQ_MAX_LOG_ARG = (1 << 24) - 1
 MM2C_MAX_SEG = 255
@@ -250,6 +259,12 @@ C_SYMBOLS = {
     "mm2c_finplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mm2c_apply_regions_batch_host": (C.c_int, [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_void_p] * 3),
     "mm2c_finish_regions_batch_host": (C.c_int, [C.c_int64, C.POINTER(FinOpt), C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 5),
+    "mm2c_pairplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "mm2c_pairplan_destroy": (None, [C.c_void_p]),
+    "mm2c_pairplan_run_device": (C.c_int, [C.c_void_p, C.POINTER(PairOpt)] + [C.c_void_p] * 8),
+    "mm2c_pairplan_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mm2c_pairplan_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mm2c_pair_ends_batch_host": (C.c_int, [C.c_int64, C.POINTER(PairOpt), C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4),
     "mm2c_errplan_create": (C.c_void_p, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mm2c_errplan_destroy": (None, [C.c_void_p]),
     "mm2c_errplan_run_device": (C.c_int, [C.c_void_p] * 9 + [C.c_int32] + [C.c_void_p] * 4),

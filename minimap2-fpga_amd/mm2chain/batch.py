@@ -1425,6 +1425,78 @@ def finish_regions_batch(opt, f_off, regs, n_in, pext, qlen, rep_len, max_log_ar
     return dict(regs=out[:n_u], n_out=n_out[:n_reads], pext=px, rc=rc)
 
 
+class PairPlan(_Handle):
+    """mm2c_pairplan_t: the two ends of a fragment paired on the GPU for batches of up to n_frags two-segment fragments, n_u_cap final regions and n_pext_cap
+    mm2c_pext_t records: mm_pair with mm_set_pe_thru (pe.c:45-63, 76-177) and the flip of map.c:455-466, in place on the regions FinPlan.run wrote.  max_log_arg:
+    the largest n_sub whose logf the plan's table holds -- the host's own logf, filled at creation."""
+
+    _destroy = "mm2c_pairplan_destroy"
+
+    def __init__(self, n_frags, n_u_cap, n_pext_cap, max_log_arg=1 << 16):
+        self.n_frags, self.n_u_cap, self.n_pext_cap, self.max_log_arg = int(n_frags), int(n_u_cap), int(n_pext_cap), int(max_log_arg)
+        self._create("mm2c_pairplan_create", self.n_frags, self.n_u_cap, self.n_pext_cap, self.max_log_arg, code=-2)
+
+    def run(self, opt, f_off: torch.Tensor, regs: torch.Tensor, n: torch.Tensor, pext: torch.Tensor, seg_len: torch.Tensor, gap_ref: torch.Tensor = None,
+            status: torch.Tensor = None, stream=None):
+        """opt: params.pair_opts(); fragment f is the segment reads 2f and 2f + 1, the final regions of segment read r are rows f_off[r] .. f_off[r] + n[r] of regs
+        (FinPlan.run's regs_out and n_out with the f_off it took); pext the records their p names; seg_len int32 per segment read; gap_ref int32 per fragment or
+        None for opt.max_gap_ref; all on the GPU.  regs is updated in place.  Returns status int32 [n_frags]: 1 for a refused fragment.  Asynchronous."""
+        for t in (f_off, regs, n, pext, seg_len) + (() if gap_ref is None else (gap_ref,)):
+            assert t.is_cuda and t.is_contiguous()
+        nr = 2 * self.n_frags
+        assert f_off.dtype == torch.int64 and f_off.numel() == nr + 1 and n.dtype == torch.int32 and n.numel() >= nr and seg_len.dtype == torch.int32 and seg_len.numel() >= nr
+        assert regs.numel() * regs.element_size() >= self.n_u_cap * REG_DTYPE.itemsize and pext.numel() * pext.element_size() >= self.n_pext_cap * PEXT_DTYPE.itemsize
+        assert gap_ref is None or (gap_ref.dtype == torch.int32 and gap_ref.numel() >= self.n_frags)
+        status = _out(status, max(self.n_frags, 1), torch.int32, f_off.device, self.n_frags * 4, "dtype")
+        N.check(self.lib.mm2c_pairplan_run_device(self.handle, C.byref(opt), f_off.data_ptr(), regs.data_ptr(), n.data_ptr(), pext.data_ptr(), seg_len.data_ptr(),
+                                                  None if gap_ref is None else gap_ref.data_ptr(), status.data_ptr(), _stream(stream)), "mm2c_pairplan_run_device")
+        return status[:self.n_frags]
+
+    def counts(self):
+        """waits for the last run() -> (return code, fragments refused, fragments with n_sub beyond the table, fragments with a proper pair) without raising"""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = self.lib.mm2c_pairplan_check(self.handle, C.byref(a), C.byref(b), C.byref(c))
+        return rc, a.value, b.value, c.value
+
+    def check(self):
+        """waits for the last run(); raises if a fragment was refused (code -2) or an n_sub lay beyond the table (code -3); returns the number of proper pairs"""
+        rc, _, _, n = self.counts()
+        N.check(rc, "mm2c_pairplan_check")
+        return n
+
+    def last_ms(self):
+        return self._ms("mm2c_pairplan_last_ms", 1)[0]
+
+
+def pair_ends_batch(opt, f_off, regs, n, pext, seg_len, gap_ref=None, max_log_arg=1 << 16, fill=None):
+    """mm2c_pair_ends_batch_host: host arrays in -> dict(regs REG_DTYPE [f_off[-1] - f_off[0]] (a copy, updated), status int32 [n_frags], rc); the regions of segment
+    read r are regs[f_off[r] - f_off[0] :][:n[r]].  rc is 0, -2 (a fragment refused on the device: nothing of it is written but its status) or -3 (an n_sub beyond
+    the table): the rest is complete all the same.  Raises for any other failure, an argument refused before the device ran included.  fill: a byte status is
+    filled with beforehand (tests)."""
+    lib = N.load()
+    fo = _i64(f_off)
+    rr = np.array(_reg_rows(regs), copy=True)
+    nn = np.ascontiguousarray(n, dtype=np.int32); q = np.ascontiguousarray(seg_len, dtype=np.int32)
+    px = np.ascontiguousarray(pext, dtype=PEXT_DTYPE).reshape(-1)
+    if fo.size % 2 != 1:
+        raise ValueError("f_off must hold 2 * n_frags + 1 offsets")
+    n_frags = (fo.size - 1) // 2
+    g = None if gap_ref is None else np.ascontiguousarray(gap_ref, dtype=np.int32)
+    if nn.size != 2 * n_frags or q.size != 2 * n_frags or (g is not None and g.size != n_frags) or not _fit(n_frags, (fo, rr.shape[0])):
+        raise ValueError("offsets do not fit the arrays")
+    f = 0 if fill is None else int(fill)
+    status = np.full(max(n_frags, 1) * 4, f, np.uint8).view(np.int32)
+    pp = px if px.size else np.zeros(1, PEXT_DTYPE)
+    rp = rr if rr.size else np.zeros((1, REG_DTYPE.itemsize), np.uint8)
+    rc = lib.mm2c_pair_ends_batch_host(n_frags, C.byref(opt), int(max_log_arg), _np_ptr(fo), _np_ptr(rp), _np_ptr(nn), px.size, _np_ptr(pp), _np_ptr(q),
+                                       None if g is None else _np_ptr(g), _np_ptr(status))
+    if rc not in (0, -3) and not (rc == -2 and b"refused, nothing of them written" in (lib.mm2c_last_error() or b"")):
+        N.check(rc, "mm2c_pair_ends_batch_host")
+    lo = int(fo[0]) if n_frags > 0 else 0
+    hi = int(fo[-1]) if n_frags > 0 else 0
+    return dict(regs=rr.reshape(-1).view(REG_DTYPE)[lo:hi], status=status[:n_frags], rc=rc)
+
+
 ERR_DTYPE = np.dtype([("n_match", "<i4"), ("n_tot", "<i4")])                   # mm2c_err_t
 
 

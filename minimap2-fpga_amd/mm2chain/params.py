@@ -1,5 +1,5 @@
 """Chaining parameter presets, mirroring options.c of the reference (file:line cited per preset)."""
-from ._native import Params, HitOpt, HitMultiOpt, MapqOpt, FinOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
+from ._native import Params, HitOpt, HitMultiOpt, MapqOpt, FinOpt, PairOpt, MM2C_F_IGNORE_SEG, MM2C_F_FORCE_GENERAL
 
 INT32_MAX = 2**31 - 1
 
@@ -93,6 +93,19 @@ def fin_opts(preset="map-ont", **over):
     v.update(over)
     return FinOpt(v["min_cnt"], v["min_chain_score"], v["min_dp_max"], v["max_clip_ratio"], v["mask_level"], v["mask_len"], int(bool(v["hard_mask_level"])), v["sub_diff"],
                   v["pri_ratio"], v["min_diff"], v["best_n"], v["match_sc"], int(bool(v["is_sr"])), int(bool(v["all_chains"])))
+
+
+def pair_opts(preset="sr", **over):
+    """mm2c_pair_opt_t as mm_map_frag hands mm_pair its options (map.c:373-374): max_gap_ref (the scalar for a run without per-fragment values: -x sr with 2 x 150
+    bases gives max(800 - 300, 100) = 500, map.c:311-313; otherwise the preset's bw), pe_bonus 33 (options.c:56), sub_diff = a * 2 + b and match_sc = a of the
+    preset, pe_ori (options.c:55: 0 = FF; sr: 0 << 1 | 1 = FR, options.c:126) and flip = 1: the flip of map.c:455-466 runs.  Keywords override single fields."""
+    a, b = FIN_PRESETS[preset][5:7]
+    v = dict(max_gap_ref=500 if preset == "sr" else KSW_PRESETS[preset][10], pe_bonus=33, sub_diff=a * 2 + b, match_sc=a, pe_ori=1 if preset == "sr" else 0, flip=1)
+    unknown = set(over) - set(v)
+    if unknown:
+        raise TypeError(f"pair_opts: unknown field(s) {sorted(unknown)}")
+    v.update(over)
+    return PairOpt(v["max_gap_ref"], v["pe_bonus"], v["sub_diff"], v["match_sc"], v["pe_ori"], int(bool(v["flip"])))
 
 
 KSW_PRESETS = {   # a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus, bw (options.c:26,45-48 and the presets of :82-151)
